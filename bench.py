@@ -14,10 +14,15 @@ state the coarser levels converged to, with the DEFAULT solver options -- the on
 converging solves of that level (when a solve converges early the start state is restored and the next begins).
 
     python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --full   # + the figures below, the secondary figure and the CPU baseline
+    python bench.py --steps K --warmup W --dump-outputs DIR  # + the last timed solve's end state as DIR/<name>.npy
     python bench.py --config 4 [--robust huber]      # BASELINE configs[4]: 1000 frames 640x384, 16x12 grid (one GPU)
     python bench.py --dense --steps 8 --warmup 1     # configs[2] dense: every masked pixel of 1766 pairs (146 M constraints)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...                     # no launcher: spawns the N ranks itself (re-exec under torch.distributed.run)
+
+A plain run sets up, warms up, times the K iterations and prints the line: metric, value, unit, ms_per_step, the workload
+(`config`) and what the timed solves did.  Everything else is measured with `--full` only.
 
 N > 1 (default `--mode shard`): the SAME problem, frame pairs sharded across the ranks (robust_cvd_amd/sharding.py),
 regularisers by frame % N; the library exchanges over RCCL.  Total work is fixed => "strong" scaling,
@@ -25,7 +30,10 @@ regularisers by frame % N; the library exchanges over RCCL.  Tota
 The ranks of the bench itself talk over gloo (barrier, the 128-byte RCCL id, the max over ranks): the library's
 communicator is the only RCCL user in the process.
 
-The JSON line also carries
+With --full the JSON line also carries
+  kernels_*    : HIP-event timing of every kernel class on a uniform sample of the timed region's launches;
+  pipeline     : the whole pipeline (normalizeDepth + every coarse-to-fine level) once more on the warm handle;
+  secondary_1766_pairs : the same recipe on the reference sampler's own flow list (N = 1, configs[2] list mode);
   roofline     : dominant kernel k_matvec_pairs -- algorithmic HBM bytes per launch / average launch duration (HIP
                  events on the solver stream, live in this run) vs the 8 TB/s HBM peak, the same for its counted
                  f64 flops vs the 78.6 TF/s vector peak (`valu`), and the PMC HBM traffic of profiles/pmc_matvec_pairs.json
@@ -184,6 +192,23 @@ def run_iterations(solver, params, pose0, theta0, count, records_out=None):
     return done, cg, solves, last
 
 
+def dump_outputs(out_dir, solver, summ):
+    """What the last timed solve hands its caller (pose_optimization_step, convert_poses=False): the pose and depth-transform
+    parameters it converged to and its costs, float64, as out_dir/<name>.npy (well under a megabyte at configs[2]).  The spatial
+    transform's parameters are written only when it has any (the benchmarked transform is the identity: none)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {
+        "pose_params": solver.get_pose_params(),                  # [F, 7]
+        "depth_xform_params": solver.get_xform_params(),          # [F, grid vertices]
+        "spatial_xform_params": solver.get_xform_params(spatial=True),
+        "costs": np.array([summ["initial_cost"], summ["final_cost"]], dtype=np.float64),
+    }
+    for name, a in arrays.items():
+        if a.size:
+            np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def matvec_bytes_per_launch(video, n_active, B):
     """Algorithmic bytes of one k_matvec_pairs launch: the 24 B constraint table entry (ndc 16 B + source depths 8 B) of
     every constraint + per work item (undirected frame pair, chunked at 768 constraints per direction) the two frames'
@@ -233,6 +258,12 @@ def main():
     ap.add_argument("--pcg-tol", type=float, default=None, help="development: PCG forcing value (default: the library's)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="development: any integer field of cvd_solver_options (e.g. coarse_rebuild_excess=8, coarse_level=2)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel timing and roofline, the warm pipeline, the secondary figure, the CPU "
+                         "baseline (and, N > 1, the single-GPU equivalence check); the --no-* / --time-* / --verify options refine it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: the last timed solve's end state (pose and depth-transform parameters, costs) "
+                         "as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary figure on the reference sampler's 1766-pair list")
     ap.add_argument("--secondary-steps", type=int, default=10)
@@ -247,6 +278,8 @@ def main():
                          "final costs must agree to 1e-6 (minutes of CPU time)")
     args = ap.parse_args()
 
+    if args.verify and not args.full:
+        ap.error("--verify needs --full")
     if args.gpus < 1:
         sys.exit("--gpus must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -288,8 +321,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(pairs_level, steps, warmup, timing, seed_offset=0):
-        """prepare + warm-up + the timed region for one flow list; returns everything the JSON line needs."""
+    def measure(pairs_level, steps, warmup, timing, seed_offset=0, dump_dir=None):
+        """prepare + warm-up + the timed region for one flow list (--full: + kernel timing, the warm pipeline and, N > 1, the
+        equivalence check); returns everything the JSON line needs."""
         video = synth.make_video(frames, width, height, seed=SEED + seed_offset, extra_offsets=pairs_level,
                                  spacing=(1e9 if args.dense else 12.5))  # (dense: the sampled list is not used)
         solver = api.Solver(local_rank)
@@ -349,14 +383,14 @@ def main():
         # HIP-event timing of the dominant kernel only (two event records per timed launch, on every 4th launch: a uniform
         # sample of the timed region; the events of hipExtLaunchKernelGGL serialise the dispatch)
         sample_every = 1 if args.time_all_kernels else args.time_every
-        if timing and not args.no_kernel_timing:
+        if args.full and timing and not args.no_kernel_timing:
             # every class, sampled (every --time-every-th launch of each class): the line carries SURVEY 8(d)'s per-phase split
             classes = None
             solver.set_kernel_timing(True, classes=classes, sample_every=sample_every)
         barrier()
         t0 = time.perf_counter()
-        records = []
-        done, total_cg, n_solves, summ = run_iterations(solver, params, pose0, theta0, steps, records)
+        records = []  # (--full: the first timed solve's iteration records, for the CPU baseline's cost comparison)
+        done, total_cg, n_solves, summ = run_iterations(solver, params, pose0, theta0, steps, records if args.full else None)
         barrier()
         dt = time.perf_counter() - t0
         assert done == steps, (done, steps)
@@ -364,6 +398,12 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        if dump_dir is not None and rank == 0:
+            dump_outputs(dump_dir, solver, summ)
+        if not args.full:
+            return dict(video=full_video, local_video=video, solver=solver, full=full, dt=dt, total_cg=total_cg, n_solves=n_solves,
+                        summ=summ, cold=cold, t_prep=t_prep, upload=upload, prep_summary=prep_summary, grid=grid,
+                        n_active=solver.num_active_constraints(), B=solver.block_size())
         comm = solver.comm_times() if shard else None
         ktimes = solver.kernel_times()
         if args.dense:
@@ -425,10 +465,54 @@ def main():
                     sample_every=sample_every, ktimes=ktimes, n_active=solver.num_active_constraints(),
                     B=solver.block_size())
 
-    m = measure(level, args.steps, args.warmup, timing=True, seed_offset=(0 if shard or world == 1 else rank))
+    m = measure(level, args.steps, args.warmup, timing=True, seed_offset=(0 if shard or world == 1 else rank),
+                dump_dir=args.dump_outputs)
 
     if rank == 0:
         video, B, n_active = m["video"], m["B"], m["n_active"]
+        out = {
+            "metric": "GN/LM iterations/sec (and ms/iter) on 300-frame 384x224 video, 1/2/4/8 GPU",
+            "value": (1 if shard else world) * args.steps / m["dt"],
+            "unit": "LM iterations/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": m["dt"] / args.steps * 1e3,
+            "higher_is_better": True,
+            # default mode: the SAME problem at every N (pairs sharded) => strong; --mode replicas: one video per GPU => weak
+            "scaling": "strong" if args.mode == "shard" else "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {
+                "workload": (f"{cfg['label']}{' dense' if args.dense else ''}: {frames}-frame {width}x{height} synthetic video, hierarchical2 two-way flow_list "
+                             f"densified to level {level} ({m['full']['pairs']} directed pairs, "
+                             + (f"DENSE mode: every masked pixel is a constraint, {n_active} flow constraints read from the flow / mask / "
+                                f"depth images" if args.dense else f"{m['full']['constraints']} flow constraints") + f"), full LM loop; timed = LM iterations at the final CTF level ({m['grid'][0]}x{m['grid'][1]} "
+                             f"bilinear grid, B={B}, {frames * B} unknowns), {'Huber' if robust else 'Cauchy'} {params.robustness}, "
+                             f"PerFrame intrinsics, default solver options"),
+                "pairs": int(m["full"]["pairs"]), "constraints": int(n_active), "unknowns": int(frames * B),
+                "parallelism": "single-gpu" if world == 1 else (f"pair-sharded dp{world} + RCCL" if shard else "video-per-gpu"),
+                "linear_solver": ("PCG on matrix-free J^T J, additive three-level preconditioner: per-frame block-Jacobi + pose-graph level (8 modes per frame; exact "
+                             "sparse factor or, for this pair graph, its temporally coarse form) + temporally coarse depth-grid level"),
+                "pcg_iterations_per_lm_iteration": m["total_cg"] / max(1, args.steps),
+                "solves_in_timed_region": m["n_solves"],
+            },
+            "last_timed_solve": {k: m["summ"][k] for k in ("num_iterations", "num_successful_steps", "total_linear_iterations",
+                                                           "initial_cost", "final_cost", "termination")},
+            # every solve builds its coarse level in line (one persistent kernel) and carries nothing over from the solve before:
+            # the timed solves ARE cold solves; the warm-up solve additionally pays first-launch costs of the final level's kernels
+            "cold_first_solve": ({**m["cold"], "note": "the warm-up solve = the first solve of the final level on this handle"}
+                                 if m["cold"] else None),
+            "prepare_seconds": m["t_prep"],
+            # host -> device hand-over of the inputs (depth maps F*H*W f32 + 16 B per constraint), once per solve sequence;
+            # never part of `value` (inputs are resident when the timed region starts)
+            "upload_seconds": m["upload"],
+            "upload_bytes": int(video.depth.nbytes + video.loc.nbytes + video.is_static.nbytes),
+            "prepare_last_level": {k: m["prep_summary"][k] for k in ("num_iterations", "total_linear_iterations", "final_cost",
+                                                                     "total_seconds")},
+        }
+    if rank == 0 and args.full:
         mv = m["ktimes"]["matvec_pairs"]
         dense_explicit = args.dense and not any(kv.replace(" ", "") == "dense_matrix_free=1" for kv in args.opt)
         if args.dense:
@@ -472,34 +556,7 @@ def main():
                 traffic, traffic_note = pmc["traffic_bytes_per_launch"], f"{pmc_name} (same kernel sources, same workload)"
         except Exception:
             pass
-        out = {
-            "metric": "GN/LM iterations/sec (and ms/iter) on 300-frame 384x224 video, 1/2/4/8 GPU",
-            "value": (1 if shard else world) * args.steps / m["dt"],
-            "unit": "LM iterations/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": m["dt"] / args.steps * 1e3,
-            "higher_is_better": True,
-            # default mode: the SAME problem at every N (pairs sharded) => strong; --mode replicas: one video per GPU => weak
-            "scaling": "strong" if args.mode == "shard" else "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": (f"{cfg['label']}{' dense' if args.dense else ''}: {frames}-frame {width}x{height} synthetic video, hierarchical2 two-way flow_list "
-                             f"densified to level {level} ({m['full']['pairs']} directed pairs, "
-                             + (f"DENSE mode: every masked pixel is a constraint, {n_active} flow constraints read from the flow / mask / "
-                                f"depth images" if args.dense else f"{m['full']['constraints']} flow constraints") + f"), full LM loop; timed = LM iterations at the final CTF level ({m['grid'][0]}x{m['grid'][1]} "
-                             f"bilinear grid, B={B}, {frames * B} unknowns), {'Huber' if robust else 'Cauchy'} {params.robustness}, "
-                             f"PerFrame intrinsics, default solver options"),
-                "pairs": int(m["full"]["pairs"]), "constraints": int(n_active), "unknowns": int(frames * B),
-                "parallelism": "single-gpu" if world == 1 else (f"pair-sharded dp{world} + RCCL" if shard else "video-per-gpu"),
-                "linear_solver": ("PCG on matrix-free J^T J, additive three-level preconditioner: per-frame block-Jacobi + pose-graph level (8 modes per frame; exact "
-                             "sparse factor or, for this pair graph, its temporally coarse form) + temporally coarse depth-grid level"),
-                "pcg_iterations_per_lm_iteration": m["total_cg"] / max(1, args.steps),
-                "solves_in_timed_region": m["n_solves"],
-            },
+        out.update({
             "roofline": {
                 "bound": "hbm", "kernel": "k_dense_walk" if (args.dense and dense_explicit) else "k_matvec_pairs", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
@@ -556,24 +613,12 @@ def main():
                              "scope allows) the finish class is empty and cg_update is the fused kernel; block_inverse includes the "
                              "in-line rebuilds of the coarse level; SURVEY 8(d)'s split per LM iteration = evaluate_assemble + "
                              "block_inverse + pcg_iterations_per_lm_iteration x (matvec_pairs + matvec_finish + cg_update) + cost"),
-            "last_timed_solve": {k: m["summ"][k] for k in ("num_iterations", "num_successful_steps", "total_linear_iterations",
-                                                           "initial_cost", "final_cost", "termination")},
-            # every solve builds its coarse level in line (one persistent kernel) and carries nothing over from the solve before:
-            # the timed solves ARE cold solves; the warm-up solve additionally pays first-launch costs of the final level's kernels
-            "cold_first_solve": ({**m["cold"], "note": "the warm-up solve = the first solve of the final level on this handle"}
-                                 if m["cold"] else None),
             "pipeline": m["pipeline"],
-            "prepare_seconds": m["t_prep"],
-            # host -> device hand-over of the inputs (depth maps F*H*W f32 + 16 B per constraint), once per solve sequence;
-            # never part of `value` (inputs are resident when the timed region starts)
-            "upload_seconds": m["upload"],
-            "upload_bytes": int(video.depth.nbytes + video.loc.nbytes + video.is_static.nbytes),
-            "prepare_last_level": {k: m["prep_summary"][k] for k in ("num_iterations", "total_linear_iterations", "final_cost",
-                                                                     "total_seconds")},
-        }
+        })
     solver_main = m.pop("solver")
     solver_main.close()
-    if args.config == 2 and level != 1 and not args.no_secondary and args.frames is None and not args.dense and world == 1:
+    if (args.full and args.config == 2 and level != 1 and not args.no_secondary and args.frames is None and not args.dense
+            and world == 1):
         # secondary figure: the reference sampler's own flow list (1766 directed pairs at 300 frames), same recipe (single-GPU
         # runs only: a multi-rank run times the headline workload and nothing else)
         m2 = measure(1, args.secondary_steps, min(args.warmup, 2), timing=False)
@@ -587,7 +632,7 @@ def main():
             }
         m2.pop("solver").close()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and not args.dense:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.dense:
             cb = cpu_baseline(params, m["video"], m["grid"], m["pose0"], m["theta0"], robust)
             # results, not only speed: the oracle's cost after ITS first LM iteration (exact sparse Cholesky step) against the
             # GPU's after the first iteration of the first timed solve (PCG step to eta), same start state

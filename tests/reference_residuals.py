@@ -11,7 +11,8 @@ container and cannot travel to the GPU box, so the pin has two halves like the o
     disparity difference, the two terms of `ConsistencyLoss.geometry_consistency_loss` itself, and central differences of
     the torch functions along every pose / focal parameter;
   * tests/test_reference_residuals.py holds the oracle's three residuals and its dual-number Jacobian columns against the
-    committed values (always) and against the live reference functions (when /root/reference is mounted).
+    committed values: every 8th constraint's derivative rows from residual_golden.npz, the 8th-from-the-4th from
+    live_golden.npz (make_live_golden.py).
 
 Conversions (derived from the two statements, checked by the test itself):
     pixel = ((ndc.x + 1) W/2, (1 - ndc.y) H/2)                      (pixel-edge NDC of the constraints)
@@ -37,6 +38,7 @@ from robust_cvd_amd import synth
 from robust_cvd_amd.ctypes_types import IntrinsicsOptimization, OptParams, StaticLossType, XformDesc
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_py", "residual_golden.npz")
+LIVE_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_py", "live_golden.npz")
 
 # name -> (frames, width, height, seed, intrinsics mode, depth grid)
 CASES = {

@@ -4,7 +4,6 @@ import importlib
 import os
 import struct
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -278,35 +277,6 @@ def test_param_map_and_warp_match_the_oracle_gathers(lib, dataset):
         idx, w = orc.gather(osd, 1.0, float(lx), float(ly))
         exp = (phi.reshape(-1, 2)[idx] * w[:, None]).sum(0)
         np.testing.assert_allclose(wmap[y, x], exp, atol=1e-7)
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference checkout not mounted")
-def test_reference_pose_optimizer_constructor_runs_unmodified(lib, dataset, monkeypatch):
-    """The reference's own pose_optimization.PoseOptimizer.__init__ (reference pose_optimization.py:99-175) against
-    this module: only cv2 (two integer constants) is stubbed because OpenCV is not installed here."""
-    v, base = dataset
-    cv2 = types.ModuleType("cv2")
-    cv2.CV_32FC3, cv2.CV_8UC1 = 21, 0
-    monkeypatch.setitem(sys.modules, "cv2", cv2)
-    monkeypatch.syspath_prepend("/root/reference")
-    sys.modules.pop("pose_optimization", None)
-    try:
-        po = importlib.import_module("pose_optimization")
-    except ImportError as e:
-        pytest.skip(f"reference helper import failed: {e}")
-    opt = types.SimpleNamespace(
-        max_iterations=1000, num_threads=12, num_steps=4, robustness=0.5, static_loss_type="ReproDisparity",
-        static_spatial_weight=1.0, static_depth_weight=1.0, smooth_loss_type="ReproDisparityLaplacian",
-        smooth_static_weight=0.0, smooth_dynamic_weight=0.0, position_regularization=0.0, scale_regularization=1.0,
-        scale_regularization_grid_size=10, deformation_regularization_initial=1.0, deformation_regularization_final=0.1,
-        adaptive_deformation_cost=0.0, spatial_deformation_regularization=1.0, graduate_deformation_regularization=False,
-        focal_regularization=1.0, coarse_to_fine=True, ctf_long=17, ctf_short=10, deferred_spatial_opt=False, dso_long=4,
-        dso_short=3, focal_long=0.3461538376301239, intr_opt="PerFrame", fix_poses=False, fix_depth_transforms=False,
-        fix_spatial_transforms=False, use_global_scale=False, dynamic_constraints="Mask", epipolar_dist_thresh=1.0)
-    p = po.PoseOptimizer(base, "midas2", list(range(v.num_frames)), opt)
-    assert p.depth_video.numFrames() == 10 and p.opt_params.ctfLong == 17
-    assert os.path.exists(os.path.join(base, "video.dat"))
-    sys.modules.pop("pose_optimization", None)
 
 
 @pytest.mark.gpu

@@ -5,8 +5,9 @@ color_down/frame_*.raw are written by the reference's Python (utils/image_io.py:
   * always: robust_cvd_amd.dataset_io.write_raw_image produces, byte for byte, what the reference's writer produced for the committed
     images (tests/golden/reference_py/raw_image_golden.npz, minted by make_raw_image_golden.py next to it), and the drop-in
     lib_python's DepthStream reads a frame file made of those reference bytes;
-  * with /root/reference mounted: the live writer against dataset_io's, the live reader on dataset_io's files, and a whole depth
-    stream written by the reference's function and imported through lib_python.
+  * what the live writer and reader returned (tests/golden/reference_py/live_golden.npz, make_live_golden.py): the writer against
+    dataset_io's, the reader on those bytes, and a whole depth stream written by the reference's function and imported through
+    lib_python.
 """
 import importlib
 import os
@@ -20,6 +21,14 @@ from robust_cvd_amd import dataset_io, synth
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_py", "raw_image_golden.npz")
 CASES = ("depth_5x7", "flow_4x6x2", "color_3x5x3")
+LIVE_GOLDEN = os.path.join(os.path.dirname(GOLDEN), "live_golden.npz")
+
+
+def live_inputs():
+    """The seeded images and depth stream of the live pin (tests/golden/reference_py/make_live_golden.py mints from the same)."""
+    rng = np.random.default_rng(5)
+    images = [rng.standard_normal(shape).astype(np.float32) for shape in ((9, 13), (6, 8, 2), (4, 4, 3))]
+    return images, synth.make_video(4, 48, 28, seed=89, spacing=8)
 
 
 @pytest.fixture(scope="module")
@@ -59,24 +68,21 @@ def test_depth_stream_reads_a_frame_the_reference_wrote(lib, tmp_path):
     np.testing.assert_allclose(src, 1.0 / disp, rtol=2e-7)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference checkout not mounted")
 def test_live_reference_writer_and_reader(lib, tmp_path):
-    from tests import reference_residuals as rres
-    rres._reference_modules()
-    from utils import image_io
-    rng = np.random.default_rng(5)
-    for shape in ((9, 13), (6, 8, 2), (4, 4, 3)):
-        img = rng.standard_normal(shape).astype(np.float32)
-        a, b = str(tmp_path / "ref.raw"), str(tmp_path / "ours.raw")
-        image_io.save_raw_float32_image(a, img)
+    """What the reference's writer and reader returned for these inputs (tests/golden/reference_py/live_golden.npz, minted by
+    make_live_golden.py next to it): the writer's bytes against dataset_io's, the reader's values against the images, and a whole
+    depth stream of the writer's files imported by the drop-in module."""
+    live = np.load(LIVE_GOLDEN)
+    images, v = live_inputs()
+    for i, img in enumerate(images):
+        b = str(tmp_path / "ours.raw")
         dataset_io.write_raw_image(b, img)
-        assert open(a, "rb").read() == open(b, "rb").read()
-        assert np.array_equal(np.asarray(image_io.load_raw_float32_image(b)).reshape(shape), img)
-    # a whole depth stream written by the reference's function, imported by the drop-in module
-    v = synth.make_video(4, 48, 28, seed=89, spacing=8)
+        assert open(b, "rb").read() == live[f"raw/image_{i}/bytes"].tobytes()
+        assert np.array_equal(live[f"raw/image_{i}/read"].reshape(img.shape), img)
     base = dataset_io.write_dataset(str(tmp_path / "video"), v)
     for i in range(v.num_frames):
-        image_io.save_raw_float32_image(os.path.join(base, "depth_midas2", "depth", f"frame_{i:06d}.raw"), 1.0 / v.depth[i])
+        with open(os.path.join(base, "depth_midas2", "depth", f"frame_{i:06d}.raw"), "wb") as f:
+            f.write(live[f"raw/stream_{i}/bytes"].tobytes())
     dv = lib.DepthVideo()
     lib.DepthVideoImporter.importVideo(dv, base, True)
     dv.createDepthStream("depth_midas2", "depth_midas2", [v.width, v.height])

@@ -4,7 +4,7 @@ and utils/geometry.py:62-138 -- was run on the drop-in's results and its outputs
 (tests/golden/reference_py/reprojection_golden.npz, minted by make_reprojection_golden.py next to it).
 
 CPU: the numpy restatement of those reference lines (tests/reference_reprojection.py) reproduces the committed reference outputs;
-with /root/reference mounted, the live reference functions map the synthetic generator's ground truth onto the flow targets.
+and what the live reference functions returned for the synthetic generator's ground truth (live_golden.npz) is its flow targets.
 GPU: a fresh drop-in run reproduces the dumped state and, through the pinned restatement, reprojects every static constraint
 onto `pixel + flow` and the rendered depth up to one global scale.
 """
@@ -55,29 +55,27 @@ def test_numpy_restatement_reproduces_the_reference_outputs():
     np.testing.assert_allclose(err, g["reprojection_error_px"], atol=1e-6)
 
 
-def _mint_module():
+def _live_mint_module():
     spec = importlib.util.spec_from_file_location(
-        "make_reprojection_golden", os.path.join(os.path.dirname(rr.GOLDEN), "make_reprojection_golden.py"))
+        "make_live_golden", os.path.join(os.path.dirname(rr.GOLDEN), "make_live_golden.py"))
     m = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(m)
     return m
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference checkout not mounted")
 def test_live_reference_functions_on_the_generators_ground_truth():
     """The synthetic generator's TRUE cameras / scales, handed to the live reference code as if they were the optimizer's
-    getters, reproject every constraint onto its flow target: generator, restatement and reference agree on every convention."""
-    mk = _mint_module()
+    getters, reproject every constraint onto its flow target: generator, restatement and reference agree on every convention.
+    (What the reference code returned is committed: tests/golden/reference_py/live_golden.npz, make_live_golden.py.)"""
+    mk = _live_mint_module()
     v = rr.make_case()
-    F, H, W = v.num_frames, v.height, v.width
-    R = synth.rodrigues(v.true_w)
-    out = dict(right=R[:, :, 0], up=R[:, :, 1], backward=R[:, :, 2], position=v.true_t,
-               hfov=np.full(F, 2 * np.arctan(v.true_fy * v.aspect)), vfov=np.full(F, 2 * np.arctan(v.true_fy)),
-               param_map=np.stack([v.frame_scale[f] * rr.grid_field(v.true_theta[f], W, H) for f in range(F)]),
-               params=v.frame_scale[:, None],
-               warp=np.zeros((F, H, W, 2), np.float32), source_depth=v.depth, width=np.int32(W), height=np.int32(H),
-               depth_desc=np.frombuffer(b"Grid(Scale, Linear, 4, 3, 1)", np.uint8))
-    ref = mk.reference_outputs(out, v)
+    live = np.load(os.path.join(os.path.dirname(rr.GOLDEN), "live_golden.npz"))
+    assert bc.input_digest(v).encode() == live["reproj/input_sha256"].tobytes(), "the seeded case drifted from the minted one"
+    out = mk.truth_outputs(v)
+    ref = {k: live["reproj/" + k] for k in ("ref_extrinsics", "ref_intrinsics")}
+    ref["target_pixel"] = rr.constraint_samples(v, out)[3]
+    ref["ref_reprojected"] = ref["target_pixel"] + live["reproj/ref_offset_from_target"].astype(np.float64)
+    assert len(live["reproj/ref_offset_from_target"]) == len(ref["target_pixel"])
     err = np.linalg.norm(ref["ref_reprojected"] - ref["target_pixel"], axis=1)
     assert err.max() < 1e-3, err.max()
     ext, intr = rr.numpy_update_poses(out)

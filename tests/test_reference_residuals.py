@@ -7,8 +7,8 @@ tests/reference_residuals.py for the conversions).  The HIP path's cost and grad
 against the same reference outputs with no oracle in between (GPU tests at the end).
 
 CPU only.  Always: against tests/golden/reference_py/residual_golden.npz (outputs of the real reference functions, minted by
-make_residual_golden.py next to it).  With /root/reference mounted: against the live functions, including
-ConsistencyLoss.geometry_consistency_loss itself.
+make_residual_golden.py next to it), and a second set of derivative rows against what the live functions returned for them
+(tests/golden/reference_py/live_golden.npz, make_live_golden.py).
 """
 import os
 
@@ -119,16 +119,28 @@ def test_oracle_depth_columns_match_the_committed_reference_differences(name):
     _check_depth_columns(name, v, p, pose, sr, sd, g[name + "/fd_depth"], g[name + "/fd_rows"])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference checkout not mounted")
 @pytest.mark.parametrize("name", sorted(rres.CASES))
 def test_oracle_residuals_match_the_live_reference_functions(name):
+    """Twice the derivative rows of the committed pin above: besides residual_golden.npz's every 8th constraint from the 0th,
+    every 8th from the 4th, whose central differences of the reference functions are committed in
+    tests/golden/reference_py/live_golden.npz (make_live_golden.py next to it); values and loss terms of every constraint."""
     v, p, pose, sr = rres.oracle_side(name)
-    ref = rres.reference_outputs(name)
-    _check(name, v, p, pose, sr, ref, np.arange(len(ref["pixel_diff"])))
+    g, live = _golden(), np.load(rres.LIVE_GOLDEN)
+    ref = {k: g[f"{name}/{k}"] for k in ("frames", "pixel_diff", "disparity_diff", "loss_reproj", "loss_disp")}
+    n = len(ref["pixel_diff"])
+    assert n == len(sr["frames"])
+    rows_a, rows_b = g[name + "/fd_rows"], live[f"res/{name}/rows"]
+    assert np.array_equal(rows_b, np.arange(4, n, 8)) and not np.intersect1d(rows_a, rows_b).size
+    rows = np.concatenate([rows_a, rows_b])
+    order = np.argsort(rows)
+    rows = rows[order]
+    ref["fd"] = np.concatenate([g[name + "/fd"], live[f"res/{name}/fd"].astype(np.float64)])[order]
+    ref["fd_depth"] = np.concatenate([g[name + "/fd_depth"], live[f"res/{name}/fd_depth"].astype(np.float64)])[order]
+    _check(name, v, p, pose, sr, ref, rows)
     from oracle import oracle as om
     _v, o, _p, _pose = rres.make_state(name)
     sd = om.static_residuals_depth(o, p, 0.1, pose)
-    _check_depth_columns(name, v, p, pose, sr, sd, ref["fd_depth"], np.arange(len(ref["pixel_diff"])))
+    _check_depth_columns(name, v, p, pose, sr, sd, ref["fd_depth"], rows)
 
 
 def test_the_pin_can_tell_a_wrong_convention():

@@ -9,7 +9,7 @@ for i in $(seq 1 $REPS); do
   tail -14 $OUT/t_all_$i.log | grep -v "$F"
 done
 [ -f $OUT/margins_1.jsonl ] && python tools/margin_report.py $OUT/margins_*.jsonl > $OUT/margins.log; head -12 $OUT/margins.log
-B="python bench.py --no-cpu-baseline --steps 20 --warmup 3"
+B="python bench.py --full --no-cpu-baseline --steps 20 --warmup 3"
 timeout 300 $B 2>> $OUT/bench.err | tee $OUT/b.json | python tools/bench_line.py
 python -c "
 import json; d=json.loads(open('$OUT/b.json').read().strip().splitlines()[-1]); print('secondary', d['secondary_1766_pairs']['value'], d['secondary_1766_pairs']['pcg_iterations_per_lm_iteration'])"

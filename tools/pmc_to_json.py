@@ -31,7 +31,7 @@ if dense:
     kernel, factor = "k_dense_walk<4", 1.0
     f, nf = avg(os.path.join(root, "pmc_FETCH_SIZE"), "FETCH_SIZE", kernel)
     w, nw = avg(os.path.join(root, "pmc_WRITE_SIZE"), "WRITE_SIZE", kernel)
-    bench_file, cmd_kernel, cmd_bench = "bench_dense_cfg.json", "k_dense_walk|k_dense_gg", "--dense --frames 300 --steps 2 --warmup 1 --no-cpu-baseline --no-secondary --no-kernel-timing"
+    bench_file, cmd_kernel, cmd_bench = "bench_dense_cfg.json", "k_dense_walk|k_dense_gg", "--full --dense --frames 300 --steps 2 --warmup 1 --no-cpu-baseline --no-secondary --no-kernel-timing"
     correction = ("MI355X_MICROARCH.md HBM section: the doubling of FETCH_SIZE applies to wide coalesced 16 B/lane streams (128 B requests "
                   "tallied at 64 B); this kernel requests 64 B lines (8 lanes x 8 B of flow per run), 32 B of source depth, 8 mask bytes and "
                   "scattered 4 B target depths: taken as is, as is WRITE_SIZE (both uncalibrated for these widths); Infinity-Cache hits are counted")
@@ -40,7 +40,7 @@ else:
     kernel, factor = "k_matvec_pairs_fast<4", 2.0  # (any workgroup-size instantiation)
     f, nf = avg(os.path.join(root, "pmc_fetch"), "FETCH_SIZE", kernel)
     w, nw = avg(os.path.join(root, "pmc_write"), "WRITE_SIZE", kernel)
-    bench_file, cmd_kernel, cmd_bench = "bench.json", "k_matvec_pairs_fast", "--steps 4 --warmup 1 --no-cpu-baseline --no-secondary --pcg-lockstep (lockstep: no early-exit launches in the average)"
+    bench_file, cmd_kernel, cmd_bench = "bench.json", "k_matvec_pairs_fast", "--full --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --pcg-lockstep (lockstep: no early-exit launches in the average)"
     correction = ("MI355X_MICROARCH.md HBM section: on gfx950 FETCH_SIZE counts a wide coalesced 16 B/lane stream at "
                   "half its bytes -> doubled; WRITE_SIZE uncalibrated, taken as is")
     files = [f"profiles/{tag}_pmc_FETCH_SIZE.csv", f"profiles/{tag}_pmc_WRITE_SIZE.csv"]

@@ -14,8 +14,8 @@ F="^RCCL\|^HIP\|^ROCm\|^Hostname\|^Librccl\|amdgpu.ids"
 bash $R/tools/pmc_refresh.sh $TAG > $OUT/pmc_refresh.log 2>&1
 mv $OUT/bench_full.json $OUT/bench.json
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --no-cpu-baseline --no-secondary"
-CMD_MAIN="python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --no-kernel-timing"
+B="python $R/bench.py --full --no-cpu-baseline --no-secondary"
+CMD_MAIN="python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --no-kernel-timing"
 $B --steps 20 --warmup 3 --time-all-kernels > $OUT/bench_allkernels.json 2>> $OUT/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $B --steps 20 --warmup 3 --no-kernel-timing > $OUT/trace.log 2>&1
 python $R/tools/lm_timeline.py $OUT/trace > $OUT/lm_timeline.txt 2>&1
@@ -24,13 +24,13 @@ python $R/tools/solve_timeline.py $OUT/trace 3 > $OUT/solve_timeline.txt 2>&1
 K="k_matvec_pairs_fast|k_pcg_tail|k_assemble_fast"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_LDS_BANK_CONFLICT --kernel-include-regex "$K" --output-format csv -d $OUT/pmc_sq_a -- $B --steps 4 --warmup 1 --pcg-lockstep > $OUT/pmc_sq_a.log 2>&1
 # BASELINE configs[4] (1000 frames 640x384, 16x12 grid), Cauchy and Huber; dense mode (configs[2] video, 300 frames)
-python $R/bench.py --config 4 --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > $OUT/bench_config4_cauchy.json 2>> $OUT/bench.err
-python $R/bench.py --config 4 --robust huber --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > $OUT/bench_config4_huber.json 2>> $OUT/bench.err
+python $R/bench.py --full --config 4 --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > $OUT/bench_config4_cauchy.json 2>> $OUT/bench.err
+python $R/bench.py --full --config 4 --robust huber --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > $OUT/bench_config4_huber.json 2>> $OUT/bench.err
 # dense mode: kernel trace, SQ counters and HBM traffic of the one-walk assembly (tools/dense_profile.sh writes into the same directory
 # and profiles/pmc_dense_walk.json, which the dense bench line below reads for roofline.traffic)
 bash $R/tools/dense_profile.sh $TAG 300 > $OUT/dense_profile.log 2>&1
-python $R/bench.py --dense --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --time-all-kernels > $OUT/bench_dense_300.json 2>> $OUT/bench.err
-python $R/bench.py --dense --steps 4 --warmup 1 --no-cpu-baseline --no-secondary > $OUT/bench_dense_300_plain.json 2>> $OUT/bench.err   # (only the hot kernel timed: the line's value without the event pairs around every class)
+python $R/bench.py --full --dense --steps 4 --warmup 1 --no-cpu-baseline --no-secondary --time-all-kernels > $OUT/bench_dense_300.json 2>> $OUT/bench.err
+python $R/bench.py --full --dense --steps 4 --warmup 1 --no-cpu-baseline --no-secondary > $OUT/bench_dense_300_plain.json 2>> $OUT/bench.err   # (only the hot kernel timed: the line's value without the event pairs around every class)
 # what one rank of an N-rank run computes per PCG iteration (pair-sharded, phantom communicator)
 timeout 300 python $R/tools/shard_sim.py 1 2 4 8 2>/dev/null | grep "^world" > $OUT/shard_sim.log
 timeout 400 python $R/tools/shard_sim.py 1 2 4 8 --dense 2>/dev/null | grep "^world" >> $OUT/shard_sim.log
