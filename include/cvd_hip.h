@@ -303,6 +303,23 @@ int32_t cvd_flow_guided_filter(cvd_handle* h, int32_t num_frames, int32_t first_
                                const float* flow_bwd, const uint8_t* mask_bwd, int32_t frame_radius,
                                int32_t spatial_radius, int32_t median, float* out, double* kernel_ms);
 
+/* DepthVideoProcessor::bilateralFilter (reference lib/Processor.cpp:183-313; Op::BilateralFilter, defaults
+ * lib/Processor.h:64-70: frame_radius 2, spatial_radius 0, depth_sigma 0.3, color_sigma 0).  The batch holds num_frames
+ * CONSECUTIVE frames; outputs are produced for batch frames [first_output, first_output + num_outputs), each from the window
+ * [k - frame_radius, k + frame_radius] x [y - r, y + r] x [x - r, x + r] clipped to the batch and the image (the caller builds
+ * the batch so that its ends are the video's ends or lie at least frame_radius away from every output).
+ *   depth [n][height][width]     DepthFrame::depth() of depth stream 0 (transformed depth)
+ *   color [n][height][width][3]  BGR f32 of the "down" colour stream; may be NULL when color_sigma <= 0
+ *   out   [num_outputs][height][width] filtered depth (weighted mean, or weighted median if median != 0)
+ * The median supports windows of up to 2048 samples per pixel ((2 spatial_radius + 1)^2 (2 min(frame_radius, n - 1) + 1));
+ * larger windows are rejected before any work.  f32 in the reference's operation order; expf is the device function
+ * (float tolerance on the mean, not bit-exact; the median returns one of the window's samples).  kernel_ms (may be NULL):
+ * kernel time, HIP events. */
+int32_t cvd_bilateral_filter(cvd_handle* h, int32_t num_frames, int32_t first_output, int32_t num_outputs, int32_t height,
+                             int32_t width, const float* depth, const float* color, int32_t frame_radius,
+                             int32_t spatial_radius, float depth_sigma, float color_sigma, int32_t median, float* out,
+                             double* kernel_ms);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

@@ -338,6 +338,26 @@ class Binding:
             _ptr(out, C.c_float), C.byref(ms) if timing else None))
         return (out, ms.value) if timing else out
 
+    def bilateral_filter(self, depth, color, frame_radius, spatial_radius=0, depth_sigma=0.3, color_sigma=0.0, median=False,
+                         first=0, count=None, timing=False):
+        """DepthVideoProcessor::bilateralFilter on a batch of consecutive frames (see include/cvd_hip.h): depth [n][h][w]
+        (transformed), color [n][h][w][3] BGR or None (only read when color_sigma > 0)."""
+        d = _f32(depth)
+        n, hh, w = d.shape
+        c = None
+        if color is not None:
+            c = _f32(color)
+            assert c.shape == (n, hh, w, 3), (c.shape, d.shape)
+        count = n - first if count is None else count
+        out = np.zeros((max(count, 0), hh, w), dtype=np.float32)
+        ms = C.c_double(0.0)
+        self._check(self._fn("bilateral_filter")(
+            self._h, C.c_int(n), C.c_int(first), C.c_int(count), C.c_int(hh), C.c_int(w), _ptr(d, C.c_float),
+            _ptr(c, C.c_float) if c is not None else None, C.c_int(frame_radius), C.c_int(spatial_radius),
+            C.c_float(depth_sigma), C.c_float(color_sigma), C.c_int(int(median)), _ptr(out, C.c_float),
+            C.byref(ms) if timing else None))
+        return (out, ms.value) if timing else out
+
     def _grid_vertices(self):
         d = self.xform_desc(False)
         if int(d.depth_type) == 3:  # Grid

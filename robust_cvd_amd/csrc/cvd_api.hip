@@ -710,6 +710,12 @@ int32_t cvd_flow_guided_filter(cvd_handle* h, int32_t numFrames, int32_t firstOu
   CVD_TRY(h, flowGuidedFilter(h, numFrames, firstOutput, numOutputs, width, height, depthWidth, depthHeight, invAspect, depth,
                               cameras, flowFwd, maskFwd, flowBwd, maskBwd, frameRadius, spatialRadius, median, out, kernelMs));
 }
+int32_t cvd_bilateral_filter(cvd_handle* h, int32_t numFrames, int32_t firstOutput, int32_t numOutputs, int32_t height,
+                             int32_t width, const float* depth, const float* color, int32_t frameRadius, int32_t spatialRadius,
+                             float depthSigma, float colorSigma, int32_t median, float* out, double* kernelMs) {
+  CVD_TRY(h, bilateralFilter(h, numFrames, firstOutput, numOutputs, width, height, depth, color, frameRadius, spatialRadius,
+                             depthSigma, colorSigma, median, out, kernelMs));
+}
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {

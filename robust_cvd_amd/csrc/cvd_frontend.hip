@@ -1,4 +1,5 @@
-// cvd_frontend.hip -- the steps either side of the solve: constraint sampling, image operators, dense consumers, flow-guided filter.
+// cvd_frontend.hip -- the steps either side of the solve: constraint sampling, image operators, dense consumers, flow-guided and
+// bilateral filters.
 #include "cvd_host.h"
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -267,6 +268,87 @@ void flowGuidedFilter(cvd_handle* h, int n, int first, int count, int w, int hh,
   HIP_CHECK(hipGetLastError());
   if (kernelMs) HIP_CHECK(hipEventRecord(e1, s));
   if (out) HIP_CHECK(hipMemcpyAsync(out, h->dFltOut.p, px * count * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (kernelMs) {
+    float ms = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    *kernelMs = ms;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+  }
+}
+
+// DepthVideoProcessor::bilateralFilter (reference lib/Processor.cpp:183-313) on a batch of consecutive frames, cvd_bilateral.h
+void bilateralFilter(cvd_handle* h, int n, int first, int count, int w, int hh, const float* depth, const float* color,
+                     int frameRadius, int spatialRadius, float depthSigma, float colorSigma, int median, float* out,
+                     double* kernelMs) {
+  if (n < 1 || first < 0 || count < 0 || first + count > n) throw std::runtime_error("invalid frame batch");
+  if (w < 1 || hh < 1) throw std::runtime_error("invalid raster");
+  if (frameRadius < 0 || spatialRadius < 0) throw std::runtime_error("negative filter radius");
+  const bool useColor = colorSigma > 0.f;
+  if (!depth || (useColor && !color)) throw std::runtime_error("null filter input");
+  const size_t px = static_cast<size_t>(w) * hh;
+  if (px * n > (1ull << 31)) throw std::runtime_error("bilateral filter batch too large for one call");
+  // [kf - R, kf + R] clipped to [0, n) is the same window with R = min(R, n - 1): the sample counts below are exact
+  const int R = std::min(frameRadius, n - 1);
+  const long long side = 2ll * spatialRadius + 1, samples = side * side * (2ll * R + 1);
+  if (median && samples > kBilateralMaxSamples)
+    throw std::runtime_error(fmt("bilateral median filter: %lld samples per pixel ((2 spatialRadius + 1)^2 (2 frameRadius + 1)) "
+                                 "exceed the supported %d", samples, kBilateralMaxSamples));
+  if (count == 0) return;
+  hipStream_t s = h->stream;
+  h->dBilDepth.upload(depth, px * n, s);
+  if (useColor) h->dBilColor.upload(color, px * n * 3, s);
+  h->dBilOut.ensure(px * count);
+  BilateralArgs A;
+  A.n = n; A.w = w; A.h = hh; A.frameRadius = R; A.spatialRadius = spatialRadius;
+  A.useDepth = depthSigma > 0.f; A.useColor = useColor;
+  A.depthSigma2 = depthSigma * depthSigma; A.colorSigma2 = colorSigma * colorSigma;
+  A.depth = h->dBilDepth.p; A.color = useColor ? h->dBilColor.p : nullptr;
+  const long long tileTexels = (kBilateralTileW + 2ll * spatialRadius) * (kBilateralTileH + 2ll * spatialRadius);
+  const size_t stageBytes = static_cast<size_t>(tileTexels) * (useColor ? 16 : 4);
+  const bool stage = spatialRadius > 0 && stageBytes <= kBilateralMaxLds;
+  int P2 = 128;
+  while (P2 < samples) P2 *= 2;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (kernelMs) { HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1)); HIP_CHECK(hipEventRecord(e0, s)); }
+  const dim3 tiles((w + kBilateralTileW - 1) / kBilateralTileW, (hh + kBilateralTileH - 1) / kBilateralTileH), block(256);
+  for (int c0 = 0; c0 < count; c0 += 65535) {  // (grid z limit)
+    const int nz = std::min(count - c0, 65535);
+    A.first = first + c0;
+    A.out = h->dBilOut.p + px * c0;
+    const dim3 grid(tiles.x, tiles.y, nz);
+    if (!median) {
+      if (stage && useColor) {
+        allowLds(k_bilateral_mean<true, true>, stageBytes);
+        hipLaunchKernelGGL((k_bilateral_mean<true, true>), grid, block, stageBytes, s, A);
+      } else if (stage) {
+        allowLds(k_bilateral_mean<false, true>, stageBytes);
+        hipLaunchKernelGGL((k_bilateral_mean<false, true>), grid, block, stageBytes, s, A);
+      }
+      else if (useColor) hipLaunchKernelGGL((k_bilateral_mean<true, false>), grid, block, 0, s, A);
+      else hipLaunchKernelGGL((k_bilateral_mean<false, false>), grid, block, 0, s, A);
+    } else if (samples <= 16) {
+      if (useColor) hipLaunchKernelGGL((k_bilateral_median_small<16, true>), grid, block, 0, s, A);
+      else hipLaunchKernelGGL((k_bilateral_median_small<16, false>), grid, block, 0, s, A);
+    } else if (samples <= 64) {
+      if (useColor) hipLaunchKernelGGL((k_bilateral_median_small<64, true>), grid, block, 0, s, A);
+      else hipLaunchKernelGGL((k_bilateral_median_small<64, false>), grid, block, 0, s, A);
+    } else {
+      const dim3 gridW(static_cast<unsigned>((px + 3) / 4), 1, nz);
+      const size_t lds = static_cast<size_t>(P2) * 2 * sizeof(float) * 4;  // <= 64 KB: P2 <= kBilateralMaxSamples
+      if (useColor) {
+        allowLds(k_bilateral_median_wave<true>, lds);
+        hipLaunchKernelGGL((k_bilateral_median_wave<true>), gridW, block, lds, s, A, P2);
+      } else {
+        allowLds(k_bilateral_median_wave<false>, lds);
+        hipLaunchKernelGGL((k_bilateral_median_wave<false>), gridW, block, lds, s, A, P2);
+      }
+    }
+    HIP_CHECK(hipGetLastError());
+  }
+  if (kernelMs) HIP_CHECK(hipEventRecord(e1, s));
+  if (out) HIP_CHECK(hipMemcpyAsync(out, h->dBilOut.p, px * count * sizeof(float), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   if (kernelMs) {
     float ms = 0.f;

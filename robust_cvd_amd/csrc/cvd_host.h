@@ -43,6 +43,7 @@
 #include "cvd_sampling.h"
 #include "cvd_imageops.h"
 #include "cvd_filter.h"
+#include "cvd_bilateral.h"
 
 
 namespace cvd {
@@ -306,6 +307,7 @@ struct cvd_handle_t {
   DevBuf<float> dFltDepth, dFltOut, dFltFlowF, dFltFlowB;  // cvd_filter.h staging
   DevBuf<unsigned char> dFltMaskF, dFltMaskB;
   DevBuf<FilterCam> dFltCams;
+  DevBuf<float> dBilDepth, dBilColor, dBilOut;  // cvd_bilateral.h staging
   // constraint sampling (cvd_sampling.h): result of the last cvd_sample_pair_constraints
   DevBuf<float2> dSampledLoc, dSampledTrip;  // 2 resp. 3 float2 per constraint
   std::vector<long long> sampledOff, sampledTripOff;
@@ -714,5 +716,8 @@ void touchModule_temporal();
 void flowGuidedFilter(cvd_handle* h, int n, int first, int count, int w, int hh, int dw, int dh, float invAspect, const float* depth,
                       const float* cameras, const float* flowF, const uint8_t* maskF, const float* flowB, const uint8_t* maskB,
                       int frameRadius, int spatialRadius, int median, float* out, double* kernelMs);
+void bilateralFilter(cvd_handle* h, int n, int first, int count, int w, int hh, const float* depth, const float* color,
+                     int frameRadius, int spatialRadius, float depthSigma, float colorSigma, int median, float* out,
+                     double* kernelMs);
 
 }  // namespace cvd
