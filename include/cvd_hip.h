@@ -320,6 +320,25 @@ int32_t cvd_bilateral_filter(cvd_handle* h, int32_t num_frames, int32_t first_ou
                              int32_t spatial_radius, float depth_sigma, float color_sigma, int32_t median, float* out,
                              double* kernel_ms);
 
+/* FlowConstraintsCollection::setStaticFlagFromRansac (the reference's pose_optimization.py:170-174 calls it for
+ * --opt.dynamic_constraints Ransac; its C++ never implemented the method: the definition is tests/epipolar_reference.py,
+ * DESIGN.md section 3.7).  Per directed pair p (constraints [offsets[p], offsets[p+1]), offsets[0] = 0) an epipolar RANSAC
+ * in f64: pixels = loc * pixel_scale (the width of the raster the constraints were sampled on), Hartley normalisation,
+ * `iterations` 8-point hypotheses drawn with splitmix64(seed << 44 | p << 24 | k << 8 | c), rank 2, inlier <=> both
+ * point-to-epipolar-line distances <= threshold_px, winner = most inliers (lowest k on ties), one least-squares refit over
+ * its inliers adopted when it keeps at least as many.  Bitwise deterministic.
+ *   loc             [C][4]  (loc0.xy, loc1.xy), C = offsets[num_pairs]; every value must be finite
+ *   is_static_out   [C]     1 = inlier of the pair's adopted F; a pair with fewer than 8 constraints, a zero spread or no valid
+ *                           hypothesis is all 1
+ *   fundamental_out [P][9]  adopted F (row-major, pixel coordinates, up to scale; 0 for an all-static pair); may be NULL
+ *   best_out        [P][2]  (winning k, inliers of the adopted F); (-1, -1) for an all-static pair; may be NULL
+ *   kernel_ms       [4]     {normalise, hypotheses, score, select} kernel time, HIP events; may be NULL
+ * Rejected before any work, with an error naming the argument: threshold_px <= 0 or non-finite, iterations outside
+ * [1, 65536], num_pairs >= 2^20, a non-finite loc, non-monotone offsets. */
+int32_t cvd_epipolar_static_flags(cvd_handle* h, int32_t num_pairs, const int64_t* offsets, const float* loc, double pixel_scale,
+                                  double threshold_px, int32_t iterations, uint64_t seed, uint8_t* is_static_out,
+                                  double* fundamental_out, int32_t* best_out, double* kernel_ms);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

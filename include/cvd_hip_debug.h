@@ -55,6 +55,11 @@ int32_t cvd_block_inverse_debug(cvd_handle* h, int32_t num_blocks, int32_t block
  * Any output pointer may be NULL. */
 /* Test hook: the dense SPD inverse of the dense coarse level (cvd_dense_inverse.h) on one n x n f64 matrix (row-major,
  * symmetric); inverse = n x n f64; failed = 1 on a non-positive pivot (inverse untouched), bit 30 = barrier timeout. */
+/* Parity hook of cvd_epipolar_static_flags: the same call, plus every hypothesis's inlier count counts_out [P][K] (-1: invalid
+ * hypothesis or all-static pair) and its denormalised F hypotheses_out [P][K][9] (0 when invalid); either may be NULL. */
+int32_t cvd_epipolar_debug(cvd_handle* h, int32_t num_pairs, const int64_t* offsets, const float* loc, double pixel_scale,
+                           double threshold_px, int32_t iterations, uint64_t seed, uint8_t* is_static_out,
+                           double* fundamental_out, int32_t* best_out, int32_t* counts_out, double* hypotheses_out);
 int32_t cvd_dense_inverse_debug(cvd_handle* h, int32_t n, const double* a, double* inverse, int32_t* failed);
 int32_t cvd_coarse_debug(cvd_handle* h, int32_t* num_unknowns, double* a_c, double* a_c_inverse, int32_t* failed);
 /* Test hook for the third level of the preconditioner (cvd_solver_options::temporal_level; state of its last build in the last

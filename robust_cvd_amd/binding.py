@@ -358,6 +358,36 @@ class Binding:
             C.byref(ms) if timing else None))
         return (out, ms.value) if timing else out
 
+    def _epipolar_args(self, offsets, loc, pixel_scale, threshold, iterations, seed):
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        lc = _f32(loc).reshape(-1, 4)
+        P = off.shape[0] - 1
+        flags = np.zeros(lc.shape[0], dtype=np.uint8)
+        F = np.zeros((max(P, 0), 3, 3), dtype=np.float64)
+        best = np.zeros((max(P, 0), 2), dtype=np.int32)
+        args = [self._h, C.c_int(P), _ptr(off, C.c_int64), _ptr(lc, C.c_float), C.c_double(pixel_scale),
+                C.c_double(threshold), C.c_int(iterations), C.c_uint64(int(seed) & ((1 << 64) - 1)), _ptr(flags, C.c_uint8),
+                _ptr(F, C.c_double), _ptr(best, C.c_int32)]
+        return P, flags, F, best, args
+
+    def epipolar_static_flags(self, offsets, loc, pixel_scale, threshold, iterations=1024, seed=0, timing=False):
+        """setStaticFlagFromRansac on a pair-constraint list (see include/cvd_hip.h cvd_epipolar_static_flags): offsets [P + 1],
+        loc [C, 4], pixel_scale = width of the sampling raster.  Returns (flags [C] uint8, F [P, 3, 3], best [P, 2]), plus the
+        per-phase kernel ms {normalise, hypotheses, score, select} when timing."""
+        P, flags, F, best, args = self._epipolar_args(offsets, loc, pixel_scale, threshold, iterations, seed)
+        ms = (C.c_double * 4)()
+        self._check(self._fn("epipolar_static_flags")(*args, ms if timing else None))
+        return (flags, F, best, list(ms)) if timing else (flags, F, best)
+
+    def epipolar_debug(self, offsets, loc, pixel_scale, threshold, iterations=1024, seed=0):
+        """Test hook (include/cvd_hip_debug.h cvd_epipolar_debug): (flags, F, best, counts [P, K], hypotheses [P, K, 3, 3])."""
+        P, flags, F, best, args = self._epipolar_args(offsets, loc, pixel_scale, threshold, iterations, seed)
+        K = max(int(iterations), 0)
+        counts = np.zeros((max(P, 0), K), dtype=np.int32)
+        hyp = np.zeros((max(P, 0), K, 3, 3), dtype=np.float64)
+        self._check(self._fn("epipolar_debug")(*args, _ptr(counts, C.c_int32), _ptr(hyp, C.c_double)))
+        return flags, F, best, counts, hyp
+
     def _grid_vertices(self):
         d = self.xform_desc(False)
         if int(d.depth_type) == 3:  # Grid

@@ -716,6 +716,12 @@ int32_t cvd_bilateral_filter(cvd_handle* h, int32_t numFrames, int32_t firstOutp
   CVD_TRY(h, bilateralFilter(h, numFrames, firstOutput, numOutputs, width, height, depth, color, frameRadius, spatialRadius,
                              depthSigma, colorSigma, median, out, kernelMs));
 }
+int32_t cvd_epipolar_static_flags(cvd_handle* h, int32_t num_pairs, const int64_t* offsets, const float* loc, double pixel_scale,
+                                  double threshold_px, int32_t iterations, uint64_t seed, uint8_t* is_static_out,
+                                  double* fundamental_out, int32_t* best_out, double* kernel_ms) {
+  CVD_TRY(h, epipolarStaticFlags(h, num_pairs, offsets, loc, pixel_scale, threshold_px, iterations, seed, is_static_out,
+                                 fundamental_out, best_out, kernel_ms, nullptr, nullptr));
+}
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {
@@ -803,6 +809,13 @@ int32_t cvd_block_inverse_debug(cvd_handle* h, int32_t num_blocks, int32_t block
     HIP_CHECK(hipStreamSynchronize(s));
     if (failed) *failed = fl;
   });
+}
+
+int32_t cvd_epipolar_debug(cvd_handle* h, int32_t num_pairs, const int64_t* offsets, const float* loc, double pixel_scale,
+                           double threshold_px, int32_t iterations, uint64_t seed, uint8_t* is_static_out,
+                           double* fundamental_out, int32_t* best_out, int32_t* counts_out, double* hypotheses_out) {
+  CVD_TRY(h, epipolarStaticFlags(h, num_pairs, offsets, loc, pixel_scale, threshold_px, iterations, seed, is_static_out,
+                                 fundamental_out, best_out, nullptr, counts_out, hypotheses_out));
 }
 
 int32_t cvd_dense_inverse_debug(cvd_handle* h, int32_t n, const double* a, double* inverse, int32_t* failed) {

@@ -1,5 +1,5 @@
-// cvd_frontend.hip -- the steps either side of the solve: constraint sampling, image operators, dense consumers, flow-guided and
-// bilateral filters.
+// cvd_frontend.hip -- the steps either side of the solve: constraint sampling, epipolar RANSAC flags, image operators, dense
+// consumers, flow-guided and bilateral filters.
 #include "cvd_host.h"
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -357,6 +357,96 @@ void bilateralFilter(cvd_handle* h, int n, int first, int count, int w, int hh, 
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
   }
+}
+
+// FlowConstraintsCollection::setStaticFlagFromRansac (no reference implementation; tests/epipolar_reference.py defines it):
+// cvd_epipolar.h's four kernels per batch of pairs.  The batch bounds the per-hypothesis buffers ([pairs][K][9] f64 + counts)
+// to ~512 MiB; the sampler key carries the global pair index, so batching does not change the result.  kernelMs (may be
+// NULL): {normalise, hypotheses, score, select} HIP-event times summed over the batches.  counts / hypotheses (test hook,
+// may be NULL): every hypothesis's inlier count [P][K] and F_pix [P][K][9].
+void epipolarStaticFlags(cvd_handle* h, int numPairs, const int64_t* offsets, const float* loc, double pixelScale,
+                         double thresholdPx, int iterations, uint64_t seed, uint8_t* isStatic, double* fundamental,
+                         int32_t* best, double* kernelMs, int32_t* counts, double* hypotheses) {
+  if (!(std::isfinite(thresholdPx) && thresholdPx > 0.0))
+    throw std::runtime_error(fmt("epipolar RANSAC: threshold_px must be finite and > 0 (got %g)", thresholdPx));
+  if (iterations < 1 || iterations > kEpiMaxIterations)
+    throw std::runtime_error(fmt("epipolar RANSAC: iterations must lie in [1, %d] (got %d)", kEpiMaxIterations, iterations));
+  if (numPairs < 0 || numPairs >= kEpiMaxPairs)
+    throw std::runtime_error(fmt("epipolar RANSAC: num_pairs must lie in [0, 2^20) (got %d)", numPairs));
+  if (!(std::isfinite(pixelScale) && pixelScale > 0.0))
+    throw std::runtime_error(fmt("epipolar RANSAC: pixel_scale must be finite and > 0 (got %g)", pixelScale));
+  if (numPairs > 0 && !offsets) throw std::runtime_error("epipolar RANSAC: null offsets");
+  if (kernelMs) std::fill(kernelMs, kernelMs + 4, 0.0);
+  if (numPairs == 0) return;
+  if (offsets[0] != 0) throw std::runtime_error("epipolar RANSAC: offsets[0] must be 0");
+  for (int p = 0; p < numPairs; ++p)
+    if (offsets[p + 1] < offsets[p]) throw std::runtime_error(fmt("epipolar RANSAC: offsets decrease at pair %d", p));
+  const long long C = offsets[numPairs];
+  if (C > 0 && (!loc || !isStatic)) throw std::runtime_error("epipolar RANSAC: null constraint locations or flags");
+  for (long long i = 0; i < 4 * C; ++i)
+    if (!std::isfinite(loc[i]))
+      throw std::runtime_error(fmt("epipolar RANSAC: non-finite constraint location (loc of constraint %lld)", i / 4));
+  const int K = iterations;
+  const size_t perPair = static_cast<size_t>(K) * (9 * sizeof(double) + sizeof(int));
+  const int batch = static_cast<int>(std::max<size_t>(1, std::min<size_t>(numPairs, (512ull << 20) / perPair)));
+  hipStream_t s = h->stream;
+  h->dEpiLoc.upload(reinterpret_cast<const float4*>(loc), static_cast<size_t>(C), s);
+  h->dEpiOff.upload(reinterpret_cast<const long long*>(offsets), static_cast<size_t>(numPairs) + 1, s);
+  h->dEpiNorm.ensure(batch);
+  h->dEpiF.ensure(static_cast<size_t>(batch) * K * 9);
+  h->dEpiCount.ensure(static_cast<size_t>(batch) * K);
+  h->dEpiFlags.ensure(static_cast<size_t>(C));
+  h->dEpiFbest.ensure(static_cast<size_t>(numPairs) * 9);
+  h->dEpiBest.ensure(static_cast<size_t>(numPairs) * 2);
+  hipEvent_t ev[5] = {};
+  if (kernelMs)
+    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+  EpiArgs A;
+  A.K = K;
+  A.seed = seed;
+  A.w = pixelScale;
+  A.thresh2 = thresholdPx * thresholdPx;
+  A.loc = h->dEpiLoc.p;
+  A.norm = h->dEpiNorm.p;
+  A.F = h->dEpiF.p;
+  A.count = h->dEpiCount.p;
+  A.flags = h->dEpiFlags.p;
+  for (int p0 = 0; p0 < numPairs; p0 += batch) {
+    const int np = std::min(batch, numPairs - p0);
+    A.numPairs = np;
+    A.pairBase = p0;
+    A.off = h->dEpiOff.p + p0;
+    A.Fbest = h->dEpiFbest.p + static_cast<size_t>(p0) * 9;
+    A.best = h->dEpiBest.p + static_cast<size_t>(p0) * 2;
+    if (kernelMs) HIP_CHECK(hipEventRecord(ev[0], s));
+    hipLaunchKernelGGL(k_epi_normalise, dim3(np), dim3(kEpiThreads), 0, s, A);
+    HIP_CHECK(hipGetLastError());
+    if (kernelMs) HIP_CHECK(hipEventRecord(ev[1], s));
+    hipLaunchKernelGGL(k_epi_hypotheses, dim3(np, (K + kEpiHypThreads - 1) / kEpiHypThreads), dim3(kEpiHypThreads), 0, s, A);
+    HIP_CHECK(hipGetLastError());
+    if (kernelMs) HIP_CHECK(hipEventRecord(ev[2], s));
+    hipLaunchKernelGGL(k_epi_score, dim3(np, (K + kEpiThreads - 1) / kEpiThreads), dim3(kEpiThreads), 0, s, A);
+    HIP_CHECK(hipGetLastError());
+    if (kernelMs) HIP_CHECK(hipEventRecord(ev[3], s));
+    hipLaunchKernelGGL(k_epi_select, dim3(np), dim3(kEpiThreads), 0, s, A);
+    HIP_CHECK(hipGetLastError());
+    if (kernelMs) HIP_CHECK(hipEventRecord(ev[4], s));
+    if (counts) h->dEpiCount.download(counts + static_cast<size_t>(p0) * K, static_cast<size_t>(np) * K, s);
+    if (hypotheses) h->dEpiF.download(hypotheses + static_cast<size_t>(p0) * K * 9, static_cast<size_t>(np) * K * 9, s);
+    if (kernelMs || counts || hypotheses) HIP_CHECK(hipStreamSynchronize(s));  // (the next batch reuses the buffers)
+    if (kernelMs)
+      for (int k = 0; k < 4; ++k) {
+        float ms = 0.f;
+        HIP_CHECK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+        kernelMs[k] += ms;
+      }
+  }
+  h->dEpiFlags.download(isStatic, static_cast<size_t>(C), s);
+  if (fundamental) h->dEpiFbest.download(fundamental, static_cast<size_t>(numPairs) * 9, s);
+  if (best) h->dEpiBest.download(best, static_cast<size_t>(numPairs) * 2, s);
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (kernelMs)
+    for (auto& e : ev) (void)hipEventDestroy(e);
 }
 
 // One kernel of this translation unit's code object is looked up at handle creation: the HIP runtime loads a unit's device

@@ -44,6 +44,7 @@
 #include "cvd_imageops.h"
 #include "cvd_filter.h"
 #include "cvd_bilateral.h"
+#include "cvd_epipolar.h"
 
 
 namespace cvd {
@@ -308,6 +309,13 @@ struct cvd_handle_t {
   DevBuf<unsigned char> dFltMaskF, dFltMaskB;
   DevBuf<FilterCam> dFltCams;
   DevBuf<float> dBilDepth, dBilColor, dBilOut;  // cvd_bilateral.h staging
+  // cvd_epipolar.h: constraints, offsets, per-pair normalisation, per-hypothesis F / counts (one batch of pairs), results
+  DevBuf<float4> dEpiLoc;
+  DevBuf<long long> dEpiOff;
+  DevBuf<EpiNorm> dEpiNorm;
+  DevBuf<double> dEpiF, dEpiFbest;
+  DevBuf<int> dEpiCount, dEpiBest;
+  DevBuf<unsigned char> dEpiFlags;
   // constraint sampling (cvd_sampling.h): result of the last cvd_sample_pair_constraints
   DevBuf<float2> dSampledLoc, dSampledTrip;  // 2 resp. 3 float2 per constraint
   std::vector<long long> sampledOff, sampledTripOff;
@@ -719,5 +727,8 @@ void flowGuidedFilter(cvd_handle* h, int n, int first, int count, int w, int hh,
 void bilateralFilter(cvd_handle* h, int n, int first, int count, int w, int hh, const float* depth, const float* color,
                      int frameRadius, int spatialRadius, float depthSigma, float colorSigma, int median, float* out,
                      double* kernelMs);
+void epipolarStaticFlags(cvd_handle* h, int numPairs, const int64_t* offsets, const float* loc, double pixelScale,
+                         double thresholdPx, int iterations, uint64_t seed, uint8_t* isStatic, double* fundamental,
+                         int32_t* best, double* kernelMs, int32_t* counts, double* hypotheses);
 
 }  // namespace cvd

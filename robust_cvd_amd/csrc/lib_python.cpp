@@ -1154,16 +1154,12 @@ struct FlowConstraintsCollection {
         kv.second.isStatic[i] = isFar(kv.first - 1, c[0], c[1]) && isFar(kv.first, c[2], c[3]) && isFar(kv.first + 1, c[4], c[5]);
       }
   }
-  // reference lib/FlowConstraints.cpp:662-748: every NON-static pair constraint stamps a disk of radius `distance` around
-  // its end point into the mask of that end point's frame; afterwards every pair / triplet constraint with an end point on
-  // a stamped pixel becomes non-static as well.  Pixel = int(loc * w) for both coordinates (:696-697: loc.y is scaled by
-  // invAspect, so `* w` lands on the row); raster = the "down" colour stream.  The reference's std::map iteration order
-  // is irrelevant: the masks are complete before the second pass.  Host loop over a host container, as in the reference.
-  void pruneStaticFlag(int distance) {
-    if (distance < 0) throw std::runtime_error("pruneStaticFlag: negative distance");
+  // raster of the "down" colour stream, the one the constraints were sampled on
+  void downRaster(const char* who, int& w, int& h) const {
     if (!video_->hasColorStream("down")) throw std::runtime_error("Color stream 'down' does not exist.");
     const ColorStream& down = *video_->colorStreams_[video_->colorStreamIndex("down")];
-    int w = down.width_, h = down.height_;
+    w = down.width_;
+    h = down.height_;
     if (w <= 0 || h <= 0) {
       // stream created without an explicit size: the reference's ColorStream takes it from its first image
       std::ifstream is(down.path_ + "/frame_" + fmtInt6(0) + down.extension_, std::ios::binary);
@@ -1175,7 +1171,17 @@ struct FlowConstraintsCollection {
         h = video_->height_;
       }
     }
-    if (w <= 0 || h <= 0) throw std::runtime_error("pruneStaticFlag: the 'down' colour stream has no size");
+    if (w <= 0 || h <= 0) throw std::runtime_error(std::string(who) + ": the 'down' colour stream has no size");
+  }
+  // reference lib/FlowConstraints.cpp:662-748: every NON-static pair constraint stamps a disk of radius `distance` around
+  // its end point into the mask of that end point's frame; afterwards every pair / triplet constraint with an end point on
+  // a stamped pixel becomes non-static as well.  Pixel = int(loc * w) for both coordinates (:696-697: loc.y is scaled by
+  // invAspect, so `* w` lands on the row); raster = the "down" colour stream.  The reference's std::map iteration order
+  // is irrelevant: the masks are complete before the second pass.  Host loop over a host container, as in the reference.
+  void pruneStaticFlag(int distance) {
+    if (distance < 0) throw std::runtime_error("pruneStaticFlag: negative distance");
+    int w, h;
+    downRaster("pruneStaticFlag", w, h);
     const int F = video_->numFrames();
     std::vector<std::vector<uint8_t>> masks(F);
     auto maskOf = [&](int f) -> std::vector<uint8_t>& {
@@ -1216,6 +1222,35 @@ struct FlowConstraintsCollection {
         const auto& c = kv.second.loc[i];
         if (hit(kv.first - 1, c[0], c[1]) || hit(kv.first, c[2], c[3]) || hit(kv.first + 1, c[4], c[5])) kv.second.isStatic[i] = 0;
       }
+  }
+  // opt.dynamic_constraints == "Ransac" (reference pose_optimization.py:170-174; the reference's C++ never implemented it):
+  // every pair's flags from an epipolar RANSAC on its own correspondences, cvd_epipolar_static_flags (definition:
+  // tests/epipolar_reference.py).  Pixels = loc * width of the "down" raster (loc.y carries invAspect / h = 1 / w, so `* w`
+  // lands on the row, as in pruneStaticFlag).  Pair flags are overwritten and triplet flags reset to static, as
+  // setStaticFlagFromDynamicMask overwrites them.  iterations / seed are extensions (defaults 1024, 0).
+  void setStaticFlagFromRansac(double thresh, int iterations, uint64_t seed) {
+    int w, h;
+    downRaster("setStaticFlagFromRansac", w, h);
+    std::vector<int64_t> off(1, 0);
+    for (auto& kv : pairs_) off.push_back(off.back() + static_cast<int64_t>(kv.second.loc.size()));
+    std::vector<float> loc(static_cast<size_t>(off.back()) * 4);
+    std::vector<uint8_t> flags(static_cast<size_t>(off.back()), 1);
+    {
+      size_t k = 0;
+      for (auto& kv : pairs_) {
+        if (!kv.second.loc.empty()) std::memcpy(loc.data() + static_cast<size_t>(off[k]) * 4, kv.second.loc.data(), kv.second.loc.size() * 16);
+        ++k;
+      }
+    }
+    Device dev(device_);
+    dev.check(cvd_epipolar_static_flags(dev.h, static_cast<int32_t>(pairs_.size()), off.data(), loc.data(), static_cast<double>(w),
+                                        thresh, iterations, seed, flags.data(), nullptr, nullptr, nullptr));
+    size_t k = 0;
+    for (auto& kv : pairs_) {
+      kv.second.isStatic.assign(flags.begin() + off[k], flags.begin() + off[k + 1]);
+      ++k;
+    }
+    for (auto& kv : triplets_) std::fill(kv.second.isStatic.begin(), kv.second.isStatic.end(), 1);
   }
   // extension: explicit flags (what setStaticFlagFromDynamicMask would compute), per pair in map order
   void setStaticFlags(int a, int b, const std::vector<uint8_t>& flags) {
@@ -1888,6 +1923,8 @@ PYBIND11_MODULE(lib_python, m) {
       .def("resetStaticFlag", &FlowConstraintsCollection::resetStaticFlag)
       .def("setStaticFlagFromDynamicMask", &FlowConstraintsCollection::setStaticFlagFromDynamicMask)
       .def("pruneStaticFlag", &FlowConstraintsCollection::pruneStaticFlag)
+      .def("setStaticFlagFromRansac", &FlowConstraintsCollection::setStaticFlagFromRansac, py::arg("thresh"),
+           py::arg("iterations") = 1024, py::arg("seed") = 0, py::call_guard<py::gil_scoped_release>())
       .def("setStaticFlags", &FlowConstraintsCollection::setStaticFlags)
       // extensions (test access): the isStatic flags and the (loc0.xy, loc1.xy) rows of one pair
       .def("staticFlags", [](const FlowConstraintsCollection& c, int a, int b) { return c.pairs_.at({a, b}).isStatic; })
