@@ -339,6 +339,30 @@ int32_t cvd_epipolar_static_flags(cvd_handle* h, int32_t num_pairs, const int64_
                                   double threshold_px, int32_t iterations, uint64_t seed, uint8_t* is_static_out,
                                   double* fundamental_out, int32_t* best_out, double* kernel_ms);
 
+/* ---- feature tracks: DepthVideoProcessor::computeTracks, reference lib/Processor.cpp:646-886 ----------
+ * Independent of cvd_set_video.  Host inputs, images of height x width (the "down" colour stream's size):
+ *   frame_active [F]          nonzero: the frame lies in frameRange and its colour image exists (others are skipped)
+ *   first_frame, last_frame   frameRange.firstFrame() / lastFrame(): continue only when f > first, spawn only when f < last
+ *   corner [F][H][W]          cornerMinEigenVal response of every active frame (cvd_corner_min_eigenval)
+ *   dyn_dist [F][dyn_h][dyn_w] distance to the nearest dynamic pixel (cvd_dynamic_distance) or NULL (no dynamic_mask stream)
+ *   flow [F-1][H][W][2], flow_mask [F-1][H][W], pair_present [F-1]: pair f -> f+1, bit 0 = its flow exists (right size),
+ *                             bit 1 = its mask exists; flow / flow_mask may be NULL when no pair has the bit
+ *   spawn_distance, prune_distance, min_dynamic_distance, min_track_length: DvpParams' track* fields and minDynamicDistance
+ * counts[3] receives {tracks created (ids 0 .. n-1), tracks kept (length >= min_track_length), their observations}; the table
+ * stays on the device until cvd_get_tracks.  kernel_ms[4] (may be NULL): {candidates, sort, walk, table} HIP-event times.
+ * Spawn candidates are ranked by descending corner response, ties by ascending pixel index (unspecified in the reference).
+ * Rejected before any work, with an error naming the value: a bad size or frame range, a negative or > 16384 distance, null
+ * inputs, images whose two LDS bitmasks exceed the LDS budget ("image too large"). */
+int32_t cvd_compute_tracks(cvd_handle* h, int32_t num_frames, int32_t height, int32_t width, float inv_aspect,
+                           const uint8_t* frame_active, int32_t first_frame, int32_t last_frame, const float* corner,
+                           const float* dyn_dist, int32_t dyn_h, int32_t dyn_w, const float* flow, const uint8_t* flow_mask,
+                           const uint8_t* pair_present, int32_t spawn_distance, int32_t prune_distance,
+                           float min_dynamic_distance, int32_t min_track_length, int64_t* counts, double* kernel_ms);
+/* The table of the last cvd_compute_tracks: per track id start_frame[n], length[n] and kept[n] (0: deleted by the length
+ * pruning, an id hole), and loc[counts[2]][2] = the kept tracks' observations (x / w, y / h * invAspect), track by track in
+ * id order, frame by frame inside a track.  Any pointer may be NULL. */
+int32_t cvd_get_tracks(cvd_handle* h, int32_t* start_frame, int32_t* length, uint8_t* kept, float* loc);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

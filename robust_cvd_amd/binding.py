@@ -388,6 +388,54 @@ class Binding:
         self._check(self._fn("epipolar_debug")(*args, _ptr(counts, C.c_int32), _ptr(hyp, C.c_double)))
         return flags, F, best, counts, hyp
 
+    def compute_tracks(self, corner, inv_aspect, active, first, last, flow=None, mask=None, pair_present=None, dyn_dist=None,
+                       spawn_distance=20, prune_distance=5, min_dynamic_distance=3, min_track_length=4, timing=False):
+        """DepthVideoProcessor::computeTracks (see include/cvd_hip.h cvd_compute_tracks): corner [F, H, W], active [F],
+        flow [F-1, H, W, 2] / mask [F-1, H, W] of the pairs f -> f+1 with pair_present [F-1] (bit 0 flow, bit 1 mask),
+        dyn_dist [F, dh, dw] or None.  Returns (start [n] int32, length [n] int32, kept [n] bool, offsets [n + 1] int64 into
+        loc, loc [m, 2] float32): the kept tracks' observations in id order; a deleted track has no locations.  Plus the
+        per-phase kernel ms {candidates, sort, walk, table} when timing."""
+        co = _f32(corner)
+        assert co.ndim == 3, co.shape
+        F, H, W = co.shape
+        act = np.ascontiguousarray(active, dtype=np.uint8).reshape(F)
+        npairs = max(F - 1, 0)
+        pp = np.zeros(max(npairs, 1), np.uint8)
+        if pair_present is not None:
+            pp[:npairs] = np.asarray(pair_present, dtype=np.uint8).reshape(npairs)
+        fl = mk = None
+        if flow is not None:
+            fl = _f32(flow)
+            assert fl.shape == (npairs, H, W, 2), fl.shape
+        if mask is not None:
+            mk = np.ascontiguousarray(mask, dtype=np.uint8)
+            assert mk.shape == (npairs, H, W), mk.shape
+        dd, dh, dw = None, 0, 0
+        if dyn_dist is not None:
+            dd = _f32(dyn_dist)
+            assert dd.ndim == 3 and dd.shape[0] == F, dd.shape
+            dh, dw = dd.shape[1], dd.shape[2]
+        counts = np.zeros(3, np.int64)
+        ms = (C.c_double * 4)()
+        self._check(self._fn("compute_tracks")(
+            self._h, C.c_int(F), C.c_int(H), C.c_int(W), C.c_float(inv_aspect), _ptr(act, C.c_uint8), C.c_int(first),
+            C.c_int(last), _ptr(co, C.c_float), _ptr(dd, C.c_float) if dd is not None else None, C.c_int(dh), C.c_int(dw),
+            _ptr(fl, C.c_float) if fl is not None else None, _ptr(mk, C.c_uint8) if mk is not None else None,
+            _ptr(pp, C.c_uint8), C.c_int(spawn_distance), C.c_int(prune_distance), C.c_float(min_dynamic_distance),
+            C.c_int(min_track_length), _ptr(counts, C.c_int64), ms if timing else None))
+        n, m = int(counts[0]), int(counts[2])
+        start = np.zeros(max(n, 1), np.int32)
+        length = np.zeros(max(n, 1), np.int32)
+        kept = np.zeros(max(n, 1), np.uint8)
+        loc = np.zeros((max(m, 1), 2), np.float32)
+        self._check(self._fn("get_tracks")(self._h, _ptr(start, C.c_int32), _ptr(length, C.c_int32), _ptr(kept, C.c_uint8),
+                                           _ptr(loc, C.c_float)))
+        start, length, kept, loc = start[:n], length[:n], kept[:n].astype(bool), loc[:m]
+        off = np.zeros(n + 1, np.int64)
+        off[1:] = np.cumsum(np.where(kept, length, 0))
+        out = (start, length, kept, off, loc)
+        return out + (list(ms),) if timing else out
+
     def _grid_vertices(self):
         d = self.xform_desc(False)
         if int(d.depth_type) == 3:  # Grid

@@ -722,6 +722,18 @@ int32_t cvd_epipolar_static_flags(cvd_handle* h, int32_t num_pairs, const int64_
   CVD_TRY(h, epipolarStaticFlags(h, num_pairs, offsets, loc, pixel_scale, threshold_px, iterations, seed, is_static_out,
                                  fundamental_out, best_out, kernel_ms, nullptr, nullptr));
 }
+int32_t cvd_compute_tracks(cvd_handle* h, int32_t num_frames, int32_t height, int32_t width, float inv_aspect,
+                           const uint8_t* frame_active, int32_t first_frame, int32_t last_frame, const float* corner,
+                           const float* dyn_dist, int32_t dyn_h, int32_t dyn_w, const float* flow, const uint8_t* flow_mask,
+                           const uint8_t* pair_present, int32_t spawn_distance, int32_t prune_distance,
+                           float min_dynamic_distance, int32_t min_track_length, int64_t* counts, double* kernel_ms) {
+  CVD_TRY(h, computeTracks(h, num_frames, height, width, inv_aspect, frame_active, first_frame, last_frame, corner, dyn_dist,
+                           dyn_h, dyn_w, flow, flow_mask, pair_present, spawn_distance, prune_distance, min_dynamic_distance,
+                           min_track_length, counts, kernel_ms));
+}
+int32_t cvd_get_tracks(cvd_handle* h, int32_t* start_frame, int32_t* length, uint8_t* kept, float* loc) {
+  CVD_TRY(h, getTracks(h, start_frame, length, kept, loc));
+}
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {

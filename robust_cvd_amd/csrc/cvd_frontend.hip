@@ -1,6 +1,7 @@
 // cvd_frontend.hip -- the steps either side of the solve: constraint sampling, epipolar RANSAC flags, image operators, dense
 // consumers, flow-guided and bilateral filters.
 #include "cvd_host.h"
+#include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 namespace cvd {
@@ -447,6 +448,215 @@ void epipolarStaticFlags(cvd_handle* h, int numPairs, const int64_t* offsets, co
   HIP_CHECK(hipStreamSynchronize(s));
   if (kernelMs)
     for (auto& e : ev) (void)hipEventDestroy(e);
+}
+
+// DepthVideoProcessor::computeTracks (reference lib/Processor.cpp:646-886), cvd_tracks.h.  Batches of frames bound the
+// candidate keys (2 x 8 B per pixel) to ~1 GiB; each batch is candidates -> segmented sort -> walk.  The walk stops before a
+// frame whose worst case does not fit the observation / track buffers; they are doubled and the walk resumes there.
+// kernelMs (may be NULL): {candidates, sort, walk, table} HIP-event times summed over the batches.
+void computeTracks(cvd_handle* h, int F, int H, int W, float invAspect, const uint8_t* active, int first, int last,
+                   const float* corner, const float* dyn, int dh, int dw, const float* flow, const uint8_t* mask,
+                   const uint8_t* pairPresent, int spawnDistance, int pruneDistance, float minDynamicDistance,
+                   int minTrackLength, int64_t* counts, double* kernelMs) {
+  if (F < 1) throw std::runtime_error(fmt("compute tracks: num_frames must be >= 1 (got %d)", F));
+  if (W < 1 || H < 1) throw std::runtime_error(fmt("compute tracks: invalid image size %d x %d", W, H));
+  if (!(std::isfinite(invAspect) && invAspect > 0.f))
+    throw std::runtime_error(fmt("compute tracks: inv_aspect must be finite and > 0 (got %g)", static_cast<double>(invAspect)));
+  if (first < 0 || last >= F || first > last)
+    throw std::runtime_error(fmt("compute tracks: frame range [%d, %d] outside [0, %d)", first, last, F));
+  constexpr int kMaxRadius = 1 << 14;
+  if (spawnDistance < 0 || spawnDistance > kMaxRadius)
+    throw std::runtime_error(fmt("compute tracks: trackSpawnDistance must lie in [0, %d] (got %d)", kMaxRadius, spawnDistance));
+  if (pruneDistance < 0 || pruneDistance > kMaxRadius)
+    throw std::runtime_error(fmt("compute tracks: trackPruneDistance must lie in [0, %d] (got %d)", kMaxRadius, pruneDistance));
+  if (!std::isfinite(minDynamicDistance))
+    throw std::runtime_error("compute tracks: minDynamicDistance must be finite");
+  if (!active || !corner || !counts) throw std::runtime_error("compute tracks: null frame flags, corner input or counts");
+  if (dyn && (dw < 1 || dh < 1)) throw std::runtime_error(fmt("compute tracks: invalid dynamic distance size %d x %d", dw, dh));
+  bool anyFlow = false, anyMask = false;
+  for (int p = 0; p + 1 < F && pairPresent; ++p) {
+    anyFlow |= (pairPresent[p] & 1) != 0;
+    anyMask |= (pairPresent[p] & 2) != 0;
+  }
+  if (F > 1 && !pairPresent) throw std::runtime_error("compute tracks: null pair flags");
+  if ((anyFlow && !flow) || (anyMask && !mask)) throw std::runtime_error("compute tracks: a present pair has a null flow or mask");
+  const size_t npx = static_cast<size_t>(W) * H;
+  if (npx * F >= (size_t(1) << 31)) throw std::runtime_error(fmt("compute tracks: %d frames of %d x %d exceed 2^31 pixels per call", F, W, H));
+  const size_t maskBytes = 2 * ((npx + 31) / 32) * sizeof(unsigned int);
+  if (maskBytes + sizeof(TrackShared) > kMaxLds)
+    throw std::runtime_error(fmt("compute tracks: image too large: the prune and spawn bitmasks of a %d x %d image need %zu B of "
+                                 "LDS (> %zu)", W, H, maskBytes, kMaxLds - sizeof(TrackShared)));
+  hipStream_t s = h->stream;
+  DevBuf<unsigned char> dActive, dPair, dMask, dTmp;
+  DevBuf<float> dCorner, dDyn;
+  DevBuf<float2> dFlow;
+  DevBuf<unsigned long long> dKeys, dKeysOut;
+  DevBuf<unsigned int> dNValid, dSeg;
+  DevBuf<int> dFrameStart, dFrameCount, dObsTrack;
+  DevBuf<float2> dObsLoc;
+  DevBuf<TrackState> dState;
+  std::vector<unsigned char> pairs(std::max(F - 1, 1), 0);
+  if (pairPresent) std::copy(pairPresent, pairPresent + (F - 1), pairs.begin());
+  dActive.upload(active, F, s);
+  dPair.upload(pairs.data(), pairs.size(), s);
+  dCorner.upload(corner, static_cast<size_t>(F) * npx, s);
+  if (dyn) dDyn.upload(dyn, static_cast<size_t>(F) * dw * dh, s);
+  if (anyFlow) dFlow.upload(reinterpret_cast<const float2*>(flow), static_cast<size_t>(F - 1) * npx, s);
+  if (anyMask) dMask.upload(mask, static_cast<size_t>(F - 1) * npx, s);
+  dFlow.ensure(1);
+  dMask.ensure(1);
+  TrackArgs A{F, W, H, invAspect, first, last, spawnDistance, pruneDistance, minDynamicDistance, dActive.p, dPair.p,
+              dCorner.p, dyn ? dDyn.p : nullptr, dyn ? dw : W, dyn ? dh : H, dFlow.p, dMask.p};
+  const int PB = static_cast<int>(std::max<size_t>(1, std::min<size_t>(F, (size_t(1) << 30) / (npx * 16))));
+  dKeys.ensure(static_cast<size_t>(PB) * npx);
+  dKeysOut.ensure(static_cast<size_t>(PB) * npx);
+  dNValid.ensure(PB);
+  std::vector<unsigned int> seg(PB + 1);
+  for (int i = 0; i <= PB; ++i) seg[i] = static_cast<unsigned int>(static_cast<size_t>(i) * npx);
+  dSeg.upload(seg.data(), seg.size(), s);
+  size_t tmpBytes = 0;
+  HIP_CHECK(rocprim::segmented_radix_sort_keys_desc(nullptr, tmpBytes, dKeys.p, dKeysOut.p,
+                                                    static_cast<unsigned int>(static_cast<size_t>(PB) * npx),
+                                                    static_cast<unsigned int>(PB), dSeg.p, dSeg.p + 1, 0, 64, s));
+  dTmp.ensure(tmpBytes);
+  // observation / track buffers: the walk's worst case per frame is (continued + spawned) <= W H each; typical videos keep
+  // a few hundred tracks per frame, so these start small and grow on demand
+  dFrameStart.ensure(F);
+  dFrameCount.ensure(F);
+  int obsCap = static_cast<int>(std::min<size_t>(npx * 4, (size_t(1) << 31) - 1));
+  int trackCap = static_cast<int>(std::min<size_t>(npx * 2, (size_t(1) << 31) - 1));
+  dObsTrack.ensure(obsCap);
+  dObsLoc.ensure(obsCap);
+  h->dTrkStart.ensure(trackCap);
+  TrackState st{0, 0, 0, 0};
+  dState.upload(&st, 1, s);
+  const size_t walkLds = maskBytes;
+  allowLds(k_track_walk, walkLds + sizeof(TrackShared));
+  hipEvent_t ev[5] = {};
+  for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+  double ms[4] = {0, 0, 0, 0};
+  auto addTime = [&](int k) {
+    float t = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
+    ms[k] += t;
+  };
+  try {
+    for (int f0 = 0; f0 < F; f0 += PB) {
+      const int nb = std::min(PB, F - f0);
+      HIP_CHECK(hipEventRecord(ev[0], s));
+      HIP_CHECK(hipMemsetAsync(dNValid.p, 0, sizeof(unsigned int) * nb, s));
+      hipLaunchKernelGGL(k_track_candidates, dim3(static_cast<unsigned>((npx + 255) / 256), nb), dim3(256), 0, s, A, f0,
+                         dKeys.p, dNValid.p);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipEventRecord(ev[1], s));
+      size_t tb = tmpBytes;
+      HIP_CHECK(rocprim::segmented_radix_sort_keys_desc(dTmp.p, tb, dKeys.p, dKeysOut.p,
+                                                        static_cast<unsigned int>(static_cast<size_t>(nb) * npx),
+                                                        static_cast<unsigned int>(nb), dSeg.p, dSeg.p + 1, 0, 64, s));
+      HIP_CHECK(hipEventRecord(ev[2], s));
+      HIP_CHECK(hipEventSynchronize(ev[2]));
+      addTime(0);
+      addTime(1);
+      for (int fw = f0; fw < f0 + nb;) {
+        TrackBufs B{dFrameStart.p, dFrameCount.p, dObsTrack.p, dObsLoc.p, h->dTrkStart.p, obsCap, trackCap};
+        HIP_CHECK(hipEventRecord(ev[2], s));
+        hipLaunchKernelGGL(k_track_walk, dim3(1), dim3(kTrackThreads), walkLds, s, A, fw, f0 + nb,
+                           dKeysOut.p + static_cast<size_t>(fw - f0) * npx, dNValid.p + (fw - f0), B, dState.p);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(ev[3], s));
+        dState.download(&st, 1, s);
+        HIP_CHECK(hipStreamSynchronize(s));
+        addTime(2);
+        if (st.stopFrame < fw) throw std::runtime_error("compute tracks: the walk made no progress");
+        fw = st.stopFrame;
+        if (fw < f0 + nb) {  // grow the buffers (keeping their contents) and resume at that frame
+          const size_t maxCap = (size_t(1) << 31) - 1;
+          const size_t no = std::min(maxCap, std::max<size_t>(2 * static_cast<size_t>(obsCap), st.obsUsed + 2 * npx));
+          const size_t nt = std::min(maxCap, std::max<size_t>(2 * static_cast<size_t>(trackCap), st.numTracks + npx));
+          if (no == static_cast<size_t>(obsCap) && nt == static_cast<size_t>(trackCap))
+            throw std::runtime_error("compute tracks: observation buffer limit reached");
+          DevBuf<int> t1, t3;
+          DevBuf<float2> t2;
+          t1.ensure(no);
+          t2.ensure(no);
+          t3.ensure(nt);
+          HIP_CHECK(hipMemcpyAsync(t1.p, dObsTrack.p, sizeof(int) * st.obsUsed, hipMemcpyDeviceToDevice, s));
+          HIP_CHECK(hipMemcpyAsync(t2.p, dObsLoc.p, sizeof(float2) * st.obsUsed, hipMemcpyDeviceToDevice, s));
+          HIP_CHECK(hipMemcpyAsync(t3.p, h->dTrkStart.p, sizeof(int) * st.numTracks, hipMemcpyDeviceToDevice, s));
+          HIP_CHECK(hipStreamSynchronize(s));
+          std::swap(t1.p, dObsTrack.p); std::swap(t1.n, dObsTrack.n);
+          std::swap(t2.p, dObsLoc.p); std::swap(t2.n, dObsLoc.n);
+          std::swap(t3.p, h->dTrkStart.p); std::swap(t3.n, h->dTrkStart.n);
+          obsCap = static_cast<int>(no);
+          trackCap = static_cast<int>(nt);
+        }
+      }
+    }
+    // the table: lengths, minTrackLength pruning, per-track location lists
+    const int T = st.numTracks, O = st.obsUsed;
+    h->dTrkLen.ensure(T);
+    h->dTrkKeptLen.ensure(static_cast<size_t>(T) + 1);
+    h->dTrkOff.ensure(static_cast<size_t>(T) + 1);
+    h->dTrkKept.ensure(T);
+    HIP_CHECK(hipEventRecord(ev[3], s));
+    long long keptObs = 0;
+    if (T > 0) {
+      HIP_CHECK(hipMemsetAsync(h->dTrkLen.p, 0, sizeof(int) * T, s));
+      HIP_CHECK(hipMemsetAsync(h->dTrkKeptLen.p + T, 0, sizeof(int), s));  // (the scan's last item: offset[T] = the total)
+      hipLaunchKernelGGL(k_track_lengths, dim3((O + 255) / 256), dim3(256), 0, s, O, dObsTrack.p, h->dTrkLen.p);
+      hipLaunchKernelGGL(k_track_keep, dim3((T + 255) / 256), dim3(256), 0, s, T, minTrackLength, h->dTrkLen.p,
+                         h->dTrkKeptLen.p, h->dTrkKept.p);
+      HIP_CHECK(hipGetLastError());
+      size_t scanBytes = 0;
+      HIP_CHECK(rocprim::exclusive_scan(nullptr, scanBytes, h->dTrkKeptLen.p, h->dTrkOff.p, 0, static_cast<size_t>(T) + 1,
+                                        rocprim::plus<int>(), s));
+      DevBuf<unsigned char> scanTmp;
+      scanTmp.ensure(scanBytes);
+      HIP_CHECK(rocprim::exclusive_scan(scanTmp.p, scanBytes, h->dTrkKeptLen.p, h->dTrkOff.p, 0, static_cast<size_t>(T) + 1,
+                                        rocprim::plus<int>(), s));
+      int total = 0;
+      HIP_CHECK(hipMemcpyAsync(&total, h->dTrkOff.p + T, sizeof(int), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      keptObs = total;
+      h->dTrkLoc.ensure(static_cast<size_t>(std::max(total, 1)));
+      hipLaunchKernelGGL(k_track_scatter, dim3(16, F), dim3(256), 0, s, dFrameStart.p, dFrameCount.p, dObsTrack.p, dObsLoc.p,
+                         h->dTrkStart.p, h->dTrkKept.p, h->dTrkOff.p, h->dTrkLoc.p);
+      HIP_CHECK(hipGetLastError());
+    }
+    HIP_CHECK(hipEventRecord(ev[4], s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    addTime(3);
+    h->trkTracks = T;
+    h->trkKeptObs = keptObs;
+    long long kept = 0;
+    if (T > 0) {
+      std::vector<unsigned char> k(T);
+      h->dTrkKept.download(k.data(), T, s);
+      HIP_CHECK(hipStreamSynchronize(s));
+      for (unsigned char v : k) kept += v;
+    }
+    counts[0] = T;
+    counts[1] = kept;
+    counts[2] = keptObs;
+  } catch (...) {
+    for (auto& e : ev) (void)hipEventDestroy(e);
+    h->trkTracks = h->trkKeptObs = 0;
+    throw;
+  }
+  for (auto& e : ev) (void)hipEventDestroy(e);
+  if (kernelMs) std::copy(ms, ms + 4, kernelMs);
+}
+
+void getTracks(cvd_handle* h, int32_t* startFrame, int32_t* length, uint8_t* kept, float* loc) {
+  hipStream_t s = h->stream;
+  const size_t T = static_cast<size_t>(h->trkTracks);
+  if (T > 0) {
+    if (startFrame) h->dTrkStart.download(startFrame, T, s);
+    if (length) h->dTrkLen.download(length, T, s);
+    if (kept) h->dTrkKept.download(kept, T, s);
+  }
+  if (loc && h->trkKeptObs > 0) h->dTrkLoc.download(reinterpret_cast<float2*>(loc), static_cast<size_t>(h->trkKeptObs), s);
+  HIP_CHECK(hipStreamSynchronize(s));
 }
 
 // One kernel of this translation unit's code object is looked up at handle creation: the HIP runtime loads a unit's device

@@ -45,6 +45,7 @@
 #include "cvd_filter.h"
 #include "cvd_bilateral.h"
 #include "cvd_epipolar.h"
+#include "cvd_tracks.h"
 
 
 namespace cvd {
@@ -319,6 +320,11 @@ struct cvd_handle_t {
   // constraint sampling (cvd_sampling.h): result of the last cvd_sample_pair_constraints
   DevBuf<float2> dSampledLoc, dSampledTrip;  // 2 resp. 3 float2 per constraint
   std::vector<long long> sampledOff, sampledTripOff;
+  // feature tracks (cvd_tracks.h): the table of the last cvd_compute_tracks
+  DevBuf<int> dTrkStart, dTrkLen, dTrkKeptLen, dTrkOff;
+  DevBuf<unsigned char> dTrkKept;
+  DevBuf<float2> dTrkLoc;
+  long long trkTracks = 0, trkKeptObs = 0;
 
   // coarse (pose-graph) level of the two-level preconditioner (cvd_coarse.h)
   struct CoarseHost {
@@ -730,5 +736,10 @@ void bilateralFilter(cvd_handle* h, int n, int first, int count, int w, int hh, 
 void epipolarStaticFlags(cvd_handle* h, int numPairs, const int64_t* offsets, const float* loc, double pixelScale,
                          double thresholdPx, int iterations, uint64_t seed, uint8_t* isStatic, double* fundamental,
                          int32_t* best, double* kernelMs, int32_t* counts, double* hypotheses);
+void computeTracks(cvd_handle* h, int F, int H, int W, float invAspect, const uint8_t* active, int first, int last,
+                   const float* corner, const float* dyn, int dh, int dw, const float* flow, const uint8_t* mask,
+                   const uint8_t* pairPresent, int spawnDistance, int pruneDistance, float minDynamicDistance,
+                   int minTrackLength, int64_t* counts, double* kernelMs);
+void getTracks(cvd_handle* h, int32_t* startFrame, int32_t* length, uint8_t* kept, float* loc);
 
 }  // namespace cvd

@@ -775,8 +775,126 @@ py::array DepthXform::paramMap(const DepthFrame& dfc) const {  // reference lib/
   return out;
 }
 
+// ---- DepthVideoTrackTable (reference lib/core/TrackTable{.h,-impl.h}, lib/Processor.h:18-28) ---------------------------
+// Sequential tracks of DepthVideoObs (2 x f32); a deleted track leaves its id behind as a hole.  File layout of
+// TrackTable::serialize: u64 numTracks; per track a bool (1 byte), for a present track u64 first frame, u64 size and size
+// observations; then u64 frame offset, u64 frame count (FrameBase writes nothing).
+struct DepthVideoTrackTable {
+  struct Track {
+    int start = 0;
+    std::vector<std::array<float, 2>> obs;
+  };
+  std::vector<std::unique_ptr<Track>> tracks;
+  size_t frameOffset = 0, numFrames = 0;
+
+  int createTrack(int frame, float x, float y) {  // ids are sequential
+    tracks.push_back(std::make_unique<Track>());
+    tracks.back()->start = frame;
+    tracks.back()->obs.push_back({x, y});
+    return static_cast<int>(tracks.size() - 1);
+  }
+  bool hasTrack(long long id) const { return id >= 0 && id < static_cast<long long>(tracks.size()) && tracks[id] != nullptr; }
+  const Track& get(long long id) const {
+    if (!hasTrack(id)) throw std::out_of_range("Track " + std::to_string(id) + " does not exist.");
+    return *tracks[id];
+  }
+  void save(const std::string& fileName) const {
+    std::ofstream os(fileName, std::ios::binary);
+    serialize(os);
+  }
+  void serialize(std::ostream& os) const {
+    wr<uint64_t>(os, tracks.size());
+    for (const auto& t : tracks) {
+      wr<uint8_t>(os, t ? 1 : 0);
+      if (!t) continue;
+      wr<uint64_t>(os, static_cast<uint64_t>(t->start));
+      wr<uint64_t>(os, t->obs.size());
+      if (!t->obs.empty()) os.write(reinterpret_cast<const char*>(t->obs.data()), t->obs.size() * 8);
+    }
+    wr<uint64_t>(os, frameOffset);
+    wr<uint64_t>(os, numFrames);
+  }
+  void load(const std::string& fileName) {
+    std::ifstream is(fileName, std::ios::binary);
+    if (!is.good()) throw std::runtime_error("Could not open file.");
+    tracks.clear();
+    const uint64_t n = rd<uint64_t>(is);
+    for (uint64_t i = 0; i < n && is; ++i) {
+      if (!rd<uint8_t>(is)) { tracks.emplace_back(); continue; }
+      auto t = std::make_unique<Track>();
+      t->start = static_cast<int>(rd<uint64_t>(is));
+      const uint64_t size = rd<uint64_t>(is);
+      if (!is || size > (uint64_t(1) << 32)) throw std::runtime_error("Corrupt track table file.");
+      t->obs.resize(size);
+      if (size) is.read(reinterpret_cast<char*>(t->obs.data()), size * 8);
+      tracks.push_back(std::move(t));
+    }
+    frameOffset = rd<uint64_t>(is);
+    numFrames = rd<uint64_t>(is);
+    if (!is) throw std::runtime_error("Truncated track table file.");
+  }
+  std::vector<long long> frameTracks(long long f) const {  // ascending id, as the reference's std::set
+    std::vector<long long> ids;
+    for (size_t i = 0; i < tracks.size(); ++i)
+      if (tracks[i] && f >= tracks[i]->start && f < tracks[i]->start + static_cast<long long>(tracks[i]->obs.size()))
+        ids.push_back(static_cast<long long>(i));
+    return ids;
+  }
+};
+
 // ---- importer (reference lib/Importer.cpp:25-38, 197-238) -------------------------------------------------
 struct DepthVideoImporter {
+  // reference lib/Importer.cpp:481-536: 'frame, trackId, x, y' lines (others are skipped), positions divided by the width of
+  // color_full frame 0, written to <path>/long_tracks.tracktable.  An observation is appended to its track as the next frame
+  // (TrackBaseSequential::addObs), whatever frame the line names.
+  static void importTracks(DepthVideo& video, const std::string& trackFile) {
+    std::ifstream f(trackFile);
+    if (f.fail()) throw std::runtime_error("Cannot open track file.");
+    const ColorStream& cs = *video.colorStreams_.at(video.colorStreamIndex("full"));
+    const std::string fn = cs.path_ + "/frame_" + fmtInt6(0) + cs.extension_;
+    int cols = 0;
+    if (cs.extension_ == ".raw") {
+      std::ifstream is(fn, std::ios::binary);
+      if (!is) throw std::runtime_error("Could not open '" + fn + "'.");
+      rd<int32_t>(is);
+      cols = rd<int32_t>(is);
+    } else {
+      if (!fileExists(fn)) throw std::runtime_error("Could not open '" + fn + "'.");
+      py::object im = py::module_::import("PIL.Image").attr("open")(fn);
+      cols = im.attr("width").cast<int>();
+    }
+    const float w = static_cast<float>(cols);
+    DepthVideoTrackTable tt;
+    int lastFrame = -1;
+    std::map<int, int> trackIdMap;
+    auto trim = [](std::string& s) {
+      const char* ws = " \t\n\r\f\v";
+      s.erase(0, s.find_first_not_of(ws));
+      s.erase(s.find_last_not_of(ws) + 1);
+    };
+    for (std::string line; std::getline(f, line);) {
+      std::vector<std::string> parts;
+      std::istringstream ls(line);
+      for (std::string token; std::getline(ls, token, ',');) parts.push_back(token);
+      if (parts.size() != 4) {
+        logInfo("ERROR: invalid line '" + line + "'.");
+        continue;
+      }
+      for (auto& s : parts) trim(s);
+      const int frame = std::atoi(parts[0].c_str());
+      const int trackId = std::atoi(parts[1].c_str());
+      const float x = static_cast<float>(std::atof(parts[2].c_str()));
+      const float y = static_cast<float>(std::atof(parts[3].c_str()));
+      if (frame < lastFrame) throw std::runtime_error("ERROR: Frames not in consecutive order.");
+      while (frame > lastFrame) { ++tt.numFrames; ++lastFrame; }
+      auto it = trackIdMap.find(trackId);
+      if (it != trackIdMap.end()) tt.tracks[it->second]->obs.push_back({x / w, y / w});
+      else trackIdMap[trackId] = tt.createTrack(frame, x / w, y / w);
+    }
+    std::ofstream os(video.path_ + "/long_tracks.tracktable", std::ios::binary);
+    tt.serialize(os);
+  }
+
   static void importVideo(DepthVideo& video, const std::string& path, bool discoverStreams) {
     std::ifstream is(path + "/frames.txt", std::ios::binary);
     if (is.fail()) throw std::runtime_error("Could not open frame file.");
@@ -1727,6 +1845,109 @@ struct DepthVideoProcessor {
     }
   }
 
+  // DepthVideoProcessor::computeTracks, reference lib/Processor.cpp:646-886 (C++ only there; an extension of this module).
+  // Files -> buffers as FlowConstraintsCollection::compute does; corner response, dynamic distance and the walk run on the
+  // device (cvd_corner_min_eigenval, cvd_dynamic_distance, cvd_compute_tracks).  A frame outside the range or without its
+  // colour image is skipped; a flow or mask that is missing or of another size counts as absent.
+  std::unique_ptr<DepthVideoTrackTable> computeTracks(const DvpParams& p) {
+    if (!video_->hasColorStream("down")) throw std::runtime_error("Color stream 'down' does not exist.");
+    const ColorStream& cs = *video_->colorStreams_[video_->colorStreamIndex("down")];
+    const int F = video_->numFrames();
+    const int first = p.frameRange.firstFrame(), last = p.frameRange.lastFrame();
+    auto table = std::make_unique<DepthVideoTrackTable>();
+    table->numFrames = static_cast<size_t>(F);
+    std::vector<uint8_t> active(F, 0);
+    std::vector<int> colorFrames;  // frames whose colour is read (in range and present)
+    for (int f = 0; f < F; ++f)
+      if (p.frameRange.inRange(f) && fileExists(cs.path_ + "/frame_" + fmtInt6(f) + cs.extension_)) {
+        active[f] = 1;
+        colorFrames.push_back(f);
+      }
+    if (colorFrames.empty()) return table;
+    FlowConstraintsCollection::Device dev(device_);
+    int w = 0, h = 0;
+    std::vector<float> corner;
+    {
+      std::vector<float> bgr;
+      for (size_t k = 0; k < colorFrames.size(); ++k) {
+        int r, c;
+        std::vector<float> im = FlowConstraintsCollection::readRawFloat(cs.path_ + "/frame_" + fmtInt6(colorFrames[k]) + cs.extension_, 3, r, c);
+        if (k == 0) { w = c; h = r; bgr.resize(colorFrames.size() * static_cast<size_t>(w) * h * 3); }
+        if (c != w || r != h) throw std::runtime_error("Color frames have inconsistent sizes.");
+        std::copy(im.begin(), im.end(), bgr.begin() + k * static_cast<size_t>(w) * h * 3);
+      }
+      std::vector<float> packed(colorFrames.size() * static_cast<size_t>(w) * h);
+      dev.check(cvd_corner_min_eigenval(dev.h, static_cast<int>(colorFrames.size()), h, w, bgr.data(), packed.data(), nullptr));
+      corner.assign(static_cast<size_t>(F) * w * h, 0.f);
+      for (size_t k = 0; k < colorFrames.size(); ++k)
+        std::copy(packed.begin() + k * static_cast<size_t>(w) * h, packed.begin() + (k + 1) * static_cast<size_t>(w) * h,
+                  corner.begin() + static_cast<size_t>(colorFrames[k]) * w * h);
+    }
+    const size_t px = static_cast<size_t>(w) * h;
+    std::vector<float> dyn;
+    int dw = 0, dh = 0;
+    if (video_->hasColorStream("dynamic_mask")) {  // reference :767-785, at the mask's own size
+      const ColorStream& ms = *video_->colorStreams_.at(video_->colorStreamIndex("dynamic_mask"));
+      std::vector<uint8_t> masks;
+      for (size_t k = 0; k < colorFrames.size(); ++k) {
+        int r, c;
+        const std::string fn = ms.path_ + "/frame_" + fmtInt6(colorFrames[k]) + ms.extension_;
+        if (!fileExists(fn)) throw std::runtime_error("Dynamic mask stream is missing a frame.");
+        std::vector<uint8_t> m = FlowConstraintsCollection::readPngGray(fn, r, c);
+        if (k == 0) { dw = c; dh = r; masks.resize(colorFrames.size() * static_cast<size_t>(dw) * dh); }
+        if (c != dw || r != dh) throw std::runtime_error("Dynamic masks have inconsistent sizes.");
+        std::copy(m.begin(), m.end(), masks.begin() + k * static_cast<size_t>(dw) * dh);
+      }
+      std::vector<float> packed(masks.size());
+      dev.check(cvd_dynamic_distance(dev.h, static_cast<int>(colorFrames.size()), dh, dw, masks.data(), packed.data(), nullptr));
+      dyn.assign(static_cast<size_t>(F) * dw * dh, 0.f);
+      for (size_t k = 0; k < colorFrames.size(); ++k)
+        std::copy(packed.begin() + k * static_cast<size_t>(dw) * dh, packed.begin() + (k + 1) * static_cast<size_t>(dw) * dh,
+                  dyn.begin() + static_cast<size_t>(colorFrames[k]) * dw * dh);
+    }
+    // pairs f -> f+1 that an active frame f+1 reads (reference loadFlow / loadFlowMask, :671-701)
+    const int P = std::max(F - 1, 0);
+    std::vector<uint8_t> present(std::max(P, 1), 0);
+    std::vector<float> flow(static_cast<size_t>(P) * px * 2, 0.f);
+    std::vector<uint8_t> mask(static_cast<size_t>(P) * px, 0);
+    for (int f = 0; f < P; ++f) {
+      if (!active[f + 1]) continue;
+      const std::string ff = video_->path_ + "/flow/flow_" + fmtInt6(f) + "_" + fmtInt6(f + 1) + ".raw";
+      const std::string mf = video_->path_ + "/flow_mask/mask_" + fmtInt6(f) + "_" + fmtInt6(f + 1) + ".png";
+      int r, c;
+      if (fileExists(ff)) {
+        std::vector<float> fl = FlowConstraintsCollection::readRawFloat(ff, 2, r, c);
+        if (c == w && r == h) { std::copy(fl.begin(), fl.end(), flow.begin() + static_cast<size_t>(f) * px * 2); present[f] |= 1; }
+      }
+      if (fileExists(mf)) {
+        std::vector<uint8_t> m = FlowConstraintsCollection::readPngGray(mf, r, c);
+        if (c == w && r == h) { std::copy(m.begin(), m.end(), mask.begin() + static_cast<size_t>(f) * px); present[f] |= 2; }
+      }
+    }
+    int64_t counts[3] = {0, 0, 0};
+    dev.check(cvd_compute_tracks(dev.h, F, h, w, video_->invAspect_, active.data(), first, last, corner.data(),
+                                 dyn.empty() ? nullptr : dyn.data(), dh, dw, P ? flow.data() : nullptr,
+                                 P ? mask.data() : nullptr, present.data(), p.trackSpawnDistance, p.trackPruneDistance,
+                                 static_cast<float>(p.minDynamicDistance), p.minTrackLength, counts, nullptr));
+    const size_t n = static_cast<size_t>(counts[0]);
+    std::vector<int32_t> start(std::max<size_t>(n, 1)), length(std::max<size_t>(n, 1));
+    std::vector<uint8_t> kept(std::max<size_t>(n, 1));
+    std::vector<float> loc(std::max<size_t>(static_cast<size_t>(counts[2]) * 2, 2));
+    dev.check(cvd_get_tracks(dev.h, start.data(), length.data(), kept.data(), loc.data()));
+    size_t o = 0;
+    table->tracks.resize(n);
+    for (size_t t = 0; t < n; ++t) {
+      if (!kept[t]) continue;  // deleteTrack: the id stays behind as a hole
+      auto tr = std::make_unique<DepthVideoTrackTable::Track>();
+      tr->start = start[t];
+      tr->obs.resize(length[t]);
+      std::memcpy(tr->obs.data(), loc.data() + 2 * o, static_cast<size_t>(length[t]) * 8);
+      o += length[t];
+      table->tracks[t] = std::move(tr);
+    }
+    return table;
+  }
+
   void process(const DvpParams& p) {  // reference lib/Processor.cpp:115-144
     switch (p.op) {
       case Op::None: break;
@@ -1942,8 +2163,28 @@ PYBIND11_MODULE(lib_python, m) {
       .def("compute", &FlowConstraintsCollection::compute, py::call_guard<py::gil_scoped_release>())
       .def_readwrite("device", &FlowConstraintsCollection::device_);
 
+  py::class_<DepthVideoTrackTable>(m, "DepthVideoTrackTable")
+      .def(py::init())
+      .def("save", &DepthVideoTrackTable::save)
+      .def("load", &DepthVideoTrackTable::load)
+      // (read-only extensions)
+      .def("numFrames", [](const DepthVideoTrackTable& t) { return t.numFrames; })
+      .def("numTracks", [](const DepthVideoTrackTable& t) { return t.tracks.size(); })
+      .def("hasTrack", &DepthVideoTrackTable::hasTrack)
+      .def("track", [](const DepthVideoTrackTable& t, long long id) {
+        const DepthVideoTrackTable::Track& tr = t.get(id);
+        const py::ssize_t n = static_cast<py::ssize_t>(tr.obs.size());
+        py::array_t<int32_t> frames(n);
+        for (py::ssize_t i = 0; i < n; ++i) frames.mutable_data()[i] = tr.start + static_cast<int32_t>(i);
+        py::array_t<float> locs({n, py::ssize_t(2)});
+        if (n) std::memcpy(locs.mutable_data(), tr.obs.data(), static_cast<size_t>(n) * 8);
+        return py::make_tuple(frames, locs);
+      })
+      .def("frameTracks", &DepthVideoTrackTable::frameTracks);
+
   py::class_<DepthVideoImporter>(m, "DepthVideoImporter")
       .def_static("importVideo", &DepthVideoImporter::importVideo)
+      .def_static("importTracks", &DepthVideoImporter::importTracks)
       .def_static("importPoses", [](DepthVideo&, const std::string&, int) { throw std::runtime_error("importPoses is outside the optimizer path of this build."); })
       .def_static("importColmapRecon", [](py::args) { throw std::runtime_error("COLMAP import is outside the optimizer path of this build."); })
       .def_static("importColmapDepth", [](py::args) { throw std::runtime_error("COLMAP import is outside the optimizer path of this build."); });
@@ -2010,6 +2251,7 @@ PYBIND11_MODULE(lib_python, m) {
       .def("gridXformSplit", &DepthVideoProcessor::gridXformSplit).def("resetPoses", &DepthVideoProcessor::resetPoses)
       .def("resetDepthXforms", &DepthVideoProcessor::resetDepthXforms).def("resetSpatialXforms", &DepthVideoProcessor::resetSpatialXforms)
       .def("normalizeDepth", &DepthVideoProcessor::normalizeDepth).def("optimizePoses", &DepthVideoProcessor::optimizePoses)
+      .def("computeTracks", &DepthVideoProcessor::computeTracks)  // (extension: C++ only in the reference)
       .def_readwrite("device", &DepthVideoProcessor::device_)
       .def_readonly("usedFlowImages", &DepthVideoProcessor::usedFlowImages_);  // (extension, with `device`)
 }
