@@ -363,6 +363,28 @@ int32_t cvd_compute_tracks(cvd_handle* h, int32_t num_frames, int32_t height, in
  * id order, frame by frame inside a track.  Any pointer may be NULL. */
 int32_t cvd_get_tracks(cvd_handle* h, int32_t* start_frame, int32_t* length, uint8_t* kept, float* loc);
 
+/* ---- flow consistency masks: Flow.compute_flow_masks, reference flow.py:180-209 + utils/consistency.py:8-67
+ * Independent of cvd_set_video.  For every pair p = (a, b) of pair_frames both directed masks, in one launch:
+ *   color [num_frames][H][W][channels]  the frames' "down" colour images (channels 1..4), passed once; pairs index into it
+ *   pair_frames [P][2]                  (a, b), a != b
+ *   flow_ab, flow_ba [P][H][W][2]       flow a -> b and b -> a, pixels
+ *   mask_ab, mask_ba [P][H][W]          255 where the pixel passes, else 0
+ * Direction a -> b at pixel (x, y): target t = (x, y) + flow_ab in f64; in bounds iff 0 <= t.x <= W - 1 and 0 <= t.y <= H - 1;
+ * S = grid_sample (bilinear, align_corners = false, border padding, f32) of the other frame's image at g = f32(2 t / size - 1),
+ * which lies HALF A PIXEL up and left of t (the reference's behaviour, kept); ef = |flow_ab + S(flow_ba)|^2,
+ * ec = |color_a - S(color_b)|^2; mask = in bounds && ef < flow_thresh^2 && ec < channels * color_thresh^2 (thresholds formed
+ * in double, rounded once to f32; a NaN fails).  Reference defaults: flow_thresh 1, color_thresh 1.
+ *   kept   [P][2]          optional (may be NULL): pixels set in mask_ab, mask_ba
+ *   errors [P][2][H][W][2] optional (may be NULL): (ef, ec) per direction, for value-level parity checks
+ *   kernel_ms              optional (may be NULL): kernel time, HIP events
+ * Every output repeats bit for bit.  Rejected before any work, with an error naming the argument and the value: sizes < 1,
+ * channels outside [1, 4], num_pairs outside [0, 65535], more than 2^28 pixels per image, a negative or non-finite threshold,
+ * a frame index out of range, a == b, null pointers.  num_pairs == 0 returns at once. */
+int32_t cvd_flow_consistency_masks(cvd_handle* h, int32_t num_frames, int32_t height, int32_t width, int32_t channels,
+                                   const float* color, int32_t num_pairs, const int32_t* pair_frames, const float* flow_ab,
+                                   const float* flow_ba, float flow_thresh, float color_thresh, uint8_t* mask_ab,
+                                   uint8_t* mask_ba, int32_t* kept, float* errors, double* kernel_ms);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

@@ -60,6 +60,13 @@ int32_t cvd_block_inverse_debug(cvd_handle* h, int32_t num_blocks, int32_t block
 int32_t cvd_epipolar_debug(cvd_handle* h, int32_t num_pairs, const int64_t* offsets, const float* loc, double pixel_scale,
                            double threshold_px, int32_t iterations, uint64_t seed, uint8_t* is_static_out,
                            double* fundamental_out, int32_t* best_out, int32_t* counts_out, double* hypotheses_out);
+/* Test and measurement hook of cvd_flow_consistency_masks: the same call with the thread-to-pixel map chosen by the caller --
+ * pixels_per_thread 0 = the product choice (4 when width % 4 == 0, else 1), 1 = one pixel per thread, 4 = four consecutive
+ * pixels of a row per thread (needs width % 4 == 0).  Both maps produce the same bits. */
+int32_t cvd_flow_masks_debug(cvd_handle* h, int32_t num_frames, int32_t height, int32_t width, int32_t channels,
+                             const float* color, int32_t num_pairs, const int32_t* pair_frames, const float* flow_ab,
+                             const float* flow_ba, float flow_thresh, float color_thresh, uint8_t* mask_ab, uint8_t* mask_ba,
+                             int32_t* kept, float* errors, double* kernel_ms, int32_t pixels_per_thread);
 int32_t cvd_dense_inverse_debug(cvd_handle* h, int32_t n, const double* a, double* inverse, int32_t* failed);
 int32_t cvd_coarse_debug(cvd_handle* h, int32_t* num_unknowns, double* a_c, double* a_c_inverse, int32_t* failed);
 /* Test hook for the third level of the preconditioner (cvd_solver_options::temporal_level; state of its last build in the last

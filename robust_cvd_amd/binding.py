@@ -436,6 +436,42 @@ class Binding:
         out = (start, length, kept, off, loc)
         return out + (list(ms),) if timing else out
 
+    def flow_consistency_masks(self, color, pair_frames, flow_ab, flow_ba, flow_thresh=1.0, color_thresh=1.0,
+                               return_errors=False, timing=False, pixels_per_thread=None):
+        """Flow.compute_flow_masks on a batch of pairs (see include/cvd_hip.h cvd_flow_consistency_masks): color [F, H, W, C]
+        (or [F, H, W]) f32, pair_frames [P, 2] indices into color, flow_ab / flow_ba [P, H, W, 2] in pixels.  Returns
+        (mask_ab [P, H, W] uint8 255 / 0, mask_ba, kept [P, 2] int32), then errors [P, 2, H, W, 2] f32 = (ef, ec) per direction
+        when return_errors, then the kernel ms when timing.  pixels_per_thread (1 or 4): test / measurement hook
+        (include/cvd_hip_debug.h cvd_flow_masks_debug); None = the product call."""
+        col = _f32(color)
+        if col.ndim == 3:
+            col = col[..., None]
+        assert col.ndim == 4, col.shape
+        F, H, W, ch = col.shape
+        pf = np.ascontiguousarray(pair_frames, dtype=np.int32).reshape(-1, 2)
+        P = pf.shape[0]
+        fab, fba = _f32(flow_ab), _f32(flow_ba)
+        assert fab.shape == (P, H, W, 2) and fba.shape == (P, H, W, 2), (fab.shape, fba.shape, col.shape)
+        mab = np.zeros((P, H, W), dtype=np.uint8)
+        mba = np.zeros((P, H, W), dtype=np.uint8)
+        kept = np.zeros((P, 2), dtype=np.int32)
+        err = np.zeros((P, 2, H, W, 2), dtype=np.float32) if return_errors else None
+        ms = C.c_double(0.0)
+        args = [self._h, C.c_int(F), C.c_int(H), C.c_int(W), C.c_int(ch), _ptr(col, C.c_float), C.c_int(P), _ptr(pf, C.c_int32),
+                _ptr(fab, C.c_float), _ptr(fba, C.c_float), C.c_float(flow_thresh), C.c_float(color_thresh), _ptr(mab, C.c_uint8),
+                _ptr(mba, C.c_uint8), _ptr(kept, C.c_int32), _ptr(err, C.c_float) if err is not None else None,
+                C.byref(ms) if timing else None]
+        if pixels_per_thread is None:
+            self._check(self._fn("flow_consistency_masks")(*args))
+        else:
+            self._check(self._fn("flow_masks_debug")(*args, C.c_int(pixels_per_thread)))
+        out = (mab, mba, kept)
+        if return_errors:
+            out += (err,)
+        if timing:
+            out += (ms.value,)
+        return out
+
     def _grid_vertices(self):
         d = self.xform_desc(False)
         if int(d.depth_type) == 3:  # Grid

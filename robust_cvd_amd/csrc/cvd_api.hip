@@ -734,6 +734,20 @@ int32_t cvd_compute_tracks(cvd_handle* h, int32_t num_frames, int32_t height, in
 int32_t cvd_get_tracks(cvd_handle* h, int32_t* start_frame, int32_t* length, uint8_t* kept, float* loc) {
   CVD_TRY(h, getTracks(h, start_frame, length, kept, loc));
 }
+int32_t cvd_flow_consistency_masks(cvd_handle* h, int32_t num_frames, int32_t height, int32_t width, int32_t channels,
+                                   const float* color, int32_t num_pairs, const int32_t* pair_frames, const float* flow_ab,
+                                   const float* flow_ba, float flow_thresh, float color_thresh, uint8_t* mask_ab,
+                                   uint8_t* mask_ba, int32_t* kept, float* errors, double* kernel_ms) {
+  CVD_TRY(h, flowConsistencyMasks(h, num_frames, height, width, channels, color, num_pairs, pair_frames, flow_ab, flow_ba,
+                                  flow_thresh, color_thresh, mask_ab, mask_ba, kept, errors, kernel_ms, 0));
+}
+int32_t cvd_flow_masks_debug(cvd_handle* h, int32_t num_frames, int32_t height, int32_t width, int32_t channels,
+                             const float* color, int32_t num_pairs, const int32_t* pair_frames, const float* flow_ab,
+                             const float* flow_ba, float flow_thresh, float color_thresh, uint8_t* mask_ab, uint8_t* mask_ba,
+                             int32_t* kept, float* errors, double* kernel_ms, int32_t pixels_per_thread) {
+  CVD_TRY(h, flowConsistencyMasks(h, num_frames, height, width, channels, color, num_pairs, pair_frames, flow_ab, flow_ba,
+                                  flow_thresh, color_thresh, mask_ab, mask_ba, kept, errors, kernel_ms, pixels_per_thread));
+}
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {

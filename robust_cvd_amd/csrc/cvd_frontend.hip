@@ -1,6 +1,7 @@
 // cvd_frontend.hip -- the steps either side of the solve: constraint sampling, epipolar RANSAC flags, image operators, dense
-// consumers, flow-guided and bilateral filters.
+// consumers, flow-guided and bilateral filters, flow consistency masks.
 #include "cvd_host.h"
+#include "cvd_flowmask.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -657,6 +658,104 @@ void getTracks(cvd_handle* h, int32_t* startFrame, int32_t* length, uint8_t* kep
   }
   if (loc && h->trkKeptObs > 0) h->dTrkLoc.download(reinterpret_cast<float2*>(loc), static_cast<size_t>(h->trkKeptObs), s);
   HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// Flow.compute_flow_masks on a batch of pairs (reference flow.py:180-209, utils/consistency.py:8-67), cvd_flowmask.h: one launch
+// for both directions of every pair.  pixelsPerThread: 0 = the product choice, 1 / 4 = that map (test and measurement hook).
+template <int C>
+static void launchFlowMasks(const FlowMaskArgs& A, int numPairs, int pix, hipStream_t s) {
+  const size_t npx = static_cast<size_t>(A.w) * A.h;
+  const size_t perBlock = static_cast<size_t>(kFlowMaskThreads) * pix;
+  const dim3 grid(static_cast<unsigned>((npx + perBlock - 1) / perBlock), numPairs, 2), block(kFlowMaskThreads);
+  if (pix == 4) hipLaunchKernelGGL((k_flow_masks<C, 4>), grid, block, 0, s, A);
+  else hipLaunchKernelGGL((k_flow_masks<C, 1>), grid, block, 0, s, A);
+}
+
+void flowConsistencyMasks(cvd_handle* h, int numFrames, int hh, int w, int channels, const float* color, int numPairs,
+                          const int32_t* pairFrames, const float* flowAB, const float* flowBA, float flowThresh,
+                          float colorThresh, uint8_t* maskAB, uint8_t* maskBA, int32_t* kept, float* errors, double* kernelMs,
+                          int pixelsPerThread) {
+  if (numFrames < 1) throw std::runtime_error(fmt("flow masks: num_frames must be >= 1 (got %d)", numFrames));
+  if (hh < 1 || w < 1) throw std::runtime_error(fmt("flow masks: invalid image size: height %d, width %d", hh, w));
+  if (channels < 1 || channels > 4) throw std::runtime_error(fmt("flow masks: channels must lie in [1, 4] (got %d)", channels));
+  if (numPairs < 0 || numPairs > 65535)
+    throw std::runtime_error(fmt("flow masks: num_pairs must lie in [0, 65535] (got %d)", numPairs));
+  if (!(std::isfinite(flowThresh) && flowThresh >= 0.f))
+    throw std::runtime_error(fmt("flow masks: flow_thresh must be finite and >= 0 (got %g)", static_cast<double>(flowThresh)));
+  if (!(std::isfinite(colorThresh) && colorThresh >= 0.f))
+    throw std::runtime_error(fmt("flow masks: color_thresh must be finite and >= 0 (got %g)", static_cast<double>(colorThresh)));
+  if (pixelsPerThread != 0 && pixelsPerThread != 1 && pixelsPerThread != 4)
+    throw std::runtime_error(fmt("flow masks: pixels_per_thread must be 0, 1 or 4 (got %d)", pixelsPerThread));
+  if (pixelsPerThread == 4 && w % 4 != 0)
+    throw std::runtime_error(fmt("flow masks: four pixels per thread need a width that is a multiple of 4 (got %d)", w));
+  const size_t npx = static_cast<size_t>(w) * hh;
+  if (npx > (size_t(1) << 28)) throw std::runtime_error(fmt("flow masks: image size %d x %d exceeds 2^28 pixels", w, hh));
+  if (kernelMs) *kernelMs = 0.0;
+  if (numPairs == 0) return;
+  if (!color) throw std::runtime_error("flow masks: null color");
+  if (!pairFrames) throw std::runtime_error("flow masks: null pair_frames");
+  if (!flowAB) throw std::runtime_error("flow masks: null flow_ab");
+  if (!flowBA) throw std::runtime_error("flow masks: null flow_ba");
+  if (!maskAB) throw std::runtime_error("flow masks: null mask_ab");
+  if (!maskBA) throw std::runtime_error("flow masks: null mask_ba");
+  for (int p = 0; p < numPairs; ++p) {
+    const int a = pairFrames[2 * p], b = pairFrames[2 * p + 1];
+    if (a < 0 || a >= numFrames || b < 0 || b >= numFrames)
+      throw std::runtime_error(fmt("flow masks: pair_frames[%d] = (%d, %d) outside [0, %d)", p, a, b, numFrames));
+    if (a == b) throw std::runtime_error(fmt("flow masks: pair_frames[%d] = (%d, %d) names one frame twice", p, a, b));
+  }
+  hipStream_t s = h->stream;
+  const size_t P = static_cast<size_t>(numPairs);
+  h->dFmColor.upload(color, static_cast<size_t>(numFrames) * npx * channels, s);
+  h->dFmPairs.upload(reinterpret_cast<const int2*>(pairFrames), P, s);
+  h->dFmFlowAB.upload(reinterpret_cast<const float2*>(flowAB), P * npx, s);
+  h->dFmFlowBA.upload(reinterpret_cast<const float2*>(flowBA), P * npx, s);
+  h->dFmMaskAB.ensure(P * npx);
+  h->dFmMaskBA.ensure(P * npx);
+  h->dFmKept.ensure(P * 2);
+  if (errors) h->dFmErr.ensure(P * 2 * npx);
+  HIP_CHECK(hipMemsetAsync(h->dFmKept.p, 0, sizeof(int) * P * 2, s));
+  FlowMaskArgs A;
+  A.w = w;
+  A.h = hh;
+  // thresholds of utils/consistency.py:53-63, computed in double and rounded once (numpy compares the f32 errors in f32)
+  A.flowT = static_cast<float>(static_cast<double>(flowThresh) * static_cast<double>(flowThresh));
+  A.colorT = static_cast<float>(channels * (static_cast<double>(colorThresh) * static_cast<double>(colorThresh)));
+  A.color = h->dFmColor.p;
+  A.pairs = h->dFmPairs.p;
+  A.flowAB = h->dFmFlowAB.p;
+  A.flowBA = h->dFmFlowBA.p;
+  A.maskAB = h->dFmMaskAB.p;
+  A.maskBA = h->dFmMaskBA.p;
+  A.kept = h->dFmKept.p;
+  A.errors = errors ? h->dFmErr.p : nullptr;
+  const int pix = pixelsPerThread ? pixelsPerThread : (w % 4 == 0 ? 4 : 1);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (kernelMs) {
+    HIP_CHECK(hipEventCreate(&e0));
+    HIP_CHECK(hipEventCreate(&e1));
+    HIP_CHECK(hipEventRecord(e0, s));
+  }
+  switch (channels) {
+    case 1: launchFlowMasks<1>(A, numPairs, pix, s); break;
+    case 2: launchFlowMasks<2>(A, numPairs, pix, s); break;
+    case 3: launchFlowMasks<3>(A, numPairs, pix, s); break;
+    default: launchFlowMasks<4>(A, numPairs, pix, s); break;
+  }
+  HIP_CHECK(hipGetLastError());
+  if (kernelMs) HIP_CHECK(hipEventRecord(e1, s));
+  h->dFmMaskAB.download(maskAB, P * npx, s);
+  h->dFmMaskBA.download(maskBA, P * npx, s);
+  if (kept) h->dFmKept.download(kept, P * 2, s);
+  if (errors) h->dFmErr.download(reinterpret_cast<float2*>(errors), P * 2 * npx, s);
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (kernelMs) {
+    float ms = 0.f;
+    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    *kernelMs = ms;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+  }
 }
 
 // One kernel of this translation unit's code object is looked up at handle creation: the HIP runtime loads a unit's device

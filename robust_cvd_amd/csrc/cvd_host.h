@@ -310,6 +310,12 @@ struct cvd_handle_t {
   DevBuf<unsigned char> dFltMaskF, dFltMaskB;
   DevBuf<FilterCam> dFltCams;
   DevBuf<float> dBilDepth, dBilColor, dBilOut;  // cvd_bilateral.h staging
+  // cvd_flowmask.h staging: colour table, pair frames, both flows, both masks, kept counts, error maps
+  DevBuf<float> dFmColor;
+  DevBuf<int2> dFmPairs;
+  DevBuf<float2> dFmFlowAB, dFmFlowBA, dFmErr;
+  DevBuf<unsigned char> dFmMaskAB, dFmMaskBA;
+  DevBuf<int> dFmKept;
   // cvd_epipolar.h: constraints, offsets, per-pair normalisation, per-hypothesis F / counts (one batch of pairs), results
   DevBuf<float4> dEpiLoc;
   DevBuf<long long> dEpiOff;
@@ -741,5 +747,9 @@ void computeTracks(cvd_handle* h, int F, int H, int W, float invAspect, const ui
                    const uint8_t* pairPresent, int spawnDistance, int pruneDistance, float minDynamicDistance,
                    int minTrackLength, int64_t* counts, double* kernelMs);
 void getTracks(cvd_handle* h, int32_t* startFrame, int32_t* length, uint8_t* kept, float* loc);
+void flowConsistencyMasks(cvd_handle* h, int numFrames, int hh, int w, int channels, const float* color, int numPairs,
+                          const int32_t* pairFrames, const float* flowAB, const float* flowBA, float flowThresh,
+                          float colorThresh, uint8_t* maskAB, uint8_t* maskBA, int32_t* kept, float* errors, double* kernelMs,
+                          int pixelsPerThread);
 
 }  // namespace cvd

@@ -23,6 +23,24 @@ def write_raw_image(path, img):
         f.write(img.tobytes())
 
 
+def read_raw_image(path):
+    """Inverse of write_raw_image (reference lib/core/CvUtil.cpp:25-36, utils/image_io.py load_raw_float32_image): float32 [H, W]
+    for one channel, else [H, W, C].  Raises ValueError naming the file when it is not a complete CV_32FC(C) raw image."""
+    with open(path, "rb") as f:
+        head = f.read(20)
+        if len(head) != 20:
+            raise ValueError(f"{path}: truncated raw image header")
+        rows, cols, cv_type, elem_size = struct.unpack("<iiiQ", head)
+        ch = (cv_type >> 3) + 1
+        if rows < 0 or cols < 0 or (cv_type & 7) != CV_32FC1 or elem_size != 4 * ch:
+            raise ValueError(f"{path}: not a float32 raw image (rows {rows}, cols {cols}, cvType {cv_type}, elemSize {elem_size})")
+        data = f.read()
+    if len(data) != rows * cols * elem_size:
+        raise ValueError(f"{path}: {len(data)} bytes of data, expected {rows * cols * elem_size} ({rows} x {cols} x {ch} f32)")
+    img = np.frombuffer(data, dtype="<f4")
+    return img.reshape(rows, cols) if ch == 1 else img.reshape(rows, cols, ch)
+
+
 def write_flow_inputs(base_dir, pairs, flows, masks, colors, dynamic_masks=None):
     """The image inputs of FlowConstraintsCollection::compute (reference lib/FlowConstraints.cpp:226-286, 401-420):
     flow/flow_%06d_%06d.raw (2 x f32, pixels), flow_mask/mask_%06d_%06d.png, color_down/frame_%06d.raw (BGR f32),
