@@ -4,7 +4,8 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
-# translation units of libcvd_hip.so (compiled in parallel; every unit includes cvd_host.h + the kernel headers it launches)
+# translation units of libcvd_hip.so (compiled in parallel).  Every unit includes cvd_host.h and, through it, the solver's kernel
+# headers; the front-end operators' kernel headers are included by cvd_frontend alone (tests/test_codegen_units.py).
 UNITS = ["cvd_api", "cvd_comm", "cvd_setup", "cvd_eval", "cvd_matvec", "cvd_precond", "cvd_temporal", "cvd_solve", "cvd_frontend"]
 LIB = os.path.join(_HERE, "lib", "libcvd_hip.so")
 OBJ = os.path.join(_HERE, "lib", "obj")

@@ -150,6 +150,7 @@ cvd_handle* cvd_create(int32_t device) {
     HIP_CHECK(hipSetDevice(device));
     auto* h = new cvd_handle_t();
     h->device = device;
+    h->frontend = makeFrontend();
     HIP_CHECK(hipDeviceGetAttribute(&h->numCU, hipDeviceAttributeMultiprocessorCount, device));
     HIP_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     // side stream of the asynchronous rebuild of the sparse coarse level (created here: the first use of a new stream
@@ -647,13 +648,7 @@ int32_t cvd_sample_pair_constraints(cvd_handle* h, int32_t numPairs, const int32
                                matchSeparation, minDynamicDistance, offsets));
 }
 int32_t cvd_get_sampled_constraints(cvd_handle* h, float* loc4) {
-  CVD_TRY(h, {
-    const size_t n = h->sampledOff.empty() ? 0 : static_cast<size_t>(h->sampledOff.back());
-    if (n) {
-      HIP_CHECK(hipMemcpyAsync(loc4, h->dSampledLoc.p, n * 2 * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-      HIP_CHECK(hipStreamSynchronize(h->stream));
-    }
-  });
+  CVD_TRY(h, getSampledConstraints(h, false, loc4));
 }
 int32_t cvd_sample_triplet_constraints(cvd_handle* h, int32_t numTriplets, const int32_t* centers, const float* corner,
                                        const float* flow10, const uint8_t* mask10, const float* flow12,
@@ -663,13 +658,7 @@ int32_t cvd_sample_triplet_constraints(cvd_handle* h, int32_t numTriplets, const
                                matchSeparation, minDynamicDistance, offsets));
 }
 int32_t cvd_get_sampled_triplet_constraints(cvd_handle* h, float* loc6) {
-  CVD_TRY(h, {
-    const size_t n = h->sampledTripOff.empty() ? 0 : static_cast<size_t>(h->sampledTripOff.back());
-    if (n) {
-      HIP_CHECK(hipMemcpyAsync(loc6, h->dSampledTrip.p, n * 3 * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-      HIP_CHECK(hipStreamSynchronize(h->stream));
-    }
-  });
+  CVD_TRY(h, getSampledConstraints(h, true, loc6));
 }
 int32_t cvd_apply_depth_xforms(cvd_handle* h, int32_t firstFrame, int32_t numFrames, float* out, double* kernelMs) {
   CVD_TRY(h, denseMaps(h, 0, firstFrame, numFrames, 0, 0, out, kernelMs));

@@ -1,11 +1,139 @@
 // cvd_frontend.hip -- the steps either side of the solve: constraint sampling, epipolar RANSAC flags, image operators, dense
-// consumers, flow-guided and bilateral filters, flow consistency masks.
+// consumers, flow-guided and bilateral filters, feature tracks, flow consistency masks.  The only unit that includes their kernel
+// headers and the only one that knows their device state (Frontend; the handle owns it through a pointer to the incomplete type).
 #include "cvd_host.h"
+#include "cvd_dense.h"
+#include "cvd_sampling.h"
+#include "cvd_imageops.h"
+#include "cvd_filter.h"
+#include "cvd_bilateral.h"
+#include "cvd_epipolar.h"
+#include "cvd_tracks.h"
 #include "cvd_flowmask.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 namespace cvd {
+
+// Device state of the operators below.  Nothing is allocated before an operator runs; the staging buffers then keep their
+// high-water size for the life of the handle.
+struct Frontend {
+  DevBuf<double> dDense;     // output of the dense consumer kernels (cvd_dense.h)
+  DevBuf<float> dImgIn, dImgGray, dImgCov, dImgOut;  // cvd_imageops.h staging
+  DevBuf<unsigned char> dImgMask;
+  DevBuf<unsigned int> dImgTmp;
+  DevBuf<float> dFltDepth, dFltOut, dFltFlowF, dFltFlowB;  // cvd_filter.h staging
+  DevBuf<unsigned char> dFltMaskF, dFltMaskB;
+  DevBuf<FilterCam> dFltCams;
+  DevBuf<float> dBilDepth, dBilColor, dBilOut;  // cvd_bilateral.h staging
+  // cvd_flowmask.h staging: colour table, pair frames, both flows, both masks, kept counts, error maps
+  DevBuf<float> dFmColor;
+  DevBuf<int2> dFmPairs;
+  DevBuf<float2> dFmFlowAB, dFmFlowBA, dFmErr;
+  DevBuf<unsigned char> dFmMaskAB, dFmMaskBA;
+  DevBuf<int> dFmKept;
+  // cvd_epipolar.h: constraints, offsets, per-pair normalisation, per-hypothesis F / counts (one batch of pairs), results
+  DevBuf<float4> dEpiLoc;
+  DevBuf<long long> dEpiOff;
+  DevBuf<EpiNorm> dEpiNorm;
+  DevBuf<double> dEpiF, dEpiFbest;
+  DevBuf<int> dEpiCount, dEpiBest;
+  DevBuf<unsigned char> dEpiFlags;
+  // constraint sampling (cvd_sampling.h): result of the last cvd_sample_pair_constraints / cvd_sample_triplet_constraints
+  DevBuf<float2> dSampledLoc, dSampledTrip;  // 2 resp. 3 float2 per constraint
+  std::vector<long long> sampledOff, sampledTripOff;
+  // feature tracks (cvd_tracks.h): the table of the last cvd_compute_tracks
+  DevBuf<int> dTrkStart, dTrkLen, dTrkKeptLen, dTrkOff;
+  DevBuf<unsigned char> dTrkKept;
+  DevBuf<float2> dTrkLoc;
+  long long trkTracks = 0, trkKeptObs = 0;
+};
+
+std::shared_ptr<Frontend> makeFrontend() { return std::make_shared<Frontend>(); }
+
+// HIP-event times of an operator's kernel phases.  mark() records the next event on the stream: the one before the first phase,
+// then one after each phase.  collect(), once the marked events have completed, adds every closed phase's milliseconds to its
+// entry of kernelMs and starts over at phase 0.  With a null kernelMs no event is created or recorded.  The entries are zeroed
+// at construction, the events destroyed with the timer (also when a HIP call in between throws).
+class KernelTimer {
+ public:
+  KernelTimer(hipStream_t stream, double* kernelMs, int phases) : s(stream), ms(kernelMs) {
+    if (!ms) return;
+    std::fill(ms, ms + phases, 0.0);
+    ev.assign(phases + 1, nullptr);
+    try {
+      for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+    } catch (...) {
+      destroy();
+      throw;
+    }
+  }
+  KernelTimer(const KernelTimer&) = delete;
+  KernelTimer& operator=(const KernelTimer&) = delete;
+  ~KernelTimer() { destroy(); }
+  void mark() {
+    if (ms) HIP_CHECK(hipEventRecord(ev[next++], s));
+  }
+  void seek(int phase) { first = next = phase; }  // the next mark() opens this phase (phases timed out of order: computeTracks)
+  void wait() {                                   // host wait for the last marked event
+    if (ms) HIP_CHECK(hipEventSynchronize(ev[next - 1]));
+  }
+  void collect() {
+    for (int k = first; ms && k + 1 < next; ++k) {
+      float t = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
+      ms[k] += t;
+    }
+    first = next = 0;
+  }
+
+ private:
+  void destroy() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  hipStream_t s;
+  double* ms;
+  std::vector<hipEvent_t> ev;
+  int first = 0, next = 0;
+};
+
+// Batched segmented key sort (rocprim, descending, bits 0..64): at most maxSegments segments of segLen keys each, back to back in
+// `keys`; run() sorts the first `segments` of them into keysOut.  Owns the segment table and rocprim's temporary storage.
+class SegmentedKeySort {
+ public:
+  SegmentedKeySort(int maxSegments, size_t segLen, unsigned long long* keys, unsigned long long* keysOut, hipStream_t stream)
+      : len(segLen), in(keys), out(keysOut), s(stream), seg(maxSegments + 1) {
+    for (int i = 0; i <= maxSegments; ++i) seg[i] = static_cast<unsigned int>(static_cast<size_t>(i) * segLen);
+    dSeg.upload(seg.data(), seg.size(), s);
+    sort(nullptr, tmpBytes, maxSegments);
+    dTmp.ensure(tmpBytes);
+  }
+  void run(int segments) {
+    size_t tb = tmpBytes;
+    sort(dTmp.p, tb, segments);
+  }
+
+ private:
+  void sort(void* tmp, size_t& bytes, int segments) {
+    HIP_CHECK(rocprim::segmented_radix_sort_keys_desc(tmp, bytes, in, out, static_cast<unsigned int>(static_cast<size_t>(segments) * len),
+                                                      static_cast<unsigned int>(segments), dSeg.p, dSeg.p + 1, 0, 64, s));
+  }
+  size_t len, tmpBytes = 0;
+  unsigned long long *in, *out;
+  hipStream_t s;
+  std::vector<unsigned int> seg;  // (outlives the asynchronous upload)
+  DevBuf<unsigned int> dSeg;
+  DevBuf<unsigned char> dTmp;
+};
+
+// checks the flow-guided and the bilateral filter share (rasterOk / inputsOk: the operator's own conditions)
+static void checkFilterBatch(int n, int first, int count, bool rasterOk, int frameRadius, int spatialRadius, bool inputsOk) {
+  if (n < 1 || first < 0 || count < 0 || first + count > n) throw std::runtime_error("invalid frame batch");
+  if (!rasterOk) throw std::runtime_error("invalid raster");
+  if (frameRadius < 0 || spatialRadius < 0) throw std::runtime_error("negative filter radius");
+  if (!inputsOk) throw std::runtime_error("null filter input");
+}
 
 // ---- constraint sampling (cvd_sampling.h) -----------------------------------------------------------
 // triplet == false: keyFrames = 2 x n frames (a, b) of the directed pairs, flow / mask = a -> b.
@@ -27,10 +155,10 @@ void sampleConstraints(cvd_handle* h, bool triplet, int num, const int32_t* keyF
   hipStream_t s = h->stream;
   DevBuf<float> dCorner, dDyn;
   DevBuf<float2> dFlow, dFlow2, dSlab;
-  DevBuf<unsigned char> dMaskS, dMaskS2, dTmp;
+  DevBuf<unsigned char> dMaskS, dMaskS2;
   DevBuf<int> dKeysF;
   DevBuf<unsigned long long> dKeys, dKeysOut;
-  DevBuf<unsigned int> dNValid, dCount, dSeg;
+  DevBuf<unsigned int> dNValid, dCount;
   DevBuf<long long> dOff;
   dCorner.upload(corner, static_cast<size_t>(h->F) * npx, s);
   if (dyn) dDyn.upload(dyn, static_cast<size_t>(h->F) * dw * dh, s);
@@ -51,15 +179,9 @@ void sampleConstraints(cvd_handle* h, bool triplet, int num, const int32_t* keyF
   dSlab.ensure(static_cast<size_t>(PB) * npx * width);
   dNValid.ensure(PB);
   dCount.ensure(PB);
-  std::vector<unsigned int> seg(PB + 1);
-  for (int i = 0; i <= PB; ++i) seg[i] = static_cast<unsigned int>(static_cast<size_t>(i) * npx);
-  dSeg.upload(seg.data(), seg.size(), s);
-  size_t tmpBytes = 0;
-  HIP_CHECK(rocprim::segmented_radix_sort_keys_desc(nullptr, tmpBytes, dKeys.p, dKeysOut.p,
-                                                    static_cast<unsigned int>(static_cast<size_t>(PB) * npx),
-                                                    static_cast<unsigned int>(PB), dSeg.p, dSeg.p + 1, 0, 64, s));
-  dTmp.ensure(tmpBytes);
-  DevBuf<float2>& result = triplet ? h->dSampledTrip : h->dSampledLoc;
+  SegmentedKeySort sorter(PB, npx, dKeys.p, dKeysOut.p, s);
+  Frontend& fe = *h->frontend;
+  DevBuf<float2>& result = triplet ? fe.dSampledTrip : fe.dSampledLoc;
   std::vector<long long> off(num + 1, 0);
   std::vector<unsigned int> cnt(PB);
   result.ensure(1);
@@ -73,10 +195,7 @@ void sampleConstraints(cvd_handle* h, bool triplet, int num, const int32_t* keyF
     else
       hipLaunchKernelGGL(k_fc_candidates, gridC, dim3(256), 0, s, A, p0, dKeysF.p, dFlow.p, dMaskS.p, dKeys.p, dNValid.p);
     HIP_CHECK(hipGetLastError());
-    size_t tb = tmpBytes;
-    HIP_CHECK(rocprim::segmented_radix_sort_keys_desc(dTmp.p, tb, dKeys.p, dKeysOut.p,
-                                                      static_cast<unsigned int>(static_cast<size_t>(nb) * npx),
-                                                      static_cast<unsigned int>(nb), dSeg.p, dSeg.p + 1, 0, 64, s));
+    sorter.run(nb);
     const size_t ldsBytes = (npx + 31) / 32 * 4;
     if (triplet) {
       allowLds(k_fc_greedy<true>, ldsBytes);
@@ -93,23 +212,27 @@ void sampleConstraints(cvd_handle* h, bool triplet, int num, const int32_t* keyF
     for (int i = 0; i < nb; ++i) off[p0 + i + 1] = off[p0 + i] + cnt[i];
     // grow the result buffer and compact this batch into it
     const size_t total = static_cast<size_t>(off[p0 + nb]) * width;
-    if (total > result.n) {
-      DevBuf<float2> bigger;
-      bigger.ensure(std::max<size_t>(total, result.n * 2));
-      if (off[p0] > 0)
-        HIP_CHECK(hipMemcpyAsync(bigger.p, result.p, sizeof(float2) * off[p0] * width, hipMemcpyDeviceToDevice, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-      std::swap(bigger.p, result.p);
-      std::swap(bigger.n, result.n);
-    }
+    if (total > result.n) result.grow(std::max<size_t>(total, result.n * 2), static_cast<size_t>(off[p0]) * width, s);
     dOff.upload(off.data(), off.size(), s);
     hipLaunchKernelGGL(k_fc_compact, dim3(16, nb), dim3(256), 0, s, static_cast<int>(npx), width, p0, dOff.p, dSlab.p,
                        result.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(s));
   }
-  (triplet ? h->sampledTripOff : h->sampledOff) = off;
+  (triplet ? fe.sampledTripOff : fe.sampledOff) = off;
   for (int i = 0; i <= num; ++i) offsets[i] = off[i];
+}
+
+// the constraints of the last sampleConstraints of that kind: 2 (pairs) resp. 3 (triplets) float2 each
+void getSampledConstraints(cvd_handle* h, bool triplet, float* out) {
+  const Frontend& fe = *h->frontend;
+  const std::vector<long long>& off = triplet ? fe.sampledTripOff : fe.sampledOff;
+  const size_t n = off.empty() ? 0 : static_cast<size_t>(off.back());
+  if (n) {
+    HIP_CHECK(hipMemcpyAsync(out, (triplet ? fe.dSampledTrip : fe.dSampledLoc).p, n * (triplet ? 3 : 2) * sizeof(float2),
+                             hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+  }
 }
 
 // ---- dense consumers of the result (cvd_dense.h) ----------------------------------------------
@@ -131,38 +254,33 @@ void denseMaps(cvd_handle* h, int kind, int first, int count, int w, int hh, voi
   if (w < 2 || hh < 2) throw std::runtime_error("raster too small");
   uploadState(h, L, h->dX);
   hipStream_t s = h->stream;
+  Frontend& fe = *h->frontend;
   const size_t pixels = static_cast<size_t>(count) * hh * w;
   const size_t bytes = pixels * (kind == 0 ? sizeof(float) : kind == 1 ? sizeof(double) * std::max(L.N, 1) : sizeof(float2));
-  h->dDense.ensure((bytes + 7) / 8);
+  fe.dDense.ensure((bytes + 7) / 8);
   if (count == 0) return;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (kernelMs) { HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1)); HIP_CHECK(hipEventRecord(e0, s)); }
+  KernelTimer timer(s, kernelMs, 1);
+  timer.mark();
   const dim3 grid((w * hh + 255) / 256, 1, count), block(256);
   if (kind == 0) {
     CVD_DISPATCH_KD(KD, {
       hipLaunchKernelGGL((k_apply_depth<KD>), grid, block, 0, s, L, w, hh, first, h->dDepth.p, h->dX.p,
-                         reinterpret_cast<float*>(h->dDense.p));
+                         reinterpret_cast<float*>(fe.dDense.p));
     });
   } else if (kind == 1) {
     CVD_DISPATCH_KD(KD, {
-      hipLaunchKernelGGL((k_param_map<KD>), grid, block, 0, s, L, w, hh, first, h->dDepth.p, h->dX.p, h->dDense.p);
+      hipLaunchKernelGGL((k_param_map<KD>), grid, block, 0, s, L, w, hh, first, h->dDepth.p, h->dX.p, fe.dDense.p);
     });
   } else {
-    if (KS == 0) hipLaunchKernelGGL((k_warp_map<0>), grid, block, 0, s, L, w, hh, first, h->dX.p, reinterpret_cast<float2*>(h->dDense.p));
-    else if (KS == 4) hipLaunchKernelGGL((k_warp_map<4>), grid, block, 0, s, L, w, hh, first, h->dX.p, reinterpret_cast<float2*>(h->dDense.p));
-    else hipLaunchKernelGGL((k_warp_map<16>), grid, block, 0, s, L, w, hh, first, h->dX.p, reinterpret_cast<float2*>(h->dDense.p));
+    if (KS == 0) hipLaunchKernelGGL((k_warp_map<0>), grid, block, 0, s, L, w, hh, first, h->dX.p, reinterpret_cast<float2*>(fe.dDense.p));
+    else if (KS == 4) hipLaunchKernelGGL((k_warp_map<4>), grid, block, 0, s, L, w, hh, first, h->dX.p, reinterpret_cast<float2*>(fe.dDense.p));
+    else hipLaunchKernelGGL((k_warp_map<16>), grid, block, 0, s, L, w, hh, first, h->dX.p, reinterpret_cast<float2*>(fe.dDense.p));
   }
   HIP_CHECK(hipGetLastError());
-  if (kernelMs) HIP_CHECK(hipEventRecord(e1, s));
-  if (out) HIP_CHECK(hipMemcpyAsync(out, h->dDense.p, bytes, hipMemcpyDeviceToHost, s));
+  timer.mark();
+  if (out) HIP_CHECK(hipMemcpyAsync(out, fe.dDense.p, bytes, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  if (kernelMs) {
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    *kernelMs = ms;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
+  timer.collect();
 }
 
 // cornerMinEigenVal of n BGR float images (kind 0) / chamfer distance transform of n 8-bit masks (kind 1)
@@ -173,42 +291,36 @@ void imageOps(cvd_handle* h, int kind, int n, int w, int hh, const void* in, flo
   hipStream_t s = h->stream;
   const size_t px = static_cast<size_t>(w) * hh, pixels = px * n;
   if (pixels > (1ull << 31)) throw std::runtime_error("image batch too large for one call");
-  h->dImgOut.ensure(pixels);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (kernelMs) { HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1)); }
+  Frontend& fe = *h->frontend;
+  fe.dImgOut.ensure(pixels);
+  KernelTimer timer(s, kernelMs, 1);
   if (kind == 0) {
-    h->dImgIn.ensure(pixels * 3);
-    h->dImgGray.ensure(pixels);
-    h->dImgCov.ensure(pixels * 3);
-    HIP_CHECK(hipMemcpyAsync(h->dImgIn.p, in, pixels * 3 * sizeof(float), hipMemcpyHostToDevice, s));
-    if (kernelMs) HIP_CHECK(hipEventRecord(e0, s));
-    hipLaunchKernelGGL(k_bgr_to_gray, dim3(static_cast<unsigned>((pixels + 255) / 256)), dim3(256), 0, s, h->dImgIn.p, pixels,
-                       h->dImgGray.p);
+    fe.dImgIn.ensure(pixels * 3);
+    fe.dImgGray.ensure(pixels);
+    fe.dImgCov.ensure(pixels * 3);
+    HIP_CHECK(hipMemcpyAsync(fe.dImgIn.p, in, pixels * 3 * sizeof(float), hipMemcpyHostToDevice, s));
+    timer.mark();
+    hipLaunchKernelGGL(k_bgr_to_gray, dim3(static_cast<unsigned>((pixels + 255) / 256)), dim3(256), 0, s, fe.dImgIn.p, pixels,
+                       fe.dImgGray.p);
     const dim3 grid(static_cast<unsigned>((px + 255) / 256), 1, n);
-    hipLaunchKernelGGL(k_sobel_cov, grid, dim3(256), 0, s, h->dImgGray.p, w, hh, h->dImgCov.p);
-    hipLaunchKernelGGL(k_box_min_eigenval, grid, dim3(256), 0, s, h->dImgCov.p, w, hh, h->dImgOut.p);
+    hipLaunchKernelGGL(k_sobel_cov, grid, dim3(256), 0, s, fe.dImgGray.p, w, hh, fe.dImgCov.p);
+    hipLaunchKernelGGL(k_box_min_eigenval, grid, dim3(256), 0, s, fe.dImgCov.p, w, hh, fe.dImgOut.p);
   } else {
     const size_t tmpPer = static_cast<size_t>(w + 4) * (hh + 4);
-    h->dImgMask.ensure(pixels);
-    h->dImgTmp.ensure(tmpPer * n);
-    HIP_CHECK(hipMemcpyAsync(h->dImgMask.p, in, pixels, hipMemcpyHostToDevice, s));
-    if (kernelMs) HIP_CHECK(hipEventRecord(e0, s));
+    fe.dImgMask.ensure(pixels);
+    fe.dImgTmp.ensure(tmpPer * n);
+    HIP_CHECK(hipMemcpyAsync(fe.dImgMask.p, in, pixels, hipMemcpyHostToDevice, s));
+    timer.mark();
     const size_t lds = kChamferThreads * sizeof(long long) + static_cast<size_t>(w) * sizeof(unsigned int);
     if (lds > 64 * 1024) throw std::runtime_error("mask too wide for the distance transform kernel");
-    hipLaunchKernelGGL(k_chamfer_5x5, dim3(n), dim3(kChamferThreads), lds, s, h->dImgMask.p, w, hh, h->dImgTmp.p,
-                       h->dImgOut.p);
+    hipLaunchKernelGGL(k_chamfer_5x5, dim3(n), dim3(kChamferThreads), lds, s, fe.dImgMask.p, w, hh, fe.dImgTmp.p,
+                       fe.dImgOut.p);
   }
   HIP_CHECK(hipGetLastError());
-  if (kernelMs) HIP_CHECK(hipEventRecord(e1, s));
-  if (out) HIP_CHECK(hipMemcpyAsync(out, h->dImgOut.p, pixels * sizeof(float), hipMemcpyDeviceToHost, s));
+  timer.mark();
+  if (out) HIP_CHECK(hipMemcpyAsync(out, fe.dImgOut.p, pixels * sizeof(float), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  if (kernelMs) {
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    *kernelMs = ms;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
+  timer.collect();
 }
 
 // Quaternion (x, y, z, w) times vector, the way Eigen evaluates it in float (uv = 2 q.vec x v; v + w uv + q.vec x uv)
@@ -223,16 +335,14 @@ void flowGuidedFilter(cvd_handle* h, int n, int first, int count, int w, int hh,
                              const float* depth, const float* cameras, const float* flowF, const uint8_t* maskF,
                              const float* flowB, const uint8_t* maskB, int frameRadius, int spatialRadius, int median,
                              float* out, double* kernelMs) {
-  if (n < 1 || first < 0 || count < 0 || first + count > n) throw std::runtime_error("invalid frame batch");
-  if (w < 1 || hh < 1 || dw < 1 || dh < 1 || !(invAspect > 0.f)) throw std::runtime_error("invalid raster");
-  if (frameRadius < 0 || spatialRadius < 0) throw std::runtime_error("negative filter radius");
-  if (!depth || !cameras || (n > 1 && frameRadius > 0 && (!flowF || !maskF || !flowB || !maskB)))
-    throw std::runtime_error("null filter input");
+  checkFilterBatch(n, first, count, w >= 1 && hh >= 1 && dw >= 1 && dh >= 1 && invAspect > 0.f, frameRadius, spatialRadius,
+                   depth && cameras && !(n > 1 && frameRadius > 0 && (!flowF || !maskF || !flowB || !maskB)));
   if (count == 0) return;
   const long long side = 2ll * spatialRadius + 1, maxSamples = side * side * (2ll * frameRadius + 1);
   if (median && maxSamples > 256)
     throw std::runtime_error("flow guided median filter: (2 spatialRadius + 1)^2 (2 frameRadius + 1) > 256 samples per pixel");
   hipStream_t s = h->stream;
+  Frontend& fe = *h->frontend;
   const size_t px = static_cast<size_t>(w) * hh, dpx = static_cast<size_t>(dw) * dh;
   std::vector<FilterCam> cams(n);
   for (int k = 0; k < n; ++k) {
@@ -245,50 +355,41 @@ void flowGuidedFilter(cvd_handle* h, int n, int first, int count, int w, int hh,
     cams[k].tanH = std::tan(c[7] / 2.f);
     cams[k].tanV = std::tan(c[8] / 2.f);
   }
-  h->dFltCams.upload(cams.data(), n, s);
-  h->dFltDepth.upload(depth, dpx * n, s);
+  fe.dFltCams.upload(cams.data(), n, s);
+  fe.dFltDepth.upload(depth, dpx * n, s);
   const size_t links = n > 1 && frameRadius > 0 ? static_cast<size_t>(n - 1) : 0;
-  h->dFltFlowF.upload(flowF, links * px * 2, s);
-  h->dFltFlowB.upload(flowB, links * px * 2, s);
-  h->dFltMaskF.upload(maskF, links * px, s);
-  h->dFltMaskB.upload(maskB, links * px, s);
-  h->dFltOut.ensure(px * count);
+  fe.dFltFlowF.upload(flowF, links * px * 2, s);
+  fe.dFltFlowB.upload(flowB, links * px * 2, s);
+  fe.dFltMaskF.upload(maskF, links * px, s);
+  fe.dFltMaskB.upload(maskB, links * px, s);
+  fe.dFltOut.ensure(px * count);
   FilterArgs A;
   A.n = n; A.first = first; A.count = count; A.w = w; A.h = hh; A.dw = dw; A.dh = dh; A.invAspect = invAspect;
   A.frameRadius = links ? frameRadius : 0; A.spatialRadius = spatialRadius; A.median = median;
-  A.depth = h->dFltDepth.p; A.cams = h->dFltCams.p;
-  A.flowFwd = reinterpret_cast<const float2*>(h->dFltFlowF.p); A.maskFwd = h->dFltMaskF.p;
-  A.flowBwd = reinterpret_cast<const float2*>(h->dFltFlowB.p); A.maskBwd = h->dFltMaskB.p;
-  A.out = h->dFltOut.p;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (kernelMs) { HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1)); HIP_CHECK(hipEventRecord(e0, s)); }
+  A.depth = fe.dFltDepth.p; A.cams = fe.dFltCams.p;
+  A.flowFwd = reinterpret_cast<const float2*>(fe.dFltFlowF.p); A.maskFwd = fe.dFltMaskF.p;
+  A.flowBwd = reinterpret_cast<const float2*>(fe.dFltFlowB.p); A.maskBwd = fe.dFltMaskB.p;
+  A.out = fe.dFltOut.p;
+  KernelTimer timer(s, kernelMs, 1);
+  timer.mark();
   const dim3 grid(static_cast<unsigned>((px + 255) / 256), 1, count), block(256);
   if (!median) hipLaunchKernelGGL((k_flow_guided_filter<0>), grid, block, 0, s, A);
   else if (maxSamples <= 16) hipLaunchKernelGGL((k_flow_guided_filter<16>), grid, block, 0, s, A);
   else if (maxSamples <= 64) hipLaunchKernelGGL((k_flow_guided_filter<64>), grid, block, 0, s, A);
   else hipLaunchKernelGGL((k_flow_guided_filter<256>), grid, block, 0, s, A);
   HIP_CHECK(hipGetLastError());
-  if (kernelMs) HIP_CHECK(hipEventRecord(e1, s));
-  if (out) HIP_CHECK(hipMemcpyAsync(out, h->dFltOut.p, px * count * sizeof(float), hipMemcpyDeviceToHost, s));
+  timer.mark();
+  if (out) HIP_CHECK(hipMemcpyAsync(out, fe.dFltOut.p, px * count * sizeof(float), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  if (kernelMs) {
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    *kernelMs = ms;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
+  timer.collect();
 }
 
 // DepthVideoProcessor::bilateralFilter (reference lib/Processor.cpp:183-313) on a batch of consecutive frames, cvd_bilateral.h
 void bilateralFilter(cvd_handle* h, int n, int first, int count, int w, int hh, const float* depth, const float* color,
                      int frameRadius, int spatialRadius, float depthSigma, float colorSigma, int median, float* out,
                      double* kernelMs) {
-  if (n < 1 || first < 0 || count < 0 || first + count > n) throw std::runtime_error("invalid frame batch");
-  if (w < 1 || hh < 1) throw std::runtime_error("invalid raster");
-  if (frameRadius < 0 || spatialRadius < 0) throw std::runtime_error("negative filter radius");
   const bool useColor = colorSigma > 0.f;
-  if (!depth || (useColor && !color)) throw std::runtime_error("null filter input");
+  checkFilterBatch(n, first, count, w >= 1 && hh >= 1, frameRadius, spatialRadius, depth && !(useColor && !color));
   const size_t px = static_cast<size_t>(w) * hh;
   if (px * n > (1ull << 31)) throw std::runtime_error("bilateral filter batch too large for one call");
   // [kf - R, kf + R] clipped to [0, n) is the same window with R = min(R, n - 1): the sample counts below are exact
@@ -299,26 +400,27 @@ void bilateralFilter(cvd_handle* h, int n, int first, int count, int w, int hh, 
                                  "exceed the supported %d", samples, kBilateralMaxSamples));
   if (count == 0) return;
   hipStream_t s = h->stream;
-  h->dBilDepth.upload(depth, px * n, s);
-  if (useColor) h->dBilColor.upload(color, px * n * 3, s);
-  h->dBilOut.ensure(px * count);
+  Frontend& fe = *h->frontend;
+  fe.dBilDepth.upload(depth, px * n, s);
+  if (useColor) fe.dBilColor.upload(color, px * n * 3, s);
+  fe.dBilOut.ensure(px * count);
   BilateralArgs A;
   A.n = n; A.w = w; A.h = hh; A.frameRadius = R; A.spatialRadius = spatialRadius;
   A.useDepth = depthSigma > 0.f; A.useColor = useColor;
   A.depthSigma2 = depthSigma * depthSigma; A.colorSigma2 = colorSigma * colorSigma;
-  A.depth = h->dBilDepth.p; A.color = useColor ? h->dBilColor.p : nullptr;
+  A.depth = fe.dBilDepth.p; A.color = useColor ? fe.dBilColor.p : nullptr;
   const long long tileTexels = (kBilateralTileW + 2ll * spatialRadius) * (kBilateralTileH + 2ll * spatialRadius);
   const size_t stageBytes = static_cast<size_t>(tileTexels) * (useColor ? 16 : 4);
   const bool stage = spatialRadius > 0 && stageBytes <= kBilateralMaxLds;
   int P2 = 128;
   while (P2 < samples) P2 *= 2;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (kernelMs) { HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1)); HIP_CHECK(hipEventRecord(e0, s)); }
+  KernelTimer timer(s, kernelMs, 1);
+  timer.mark();
   const dim3 tiles((w + kBilateralTileW - 1) / kBilateralTileW, (hh + kBilateralTileH - 1) / kBilateralTileH), block(256);
   for (int c0 = 0; c0 < count; c0 += 65535) {  // (grid z limit)
     const int nz = std::min(count - c0, 65535);
     A.first = first + c0;
-    A.out = h->dBilOut.p + px * c0;
+    A.out = fe.dBilOut.p + px * c0;
     const dim3 grid(tiles.x, tiles.y, nz);
     if (!median) {
       if (stage && useColor) {
@@ -349,16 +451,10 @@ void bilateralFilter(cvd_handle* h, int n, int first, int count, int w, int hh, 
     }
     HIP_CHECK(hipGetLastError());
   }
-  if (kernelMs) HIP_CHECK(hipEventRecord(e1, s));
-  if (out) HIP_CHECK(hipMemcpyAsync(out, h->dBilOut.p, px * count * sizeof(float), hipMemcpyDeviceToHost, s));
+  timer.mark();
+  if (out) HIP_CHECK(hipMemcpyAsync(out, fe.dBilOut.p, px * count * sizeof(float), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
-  if (kernelMs) {
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    *kernelMs = ms;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
+  timer.collect();
 }
 
 // FlowConstraintsCollection::setStaticFlagFromRansac (no reference implementation; tests/epipolar_reference.py defines it):
@@ -392,63 +488,55 @@ void epipolarStaticFlags(cvd_handle* h, int numPairs, const int64_t* offsets, co
   const size_t perPair = static_cast<size_t>(K) * (9 * sizeof(double) + sizeof(int));
   const int batch = static_cast<int>(std::max<size_t>(1, std::min<size_t>(numPairs, (512ull << 20) / perPair)));
   hipStream_t s = h->stream;
-  h->dEpiLoc.upload(reinterpret_cast<const float4*>(loc), static_cast<size_t>(C), s);
-  h->dEpiOff.upload(reinterpret_cast<const long long*>(offsets), static_cast<size_t>(numPairs) + 1, s);
-  h->dEpiNorm.ensure(batch);
-  h->dEpiF.ensure(static_cast<size_t>(batch) * K * 9);
-  h->dEpiCount.ensure(static_cast<size_t>(batch) * K);
-  h->dEpiFlags.ensure(static_cast<size_t>(C));
-  h->dEpiFbest.ensure(static_cast<size_t>(numPairs) * 9);
-  h->dEpiBest.ensure(static_cast<size_t>(numPairs) * 2);
-  hipEvent_t ev[5] = {};
-  if (kernelMs)
-    for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
+  Frontend& fe = *h->frontend;
+  fe.dEpiLoc.upload(reinterpret_cast<const float4*>(loc), static_cast<size_t>(C), s);
+  fe.dEpiOff.upload(reinterpret_cast<const long long*>(offsets), static_cast<size_t>(numPairs) + 1, s);
+  fe.dEpiNorm.ensure(batch);
+  fe.dEpiF.ensure(static_cast<size_t>(batch) * K * 9);
+  fe.dEpiCount.ensure(static_cast<size_t>(batch) * K);
+  fe.dEpiFlags.ensure(static_cast<size_t>(C));
+  fe.dEpiFbest.ensure(static_cast<size_t>(numPairs) * 9);
+  fe.dEpiBest.ensure(static_cast<size_t>(numPairs) * 2);
+  KernelTimer timer(s, kernelMs, 4);
   EpiArgs A;
   A.K = K;
   A.seed = seed;
   A.w = pixelScale;
   A.thresh2 = thresholdPx * thresholdPx;
-  A.loc = h->dEpiLoc.p;
-  A.norm = h->dEpiNorm.p;
-  A.F = h->dEpiF.p;
-  A.count = h->dEpiCount.p;
-  A.flags = h->dEpiFlags.p;
+  A.loc = fe.dEpiLoc.p;
+  A.norm = fe.dEpiNorm.p;
+  A.F = fe.dEpiF.p;
+  A.count = fe.dEpiCount.p;
+  A.flags = fe.dEpiFlags.p;
   for (int p0 = 0; p0 < numPairs; p0 += batch) {
     const int np = std::min(batch, numPairs - p0);
     A.numPairs = np;
     A.pairBase = p0;
-    A.off = h->dEpiOff.p + p0;
-    A.Fbest = h->dEpiFbest.p + static_cast<size_t>(p0) * 9;
-    A.best = h->dEpiBest.p + static_cast<size_t>(p0) * 2;
-    if (kernelMs) HIP_CHECK(hipEventRecord(ev[0], s));
+    A.off = fe.dEpiOff.p + p0;
+    A.Fbest = fe.dEpiFbest.p + static_cast<size_t>(p0) * 9;
+    A.best = fe.dEpiBest.p + static_cast<size_t>(p0) * 2;
+    timer.mark();
     hipLaunchKernelGGL(k_epi_normalise, dim3(np), dim3(kEpiThreads), 0, s, A);
     HIP_CHECK(hipGetLastError());
-    if (kernelMs) HIP_CHECK(hipEventRecord(ev[1], s));
+    timer.mark();
     hipLaunchKernelGGL(k_epi_hypotheses, dim3(np, (K + kEpiHypThreads - 1) / kEpiHypThreads), dim3(kEpiHypThreads), 0, s, A);
     HIP_CHECK(hipGetLastError());
-    if (kernelMs) HIP_CHECK(hipEventRecord(ev[2], s));
+    timer.mark();
     hipLaunchKernelGGL(k_epi_score, dim3(np, (K + kEpiThreads - 1) / kEpiThreads), dim3(kEpiThreads), 0, s, A);
     HIP_CHECK(hipGetLastError());
-    if (kernelMs) HIP_CHECK(hipEventRecord(ev[3], s));
+    timer.mark();
     hipLaunchKernelGGL(k_epi_select, dim3(np), dim3(kEpiThreads), 0, s, A);
     HIP_CHECK(hipGetLastError());
-    if (kernelMs) HIP_CHECK(hipEventRecord(ev[4], s));
-    if (counts) h->dEpiCount.download(counts + static_cast<size_t>(p0) * K, static_cast<size_t>(np) * K, s);
-    if (hypotheses) h->dEpiF.download(hypotheses + static_cast<size_t>(p0) * K * 9, static_cast<size_t>(np) * K * 9, s);
+    timer.mark();
+    if (counts) fe.dEpiCount.download(counts + static_cast<size_t>(p0) * K, static_cast<size_t>(np) * K, s);
+    if (hypotheses) fe.dEpiF.download(hypotheses + static_cast<size_t>(p0) * K * 9, static_cast<size_t>(np) * K * 9, s);
     if (kernelMs || counts || hypotheses) HIP_CHECK(hipStreamSynchronize(s));  // (the next batch reuses the buffers)
-    if (kernelMs)
-      for (int k = 0; k < 4; ++k) {
-        float ms = 0.f;
-        HIP_CHECK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-        kernelMs[k] += ms;
-      }
+    timer.collect();
   }
-  h->dEpiFlags.download(isStatic, static_cast<size_t>(C), s);
-  if (fundamental) h->dEpiFbest.download(fundamental, static_cast<size_t>(numPairs) * 9, s);
-  if (best) h->dEpiBest.download(best, static_cast<size_t>(numPairs) * 2, s);
+  fe.dEpiFlags.download(isStatic, static_cast<size_t>(C), s);
+  if (fundamental) fe.dEpiFbest.download(fundamental, static_cast<size_t>(numPairs) * 9, s);
+  if (best) fe.dEpiBest.download(best, static_cast<size_t>(numPairs) * 2, s);
   HIP_CHECK(hipStreamSynchronize(s));
-  if (kernelMs)
-    for (auto& e : ev) (void)hipEventDestroy(e);
 }
 
 // DepthVideoProcessor::computeTracks (reference lib/Processor.cpp:646-886), cvd_tracks.h.  Batches of frames bound the
@@ -488,11 +576,11 @@ void computeTracks(cvd_handle* h, int F, int H, int W, float invAspect, const ui
     throw std::runtime_error(fmt("compute tracks: image too large: the prune and spawn bitmasks of a %d x %d image need %zu B of "
                                  "LDS (> %zu)", W, H, maskBytes, kMaxLds - sizeof(TrackShared)));
   hipStream_t s = h->stream;
-  DevBuf<unsigned char> dActive, dPair, dMask, dTmp;
+  DevBuf<unsigned char> dActive, dPair, dMask;
   DevBuf<float> dCorner, dDyn;
   DevBuf<float2> dFlow;
   DevBuf<unsigned long long> dKeys, dKeysOut;
-  DevBuf<unsigned int> dNValid, dSeg;
+  DevBuf<unsigned int> dNValid;
   DevBuf<int> dFrameStart, dFrameCount, dObsTrack;
   DevBuf<float2> dObsLoc;
   DevBuf<TrackState> dState;
@@ -512,14 +600,8 @@ void computeTracks(cvd_handle* h, int F, int H, int W, float invAspect, const ui
   dKeys.ensure(static_cast<size_t>(PB) * npx);
   dKeysOut.ensure(static_cast<size_t>(PB) * npx);
   dNValid.ensure(PB);
-  std::vector<unsigned int> seg(PB + 1);
-  for (int i = 0; i <= PB; ++i) seg[i] = static_cast<unsigned int>(static_cast<size_t>(i) * npx);
-  dSeg.upload(seg.data(), seg.size(), s);
-  size_t tmpBytes = 0;
-  HIP_CHECK(rocprim::segmented_radix_sort_keys_desc(nullptr, tmpBytes, dKeys.p, dKeysOut.p,
-                                                    static_cast<unsigned int>(static_cast<size_t>(PB) * npx),
-                                                    static_cast<unsigned int>(PB), dSeg.p, dSeg.p + 1, 0, 64, s));
-  dTmp.ensure(tmpBytes);
+  SegmentedKeySort sorter(PB, npx, dKeys.p, dKeysOut.p, s);
+  Frontend& fe = *h->frontend;
   // observation / track buffers: the walk's worst case per frame is (continued + spawned) <= W H each; typical videos keep
   // a few hundred tracks per frame, so these start small and grow on demand
   dFrameStart.ensure(F);
@@ -528,46 +610,38 @@ void computeTracks(cvd_handle* h, int F, int H, int W, float invAspect, const ui
   int trackCap = static_cast<int>(std::min<size_t>(npx * 2, (size_t(1) << 31) - 1));
   dObsTrack.ensure(obsCap);
   dObsLoc.ensure(obsCap);
-  h->dTrkStart.ensure(trackCap);
+  fe.dTrkStart.ensure(trackCap);
   TrackState st{0, 0, 0, 0};
   dState.upload(&st, 1, s);
   const size_t walkLds = maskBytes;
   allowLds(k_track_walk, walkLds + sizeof(TrackShared));
-  hipEvent_t ev[5] = {};
-  for (auto& e : ev) HIP_CHECK(hipEventCreate(&e));
-  double ms[4] = {0, 0, 0, 0};
-  auto addTime = [&](int k) {
-    float t = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
-    ms[k] += t;
-  };
+  // (always timed: the host waits for the sort through the timer's event; kernelMs is written on success only)
+  double ms[4];
+  KernelTimer timer(s, ms, 4);
   try {
     for (int f0 = 0; f0 < F; f0 += PB) {
       const int nb = std::min(PB, F - f0);
-      HIP_CHECK(hipEventRecord(ev[0], s));
+      timer.mark();
       HIP_CHECK(hipMemsetAsync(dNValid.p, 0, sizeof(unsigned int) * nb, s));
       hipLaunchKernelGGL(k_track_candidates, dim3(static_cast<unsigned>((npx + 255) / 256), nb), dim3(256), 0, s, A, f0,
                          dKeys.p, dNValid.p);
       HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipEventRecord(ev[1], s));
-      size_t tb = tmpBytes;
-      HIP_CHECK(rocprim::segmented_radix_sort_keys_desc(dTmp.p, tb, dKeys.p, dKeysOut.p,
-                                                        static_cast<unsigned int>(static_cast<size_t>(nb) * npx),
-                                                        static_cast<unsigned int>(nb), dSeg.p, dSeg.p + 1, 0, 64, s));
-      HIP_CHECK(hipEventRecord(ev[2], s));
-      HIP_CHECK(hipEventSynchronize(ev[2]));
-      addTime(0);
-      addTime(1);
+      timer.mark();
+      sorter.run(nb);
+      timer.mark();
+      timer.wait();
+      timer.collect();
       for (int fw = f0; fw < f0 + nb;) {
-        TrackBufs B{dFrameStart.p, dFrameCount.p, dObsTrack.p, dObsLoc.p, h->dTrkStart.p, obsCap, trackCap};
-        HIP_CHECK(hipEventRecord(ev[2], s));
+        TrackBufs B{dFrameStart.p, dFrameCount.p, dObsTrack.p, dObsLoc.p, fe.dTrkStart.p, obsCap, trackCap};
+        timer.seek(2);
+        timer.mark();
         hipLaunchKernelGGL(k_track_walk, dim3(1), dim3(kTrackThreads), walkLds, s, A, fw, f0 + nb,
                            dKeysOut.p + static_cast<size_t>(fw - f0) * npx, dNValid.p + (fw - f0), B, dState.p);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(ev[3], s));
+        timer.mark();
         dState.download(&st, 1, s);
         HIP_CHECK(hipStreamSynchronize(s));
-        addTime(2);
+        timer.collect();
         if (st.stopFrame < fw) throw std::runtime_error("compute tracks: the walk made no progress");
         fw = st.stopFrame;
         if (fw < f0 + nb) {  // grow the buffers (keeping their contents) and resume at that frame
@@ -576,18 +650,9 @@ void computeTracks(cvd_handle* h, int F, int H, int W, float invAspect, const ui
           const size_t nt = std::min(maxCap, std::max<size_t>(2 * static_cast<size_t>(trackCap), st.numTracks + npx));
           if (no == static_cast<size_t>(obsCap) && nt == static_cast<size_t>(trackCap))
             throw std::runtime_error("compute tracks: observation buffer limit reached");
-          DevBuf<int> t1, t3;
-          DevBuf<float2> t2;
-          t1.ensure(no);
-          t2.ensure(no);
-          t3.ensure(nt);
-          HIP_CHECK(hipMemcpyAsync(t1.p, dObsTrack.p, sizeof(int) * st.obsUsed, hipMemcpyDeviceToDevice, s));
-          HIP_CHECK(hipMemcpyAsync(t2.p, dObsLoc.p, sizeof(float2) * st.obsUsed, hipMemcpyDeviceToDevice, s));
-          HIP_CHECK(hipMemcpyAsync(t3.p, h->dTrkStart.p, sizeof(int) * st.numTracks, hipMemcpyDeviceToDevice, s));
-          HIP_CHECK(hipStreamSynchronize(s));
-          std::swap(t1.p, dObsTrack.p); std::swap(t1.n, dObsTrack.n);
-          std::swap(t2.p, dObsLoc.p); std::swap(t2.n, dObsLoc.n);
-          std::swap(t3.p, h->dTrkStart.p); std::swap(t3.n, h->dTrkStart.n);
+          dObsTrack.grow(no, st.obsUsed, s);
+          dObsLoc.grow(no, st.obsUsed, s);
+          fe.dTrkStart.grow(nt, st.numTracks, s);
           obsCap = static_cast<int>(no);
           trackCap = static_cast<int>(nt);
         }
@@ -595,44 +660,45 @@ void computeTracks(cvd_handle* h, int F, int H, int W, float invAspect, const ui
     }
     // the table: lengths, minTrackLength pruning, per-track location lists
     const int T = st.numTracks, O = st.obsUsed;
-    h->dTrkLen.ensure(T);
-    h->dTrkKeptLen.ensure(static_cast<size_t>(T) + 1);
-    h->dTrkOff.ensure(static_cast<size_t>(T) + 1);
-    h->dTrkKept.ensure(T);
-    HIP_CHECK(hipEventRecord(ev[3], s));
+    fe.dTrkLen.ensure(T);
+    fe.dTrkKeptLen.ensure(static_cast<size_t>(T) + 1);
+    fe.dTrkOff.ensure(static_cast<size_t>(T) + 1);
+    fe.dTrkKept.ensure(T);
+    timer.seek(3);
+    timer.mark();
     long long keptObs = 0;
     if (T > 0) {
-      HIP_CHECK(hipMemsetAsync(h->dTrkLen.p, 0, sizeof(int) * T, s));
-      HIP_CHECK(hipMemsetAsync(h->dTrkKeptLen.p + T, 0, sizeof(int), s));  // (the scan's last item: offset[T] = the total)
-      hipLaunchKernelGGL(k_track_lengths, dim3((O + 255) / 256), dim3(256), 0, s, O, dObsTrack.p, h->dTrkLen.p);
-      hipLaunchKernelGGL(k_track_keep, dim3((T + 255) / 256), dim3(256), 0, s, T, minTrackLength, h->dTrkLen.p,
-                         h->dTrkKeptLen.p, h->dTrkKept.p);
+      HIP_CHECK(hipMemsetAsync(fe.dTrkLen.p, 0, sizeof(int) * T, s));
+      HIP_CHECK(hipMemsetAsync(fe.dTrkKeptLen.p + T, 0, sizeof(int), s));  // (the scan's last item: offset[T] = the total)
+      hipLaunchKernelGGL(k_track_lengths, dim3((O + 255) / 256), dim3(256), 0, s, O, dObsTrack.p, fe.dTrkLen.p);
+      hipLaunchKernelGGL(k_track_keep, dim3((T + 255) / 256), dim3(256), 0, s, T, minTrackLength, fe.dTrkLen.p,
+                         fe.dTrkKeptLen.p, fe.dTrkKept.p);
       HIP_CHECK(hipGetLastError());
       size_t scanBytes = 0;
-      HIP_CHECK(rocprim::exclusive_scan(nullptr, scanBytes, h->dTrkKeptLen.p, h->dTrkOff.p, 0, static_cast<size_t>(T) + 1,
+      HIP_CHECK(rocprim::exclusive_scan(nullptr, scanBytes, fe.dTrkKeptLen.p, fe.dTrkOff.p, 0, static_cast<size_t>(T) + 1,
                                         rocprim::plus<int>(), s));
       DevBuf<unsigned char> scanTmp;
       scanTmp.ensure(scanBytes);
-      HIP_CHECK(rocprim::exclusive_scan(scanTmp.p, scanBytes, h->dTrkKeptLen.p, h->dTrkOff.p, 0, static_cast<size_t>(T) + 1,
+      HIP_CHECK(rocprim::exclusive_scan(scanTmp.p, scanBytes, fe.dTrkKeptLen.p, fe.dTrkOff.p, 0, static_cast<size_t>(T) + 1,
                                         rocprim::plus<int>(), s));
       int total = 0;
-      HIP_CHECK(hipMemcpyAsync(&total, h->dTrkOff.p + T, sizeof(int), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(&total, fe.dTrkOff.p + T, sizeof(int), hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
       keptObs = total;
-      h->dTrkLoc.ensure(static_cast<size_t>(std::max(total, 1)));
+      fe.dTrkLoc.ensure(static_cast<size_t>(std::max(total, 1)));
       hipLaunchKernelGGL(k_track_scatter, dim3(16, F), dim3(256), 0, s, dFrameStart.p, dFrameCount.p, dObsTrack.p, dObsLoc.p,
-                         h->dTrkStart.p, h->dTrkKept.p, h->dTrkOff.p, h->dTrkLoc.p);
+                         fe.dTrkStart.p, fe.dTrkKept.p, fe.dTrkOff.p, fe.dTrkLoc.p);
       HIP_CHECK(hipGetLastError());
     }
-    HIP_CHECK(hipEventRecord(ev[4], s));
+    timer.mark();
     HIP_CHECK(hipStreamSynchronize(s));
-    addTime(3);
-    h->trkTracks = T;
-    h->trkKeptObs = keptObs;
+    timer.collect();
+    fe.trkTracks = T;
+    fe.trkKeptObs = keptObs;
     long long kept = 0;
     if (T > 0) {
       std::vector<unsigned char> k(T);
-      h->dTrkKept.download(k.data(), T, s);
+      fe.dTrkKept.download(k.data(), T, s);
       HIP_CHECK(hipStreamSynchronize(s));
       for (unsigned char v : k) kept += v;
     }
@@ -640,23 +706,22 @@ void computeTracks(cvd_handle* h, int F, int H, int W, float invAspect, const ui
     counts[1] = kept;
     counts[2] = keptObs;
   } catch (...) {
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    h->trkTracks = h->trkKeptObs = 0;
+    fe.trkTracks = fe.trkKeptObs = 0;
     throw;
   }
-  for (auto& e : ev) (void)hipEventDestroy(e);
   if (kernelMs) std::copy(ms, ms + 4, kernelMs);
 }
 
 void getTracks(cvd_handle* h, int32_t* startFrame, int32_t* length, uint8_t* kept, float* loc) {
   hipStream_t s = h->stream;
-  const size_t T = static_cast<size_t>(h->trkTracks);
+  const Frontend& fe = *h->frontend;
+  const size_t T = static_cast<size_t>(fe.trkTracks);
   if (T > 0) {
-    if (startFrame) h->dTrkStart.download(startFrame, T, s);
-    if (length) h->dTrkLen.download(length, T, s);
-    if (kept) h->dTrkKept.download(kept, T, s);
+    if (startFrame) fe.dTrkStart.download(startFrame, T, s);
+    if (length) fe.dTrkLen.download(length, T, s);
+    if (kept) fe.dTrkKept.download(kept, T, s);
   }
-  if (loc && h->trkKeptObs > 0) h->dTrkLoc.download(reinterpret_cast<float2*>(loc), static_cast<size_t>(h->trkKeptObs), s);
+  if (loc && fe.trkKeptObs > 0) fe.dTrkLoc.download(reinterpret_cast<float2*>(loc), static_cast<size_t>(fe.trkKeptObs), s);
   HIP_CHECK(hipStreamSynchronize(s));
 }
 
@@ -706,36 +771,33 @@ void flowConsistencyMasks(cvd_handle* h, int numFrames, int hh, int w, int chann
   }
   hipStream_t s = h->stream;
   const size_t P = static_cast<size_t>(numPairs);
-  h->dFmColor.upload(color, static_cast<size_t>(numFrames) * npx * channels, s);
-  h->dFmPairs.upload(reinterpret_cast<const int2*>(pairFrames), P, s);
-  h->dFmFlowAB.upload(reinterpret_cast<const float2*>(flowAB), P * npx, s);
-  h->dFmFlowBA.upload(reinterpret_cast<const float2*>(flowBA), P * npx, s);
-  h->dFmMaskAB.ensure(P * npx);
-  h->dFmMaskBA.ensure(P * npx);
-  h->dFmKept.ensure(P * 2);
-  if (errors) h->dFmErr.ensure(P * 2 * npx);
-  HIP_CHECK(hipMemsetAsync(h->dFmKept.p, 0, sizeof(int) * P * 2, s));
+  Frontend& fe = *h->frontend;
+  fe.dFmColor.upload(color, static_cast<size_t>(numFrames) * npx * channels, s);
+  fe.dFmPairs.upload(reinterpret_cast<const int2*>(pairFrames), P, s);
+  fe.dFmFlowAB.upload(reinterpret_cast<const float2*>(flowAB), P * npx, s);
+  fe.dFmFlowBA.upload(reinterpret_cast<const float2*>(flowBA), P * npx, s);
+  fe.dFmMaskAB.ensure(P * npx);
+  fe.dFmMaskBA.ensure(P * npx);
+  fe.dFmKept.ensure(P * 2);
+  if (errors) fe.dFmErr.ensure(P * 2 * npx);
+  HIP_CHECK(hipMemsetAsync(fe.dFmKept.p, 0, sizeof(int) * P * 2, s));
   FlowMaskArgs A;
   A.w = w;
   A.h = hh;
   // thresholds of utils/consistency.py:53-63, computed in double and rounded once (numpy compares the f32 errors in f32)
   A.flowT = static_cast<float>(static_cast<double>(flowThresh) * static_cast<double>(flowThresh));
   A.colorT = static_cast<float>(channels * (static_cast<double>(colorThresh) * static_cast<double>(colorThresh)));
-  A.color = h->dFmColor.p;
-  A.pairs = h->dFmPairs.p;
-  A.flowAB = h->dFmFlowAB.p;
-  A.flowBA = h->dFmFlowBA.p;
-  A.maskAB = h->dFmMaskAB.p;
-  A.maskBA = h->dFmMaskBA.p;
-  A.kept = h->dFmKept.p;
-  A.errors = errors ? h->dFmErr.p : nullptr;
+  A.color = fe.dFmColor.p;
+  A.pairs = fe.dFmPairs.p;
+  A.flowAB = fe.dFmFlowAB.p;
+  A.flowBA = fe.dFmFlowBA.p;
+  A.maskAB = fe.dFmMaskAB.p;
+  A.maskBA = fe.dFmMaskBA.p;
+  A.kept = fe.dFmKept.p;
+  A.errors = errors ? fe.dFmErr.p : nullptr;
   const int pix = pixelsPerThread ? pixelsPerThread : (w % 4 == 0 ? 4 : 1);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (kernelMs) {
-    HIP_CHECK(hipEventCreate(&e0));
-    HIP_CHECK(hipEventCreate(&e1));
-    HIP_CHECK(hipEventRecord(e0, s));
-  }
+  KernelTimer timer(s, kernelMs, 1);
+  timer.mark();
   switch (channels) {
     case 1: launchFlowMasks<1>(A, numPairs, pix, s); break;
     case 2: launchFlowMasks<2>(A, numPairs, pix, s); break;
@@ -743,19 +805,13 @@ void flowConsistencyMasks(cvd_handle* h, int numFrames, int hh, int w, int chann
     default: launchFlowMasks<4>(A, numPairs, pix, s); break;
   }
   HIP_CHECK(hipGetLastError());
-  if (kernelMs) HIP_CHECK(hipEventRecord(e1, s));
-  h->dFmMaskAB.download(maskAB, P * npx, s);
-  h->dFmMaskBA.download(maskBA, P * npx, s);
-  if (kept) h->dFmKept.download(kept, P * 2, s);
-  if (errors) h->dFmErr.download(reinterpret_cast<float2*>(errors), P * 2 * npx, s);
+  timer.mark();
+  fe.dFmMaskAB.download(maskAB, P * npx, s);
+  fe.dFmMaskBA.download(maskBA, P * npx, s);
+  if (kept) fe.dFmKept.download(kept, P * 2, s);
+  if (errors) fe.dFmErr.download(reinterpret_cast<float2*>(errors), P * 2 * npx, s);
   HIP_CHECK(hipStreamSynchronize(s));
-  if (kernelMs) {
-    float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    *kernelMs = ms;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-  }
+  timer.collect();
 }
 
 // One kernel of this translation unit's code object is looked up at handle creation: the HIP runtime loads a unit's device

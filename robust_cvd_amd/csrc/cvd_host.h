@@ -1,5 +1,7 @@
 // cvd_host.h -- host-side state shared by the translation units of libcvd_hip.so: error macros, device buffers, the
-// handle (one DepthVideo + depth stream), the per-solve context and the functions the units call across.
+// handle (one DepthVideo + depth stream), the per-solve context and the functions the units call across.  It includes the
+// solver's kernel headers, whose types the handle embeds; the front-end operators' headers and device state belong to
+// cvd_frontend.hip alone (cvd::Frontend, an incomplete type here).
 // gfx950 only.  There is NO CPU path.
 #pragma once
 
@@ -39,13 +41,6 @@
 #include "cvd_cross.h"
 #include "cvd_dense_walk.h"
 #include "cvd_triplets.h"
-#include "cvd_dense.h"
-#include "cvd_sampling.h"
-#include "cvd_imageops.h"
-#include "cvd_filter.h"
-#include "cvd_bilateral.h"
-#include "cvd_epipolar.h"
-#include "cvd_tracks.h"
 
 
 namespace cvd {
@@ -101,6 +96,15 @@ struct DevBuf {
   }
   void download(T* dst, size_t count, hipStream_t s) const {
     if (count) HIP_CHECK(hipMemcpyAsync(dst, p, count * sizeof(T), hipMemcpyDeviceToHost, s));
+  }
+  // a buffer of newCount elements that keeps the first keepCount (copied on s, which is idle again on return)
+  void grow(size_t newCount, size_t keepCount, hipStream_t s) {
+    DevBuf<T> bigger;
+    bigger.ensure(newCount);
+    if (keepCount) HIP_CHECK(hipMemcpyAsync(bigger.p, p, keepCount * sizeof(T), hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    std::swap(p, bigger.p);
+    std::swap(n, bigger.n);
   }
 };
 
@@ -166,12 +170,14 @@ enum ProblemKind { PK_POSE_STEP = 0, PK_NORMALIZE = 1 };
 // exchange layer of the pair-sharded mode (cvd_comm.hip)
 enum CommType { CT_F64 = 0, CT_F32, CT_I32, CT_U64 };
 struct LocalGroup;  // test backend: the ranks are handles of one process on one device
+struct Frontend;    // device state of the front-end operators (cvd_frontend.hip)
 
 }  // namespace cvd
 
 namespace cvd {
 std::shared_ptr<LocalGroup> joinLocalGroup(unsigned long long key, int world);
 void leaveLocalGroup(LocalGroup& g);
+std::shared_ptr<Frontend> makeFrontend();
 }
 
 using namespace cvd;
@@ -296,41 +302,13 @@ struct cvd_handle_t {
   DevBuf<float> dMinv;
   DevBuf<double> dFdot, dCostItem, dCostFrame, dScal, dHd, dFocal;
   DevBuf<double> dStatPart;  // per-workgroup partials of k_step_stats
-  DevBuf<double> dDense;     // output of the dense consumer kernels (cvd_dense.h)
-  DevBuf<float> dImgIn, dImgGray, dImgCov, dImgOut;  // cvd_imageops.h staging
-  DevBuf<unsigned char> dImgMask;
-  DevBuf<unsigned int> dImgTmp;
   // AdaptiveDeformationCost: dynamic masks of all frames (cvd_set_dynamic_masks) and the vertex weights of the
   // current depth grid
   DevBuf<unsigned char> dDynMask;
   DevBuf<double> dAdaptW;
   int dynW = 0, dynH = 0, adaptGx = 0, adaptGy = 0;
   bool haveDynMasks = false;
-  DevBuf<float> dFltDepth, dFltOut, dFltFlowF, dFltFlowB;  // cvd_filter.h staging
-  DevBuf<unsigned char> dFltMaskF, dFltMaskB;
-  DevBuf<FilterCam> dFltCams;
-  DevBuf<float> dBilDepth, dBilColor, dBilOut;  // cvd_bilateral.h staging
-  // cvd_flowmask.h staging: colour table, pair frames, both flows, both masks, kept counts, error maps
-  DevBuf<float> dFmColor;
-  DevBuf<int2> dFmPairs;
-  DevBuf<float2> dFmFlowAB, dFmFlowBA, dFmErr;
-  DevBuf<unsigned char> dFmMaskAB, dFmMaskBA;
-  DevBuf<int> dFmKept;
-  // cvd_epipolar.h: constraints, offsets, per-pair normalisation, per-hypothesis F / counts (one batch of pairs), results
-  DevBuf<float4> dEpiLoc;
-  DevBuf<long long> dEpiOff;
-  DevBuf<EpiNorm> dEpiNorm;
-  DevBuf<double> dEpiF, dEpiFbest;
-  DevBuf<int> dEpiCount, dEpiBest;
-  DevBuf<unsigned char> dEpiFlags;
-  // constraint sampling (cvd_sampling.h): result of the last cvd_sample_pair_constraints
-  DevBuf<float2> dSampledLoc, dSampledTrip;  // 2 resp. 3 float2 per constraint
-  std::vector<long long> sampledOff, sampledTripOff;
-  // feature tracks (cvd_tracks.h): the table of the last cvd_compute_tracks
-  DevBuf<int> dTrkStart, dTrkLen, dTrkKeptLen, dTrkOff;
-  DevBuf<unsigned char> dTrkKept;
-  DevBuf<float2> dTrkLoc;
-  long long trkTracks = 0, trkKeptObs = 0;
+  std::shared_ptr<Frontend> frontend;  // the front-end operators' buffers and last results (cvd_create: makeFrontend)
 
   // coarse (pose-graph) level of the two-level preconditioner (cvd_coarse.h)
   struct CoarseHost {
@@ -724,6 +702,7 @@ void evaluate(cvd_handle* h, const cvd_opt_params& p, double depthDeformReg, con
 void sampleConstraints(cvd_handle* h, bool triplet, int num, const int32_t* keyFrames, const float* corner, const float* flow,
                        const uint8_t* mask, const float* flow2, const uint8_t* mask2, const float* dyn, int dw, int dh,
                        int matchSeparation, float minDynamicDistance, int64_t* offsets);
+void getSampledConstraints(cvd_handle* h, bool triplet, float* out);
 void denseMaps(cvd_handle* h, int kind, int first, int count, int w, int hh, void* out, double* kernelMs);
 void imageOps(cvd_handle* h, int kind, int n, int w, int hh, const void* in, float* out, double* kernelMs);
 void touchModule_setup();
