@@ -385,6 +385,57 @@ int32_t cvd_flow_consistency_masks(cvd_handle* h, int32_t num_frames, int32_t he
                                    const float* flow_ba, float flow_thresh, float color_thresh, uint8_t* mask_ab,
                                    uint8_t* mask_ba, int32_t* kept, float* errors, double* kernel_ms);
 
+/* ---- geometric consistency loss of flow pairs and its depth gradient: the static terms of the reference's fine-tuning loss,
+ * ConsistencyLoss (loss/consistency_loss.py:92-182, 219-239; utils/geometry.py; utils/loss.py:62-80), DESIGN.md §3.10.
+ * Independent of cvd_set_video.  One forward pass over all pairs and both directions, one backward pass; every real array has
+ * the precision desc names (float or double):
+ *   depth      [F][H][W]
+ *   extrinsics [F][3][4]       [R | t], columns right / up / backward (the camera looks down -z)
+ *   intrinsics [F][4]          (fx, fy, cx, cy), pixels
+ *   warp       [F][2][H][W]    pixel offsets added to the pixel grid, planar (x then y); read only when desc.have_warp
+ *   pair_frames [P][2]         (a, b), a != b
+ *   flow_ab, flow_ba [P][2][H][W]  planar flow a -> b on a's raster, b -> a on b's raster, pixels
+ *   weight_ab, weight_ba [P][H][W] weights of the samples (the reference's masks; multiplied, not tested)
+ * Per pair and direction (ref r, target t): pix = (x, y) + warp_r; X_t = R_t^T (R_r ray(pix) D_r + t_r - t_t); the reprojection
+ * error |project_t(X_t) - (pix + flow)|, the disparity error 1 / X_t.z - 1 / z_w and the depth-ratio error
+ * lambda_depth_ratio log(min / max of |z_w|, |X_t.z|), z_w = -D_t sampled bilinearly at (pix + flow) size / (size - 1) - 0.5
+ * (clamped to the image: grid_sample, align_corners = false, border).  Each goes through the distance rho and a weighted mean
+ * sum w rho / max(sum w, 1e-6); per pair  reproj = lambda_reprojection mean_k(.),  disp = lambda_disparity mean_k(fbar_k .) with
+ * fbar_k the mean focal length of the ref frames of all pairs,  depth ratio = mean_k(.);  a term exists only when its lambda
+ * is > 0 (else 0);  total = mean over pairs of the sum of the terms.
+ *   total [1], terms [P][3]    (reproj, disp, depth ratio), double in both precisions
+ *   grad  [F][H][W]            optional (may be NULL): d total / d depth, in the arrays' precision
+ *   kernel_ms [2]              optional (may be NULL): {forward, backward} kernel times, HIP events
+ * The forward results repeat bit for bit; the gradient is accumulated with float atomics (in a fixed order in the deterministic
+ * build).  Rejected before any device work: a desc of another header revision (struct_size), width or height < 2, num_pairs < 1,
+ * a pair frame out of range or a pair naming one frame twice, a negative or non-finite lambda, distance_scale <= 0, a non-finite
+ * distance_alpha, null arrays.  All lambdas 0: zeros. */
+enum { CVD_PRECISION_F32 = 0, CVD_PRECISION_F64 = 1 };
+enum { CVD_DISTANCE_L1 = 0, CVD_DISTANCE_L2 = 1, CVD_DISTANCE_SMOOTH_L1 = 2, CVD_DISTANCE_CAUCHY = 3, CVD_DISTANCE_GENERAL = 4 };
+typedef struct cvd_consistency_desc {
+  uint64_t struct_size;        /* CVD_STRUCT_STAMP(cvd_consistency_desc), set by the caller */
+  int32_t precision;           /* CVD_PRECISION_* of every real array */
+  int32_t num_frames, num_pairs, height, width;
+  int32_t distance_type;       /* CVD_DISTANCE_*: l1 = |e / scale|; l2 / smooth_l1 / cauchy / general = the general robust loss
+                                  (reference loss/general.py, exact branch) at alpha = 2 / 1 / 0 / distance_alpha */
+  int32_t have_warp;
+  int32_t reserved;            /* 0 */
+  double lambda_reprojection, lambda_disparity, lambda_depth_ratio;   /* reference defaults 1, 0, 100 */
+  double distance_scale, distance_alpha;
+} cvd_consistency_desc;
+int32_t cvd_consistency_loss(cvd_handle* h, const cvd_consistency_desc* desc, const void* depth, const void* extrinsics,
+                             const void* intrinsics, const void* warp, const int32_t* pair_frames, const void* flow_ab,
+                             const void* flow_ba, const void* weight_ab, const void* weight_ba, double* total, double* terms,
+                             void* grad, double* kernel_ms);
+/* The same on DEVICE arrays (inputs and results), enqueued on `stream` (a hipStream_t of the handle's device): no copy and no
+ * host synchronisation; the results are valid once the stream reaches the end of the call.  One call at a time per handle (its
+ * scratch buffers are shared).  pair_frames cannot be checked before the launch here: a pair that names a frame outside [0, F)
+ * or one frame twice is never dereferenced, and its terms and the total come back NaN. */
+int32_t cvd_consistency_loss_device(cvd_handle* h, const cvd_consistency_desc* desc, const void* depth, const void* extrinsics,
+                                    const void* intrinsics, const void* warp, const int32_t* pair_frames, const void* flow_ab,
+                                    const void* flow_ba, const void* weight_ab, const void* weight_ba, double* total,
+                                    double* terms, void* grad, void* stream);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

@@ -58,7 +58,46 @@ class DebugOptions(C.Structure):
     ]
 
 
+class ConsistencyDesc(C.Structure):
+    """include/cvd_hip.h cvd_consistency_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("precision", C.c_int32),
+        ("num_frames", C.c_int32),
+        ("num_pairs", C.c_int32),
+        ("height", C.c_int32),
+        ("width", C.c_int32),
+        ("distance_type", C.c_int32),
+        ("have_warp", C.c_int32),
+        ("reserved", C.c_int32),
+        ("lambda_reprojection", C.c_double),
+        ("lambda_disparity", C.c_double),
+        ("lambda_depth_ratio", C.c_double),
+        ("distance_scale", C.c_double),
+        ("distance_alpha", C.c_double),
+    ]
+
+
+DISTANCE_TYPES = {"l1": 0, "l2": 1, "smooth_l1": 2, "cauchy": 3, "general": 4}  # include/cvd_hip.h CVD_DISTANCE_*
+CONSISTENCY_TERMS = ("reproj", "disp", "depth ratio")   # the keys of the reference's batch_losses, in the order of terms[P][3]
+
 ABI_REVISION = 6  # include/cvd_hip.h: CVD_ABI_REVISION
+
+
+def consistency_desc(precision, num_frames, num_pairs, height, width, distance="l1", scale=1.0, alpha=1.0,
+                     lambdas=(1.0, 0.0, 100.0), have_warp=False):
+    """A stamped cvd_consistency_desc; precision: 0 / numpy float32 = f32, 1 / float64 = f64."""
+    if distance not in DISTANCE_TYPES:
+        raise ValueError(f"unknown distance {distance!r} (one of {sorted(DISTANCE_TYPES)})")
+    d = ConsistencyDesc()
+    d.struct_size = C.sizeof(ConsistencyDesc) | (ABI_REVISION << 32)
+    d.precision = int(precision)
+    d.num_frames, d.num_pairs, d.height, d.width = int(num_frames), int(num_pairs), int(height), int(width)
+    d.distance_type = DISTANCE_TYPES[distance]
+    d.have_warp = int(bool(have_warp))
+    d.lambda_reprojection, d.lambda_disparity, d.lambda_depth_ratio = (float(v) for v in lambdas)
+    d.distance_scale, d.distance_alpha = float(scale), float(alpha)
+    return d
 
 
 def load_library(variant=None):
@@ -104,7 +143,7 @@ EXPORTED_SYMBOLS = [
     "cvd_reset_poses", "cvd_reset_depth_xforms", "cvd_reset_spatial_xforms", "cvd_grid_xform_split",
     "cvd_get_xform_desc", "cvd_num_xform_params", "cvd_get_xform_params", "cvd_set_xform_params",
     "cvd_get_pose_params", "cvd_set_pose_params", "cvd_block_size", "cvd_normalize_depth", "cvd_pose_optimization",
-    "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
+    "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
     "cvd_get_kernel_times", "cvd_get_comm_times", "cvd_get_dense_times", "cvd_set_kernel_timing", "cvd_num_active_constraints", "cvd_coarse_debug", "cvd_temporal_debug", "cvd_path_info", "cvd_abi_revision",
     "cvd_block_inverse_debug", "cvd_dense_inverse_debug", "cvd_epipolar_debug", "cvd_flow_masks_debug",
 ]
@@ -232,6 +271,51 @@ class Solver(Binding):
         n = (C.c_int64 * 3)()
         self._check(self._fn("get_comm_times")(self._h, ms, n))
         return {k: {"avg_ms": ms[i], "count": n[i]} for i, k in enumerate(("evaluate_exchange", "product_exchange", "coarse_exchange"))}
+
+    def consistency_loss(self, depth, extrinsics, intrinsics, pair_frames, flow_ab, flow_ba, weight_ab, weight_ba, warp=None, *,
+                         distance="l1", scale=1.0, alpha=1.0, lambdas=(1.0, 0.0, 100.0), grad=False, timing=False):
+        """The static terms of the reference's fine-tuning loss (loss/consistency_loss.py ConsistencyLoss) over a table of frames
+        and pairs, and its gradient with respect to the depth maps (include/cvd_hip.h cvd_consistency_loss).
+        numpy arrays, all float32 or all float64 -- the dtype of `depth` picks the kernels' precision: depth [F, H, W],
+        extrinsics [F, 3, 4], intrinsics [F, 4], pair_frames [P, 2], flow_ab / flow_ba [P, 2, H, W] (pixels, planar),
+        weight_ab / weight_ba [P, H, W] (or [P, 1, H, W]), warp [F, 2, H, W] pixel offsets or None.  lambdas = (reprojection,
+        disparity, depth ratio).  Returns (total, {"reproj", "disp", "depth ratio"}: [P] float64, only the terms whose lambda
+        is > 0), then d total / d depth [F, H, W] when grad, then {"forward", "backward"} kernel ms when timing."""
+        import numpy as np
+        depth = np.asarray(depth)
+        if depth.dtype not in (np.float32, np.float64):
+            raise TypeError(f"consistency_loss: depth must be float32 or float64 (got {depth.dtype})")
+        dt = depth.dtype
+        arr = lambda a: np.ascontiguousarray(a, dtype=dt)
+        depth = arr(depth)
+        assert depth.ndim == 3, depth.shape
+        F, H, W = depth.shape
+        pf = np.ascontiguousarray(pair_frames, dtype=np.int32).reshape(-1, 2)
+        P = pf.shape[0]
+        ext, intr = arr(extrinsics), arr(intrinsics)
+        fab, fba = arr(flow_ab), arr(flow_ba)
+        wab, wba = arr(weight_ab).reshape(-1, H, W), arr(weight_ba).reshape(-1, H, W)
+        wp = None if warp is None else arr(warp)
+        assert ext.shape == (F, 3, 4) and intr.shape == (F, 4), (ext.shape, intr.shape)
+        assert fab.shape == (P, 2, H, W) and fba.shape == (P, 2, H, W), (fab.shape, fba.shape)
+        assert wab.shape == (P, H, W) and wba.shape == (P, H, W), (wab.shape, wba.shape)
+        assert wp is None or wp.shape == (F, 2, H, W), wp.shape
+        desc = consistency_desc(dt == np.float64, F, P, H, W, distance, scale, alpha, lambdas, wp is not None)
+        total = C.c_double(0.0)
+        terms = np.zeros((max(P, 1), 3), np.float64)
+        g = np.zeros((F, H, W), dt) if grad else None
+        ms = (C.c_double * 2)()
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        self._check(self._fn("consistency_loss")(self._h, C.byref(desc), vp(depth), vp(ext), vp(intr), vp(wp),
+                                                 pf.ctypes.data_as(C.POINTER(C.c_int32)), vp(fab), vp(fba), vp(wab), vp(wba),
+                                                 C.byref(total), terms.ctypes.data_as(C.POINTER(C.c_double)), vp(g),
+                                                 ms if timing else None))
+        out = (total.value, {k: terms[:P, i].copy() for i, k in enumerate(CONSISTENCY_TERMS) if lambdas[i] > 0})
+        if grad:
+            out += (g,)
+        if timing:
+            out += ({"forward": ms[0], "backward": ms[1]},)
+        return out
 
     def num_active_constraints(self):
         return int(self._lib.cvd_num_active_constraints(self._h))

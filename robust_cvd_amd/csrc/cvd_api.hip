@@ -737,6 +737,20 @@ int32_t cvd_flow_masks_debug(cvd_handle* h, int32_t num_frames, int32_t height, 
   CVD_TRY(h, flowConsistencyMasks(h, num_frames, height, width, channels, color, num_pairs, pair_frames, flow_ab, flow_ba,
                                   flow_thresh, color_thresh, mask_ab, mask_ba, kept, errors, kernel_ms, pixels_per_thread));
 }
+int32_t cvd_consistency_loss(cvd_handle* h, const cvd_consistency_desc* desc, const void* depth, const void* extrinsics,
+                             const void* intrinsics, const void* warp, const int32_t* pair_frames, const void* flow_ab,
+                             const void* flow_ba, const void* weight_ab, const void* weight_ba, double* total, double* terms,
+                             void* grad, double* kernel_ms) {
+  CVD_TRY(h, consistencyLoss(h, desc, depth, extrinsics, intrinsics, warp, pair_frames, flow_ab, flow_ba, weight_ab, weight_ba,
+                             total, terms, grad, kernel_ms));
+}
+int32_t cvd_consistency_loss_device(cvd_handle* h, const cvd_consistency_desc* desc, const void* depth, const void* extrinsics,
+                                    const void* intrinsics, const void* warp, const int32_t* pair_frames, const void* flow_ab,
+                                    const void* flow_ba, const void* weight_ab, const void* weight_ba, double* total,
+                                    double* terms, void* grad, void* stream) {
+  CVD_TRY(h, consistencyLossDevice(h, desc, depth, extrinsics, intrinsics, warp, pair_frames, flow_ab, flow_ba, weight_ab,
+                                   weight_ba, total, terms, grad, static_cast<hipStream_t>(stream)));
+}
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {

@@ -1,6 +1,7 @@
 // cvd_frontend.hip -- the steps either side of the solve: constraint sampling, epipolar RANSAC flags, image operators, dense
-// consumers, flow-guided and bilateral filters, feature tracks, flow consistency masks.  The only unit that includes their kernel
-// headers and the only one that knows their device state (Frontend; the handle owns it through a pointer to the incomplete type).
+// consumers, flow-guided and bilateral filters, feature tracks, flow consistency masks, the fine-tuning consistency loss.  The
+// only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
+// through a pointer to the incomplete type).
 #include "cvd_host.h"
 #include "cvd_dense.h"
 #include "cvd_sampling.h"
@@ -10,6 +11,7 @@
 #include "cvd_epipolar.h"
 #include "cvd_tracks.h"
 #include "cvd_flowmask.h"
+#include "cvd_consistency.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -47,6 +49,11 @@ struct Frontend {
   DevBuf<unsigned char> dTrkKept;
   DevBuf<float2> dTrkLoc;
   long long trkTracks = 0, trkKeptObs = 0;
+  // cvd_consistency.h: per-workgroup partial sums, per-(pair, direction) sums and backward factors; then the staging of the
+  // host-array entry point (inputs in the order of ConsistencyArrays, pair frames, total + terms, gradient)
+  DevBuf<double> dConsSlab, dConsSums, dConsCoef, dConsOut;
+  DevBuf<unsigned char> dConsIn[8], dConsGrad;
+  DevBuf<int2> dConsPairs;
 };
 
 std::shared_ptr<Frontend> makeFrontend() { return std::make_shared<Frontend>(); }
@@ -810,6 +817,170 @@ void flowConsistencyMasks(cvd_handle* h, int numFrames, int hh, int w, int chann
   fe.dFmMaskBA.download(maskBA, P * npx, s);
   if (kept) fe.dFmKept.download(kept, P * 2, s);
   if (errors) fe.dFmErr.download(reinterpret_cast<float2*>(errors), P * 2 * npx, s);
+  HIP_CHECK(hipStreamSynchronize(s));
+  timer.collect();
+}
+
+// ---- consistency loss of flow pairs and its depth gradient (reference loss/consistency_loss.py, cvd_consistency.h) ----------
+namespace {
+constexpr int kConsArrays = 8;  // depth, extrinsics, intrinsics, warp, flow a->b, flow b->a, weight a->b, weight b->a
+struct ConsistencyArrays {
+  const void *depth, *ext, *intr, *warp, *flowAB, *flowBA, *weightAB, *weightBA;
+  const int32_t* pairs;
+};
+
+void checkConsistency(const cvd_consistency_desc* d, const ConsistencyArrays& in, const double* total, const double* terms) {
+  if (!d) throw std::runtime_error("consistency loss: null desc");
+  if (d->struct_size != CVD_STRUCT_STAMP(cvd_consistency_desc))
+    throw std::runtime_error(fmt("consistency loss: desc.struct_size %llu is not this library's %llu (built against another revision "
+                                 "of cvd_hip.h)", static_cast<unsigned long long>(d->struct_size),
+                                 static_cast<unsigned long long>(CVD_STRUCT_STAMP(cvd_consistency_desc))));
+  if (d->precision != CVD_PRECISION_F32 && d->precision != CVD_PRECISION_F64)
+    throw std::runtime_error(fmt("consistency loss: precision must be 0 (f32) or 1 (f64) (got %d)", d->precision));
+  if (d->width < 2 || d->height < 2)
+    throw std::runtime_error(fmt("consistency loss: width and height must be >= 2 (got %d x %d)", d->width, d->height));
+  if (static_cast<size_t>(d->width) * d->height > (size_t(1) << 28))
+    throw std::runtime_error(fmt("consistency loss: image size %d x %d exceeds 2^28 pixels", d->width, d->height));
+  if (d->num_frames < 2) throw std::runtime_error(fmt("consistency loss: num_frames must be >= 2 (got %d)", d->num_frames));
+  if (d->num_pairs < 1 || d->num_pairs > 65535)
+    throw std::runtime_error(fmt("consistency loss: num_pairs must lie in [1, 65535] (got %d)", d->num_pairs));
+  const double lam[3] = {d->lambda_reprojection, d->lambda_disparity, d->lambda_depth_ratio};
+  const char* lamName[3] = {"lambda_reprojection", "lambda_disparity", "lambda_depth_ratio"};
+  for (int k = 0; k < 3; ++k)
+    if (!(std::isfinite(lam[k]) && lam[k] >= 0.0))
+      throw std::runtime_error(fmt("consistency loss: %s must be finite and >= 0 (got %g)", lamName[k], lam[k]));
+  if (d->distance_type < CVD_DISTANCE_L1 || d->distance_type > CVD_DISTANCE_GENERAL)
+    throw std::runtime_error(fmt("consistency loss: distance_type must lie in [0, 4] (got %d)", d->distance_type));
+  if (!(std::isfinite(d->distance_scale) && d->distance_scale > 0.0))
+    throw std::runtime_error(fmt("consistency loss: distance_scale must be finite and > 0 (got %g)", d->distance_scale));
+  if (!std::isfinite(d->distance_alpha))
+    throw std::runtime_error(fmt("consistency loss: distance_alpha must be finite (got %g)", d->distance_alpha));
+  const void* arr[] = {in.depth, in.ext, in.intr, in.pairs, in.flowAB, in.flowBA, in.weightAB, in.weightBA, total, terms};
+  const char* arrName[] = {"depth", "extrinsics", "intrinsics", "pair_frames", "flow_ab", "flow_ba", "weight_ab", "weight_ba",
+                           "total", "terms"};
+  for (int k = 0; k < 10; ++k)
+    if (!arr[k]) throw std::runtime_error(fmt("consistency loss: null %s", arrName[k]));
+  if (d->have_warp && !in.warp) throw std::runtime_error("consistency loss: null warp (desc.have_warp is set)");
+}
+
+template <typename T>
+void launchConsistency(cvd_handle* h, const cvd_consistency_desc& d, const ConsistencyArrays& in, double* total, double* terms,
+                       void* grad, hipStream_t s, KernelTimer& timer) {
+  const int P = d.num_pairs, F = d.num_frames;
+  const size_t npx = static_cast<size_t>(d.width) * d.height;
+  Frontend& fe = *h->frontend;
+  timer.mark();
+  if (d.lambda_reprojection == 0.0 && d.lambda_disparity == 0.0 && d.lambda_depth_ratio == 0.0) {  // no term exists
+    HIP_CHECK(hipMemsetAsync(total, 0, sizeof(double), s));
+    HIP_CHECK(hipMemsetAsync(terms, 0, sizeof(double) * 3 * P, s));
+    timer.mark();
+    if (grad) HIP_CHECK(hipMemsetAsync(grad, 0, sizeof(T) * F * npx, s));
+    timer.mark();
+    return;
+  }
+  // four pixels per thread: rows of whole 4-pixel groups and tables aligned for the vector loads
+  const void* vec[] = {in.depth, in.warp, in.flowAB, in.flowBA, in.weightAB, in.weightBA};
+  bool four = d.width % 4 == 0;
+  for (const void* p : vec) four = four && reinterpret_cast<uintptr_t>(p) % (4 * sizeof(T)) == 0;
+  const int pix = four ? 4 : 1;
+  const int nb = static_cast<int>((npx + static_cast<size_t>(kConsThreads) * pix - 1) / (static_cast<size_t>(kConsThreads) * pix));
+  fe.dConsSlab.ensure(static_cast<size_t>(P) * 2 * nb * 4);
+  fe.dConsSums.ensure(static_cast<size_t>(P) * 8);
+  fe.dConsCoef.ensure(static_cast<size_t>(P) * 6);
+  ConsArgs<T> A{};
+  A.F = F; A.P = P; A.W = d.width; A.H = d.height;
+  A.useRep = d.lambda_reprojection > 0.0; A.useDsp = d.lambda_disparity > 0.0; A.useRat = d.lambda_depth_ratio > 0.0;
+  A.nb = nb;
+  A.lamRat = static_cast<T>(d.lambda_depth_ratio);
+  A.scale = static_cast<T>(d.distance_scale);
+  // l2 / smooth_l1 / cauchy are the general loss at alpha = 2 / 1 / 0 (reference loss/distance.py); the branch is chosen from
+  // alpha in the kernel's precision, as the reference's torch.where does
+  A.alpha = static_cast<T>(d.distance_type == CVD_DISTANCE_L2 ? 2.0 : d.distance_type == CVD_DISTANCE_SMOOTH_L1 ? 1.0
+                           : d.distance_type == CVD_DISTANCE_CAUCHY ? 0.0 : d.distance_alpha);
+  A.rho = d.distance_type == CVD_DISTANCE_L1 ? CONS_RHO_L1 : A.alpha == T(2) ? CONS_RHO_TWO : A.alpha == T(0) ? CONS_RHO_ZERO
+                                                                                                              : CONS_RHO_GENERAL;
+  const T eps = static_cast<T>(std::numeric_limits<float>::epsilon());
+  A.beta = std::max(eps, std::abs(A.alpha - T(2)));
+  A.alphaSafe = (A.alpha >= T(0) ? T(1) : T(-1)) * std::max(eps, std::abs(A.alpha));
+  A.depth = static_cast<const T*>(in.depth);
+  A.ext = static_cast<const T*>(in.ext);
+  A.intr = static_cast<const T*>(in.intr);
+  A.warp = d.have_warp ? static_cast<const T*>(in.warp) : nullptr;
+  A.pairs = reinterpret_cast<const int2*>(in.pairs);
+  A.flow[0] = static_cast<const T*>(in.flowAB);
+  A.flow[1] = static_cast<const T*>(in.flowBA);
+  A.weight[0] = static_cast<const T*>(in.weightAB);
+  A.weight[1] = static_cast<const T*>(in.weightBA);
+  A.slab = fe.dConsSlab.p;
+  A.coef = fe.dConsCoef.p;
+  A.grad = static_cast<T*>(grad);
+  ConsFinishArgs FA{F, P, nb, d.lambda_reprojection, d.lambda_disparity, d.lambda_depth_ratio, A.pairs, fe.dConsSlab.p,
+                    fe.dConsSums.p, fe.dConsCoef.p, terms, total};
+  const dim3 grid(nb, P, 2), block(kConsThreads);
+  if (pix == 4) hipLaunchKernelGGL((k_cons_forward<T, 4>), grid, block, 0, s, A);
+  else hipLaunchKernelGGL((k_cons_forward<T, 1>), grid, block, 0, s, A);
+  hipLaunchKernelGGL(k_cons_finish_pairs, dim3(P), dim3(64), 0, s, FA);
+  hipLaunchKernelGGL((k_cons_finish_total<T>), dim3(1), block, 0, s, FA, A.intr);
+  HIP_CHECK(hipGetLastError());
+  timer.mark();
+  if (grad) {
+    HIP_CHECK(hipMemsetAsync(grad, 0, sizeof(T) * F * npx, s));
+#if CVD_DETERMINISTIC
+    hipLaunchKernelGGL((k_cons_backward_det<T>), dim3(F), dim3(kConsDetThreads), 0, s, A);
+#else
+    if (pix == 4) hipLaunchKernelGGL((k_cons_backward<T, 4>), grid, block, 0, s, A);
+    else hipLaunchKernelGGL((k_cons_backward<T, 1>), grid, block, 0, s, A);
+#endif
+    HIP_CHECK(hipGetLastError());
+  }
+  timer.mark();
+}
+}  // namespace
+
+// Device arrays in, device results out, on the caller's stream: no copy and no host wait.  The pair table lives on the device and
+// cannot be checked here; the kernels never dereference a pair that names a frame out of range (or one frame twice) and return NaN.
+void consistencyLossDevice(cvd_handle* h, const cvd_consistency_desc* d, const void* depth, const void* ext, const void* intr,
+                           const void* warp, const int32_t* pairFrames, const void* flowAB, const void* flowBA,
+                           const void* weightAB, const void* weightBA, double* total, double* terms, void* grad, hipStream_t s) {
+  const ConsistencyArrays in{depth, ext, intr, warp, flowAB, flowBA, weightAB, weightBA, pairFrames};
+  checkConsistency(d, in, total, terms);
+  KernelTimer timer(s, nullptr, 2);
+  if (d->precision == CVD_PRECISION_F64) launchConsistency<double>(h, *d, in, total, terms, grad, s, timer);
+  else launchConsistency<float>(h, *d, in, total, terms, grad, s, timer);
+}
+
+// Host arrays in, host results out.  kernelMs (may be NULL): {forward + finish, backward} HIP-event times.
+void consistencyLoss(cvd_handle* h, const cvd_consistency_desc* d, const void* depth, const void* ext, const void* intr,
+                     const void* warp, const int32_t* pairFrames, const void* flowAB, const void* flowBA, const void* weightAB,
+                     const void* weightBA, double* total, double* terms, void* grad, double* kernelMs) {
+  checkConsistency(d, ConsistencyArrays{depth, ext, intr, warp, flowAB, flowBA, weightAB, weightBA, pairFrames}, total, terms);
+  const int P = d->num_pairs, F = d->num_frames;
+  for (int p = 0; p < P; ++p) {
+    const int a = pairFrames[2 * p], b = pairFrames[2 * p + 1];
+    if (a < 0 || a >= F || b < 0 || b >= F)
+      throw std::runtime_error(fmt("consistency loss: pair_frames[%d] = (%d, %d) outside [0, %d)", p, a, b, F));
+    if (a == b) throw std::runtime_error(fmt("consistency loss: pair_frames[%d] = (%d, %d) names one frame twice", p, a, b));
+  }
+  hipStream_t s = h->stream;
+  Frontend& fe = *h->frontend;
+  const size_t es = d->precision == CVD_PRECISION_F64 ? 8 : 4, npx = static_cast<size_t>(d->width) * d->height;
+  const void* src[kConsArrays] = {depth, ext, intr, d->have_warp ? warp : nullptr, flowAB, flowBA, weightAB, weightBA};
+  const size_t count[kConsArrays] = {F * npx, size_t(F) * 12, size_t(F) * 4, F * 2 * npx, P * 2 * npx, P * 2 * npx, P * npx, P * npx};
+  const void* dev[kConsArrays];
+  for (int k = 0; k < kConsArrays; ++k) {
+    if (src[k]) fe.dConsIn[k].upload(static_cast<const unsigned char*>(src[k]), count[k] * es, s);
+    dev[k] = src[k] ? fe.dConsIn[k].p : nullptr;
+  }
+  fe.dConsPairs.upload(reinterpret_cast<const int2*>(pairFrames), P, s);
+  fe.dConsOut.ensure(1 + 3 * static_cast<size_t>(P));
+  if (grad) fe.dConsGrad.ensure(F * npx * es);
+  const ConsistencyArrays in{dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], reinterpret_cast<const int32_t*>(fe.dConsPairs.p)};
+  KernelTimer timer(s, kernelMs, 2);
+  if (es == 8) launchConsistency<double>(h, *d, in, fe.dConsOut.p, fe.dConsOut.p + 1, grad ? fe.dConsGrad.p : nullptr, s, timer);
+  else launchConsistency<float>(h, *d, in, fe.dConsOut.p, fe.dConsOut.p + 1, grad ? fe.dConsGrad.p : nullptr, s, timer);
+  HIP_CHECK(hipMemcpyAsync(total, fe.dConsOut.p, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(terms, fe.dConsOut.p + 1, sizeof(double) * 3 * P, hipMemcpyDeviceToHost, s));
+  if (grad) HIP_CHECK(hipMemcpyAsync(grad, fe.dConsGrad.p, F * npx * es, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   timer.collect();
 }

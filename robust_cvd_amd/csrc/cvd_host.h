@@ -730,5 +730,11 @@ void flowConsistencyMasks(cvd_handle* h, int numFrames, int hh, int w, int chann
                           const int32_t* pairFrames, const float* flowAB, const float* flowBA, float flowThresh,
                           float colorThresh, uint8_t* maskAB, uint8_t* maskBA, int32_t* kept, float* errors, double* kernelMs,
                           int pixelsPerThread);
+void consistencyLoss(cvd_handle* h, const cvd_consistency_desc* d, const void* depth, const void* ext, const void* intr,
+                     const void* warp, const int32_t* pairFrames, const void* flowAB, const void* flowBA, const void* weightAB,
+                     const void* weightBA, double* total, double* terms, void* grad, double* kernelMs);
+void consistencyLossDevice(cvd_handle* h, const cvd_consistency_desc* d, const void* depth, const void* ext, const void* intr,
+                           const void* warp, const int32_t* pairFrames, const void* flowAB, const void* flowBA,
+                           const void* weightAB, const void* weightBA, double* total, double* terms, void* grad, hipStream_t s);
 
 }  // namespace cvd
