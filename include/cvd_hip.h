@@ -436,6 +436,64 @@ int32_t cvd_consistency_loss_device(cvd_handle* h, const cvd_consistency_desc* d
                                     const void* flow_ba, const void* weight_ab, const void* weight_ba, double* total,
                                     double* terms, void* grad, void* stream);
 
+/* ---- scene-flow loss of flow pairs and its depth gradient: the reference's SceneFlowLoss (loss/scene_flow_loss.py:31-356;
+ * utils/geometry.py; utils/loss.py:62-80), DESIGN.md §3.11.  The static term compares matched points in world space; the three
+ * temporally smooth terms ask the forward and backward scene flow of an anchor frame to its temporal neighbours to cancel.
+ * Independent of cvd_set_video; tables and precision as for cvd_consistency_loss, and in addition
+ *   flows[2], masks[2]          per direction k (0: a -> b on a's raster, 1: b -> a on b's): [P][2][H][W] pixels, [P][H][W]
+ *   neighbor_frames [P][4]      (a - 1, a + 1, b - 1, b + 1) as the loader clamps them: a boundary anchor names itself
+ *   neighbor_flows[4], neighbor_masks[4]   anchor -> neighbour, in the order of neighbor_frames: [P][2][H][W], [P][H][W]
+ *   valid [P][2]                0 / 1 per anchor: both neighbours of the anchor exist
+ * flows / masks / neighbor_flows / neighbor_masks are (host) arrays of 2 / 2 / 4 / 4 array pointers.
+ * With X_f(x, y) = ray_f((x, y) + warp_f) D_f the camera-space point map of frame f, Xw_f = R_f X_f + t_f and S_f(m) the
+ * bilinear sample of the three-channel map X_f at pixel position m (m size / (size - 1) - 0.5, clamped: grid_sample, bilinear,
+ * align_corners = false, border):
+ *   static  (pair, direction k; ref r, target t)   Y = R_t S_t(pix_r + flow_k) + t_t,  d = |Xw_r - Y|,  w = mask_k / |D_r|
+ *           static = lambda_static mean_k sum w rho_static(d) / max(sum w, 1e-6)     (w is a function of the depth, also in grad)
+ *   smooth  (pair, anchor al; frame r, neighbours n-, n+)   Y+- = R_n S_n(pix_r + neighbor_flow) + t_n,
+ *           X_s = R_r^T (Y+ + Y- - Xw_r - t_r),  w = valid neighbor_mask- neighbor_mask+,
+ *           e_rep = |project_r(X_s) - pix_r|,  e_dsp = 1 / X_s.z - 1 / X_r.z,
+ *           e_rat = lambda_smooth_depth_ratio log(min / max of |X_r.z|, |X_s.z|);  each through rho_smooth and the weighted mean;
+ *           smooth_reproj = lambda mean_al(.),  smooth_disparity = lambda mean_al(fbar_al .) with fbar_al the mean focal length of
+ *           anchor al's frames over all pairs,  smooth_depth_ratio = mean_al(.)
+ * A term exists only when its lambda is > 0 (else 0); total = mean over pairs of the sum of the terms.
+ *   total [1], terms [P][4]     (static, smooth_reproj, smooth_disparity, smooth_depth_ratio), double in both precisions
+ *   grad  [F][H][W]             optional (may be NULL): d total / d depth, in the arrays' precision
+ *   maps  [6][P][3][H][W]       optional (may be NULL): the reference's visualisation maps, in the arrays' precision:
+ *                               w (Xw_r - Y) of direction 0 / 1, then per anchor w (Y+ - Xw_r), w (Y- - Xw_r); zeros for a part
+ *                               whose lambdas are all 0.  Nothing is written (or computed) for them when NULL.
+ *   kernel_ms [2]               optional (may be NULL): {forward, backward} kernel times, HIP events
+ * flows / masks may be NULL when lambda_static is 0; neighbor_frames / neighbor_flows / neighbor_masks / valid may be NULL when
+ * the three smooth lambdas are 0.  The forward results repeat bit for bit; the gradient is accumulated with float atomics (in a
+ * fixed order in the deterministic build).  Rejected before any device work: a desc of another header revision (struct_size),
+ * width or height < 2, num_frames < 2, num_pairs < 1, a pair or neighbour frame out of range or a pair naming one frame twice, a
+ * negative or non-finite lambda, distance_scale <= 0, a non-finite distance_alpha, a null array an enabled term reads.  All
+ * lambdas 0: zeros. */
+typedef struct cvd_scene_flow_desc {
+  uint64_t struct_size;        /* CVD_STRUCT_STAMP(cvd_scene_flow_desc), set by the caller */
+  int32_t precision;           /* CVD_PRECISION_* of every real array */
+  int32_t num_frames, num_pairs, height, width;
+  int32_t distance_type_static, distance_type_smooth;   /* CVD_DISTANCE_*; both use distance_scale and distance_alpha */
+  int32_t have_warp;
+  double lambda_static, lambda_smooth_reprojection, lambda_smooth_disparity, lambda_smooth_depth_ratio;
+  double distance_scale, distance_alpha;
+} cvd_scene_flow_desc;
+int32_t cvd_scene_flow_loss(cvd_handle* h, const cvd_scene_flow_desc* desc, const void* depth, const void* extrinsics,
+                            const void* intrinsics, const void* warp, const int32_t* pair_frames, const void* const* flows,
+                            const void* const* masks, const int32_t* neighbor_frames, const void* const* neighbor_flows,
+                            const void* const* neighbor_masks, const void* valid, double* total, double* terms, void* grad,
+                            void* maps, double* kernel_ms);
+/* The same on DEVICE arrays (inputs and results; the four pointer arrays themselves stay host arrays), enqueued on `stream`: no
+ * copy and no host synchronisation.  One call at a time per handle.  pair_frames and neighbor_frames cannot be checked before the
+ * launch here: a pair or neighbour that names a frame outside [0, F), or a pair of one frame twice, is never dereferenced, and
+ * its terms and the total come back NaN.  With lambda_smooth_disparity > 0 such a pair also leaves the mean focal length over
+ * all pairs undefined: the smooth_disparity term of EVERY pair is then NaN, and so is the gradient it reaches. */
+int32_t cvd_scene_flow_loss_device(cvd_handle* h, const cvd_scene_flow_desc* desc, const void* depth, const void* extrinsics,
+                                   const void* intrinsics, const void* warp, const int32_t* pair_frames, const void* const* flows,
+                                   const void* const* masks, const int32_t* neighbor_frames, const void* const* neighbor_flows,
+                                   const void* const* neighbor_masks, const void* valid, double* total, double* terms,
+                                   void* grad, void* maps, void* stream);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

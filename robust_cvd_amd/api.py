@@ -78,8 +78,31 @@ class ConsistencyDesc(C.Structure):
     ]
 
 
+class SceneFlowDesc(C.Structure):
+    """include/cvd_hip.h cvd_scene_flow_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("precision", C.c_int32),
+        ("num_frames", C.c_int32),
+        ("num_pairs", C.c_int32),
+        ("height", C.c_int32),
+        ("width", C.c_int32),
+        ("distance_type_static", C.c_int32),
+        ("distance_type_smooth", C.c_int32),
+        ("have_warp", C.c_int32),
+        ("lambda_static", C.c_double),
+        ("lambda_smooth_reprojection", C.c_double),
+        ("lambda_smooth_disparity", C.c_double),
+        ("lambda_smooth_depth_ratio", C.c_double),
+        ("distance_scale", C.c_double),
+        ("distance_alpha", C.c_double),
+    ]
+
+
 DISTANCE_TYPES = {"l1": 0, "l2": 1, "smooth_l1": 2, "cauchy": 3, "general": 4}  # include/cvd_hip.h CVD_DISTANCE_*
 CONSISTENCY_TERMS = ("reproj", "disp", "depth ratio")   # the keys of the reference's batch_losses, in the order of terms[P][3]
+# the keys of the reference's SceneFlowLoss batch_losses, in the order of terms[P][4]
+SCENE_FLOW_TERMS = ("static", "smooth_reproj", "smooth_disparity", "smooth_depth_ratio")
 
 ABI_REVISION = 6  # include/cvd_hip.h: CVD_ABI_REVISION
 
@@ -96,6 +119,24 @@ def consistency_desc(precision, num_frames, num_pairs, height, width, distance="
     d.distance_type = DISTANCE_TYPES[distance]
     d.have_warp = int(bool(have_warp))
     d.lambda_reprojection, d.lambda_disparity, d.lambda_depth_ratio = (float(v) for v in lambdas)
+    d.distance_scale, d.distance_alpha = float(scale), float(alpha)
+    return d
+
+
+def scene_flow_desc(precision, num_frames, num_pairs, height, width, distance_static="l1", distance_smooth="l1", scale=1.0,
+                    alpha=1.0, lambdas=(1.0, 1.0, 0.0, 100.0), have_warp=False):
+    """A stamped cvd_scene_flow_desc; lambdas = (static, smooth reprojection, smooth disparity, smooth depth ratio)."""
+    for distance in (distance_static, distance_smooth):
+        if distance not in DISTANCE_TYPES:
+            raise ValueError(f"unknown distance {distance!r} (one of {sorted(DISTANCE_TYPES)})")
+    d = SceneFlowDesc()
+    d.struct_size = C.sizeof(SceneFlowDesc) | (ABI_REVISION << 32)
+    d.precision = int(precision)
+    d.num_frames, d.num_pairs, d.height, d.width = int(num_frames), int(num_pairs), int(height), int(width)
+    d.distance_type_static, d.distance_type_smooth = DISTANCE_TYPES[distance_static], DISTANCE_TYPES[distance_smooth]
+    d.have_warp = int(bool(have_warp))
+    (d.lambda_static, d.lambda_smooth_reprojection, d.lambda_smooth_disparity,
+     d.lambda_smooth_depth_ratio) = (float(v) for v in lambdas)
     d.distance_scale, d.distance_alpha = float(scale), float(alpha)
     return d
 
@@ -143,7 +184,7 @@ EXPORTED_SYMBOLS = [
     "cvd_reset_poses", "cvd_reset_depth_xforms", "cvd_reset_spatial_xforms", "cvd_grid_xform_split",
     "cvd_get_xform_desc", "cvd_num_xform_params", "cvd_get_xform_params", "cvd_set_xform_params",
     "cvd_get_pose_params", "cvd_set_pose_params", "cvd_block_size", "cvd_normalize_depth", "cvd_pose_optimization",
-    "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
+    "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_scene_flow_loss", "cvd_scene_flow_loss_device", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
     "cvd_get_kernel_times", "cvd_get_comm_times", "cvd_get_dense_times", "cvd_set_kernel_timing", "cvd_num_active_constraints", "cvd_coarse_debug", "cvd_temporal_debug", "cvd_path_info", "cvd_abi_revision",
     "cvd_block_inverse_debug", "cvd_dense_inverse_debug", "cvd_epipolar_debug", "cvd_flow_masks_debug",
 ]
@@ -313,6 +354,79 @@ class Solver(Binding):
         out = (total.value, {k: terms[:P, i].copy() for i, k in enumerate(CONSISTENCY_TERMS) if lambdas[i] > 0})
         if grad:
             out += (g,)
+        if timing:
+            out += ({"forward": ms[0], "backward": ms[1]},)
+        return out
+
+    def scene_flow_loss(self, depth, extrinsics, intrinsics, pair_frames, flows=None, masks=None, neighbor_frames=None,
+                        neighbor_flows=None, neighbor_masks=None, valid=None, warp=None, *, distance_static="l1",
+                        distance_smooth="l1", scale=1.0, alpha=1.0, lambdas=(1.0, 1.0, 0.0, 100.0), grad=False, maps=False,
+                        timing=False):
+        """The reference's SceneFlowLoss (loss/scene_flow_loss.py) over a table of frames and pairs, and its gradient with respect
+        to the depth maps (include/cvd_hip.h cvd_scene_flow_loss).  numpy arrays, all float32 or all float64 --
+        the dtype of `depth` picks the kernels' precision: depth [F, H, W], extrinsics [F, 3, 4], intrinsics [F, 4], pair_frames
+        [P, 2]; flows / masks: 2 arrays [P, 2, H, W] / [P, H, W] (or [P, 1, H, W]) per direction, None when lambdas[0] is 0;
+        neighbor_frames [P, 4] = (a-1, a+1, b-1, b+1), neighbor_flows / neighbor_masks: 4 arrays in that order, valid [P, 2], all
+        None when the three smooth lambdas are 0; warp [F, 2, H, W] pixel offsets or None.  lambdas = (static, smooth
+        reprojection, smooth disparity, smooth depth ratio).  Returns (total, {term: [P] float64} of the terms whose lambda is
+        > 0), then d total / d depth [F, H, W] when grad, then the six visualisation maps [6, P, 3, H, W] when maps, then
+        {"forward", "backward"} kernel ms when timing."""
+        import numpy as np
+        depth = np.asarray(depth)
+        if depth.dtype not in (np.float32, np.float64):
+            raise TypeError(f"scene_flow_loss: depth must be float32 or float64 (got {depth.dtype})")
+        dt = depth.dtype
+        arr = lambda a: np.ascontiguousarray(a, dtype=dt)
+        depth = arr(depth)
+
+        def shaped(name, a, shape):
+            if a.shape != shape:
+                raise ValueError(f"scene_flow_loss: {name} has shape {a.shape}, expected {shape}")
+            return a
+        if depth.ndim != 3:
+            raise ValueError(f"scene_flow_loss: depth has shape {depth.shape}, expected [F, H, W]")
+        F, H, W = depth.shape
+        pf = np.ascontiguousarray(pair_frames, dtype=np.int32).reshape(-1, 2)
+        P = pf.shape[0]
+        ext, intr = shaped("extrinsics", arr(extrinsics), (F, 3, 4)), shaped("intrinsics", arr(intrinsics), (F, 4))
+        wp = None if warp is None else shaped("warp", arr(warp), (F, 2, H, W))
+        keep = [depth, ext, intr, wp, pf]   # the converted arrays live until the call returns
+
+        def group(name, arrays, n, shape):
+            """pointer array of the n arrays of one argument, or None (the library names a missing group an enabled term needs)"""
+            if arrays is None:
+                return None
+            arrays = list(arrays)
+            if len(arrays) != n:
+                raise ValueError(f"scene_flow_loss: {name} has {len(arrays)} arrays, expected {n}")
+            conv = [shaped(f"{name}[{k}]", arr(a).reshape((-1,) + shape[1:]), shape) for k, a in enumerate(arrays)]
+            keep.extend(conv)
+            return (C.c_void_p * n)(*[a.ctypes.data for a in conv])
+
+        fl, mk = group("flows", flows, 2, (P, 2, H, W)), group("masks", masks, 2, (P, H, W))
+        nfl = group("neighbor_flows", neighbor_flows, 4, (P, 2, H, W))
+        nmk = group("neighbor_masks", neighbor_masks, 4, (P, H, W))
+        nf = None if neighbor_frames is None else shaped(
+            "neighbor_frames", np.ascontiguousarray(neighbor_frames, dtype=np.int32).reshape(-1, 4), (P, 4))
+        vl = None if valid is None else shaped("valid", arr(valid).reshape(-1, 2), (P, 2))
+        desc = scene_flow_desc(dt == np.float64, F, P, H, W, distance_static, distance_smooth, scale, alpha, lambdas,
+                               wp is not None)
+        total = C.c_double(0.0)
+        terms = np.zeros((max(P, 1), 4), np.float64)
+        g = np.zeros((F, H, W), dt) if grad else None
+        mp = np.zeros((6, max(P, 1), 3, H, W), dt) if maps else None
+        ms = (C.c_double * 2)()
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._fn("scene_flow_loss")(self._h, C.byref(desc), vp(depth), vp(ext), vp(intr), vp(wp), ip(pf), fl, mk,
+                                                ip(nf), nfl, nmk, vp(vl), C.byref(total),
+                                                terms.ctypes.data_as(C.POINTER(C.c_double)), vp(g), vp(mp),
+                                                ms if timing else None))
+        out = (total.value, {k: terms[:P, i].copy() for i, k in enumerate(SCENE_FLOW_TERMS) if lambdas[i] > 0})
+        if grad:
+            out += (g,)
+        if maps:
+            out += (mp[:, :P],)
         if timing:
             out += ({"forward": ms[0], "backward": ms[1]},)
         return out

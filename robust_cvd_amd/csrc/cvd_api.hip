@@ -751,6 +751,22 @@ int32_t cvd_consistency_loss_device(cvd_handle* h, const cvd_consistency_desc* d
   CVD_TRY(h, consistencyLossDevice(h, desc, depth, extrinsics, intrinsics, warp, pair_frames, flow_ab, flow_ba, weight_ab,
                                    weight_ba, total, terms, grad, static_cast<hipStream_t>(stream)));
 }
+int32_t cvd_scene_flow_loss(cvd_handle* h, const cvd_scene_flow_desc* desc, const void* depth, const void* extrinsics,
+                            const void* intrinsics, const void* warp, const int32_t* pair_frames, const void* const* flows,
+                            const void* const* masks, const int32_t* neighbor_frames, const void* const* neighbor_flows,
+                            const void* const* neighbor_masks, const void* valid, double* total, double* terms, void* grad,
+                            void* maps, double* kernel_ms) {
+  CVD_TRY(h, sceneFlowLoss(h, desc, depth, extrinsics, intrinsics, warp, pair_frames, flows, masks, neighbor_frames, neighbor_flows,
+                           neighbor_masks, valid, total, terms, grad, maps, kernel_ms));
+}
+int32_t cvd_scene_flow_loss_device(cvd_handle* h, const cvd_scene_flow_desc* desc, const void* depth, const void* extrinsics,
+                                   const void* intrinsics, const void* warp, const int32_t* pair_frames, const void* const* flows,
+                                   const void* const* masks, const int32_t* neighbor_frames, const void* const* neighbor_flows,
+                                   const void* const* neighbor_masks, const void* valid, double* total, double* terms,
+                                   void* grad, void* maps, void* stream) {
+  CVD_TRY(h, sceneFlowLossDevice(h, desc, depth, extrinsics, intrinsics, warp, pair_frames, flows, masks, neighbor_frames,
+                                 neighbor_flows, neighbor_masks, valid, total, terms, grad, maps, static_cast<hipStream_t>(stream)));
+}
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {

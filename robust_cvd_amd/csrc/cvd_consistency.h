@@ -121,28 +121,42 @@ __device__ __forceinline__ double consFloor(double v) { return floor(v); }
 __device__ __forceinline__ float consClamp(float v, float hi) { return fminf(fmaxf(v, 0.f), hi); }  // (NaN -> 0, as grid_sample)
 __device__ __forceinline__ double consClamp(double v, double hi) { return fmin(fmax(v, 0.0), hi); }
 
-// rho(e) and d rho / d e
+// one robust distance: kind (ConsRho), scale, and the constants of the general branch (beta = max(eps32, |alpha - 2|),
+// alphaSafe = sign(alpha) max(eps32, |alpha|))
 template <typename T>
-__device__ __forceinline__ T consRho(const ConsArgs<T>& A, T e, T& d) {
-  const T q = e / A.scale;
-  if (A.rho == CONS_RHO_L1) {
-    d = (e > T(0) ? T(1) : (e < T(0) ? T(-1) : T(0))) / A.scale;
+struct ConsDistance {
+  int kind;
+  T scale, alpha, beta, alphaSafe;
+};
+
+// rho(e) and d rho / d e of the distance R
+template <typename T>
+__device__ __forceinline__ T consRhoOf(const ConsDistance<T>& R, T e, T& d) {
+  const T q = e / R.scale;
+  if (R.kind == CONS_RHO_L1) {
+    d = (e > T(0) ? T(1) : (e < T(0) ? T(-1) : T(0))) / R.scale;
     return consAbs(q);
   }
   const T s = q * q, hs = T(0.5) * s;
-  if (A.rho == CONS_RHO_TWO) {
-    d = q / A.scale;
+  if (R.kind == CONS_RHO_TWO) {
+    d = q / R.scale;
     return hs;
   }
-  if (A.rho == CONS_RHO_ZERO) {
+  if (R.kind == CONS_RHO_ZERO) {
     const T cap = T(33e37);
-    d = hs < cap ? (q / A.scale) / (T(1) + hs) : T(0);
+    d = hs < cap ? (q / R.scale) / (T(1) + hs) : T(0);
     return consLog1p(hs < cap ? hs : cap);
   }
-  const T base = s / A.beta + T(1);
-  const T pw = consPow(base, T(0.5) * A.alpha);
-  d = (A.alpha / A.alphaSafe) * (pw / base) * (q / A.scale);
-  return (A.beta / A.alphaSafe) * (pw - T(1));
+  const T base = s / R.beta + T(1);
+  const T pw = consPow(base, T(0.5) * R.alpha);
+  d = (R.alpha / R.alphaSafe) * (pw / base) * (q / R.scale);
+  return (R.beta / R.alphaSafe) * (pw - T(1));
+}
+
+// the consistency loss's one distance
+template <typename T>
+__device__ __forceinline__ T consRho(const ConsArgs<T>& A, T e, T& d) {
+  return consRhoOf(ConsDistance<T>{A.rho, A.scale, A.alpha, A.beta, A.alphaSafe}, e, d);
 }
 
 // One sample.  Forward (GRAD = false): adds (w, w rho_rep, w rho_dsp, w rho_rat) to acc.  Backward: cf = the three factors

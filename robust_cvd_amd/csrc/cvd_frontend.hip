@@ -1,6 +1,6 @@
 // cvd_frontend.hip -- the steps either side of the solve: constraint sampling, epipolar RANSAC flags, image operators, dense
-// consumers, flow-guided and bilateral filters, feature tracks, flow consistency masks, the fine-tuning consistency loss.  The
-// only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
+// consumers, flow-guided and bilateral filters, feature tracks, flow consistency masks, the fine-tuning consistency and
+// scene-flow losses.  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
 // through a pointer to the incomplete type).
 #include "cvd_host.h"
 #include "cvd_dense.h"
@@ -12,6 +12,7 @@
 #include "cvd_tracks.h"
 #include "cvd_flowmask.h"
 #include "cvd_consistency.h"
+#include "cvd_sceneflow.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -54,6 +55,12 @@ struct Frontend {
   DevBuf<double> dConsSlab, dConsSums, dConsCoef, dConsOut;
   DevBuf<unsigned char> dConsIn[8], dConsGrad;
   DevBuf<int2> dConsPairs;
+  // cvd_sceneflow.h: the same; the staging in the order of SceneFlowArrays::real, then pair and neighbour frames, total + terms,
+  // gradient, maps
+  DevBuf<double> dSfSlab, dSfSums, dSfCoef, dSfOut;
+  DevBuf<unsigned char> dSfIn[17], dSfGrad, dSfMaps;
+  DevBuf<int2> dSfPairs;
+  DevBuf<int> dSfNbrs;
 };
 
 std::shared_ptr<Frontend> makeFrontend() { return std::make_shared<Frontend>(); }
@@ -863,6 +870,20 @@ void checkConsistency(const cvd_consistency_desc* d, const ConsistencyArrays& in
   if (d->have_warp && !in.warp) throw std::runtime_error("consistency loss: null warp (desc.have_warp is set)");
 }
 
+// One distance of the fine-tuning losses for the kernels.  l2 / smooth_l1 / cauchy are the general loss at alpha = 2 / 1 / 0
+// (reference loss/distance.py); the branch is chosen from alpha in the kernel's precision, as the reference's torch.where does.
+template <typename T>
+ConsDistance<T> robustDistance(int type, double scale, double alpha) {
+  ConsDistance<T> r;
+  r.scale = static_cast<T>(scale);
+  r.alpha = static_cast<T>(type == CVD_DISTANCE_L2 ? 2.0 : type == CVD_DISTANCE_SMOOTH_L1 ? 1.0 : type == CVD_DISTANCE_CAUCHY ? 0.0 : alpha);
+  r.kind = type == CVD_DISTANCE_L1 ? CONS_RHO_L1 : r.alpha == T(2) ? CONS_RHO_TWO : r.alpha == T(0) ? CONS_RHO_ZERO : CONS_RHO_GENERAL;
+  const T eps = static_cast<T>(std::numeric_limits<float>::epsilon());
+  r.beta = std::max(eps, std::abs(r.alpha - T(2)));
+  r.alphaSafe = (r.alpha >= T(0) ? T(1) : T(-1)) * std::max(eps, std::abs(r.alpha));
+  return r;
+}
+
 template <typename T>
 void launchConsistency(cvd_handle* h, const cvd_consistency_desc& d, const ConsistencyArrays& in, double* total, double* terms,
                        void* grad, hipStream_t s, KernelTimer& timer) {
@@ -892,16 +913,8 @@ void launchConsistency(cvd_handle* h, const cvd_consistency_desc& d, const Consi
   A.useRep = d.lambda_reprojection > 0.0; A.useDsp = d.lambda_disparity > 0.0; A.useRat = d.lambda_depth_ratio > 0.0;
   A.nb = nb;
   A.lamRat = static_cast<T>(d.lambda_depth_ratio);
-  A.scale = static_cast<T>(d.distance_scale);
-  // l2 / smooth_l1 / cauchy are the general loss at alpha = 2 / 1 / 0 (reference loss/distance.py); the branch is chosen from
-  // alpha in the kernel's precision, as the reference's torch.where does
-  A.alpha = static_cast<T>(d.distance_type == CVD_DISTANCE_L2 ? 2.0 : d.distance_type == CVD_DISTANCE_SMOOTH_L1 ? 1.0
-                           : d.distance_type == CVD_DISTANCE_CAUCHY ? 0.0 : d.distance_alpha);
-  A.rho = d.distance_type == CVD_DISTANCE_L1 ? CONS_RHO_L1 : A.alpha == T(2) ? CONS_RHO_TWO : A.alpha == T(0) ? CONS_RHO_ZERO
-                                                                                                              : CONS_RHO_GENERAL;
-  const T eps = static_cast<T>(std::numeric_limits<float>::epsilon());
-  A.beta = std::max(eps, std::abs(A.alpha - T(2)));
-  A.alphaSafe = (A.alpha >= T(0) ? T(1) : T(-1)) * std::max(eps, std::abs(A.alpha));
+  const ConsDistance<T> rho = robustDistance<T>(d.distance_type, d.distance_scale, d.distance_alpha);
+  A.rho = rho.kind; A.scale = rho.scale; A.alpha = rho.alpha; A.beta = rho.beta; A.alphaSafe = rho.alphaSafe;
   A.depth = static_cast<const T*>(in.depth);
   A.ext = static_cast<const T*>(in.ext);
   A.intr = static_cast<const T*>(in.intr);
@@ -981,6 +994,228 @@ void consistencyLoss(cvd_handle* h, const cvd_consistency_desc* d, const void* d
   HIP_CHECK(hipMemcpyAsync(total, fe.dConsOut.p, sizeof(double), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipMemcpyAsync(terms, fe.dConsOut.p + 1, sizeof(double) * 3 * P, hipMemcpyDeviceToHost, s));
   if (grad) HIP_CHECK(hipMemcpyAsync(grad, fe.dConsGrad.p, F * npx * es, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  timer.collect();
+}
+
+// ---- scene-flow loss of flow pairs and its depth gradient (reference loss/scene_flow_loss.py, cvd_sceneflow.h) --------------
+namespace {
+constexpr int kSfArrays = 17;
+// real[]: depth, extrinsics, intrinsics, warp, flows[2], masks[2], neighbor_flows[4], neighbor_masks[4], valid
+struct SceneFlowArrays {
+  const void* real[kSfArrays];
+  const int32_t *pairs, *nbrs;
+};
+const char* const kSfNames[kSfArrays] = {"depth", "extrinsics", "intrinsics", "warp", "flows[0]", "flows[1]", "masks[0]", "masks[1]",
+                                         "neighbor_flows[0]", "neighbor_flows[1]", "neighbor_flows[2]", "neighbor_flows[3]",
+                                         "neighbor_masks[0]", "neighbor_masks[1]", "neighbor_masks[2]", "neighbor_masks[3]", "valid"};
+
+bool sfHasStatic(const cvd_scene_flow_desc& d) { return d.lambda_static > 0.0; }
+bool sfHasSmooth(const cvd_scene_flow_desc& d) {
+  return d.lambda_smooth_reprojection > 0.0 || d.lambda_smooth_disparity > 0.0 || d.lambda_smooth_depth_ratio > 0.0;
+}
+
+// checks the desc and gathers the arrays; an array group the enabled terms do not read may be NULL (and is then never read)
+SceneFlowArrays checkSceneFlow(const cvd_scene_flow_desc* d, const void* depth, const void* ext, const void* intr, const void* warp,
+                               const int32_t* pairs, const void* const* flows, const void* const* masks, const int32_t* nbrs,
+                               const void* const* nflows, const void* const* nmasks, const void* valid, const double* total,
+                               const double* terms) {
+  if (!d) throw std::runtime_error("scene flow loss: null desc");
+  if (d->struct_size != CVD_STRUCT_STAMP(cvd_scene_flow_desc))
+    throw std::runtime_error(fmt("scene flow loss: desc.struct_size %llu is not this library's %llu (built against another revision "
+                                 "of cvd_hip.h)", static_cast<unsigned long long>(d->struct_size),
+                                 static_cast<unsigned long long>(CVD_STRUCT_STAMP(cvd_scene_flow_desc))));
+  if (d->precision != CVD_PRECISION_F32 && d->precision != CVD_PRECISION_F64)
+    throw std::runtime_error(fmt("scene flow loss: precision must be 0 (f32) or 1 (f64) (got %d)", d->precision));
+  if (d->width < 2 || d->height < 2)
+    throw std::runtime_error(fmt("scene flow loss: width and height must be >= 2 (got %d x %d)", d->width, d->height));
+  if (static_cast<size_t>(d->width) * d->height > (size_t(1) << 28))
+    throw std::runtime_error(fmt("scene flow loss: image size %d x %d exceeds 2^28 pixels", d->width, d->height));
+  if (d->num_frames < 2) throw std::runtime_error(fmt("scene flow loss: num_frames must be >= 2 (got %d)", d->num_frames));
+  if (d->num_pairs < 1 || d->num_pairs > 65535)
+    throw std::runtime_error(fmt("scene flow loss: num_pairs must lie in [1, 65535] (got %d)", d->num_pairs));
+  const double lam[4] = {d->lambda_static, d->lambda_smooth_reprojection, d->lambda_smooth_disparity, d->lambda_smooth_depth_ratio};
+  const char* lamName[4] = {"lambda_static", "lambda_smooth_reprojection", "lambda_smooth_disparity", "lambda_smooth_depth_ratio"};
+  for (int k = 0; k < 4; ++k)
+    if (!(std::isfinite(lam[k]) && lam[k] >= 0.0))
+      throw std::runtime_error(fmt("scene flow loss: %s must be finite and >= 0 (got %g)", lamName[k], lam[k]));
+  const int dist[2] = {d->distance_type_static, d->distance_type_smooth};
+  const char* distName[2] = {"distance_type_static", "distance_type_smooth"};
+  for (int k = 0; k < 2; ++k)
+    if (dist[k] < CVD_DISTANCE_L1 || dist[k] > CVD_DISTANCE_GENERAL)
+      throw std::runtime_error(fmt("scene flow loss: %s must lie in [0, 4] (got %d)", distName[k], dist[k]));
+  if (!(std::isfinite(d->distance_scale) && d->distance_scale > 0.0))
+    throw std::runtime_error(fmt("scene flow loss: distance_scale must be finite and > 0 (got %g)", d->distance_scale));
+  if (!std::isfinite(d->distance_alpha))
+    throw std::runtime_error(fmt("scene flow loss: distance_alpha must be finite (got %g)", d->distance_alpha));
+  const bool st = sfHasStatic(*d), sm = sfHasSmooth(*d);
+  if (st && !flows) throw std::runtime_error("scene flow loss: null flows (lambda_static > 0)");
+  if (st && !masks) throw std::runtime_error("scene flow loss: null masks (lambda_static > 0)");
+  if (sm && !nbrs) throw std::runtime_error("scene flow loss: null neighbor_frames (a smooth lambda > 0)");
+  if (sm && !nflows) throw std::runtime_error("scene flow loss: null neighbor_flows (a smooth lambda > 0)");
+  if (sm && !nmasks) throw std::runtime_error("scene flow loss: null neighbor_masks (a smooth lambda > 0)");
+  SceneFlowArrays in{};
+  in.real[0] = depth; in.real[1] = ext; in.real[2] = intr;
+  in.real[3] = d->have_warp ? warp : nullptr;
+  for (int k = 0; k < 2 && st; ++k) {
+    in.real[4 + k] = flows[k];
+    in.real[6 + k] = masks[k];
+  }
+  for (int k = 0; k < 4 && sm; ++k) {
+    in.real[8 + k] = nflows[k];
+    in.real[12 + k] = nmasks[k];
+  }
+  in.real[16] = sm ? valid : nullptr;
+  in.pairs = pairs;
+  in.nbrs = sm ? nbrs : nullptr;
+  for (int k = 0; k < kSfArrays; ++k) {
+    const bool needed = k < 3 || (k == 3 && d->have_warp) || (k >= 4 && k < 8 && st) || (k >= 8 && sm);
+    if (needed && !in.real[k])
+      throw std::runtime_error(fmt("scene flow loss: null %s%s", kSfNames[k], k == 3 ? " (desc.have_warp is set)" : ""));
+  }
+  if (!pairs) throw std::runtime_error("scene flow loss: null pair_frames");
+  if (!total) throw std::runtime_error("scene flow loss: null total");
+  if (!terms) throw std::runtime_error("scene flow loss: null terms");
+  return in;
+}
+
+template <typename T>
+void launchSceneFlow(cvd_handle* h, const cvd_scene_flow_desc& d, const SceneFlowArrays& in, double* total, double* terms, void* grad,
+                     void* maps, hipStream_t s, KernelTimer& timer) {
+  const int P = d.num_pairs, F = d.num_frames;
+  const size_t npx = static_cast<size_t>(d.width) * d.height;
+  Frontend& fe = *h->frontend;
+  timer.mark();
+  if (!sfHasStatic(d) && !sfHasSmooth(d)) {  // no term exists
+    HIP_CHECK(hipMemsetAsync(total, 0, sizeof(double), s));
+    HIP_CHECK(hipMemsetAsync(terms, 0, sizeof(double) * 4 * P, s));
+    if (maps) HIP_CHECK(hipMemsetAsync(maps, 0, sizeof(T) * 6 * P * 3 * npx, s));
+    timer.mark();
+    if (grad) HIP_CHECK(hipMemsetAsync(grad, 0, sizeof(T) * F * npx, s));
+    timer.mark();
+    return;
+  }
+  // four pixels per thread: rows of whole 4-pixel groups and every per-pixel table aligned for the vector loads (null: not read)
+  bool four = d.width % 4 == 0;
+  for (int k = 0; k < 16; ++k)
+    if (k != 1 && k != 2) four = four && reinterpret_cast<uintptr_t>(in.real[k]) % (4 * sizeof(T)) == 0;
+  const int pix = four ? 4 : 1;
+  const int nb = static_cast<int>((npx + static_cast<size_t>(kConsThreads) * pix - 1) / (static_cast<size_t>(kConsThreads) * pix));
+  fe.dSfSlab.ensure(static_cast<size_t>(P) * 4 * nb * 4);
+  fe.dSfSums.ensure(static_cast<size_t>(P) * 16);
+  fe.dSfCoef.ensure(static_cast<size_t>(P) * 12);
+  SfArgs<T> A{};
+  A.F = F; A.P = P; A.W = d.width; A.H = d.height;
+  A.useStatic = sfHasStatic(d);
+  A.useRep = d.lambda_smooth_reprojection > 0.0; A.useDsp = d.lambda_smooth_disparity > 0.0; A.useRat = d.lambda_smooth_depth_ratio > 0.0;
+  A.nb = nb;
+  A.lamRat = static_cast<T>(d.lambda_smooth_depth_ratio);
+  A.rhoS = robustDistance<T>(d.distance_type_static, d.distance_scale, d.distance_alpha);
+  A.rhoM = robustDistance<T>(d.distance_type_smooth, d.distance_scale, d.distance_alpha);
+  A.depth = static_cast<const T*>(in.real[0]);
+  A.ext = static_cast<const T*>(in.real[1]);
+  A.intr = static_cast<const T*>(in.real[2]);
+  A.warp = static_cast<const T*>(in.real[3]);
+  A.pairs = reinterpret_cast<const int2*>(in.pairs);
+  A.nbrs = in.nbrs;
+  for (int k = 0; k < 2; ++k) {
+    A.flow[k] = static_cast<const T*>(in.real[4 + k]);
+    A.mask[k] = static_cast<const T*>(in.real[6 + k]);
+  }
+  for (int k = 0; k < 4; ++k) {
+    A.nflow[k] = static_cast<const T*>(in.real[8 + k]);
+    A.nmask[k] = static_cast<const T*>(in.real[12 + k]);
+  }
+  A.valid = static_cast<const T*>(in.real[16]);
+  A.slab = fe.dSfSlab.p;
+  A.coef = fe.dSfCoef.p;
+  A.grad = static_cast<T*>(grad);
+  A.maps = static_cast<T*>(maps);
+  SfFinishArgs FA{F, P, nb, d.lambda_static, d.lambda_smooth_reprojection, d.lambda_smooth_disparity, d.lambda_smooth_depth_ratio,
+                  A.pairs, A.nbrs, fe.dSfSlab.p, fe.dSfSums.p, fe.dSfCoef.p, terms, total};
+  const dim3 grid(nb, P, 4), block(kConsThreads);
+  if (pix == 4) hipLaunchKernelGGL((k_sf_forward<T, 4>), grid, block, 0, s, A);
+  else hipLaunchKernelGGL((k_sf_forward<T, 1>), grid, block, 0, s, A);
+  hipLaunchKernelGGL(k_sf_finish_pairs, dim3(P), dim3(64), 0, s, FA);
+  hipLaunchKernelGGL((k_sf_finish_total<T>), dim3(1), block, 0, s, FA, A.intr);
+  HIP_CHECK(hipGetLastError());
+  timer.mark();
+  if (grad) {
+    HIP_CHECK(hipMemsetAsync(grad, 0, sizeof(T) * F * npx, s));
+#if CVD_DETERMINISTIC
+    hipLaunchKernelGGL((k_sf_backward_det<T>), dim3(F), dim3(kConsDetThreads), 0, s, A);
+#else
+    if (pix == 4) hipLaunchKernelGGL((k_sf_backward<T, 4>), grid, block, 0, s, A);
+    else hipLaunchKernelGGL((k_sf_backward<T, 1>), grid, block, 0, s, A);
+#endif
+    HIP_CHECK(hipGetLastError());
+  }
+  timer.mark();
+}
+}  // namespace
+
+// Device arrays in, device results out, on the caller's stream: no copy and no host wait.  flows / masks / nflows / nmasks are
+// HOST arrays of 2 / 2 / 4 / 4 device pointers.  The frame tables live on the device and cannot be checked here; the kernels never
+// dereference a pair or neighbour that names a frame out of range (or a pair of one frame twice) and return NaN.
+void sceneFlowLossDevice(cvd_handle* h, const cvd_scene_flow_desc* d, const void* depth, const void* ext, const void* intr,
+                         const void* warp, const int32_t* pairFrames, const void* const* flows, const void* const* masks,
+                         const int32_t* neighborFrames, const void* const* nflows, const void* const* nmasks, const void* valid,
+                         double* total, double* terms, void* grad, void* maps, hipStream_t s) {
+  const SceneFlowArrays in = checkSceneFlow(d, depth, ext, intr, warp, pairFrames, flows, masks, neighborFrames, nflows, nmasks,
+                                            valid, total, terms);
+  KernelTimer timer(s, nullptr, 2);
+  if (d->precision == CVD_PRECISION_F64) launchSceneFlow<double>(h, *d, in, total, terms, grad, maps, s, timer);
+  else launchSceneFlow<float>(h, *d, in, total, terms, grad, maps, s, timer);
+}
+
+// Host arrays in, host results out.  kernelMs (may be NULL): {forward + finish, backward} HIP-event times.
+void sceneFlowLoss(cvd_handle* h, const cvd_scene_flow_desc* d, const void* depth, const void* ext, const void* intr,
+                   const void* warp, const int32_t* pairFrames, const void* const* flows, const void* const* masks,
+                   const int32_t* neighborFrames, const void* const* nflows, const void* const* nmasks, const void* valid,
+                   double* total, double* terms, void* grad, void* maps, double* kernelMs) {
+  const SceneFlowArrays host = checkSceneFlow(d, depth, ext, intr, warp, pairFrames, flows, masks, neighborFrames, nflows, nmasks,
+                                              valid, total, terms);
+  const int P = d->num_pairs, F = d->num_frames;
+  for (int p = 0; p < P; ++p) {
+    const int a = pairFrames[2 * p], b = pairFrames[2 * p + 1];
+    if (a < 0 || a >= F || b < 0 || b >= F)
+      throw std::runtime_error(fmt("scene flow loss: pair_frames[%d] = (%d, %d) outside [0, %d)", p, a, b, F));
+    if (a == b) throw std::runtime_error(fmt("scene flow loss: pair_frames[%d] = (%d, %d) names one frame twice", p, a, b));
+    for (int j = 0; j < 4 && host.nbrs; ++j) {
+      const int n = host.nbrs[4 * p + j];
+      if (n < 0 || n >= F) throw std::runtime_error(fmt("scene flow loss: neighbor_frames[%d][%d] = %d outside [0, %d)", p, j, n, F));
+    }
+  }
+  hipStream_t s = h->stream;
+  Frontend& fe = *h->frontend;
+  const size_t es = d->precision == CVD_PRECISION_F64 ? 8 : 4, npx = static_cast<size_t>(d->width) * d->height;
+  SceneFlowArrays in{};
+  for (int k = 0; k < kSfArrays; ++k) {
+    if (!host.real[k]) continue;
+    const size_t count = k == 0 ? F * npx : k == 1 ? size_t(F) * 12 : k == 2 ? size_t(F) * 4 : k == 3 ? F * 2 * npx
+                         : k == 16 ? size_t(P) * 2 : (k < 6 || (k >= 8 && k < 12)) ? P * 2 * npx : P * npx;
+    fe.dSfIn[k].upload(static_cast<const unsigned char*>(host.real[k]), count * es, s);
+    in.real[k] = fe.dSfIn[k].p;
+  }
+  fe.dSfPairs.upload(reinterpret_cast<const int2*>(pairFrames), P, s);
+  in.pairs = reinterpret_cast<const int32_t*>(fe.dSfPairs.p);
+  if (host.nbrs) {
+    fe.dSfNbrs.upload(host.nbrs, static_cast<size_t>(P) * 4, s);
+    in.nbrs = fe.dSfNbrs.p;
+  }
+  fe.dSfOut.ensure(1 + 4 * static_cast<size_t>(P));
+  if (grad) fe.dSfGrad.ensure(F * npx * es);
+  const size_t mapBytes = static_cast<size_t>(6) * P * 3 * npx * es;
+  if (maps) fe.dSfMaps.ensure(mapBytes);
+  KernelTimer timer(s, kernelMs, 2);
+  void* dGrad = grad ? fe.dSfGrad.p : nullptr;
+  void* dMaps = maps ? fe.dSfMaps.p : nullptr;
+  if (es == 8) launchSceneFlow<double>(h, *d, in, fe.dSfOut.p, fe.dSfOut.p + 1, dGrad, dMaps, s, timer);
+  else launchSceneFlow<float>(h, *d, in, fe.dSfOut.p, fe.dSfOut.p + 1, dGrad, dMaps, s, timer);
+  HIP_CHECK(hipMemcpyAsync(total, fe.dSfOut.p, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(terms, fe.dSfOut.p + 1, sizeof(double) * 4 * P, hipMemcpyDeviceToHost, s));
+  if (grad) HIP_CHECK(hipMemcpyAsync(grad, fe.dSfGrad.p, F * npx * es, hipMemcpyDeviceToHost, s));
+  if (maps) HIP_CHECK(hipMemcpyAsync(maps, fe.dSfMaps.p, mapBytes, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   timer.collect();
 }

@@ -736,5 +736,13 @@ void consistencyLoss(cvd_handle* h, const cvd_consistency_desc* d, const void* d
 void consistencyLossDevice(cvd_handle* h, const cvd_consistency_desc* d, const void* depth, const void* ext, const void* intr,
                            const void* warp, const int32_t* pairFrames, const void* flowAB, const void* flowBA,
                            const void* weightAB, const void* weightBA, double* total, double* terms, void* grad, hipStream_t s);
+void sceneFlowLoss(cvd_handle* h, const cvd_scene_flow_desc* d, const void* depth, const void* ext, const void* intr,
+                   const void* warp, const int32_t* pairFrames, const void* const* flows, const void* const* masks,
+                   const int32_t* neighborFrames, const void* const* nflows, const void* const* nmasks, const void* valid,
+                   double* total, double* terms, void* grad, void* maps, double* kernelMs);
+void sceneFlowLossDevice(cvd_handle* h, const cvd_scene_flow_desc* d, const void* depth, const void* ext, const void* intr,
+                         const void* warp, const int32_t* pairFrames, const void* const* flows, const void* const* masks,
+                         const int32_t* neighborFrames, const void* const* nflows, const void* const* nmasks, const void* valid,
+                         double* total, double* terms, void* grad, void* maps, hipStream_t s);
 
 }  // namespace cvd
