@@ -494,6 +494,42 @@ int32_t cvd_scene_flow_loss_device(cvd_handle* h, const cvd_scene_flow_desc* des
                                    const void* const* neighbor_masks, const void* valid, double* total, double* terms,
                                    void* grad, void* maps, void* stream);
 
+/* ---- spatial smoothness and contrast losses and their depth gradient: the reference's DisparitySmoothLoss
+ * (loss/disparity_smooth_loss.py:15-56) and ContrastLoss (loss/contrast_loss.py:13-79), DESIGN.md §3.12.  Independent of
+ * cvd_set_video.  One pass computes both terms and, on request, the complete gradient; every real array has the precision desc
+ * names.  F = num_frames = B frames_per_sample; frame f belongs to sample f / frames_per_sample:
+ *   depth      [F][H][W]       the predicted depths D
+ *   depth_orig [F][H][W]       the original estimator's depths Do; read only when lambda_contrast_loss > 0 (else may be NULL)
+ *   image      [F][3][H][W]    colours I; read only when lambda_disparity_smooth > 0 (else may be NULL)
+ * With d = 1 / D and N = frames_per_sample:
+ *   x-edge (x < W-1)  s_x = exp(-mean_c |I_c(x,y) - I_c(x+1,y)| / sigma_color_grad) |d(x,y) - d(x+1,y)|;  y-edge likewise
+ *   smooth[b] = lambda_disparity_smooth [ sum_{f in b} sum s_x / (N H (W-1)) + sum_{f in b} sum s_y / (N (H-1) W) ]
+ *   r(a, b) = max(a, b) / (min(a, b) + 1e-10)
+ *   h-edge (x < W-1)  c_h = [ r(Do(x+1,y), Do(x,y)) > contrast_thresh ] (contrast_thresh - r(D(x+1,y), D(x,y)))^2;  v-edge likewise
+ *   contrast = lambda_contrast_loss (sum c_h + sum c_v) / F
+ *   total = mean_b smooth[b] + contrast            (a term exists only when its lambda is > 0, else 0)
+ *   total [1], smooth [B], contrast [1]   double in both precisions
+ *   grad  [F][H][W]            optional (may be NULL): d total / d depth, in the arrays' precision, written once per pixel
+ *   kernel_ms [1]              optional (may be NULL): kernel time, HIP events
+ * No atomics: values and gradient repeat bit for bit on every build.  Rejected before any device work: a desc of another header
+ * revision (struct_size), width or height < 2 (the reference returns NaN there), num_frames < 1 or not a multiple of
+ * frames_per_sample, a negative or non-finite lambda, sigma_color_grad <= 0 with the smoothness term on, a non-finite
+ * contrast_thresh with the contrast term on, a null table an enabled term reads, null results.  Both lambdas 0: zeros. */
+typedef struct cvd_spatial_desc {
+  uint64_t struct_size;        /* CVD_STRUCT_STAMP(cvd_spatial_desc), set by the caller */
+  int32_t precision;           /* CVD_PRECISION_* of every real array */
+  int32_t num_frames, frames_per_sample, height, width;
+  int32_t reserved;            /* 0 */
+  double lambda_disparity_smooth, sigma_color_grad;   /* reference defaults 0, 1 */
+  double lambda_contrast_loss, contrast_thresh;       /* reference defaults 1, 1.05 */
+} cvd_spatial_desc;
+int32_t cvd_spatial_losses(cvd_handle* h, const cvd_spatial_desc* desc, const void* depth, const void* depth_orig,
+                           const void* image, double* total, double* smooth, double* contrast, void* grad, double* kernel_ms);
+/* The same on DEVICE arrays (inputs and results), enqueued on `stream`: no copy and no host synchronisation.  One call at a time
+ * per handle. */
+int32_t cvd_spatial_losses_device(cvd_handle* h, const cvd_spatial_desc* desc, const void* depth, const void* depth_orig,
+                                  const void* image, double* total, double* smooth, double* contrast, void* grad, void* stream);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

@@ -99,6 +99,23 @@ class SceneFlowDesc(C.Structure):
     ]
 
 
+class SpatialDesc(C.Structure):
+    """include/cvd_hip.h cvd_spatial_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("precision", C.c_int32),
+        ("num_frames", C.c_int32),
+        ("frames_per_sample", C.c_int32),
+        ("height", C.c_int32),
+        ("width", C.c_int32),
+        ("reserved", C.c_int32),
+        ("lambda_disparity_smooth", C.c_double),
+        ("sigma_color_grad", C.c_double),
+        ("lambda_contrast_loss", C.c_double),
+        ("contrast_thresh", C.c_double),
+    ]
+
+
 DISTANCE_TYPES = {"l1": 0, "l2": 1, "smooth_l1": 2, "cauchy": 3, "general": 4}  # include/cvd_hip.h CVD_DISTANCE_*
 CONSISTENCY_TERMS = ("reproj", "disp", "depth ratio")   # the keys of the reference's batch_losses, in the order of terms[P][3]
 # the keys of the reference's SceneFlowLoss batch_losses, in the order of terms[P][4]
@@ -138,6 +155,18 @@ def scene_flow_desc(precision, num_frames, num_pairs, height, width, distance_st
     (d.lambda_static, d.lambda_smooth_reprojection, d.lambda_smooth_disparity,
      d.lambda_smooth_depth_ratio) = (float(v) for v in lambdas)
     d.distance_scale, d.distance_alpha = float(scale), float(alpha)
+    return d
+
+
+def spatial_desc(precision, num_frames, frames_per_sample, height, width, lambda_disparity_smooth=0.0, sigma_color_grad=1.0,
+                 lambda_contrast_loss=0.0, contrast_thresh=1.05):
+    """A stamped cvd_spatial_desc; precision: 0 / numpy float32 = f32, 1 / float64 = f64."""
+    d = SpatialDesc()
+    d.struct_size = C.sizeof(SpatialDesc) | (ABI_REVISION << 32)
+    d.precision = int(precision)
+    d.num_frames, d.frames_per_sample, d.height, d.width = int(num_frames), int(frames_per_sample), int(height), int(width)
+    d.lambda_disparity_smooth, d.sigma_color_grad = float(lambda_disparity_smooth), float(sigma_color_grad)
+    d.lambda_contrast_loss, d.contrast_thresh = float(lambda_contrast_loss), float(contrast_thresh)
     return d
 
 
@@ -184,7 +213,7 @@ EXPORTED_SYMBOLS = [
     "cvd_reset_poses", "cvd_reset_depth_xforms", "cvd_reset_spatial_xforms", "cvd_grid_xform_split",
     "cvd_get_xform_desc", "cvd_num_xform_params", "cvd_get_xform_params", "cvd_set_xform_params",
     "cvd_get_pose_params", "cvd_set_pose_params", "cvd_block_size", "cvd_normalize_depth", "cvd_pose_optimization",
-    "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_scene_flow_loss", "cvd_scene_flow_loss_device", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
+    "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_scene_flow_loss", "cvd_scene_flow_loss_device", "cvd_spatial_losses", "cvd_spatial_losses_device", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
     "cvd_get_kernel_times", "cvd_get_comm_times", "cvd_get_dense_times", "cvd_set_kernel_timing", "cvd_num_active_constraints", "cvd_coarse_debug", "cvd_temporal_debug", "cvd_path_info", "cvd_abi_revision",
     "cvd_block_inverse_debug", "cvd_dense_inverse_debug", "cvd_epipolar_debug", "cvd_flow_masks_debug",
 ]
@@ -429,6 +458,52 @@ class Solver(Binding):
             out += (mp[:, :P],)
         if timing:
             out += ({"forward": ms[0], "backward": ms[1]},)
+        return out
+
+    def spatial_losses(self, depth, depth_orig=None, image=None, *, frames_per_sample, lambda_disparity_smooth=0.0,
+                       sigma_color_grad=1.0, lambda_contrast_loss=0.0, contrast_thresh=1.05, grad=False, timing=False):
+        """The reference's DisparitySmoothLoss and ContrastLoss (loss/disparity_smooth_loss.py, loss/contrast_loss.py) over a table
+        of frames in one pass, and the gradient with respect to the depth maps (include/cvd_hip.h cvd_spatial_losses, DESIGN.md
+        §3.12).  numpy arrays, all float32 or all float64 -- the dtype of `depth` picks the kernels' precision: depth [F, H, W]
+        (or [B, N, H, W]), depth_orig likewise (None when lambda_contrast_loss is 0), image [F, 3, H, W] (or [B, N, 3, H, W]; None
+        when lambda_disparity_smooth is 0).  Frame f belongs to sample f // frames_per_sample.  Returns (total, smooth [B]
+        float64, contrast), then d total / d depth [F, H, W] when grad, then the kernel ms when timing."""
+        import numpy as np
+        depth = np.asarray(depth)
+        if depth.dtype not in (np.float32, np.float64):
+            raise TypeError(f"spatial_losses: depth must be float32 or float64 (got {depth.dtype})")
+        dt = depth.dtype
+        if depth.ndim not in (3, 4):
+            raise ValueError(f"spatial_losses: depth has shape {depth.shape}, expected [F, H, W]")
+        H, W = depth.shape[-2:]
+        depth = np.ascontiguousarray(depth).reshape(-1, H, W)
+        F = depth.shape[0]
+
+        def table(name, a, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.size != int(np.prod(shape)) or a.shape[-2:] != (H, W):
+                raise ValueError(f"spatial_losses: {name} has shape {a.shape}, expected {shape}")
+            return a.reshape(shape)
+        do = table("depth_orig", depth_orig, (F, H, W))
+        im = table("image", image, (F, 3, H, W))
+        N = int(frames_per_sample)
+        desc = spatial_desc(dt == np.float64, F, N, H, W, lambda_disparity_smooth, sigma_color_grad, lambda_contrast_loss,
+                            contrast_thresh)
+        total, contrast = C.c_double(0.0), C.c_double(0.0)
+        smooth = np.zeros(max(F // max(N, 1), 1), np.float64)
+        g = np.zeros((F, H, W), dt) if grad else None
+        ms = (C.c_double * 1)()
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        self._check(self._fn("spatial_losses")(self._h, C.byref(desc), vp(depth), vp(do), vp(im), C.byref(total),
+                                               smooth.ctypes.data_as(C.POINTER(C.c_double)), C.byref(contrast), vp(g),
+                                               ms if timing else None))
+        out = (total.value, smooth[:F // N].copy(), contrast.value)
+        if grad:
+            out += (g,)
+        if timing:
+            out += (ms[0],)
         return out
 
     def num_active_constraints(self):

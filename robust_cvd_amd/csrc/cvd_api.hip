@@ -767,6 +767,15 @@ int32_t cvd_scene_flow_loss_device(cvd_handle* h, const cvd_scene_flow_desc* des
   CVD_TRY(h, sceneFlowLossDevice(h, desc, depth, extrinsics, intrinsics, warp, pair_frames, flows, masks, neighbor_frames,
                                  neighbor_flows, neighbor_masks, valid, total, terms, grad, maps, static_cast<hipStream_t>(stream)));
 }
+int32_t cvd_spatial_losses(cvd_handle* h, const cvd_spatial_desc* desc, const void* depth, const void* depth_orig, const void* image,
+                           double* total, double* smooth, double* contrast, void* grad, double* kernel_ms) {
+  CVD_TRY(h, spatialLosses(h, desc, depth, depth_orig, image, total, smooth, contrast, grad, kernel_ms));
+}
+int32_t cvd_spatial_losses_device(cvd_handle* h, const cvd_spatial_desc* desc, const void* depth, const void* depth_orig,
+                                  const void* image, double* total, double* smooth, double* contrast, void* grad, void* stream) {
+  CVD_TRY(h, spatialLossesDevice(h, desc, depth, depth_orig, image, total, smooth, contrast, grad,
+                                 static_cast<hipStream_t>(stream)));
+}
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {

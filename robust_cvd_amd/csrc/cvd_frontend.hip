@@ -1,6 +1,6 @@
 // cvd_frontend.hip -- the steps either side of the solve: constraint sampling, epipolar RANSAC flags, image operators, dense
-// consumers, flow-guided and bilateral filters, feature tracks, flow consistency masks, the fine-tuning consistency and
-// scene-flow losses.  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
+// consumers, flow-guided and bilateral filters, feature tracks, flow consistency masks, the fine-tuning consistency,
+// scene-flow and spatial losses.  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
 // through a pointer to the incomplete type).
 #include "cvd_host.h"
 #include "cvd_dense.h"
@@ -13,6 +13,7 @@
 #include "cvd_flowmask.h"
 #include "cvd_consistency.h"
 #include "cvd_sceneflow.h"
+#include "cvd_spatial.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -61,6 +62,10 @@ struct Frontend {
   DevBuf<unsigned char> dSfIn[17], dSfGrad, dSfMaps;
   DevBuf<int2> dSfPairs;
   DevBuf<int> dSfNbrs;
+  // cvd_spatial.h: per-workgroup partial sums, per-sample contrast sums; then the staging of the host-array entry point (depth,
+  // depth_orig, image; total + contrast + smooth[B]; gradient)
+  DevBuf<double> dSpSlab, dSpPart, dSpOut;
+  DevBuf<unsigned char> dSpIn[3], dSpGrad;
 };
 
 std::shared_ptr<Frontend> makeFrontend() { return std::make_shared<Frontend>(); }
@@ -1216,6 +1221,150 @@ void sceneFlowLoss(cvd_handle* h, const cvd_scene_flow_desc* d, const void* dept
   HIP_CHECK(hipMemcpyAsync(terms, fe.dSfOut.p + 1, sizeof(double) * 4 * P, hipMemcpyDeviceToHost, s));
   if (grad) HIP_CHECK(hipMemcpyAsync(grad, fe.dSfGrad.p, F * npx * es, hipMemcpyDeviceToHost, s));
   if (maps) HIP_CHECK(hipMemcpyAsync(maps, fe.dSfMaps.p, mapBytes, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  timer.collect();
+}
+
+// ---- spatial smoothness and contrast losses and their depth gradient (reference loss/disparity_smooth_loss.py,
+// loss/contrast_loss.py; cvd_spatial.h) ----------------------------------------------------------------------------------------
+namespace {
+bool spHasSmooth(const cvd_spatial_desc& d) { return d.lambda_disparity_smooth > 0.0; }
+bool spHasContrast(const cvd_spatial_desc& d) { return d.lambda_contrast_loss > 0.0; }
+
+// checks the desc and the pointers; a table the enabled terms do not read may be NULL (and is then never read)
+void checkSpatial(const cvd_spatial_desc* d, const void* depth, const void* depthOrig, const void* image, const double* total,
+                  const double* smooth, const double* contrast) {
+  if (!d) throw std::runtime_error("spatial losses: null desc");
+  if (d->struct_size != CVD_STRUCT_STAMP(cvd_spatial_desc))
+    throw std::runtime_error(fmt("spatial losses: desc.struct_size %llu is not this library's %llu (built against another revision "
+                                 "of cvd_hip.h)", static_cast<unsigned long long>(d->struct_size),
+                                 static_cast<unsigned long long>(CVD_STRUCT_STAMP(cvd_spatial_desc))));
+  if (d->precision != CVD_PRECISION_F32 && d->precision != CVD_PRECISION_F64)
+    throw std::runtime_error(fmt("spatial losses: precision must be 0 (f32) or 1 (f64) (got %d)", d->precision));
+  if (d->width < 2 || d->height < 2)
+    throw std::runtime_error(fmt("spatial losses: width and height must be >= 2 (got %d x %d)", d->width, d->height));
+  if (static_cast<size_t>(d->width) * d->height > (size_t(1) << 28))
+    throw std::runtime_error(fmt("spatial losses: image size %d x %d exceeds 2^28 pixels", d->width, d->height));
+  if (d->num_frames < 1) throw std::runtime_error(fmt("spatial losses: num_frames must be >= 1 (got %d)", d->num_frames));
+  if (d->frames_per_sample < 1)
+    throw std::runtime_error(fmt("spatial losses: frames_per_sample must be >= 1 (got %d)", d->frames_per_sample));
+  if (d->num_frames % d->frames_per_sample != 0)
+    throw std::runtime_error(fmt("spatial losses: num_frames %d is not a multiple of frames_per_sample %d", d->num_frames,
+                                 d->frames_per_sample));
+  const double lam[2] = {d->lambda_disparity_smooth, d->lambda_contrast_loss};
+  const char* lamName[2] = {"lambda_disparity_smooth", "lambda_contrast_loss"};
+  for (int k = 0; k < 2; ++k)
+    if (!(std::isfinite(lam[k]) && lam[k] >= 0.0))
+      throw std::runtime_error(fmt("spatial losses: %s must be finite and >= 0 (got %g)", lamName[k], lam[k]));
+  if (spHasSmooth(*d) && !(std::isfinite(d->sigma_color_grad) && d->sigma_color_grad > 0.0))
+    throw std::runtime_error(fmt("spatial losses: sigma_color_grad must be finite and > 0 (got %g)", d->sigma_color_grad));
+  if (spHasContrast(*d) && !std::isfinite(d->contrast_thresh))
+    throw std::runtime_error(fmt("spatial losses: contrast_thresh must be finite (got %g)", d->contrast_thresh));
+  if (!depth) throw std::runtime_error("spatial losses: null depth");
+  if (spHasContrast(*d) && !depthOrig) throw std::runtime_error("spatial losses: null depth_orig (lambda_contrast_loss > 0)");
+  if (spHasSmooth(*d) && !image) throw std::runtime_error("spatial losses: null image (lambda_disparity_smooth > 0)");
+  if (!total) throw std::runtime_error("spatial losses: null total");
+  if (!smooth) throw std::runtime_error("spatial losses: null smooth");
+  if (!contrast) throw std::runtime_error("spatial losses: null contrast");
+  // one workgroup per 256 pixels of a frame at least: the grid's x extent
+  const size_t npx = static_cast<size_t>(d->width) * d->height;
+  if (((npx + kConsThreads - 1) / kConsThreads) * static_cast<size_t>(d->num_frames) >= (size_t(1) << 31))
+    throw std::runtime_error(fmt("spatial losses: %d frames of %d x %d exceed the grid", d->num_frames, d->width, d->height));
+}
+
+template <typename T, int PIX>
+void launchSpatialPass(const SpArgs<T>& A, bool grad, hipStream_t s) {
+  const dim3 grid(static_cast<unsigned>(static_cast<size_t>(A.nb) * A.F)), block(kConsThreads);
+  if (grad) hipLaunchKernelGGL((k_sp_pass<T, PIX, true>), grid, block, 0, s, A);
+  else hipLaunchKernelGGL((k_sp_pass<T, PIX, false>), grid, block, 0, s, A);
+}
+
+// device pointers in, device results out, on s; the timer's one phase is the pass and its finish
+template <typename T>
+void launchSpatial(cvd_handle* h, const cvd_spatial_desc& d, const void* depth, const void* depthOrig, const void* image,
+                   double* total, double* smooth, double* contrast, void* grad, hipStream_t s, KernelTimer& timer) {
+  const int F = d.num_frames, N = d.frames_per_sample, B = F / N, W = d.width, H = d.height;
+  const size_t npx = static_cast<size_t>(W) * H;
+  const bool sm = spHasSmooth(d), ct = spHasContrast(d);
+  Frontend& fe = *h->frontend;
+  timer.mark();
+  if (!sm && !ct) {  // no term exists
+    HIP_CHECK(hipMemsetAsync(total, 0, sizeof(double), s));
+    HIP_CHECK(hipMemsetAsync(smooth, 0, sizeof(double) * B, s));
+    HIP_CHECK(hipMemsetAsync(contrast, 0, sizeof(double), s));
+    if (grad) HIP_CHECK(hipMemsetAsync(grad, 0, sizeof(T) * F * npx, s));
+    timer.mark();
+    return;
+  }
+  // four pixels per thread: rows of whole 4-pixel groups and every table read or written aligned for the vector accesses
+  bool four = W % 4 == 0;
+  for (const void* p : {depth, ct ? depthOrig : nullptr, sm ? image : nullptr, static_cast<const void*>(grad)})
+    four = four && reinterpret_cast<uintptr_t>(p) % (4 * sizeof(T)) == 0;
+  const int pix = four ? 4 : 1;
+  const int nb = static_cast<int>((npx + static_cast<size_t>(kConsThreads) * pix - 1) / (static_cast<size_t>(kConsThreads) * pix));
+  fe.dSpSlab.ensure(static_cast<size_t>(F) * nb * 3);
+  fe.dSpPart.ensure(static_cast<size_t>(B));
+  SpArgs<T> A{};
+  A.F = F; A.W = W; A.H = H; A.nb = nb;
+  A.useSmooth = sm; A.useContrast = ct;
+  A.sigma = static_cast<T>(d.sigma_color_grad);
+  A.tau = static_cast<T>(d.contrast_thresh);
+  // smooth = mean_b S_b: an x-edge of any frame weighs lambda_s / (B N H (W-1)), a y-edge lambda_s / (B N (H-1) W); an edge's
+  // contrast value lambda_c / F
+  const double nx = static_cast<double>(N) * H * (W - 1), ny = static_cast<double>(N) * (H - 1) * W;
+  A.kx = static_cast<T>(sm ? d.lambda_disparity_smooth / (nx * B) : 0.0);
+  A.ky = static_cast<T>(sm ? d.lambda_disparity_smooth / (ny * B) : 0.0);
+  A.kc = static_cast<T>(ct ? d.lambda_contrast_loss / F : 0.0);
+  A.depth = static_cast<const T*>(depth);
+  A.depthOrig = ct ? static_cast<const T*>(depthOrig) : nullptr;
+  A.image = sm ? static_cast<const T*>(image) : nullptr;
+  A.slab = fe.dSpSlab.p;
+  A.grad = static_cast<T*>(grad);
+  if (pix == 4) launchSpatialPass<T, 4>(A, grad != nullptr, s);
+  else launchSpatialPass<T, 1>(A, grad != nullptr, s);
+  SpFinishArgs FA{F, N, nb, sm, ct, d.lambda_disparity_smooth, nx, ny, d.lambda_contrast_loss, fe.dSpSlab.p, fe.dSpPart.p,
+                  total, smooth, contrast};
+  hipLaunchKernelGGL(k_sp_finish, dim3(1), dim3(kSpFinishThreads), 0, s, FA);
+  HIP_CHECK(hipGetLastError());
+  timer.mark();
+}
+}  // namespace
+
+// Device arrays in, device results out, on the caller's stream: no copy and no host wait.
+void spatialLossesDevice(cvd_handle* h, const cvd_spatial_desc* d, const void* depth, const void* depthOrig, const void* image,
+                         double* total, double* smooth, double* contrast, void* grad, hipStream_t s) {
+  checkSpatial(d, depth, depthOrig, image, total, smooth, contrast);
+  KernelTimer timer(s, nullptr, 1);
+  if (d->precision == CVD_PRECISION_F64) launchSpatial<double>(h, *d, depth, depthOrig, image, total, smooth, contrast, grad, s, timer);
+  else launchSpatial<float>(h, *d, depth, depthOrig, image, total, smooth, contrast, grad, s, timer);
+}
+
+// Host arrays in, host results out.  kernelMs (may be NULL): {pass + finish} HIP-event time.
+void spatialLosses(cvd_handle* h, const cvd_spatial_desc* d, const void* depth, const void* depthOrig, const void* image,
+                   double* total, double* smooth, double* contrast, void* grad, double* kernelMs) {
+  checkSpatial(d, depth, depthOrig, image, total, smooth, contrast);
+  hipStream_t s = h->stream;
+  Frontend& fe = *h->frontend;
+  const size_t es = d->precision == CVD_PRECISION_F64 ? 8 : 4, npx = static_cast<size_t>(d->width) * d->height;
+  const size_t F = d->num_frames, B = F / d->frames_per_sample;
+  const void* host[3] = {depth, spHasContrast(*d) ? depthOrig : nullptr, spHasSmooth(*d) ? image : nullptr};
+  const void* in[3] = {nullptr, nullptr, nullptr};
+  for (int k = 0; k < 3; ++k) {
+    if (!host[k]) continue;
+    fe.dSpIn[k].upload(static_cast<const unsigned char*>(host[k]), F * (k == 2 ? 3 : 1) * npx * es, s);
+    in[k] = fe.dSpIn[k].p;
+  }
+  fe.dSpOut.ensure(2 + B);
+  if (grad) fe.dSpGrad.ensure(F * npx * es);
+  KernelTimer timer(s, kernelMs, 1);
+  void* dGrad = grad ? fe.dSpGrad.p : nullptr;
+  double* out = fe.dSpOut.p;
+  if (es == 8) launchSpatial<double>(h, *d, in[0], in[1], in[2], out, out + 2, out + 1, dGrad, s, timer);
+  else launchSpatial<float>(h, *d, in[0], in[1], in[2], out, out + 2, out + 1, dGrad, s, timer);
+  HIP_CHECK(hipMemcpyAsync(total, out, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(contrast, out + 1, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(smooth, out + 2, sizeof(double) * B, hipMemcpyDeviceToHost, s));
+  if (grad) HIP_CHECK(hipMemcpyAsync(grad, fe.dSpGrad.p, F * npx * es, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   timer.collect();
 }

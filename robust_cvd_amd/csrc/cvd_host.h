@@ -744,5 +744,9 @@ void sceneFlowLossDevice(cvd_handle* h, const cvd_scene_flow_desc* d, const void
                          const void* warp, const int32_t* pairFrames, const void* const* flows, const void* const* masks,
                          const int32_t* neighborFrames, const void* const* nflows, const void* const* nmasks, const void* valid,
                          double* total, double* terms, void* grad, void* maps, hipStream_t s);
+void spatialLosses(cvd_handle* h, const cvd_spatial_desc* d, const void* depth, const void* depthOrig, const void* image,
+                   double* total, double* smooth, double* contrast, void* grad, double* kernelMs);
+void spatialLossesDevice(cvd_handle* h, const cvd_spatial_desc* d, const void* depth, const void* depthOrig, const void* image,
+                         double* total, double* smooth, double* contrast, void* grad, hipStream_t s);
 
 }  // namespace cvd
