@@ -16,40 +16,15 @@ Differences from the reference: `batch_losses` come back detached (the reference
 training loop only logs them), gradients flow to `depths` only (not to cameras or flows), and metadata["warp"] is NOT scaled in
 place (the reference multiplies it by W/2, H/2 through a view on every call; this module scales a copy).
 
-This is the only module of the package that imports torch.
+Import this module (torch) before anything loads libcvd_hip.so.  The handle, the tensor checks and the autograd function are those
+of robust_cvd_amd.torch_common, shared with scene_flow.py and spatial_losses.py.
 """
 import ctypes as C
 
 import torch
 
 from . import api
-
-
-class _ConsistencyFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, table, module, desc, arrays):
-        """table [F, H, W] contiguous; returns (total, terms [P, 3] float64).  The gradient table is computed by the same call
-        when `table` needs it and kept for backward."""
-        need_grad = table.requires_grad
-        P = desc.num_pairs
-        out = torch.empty(1 + 3 * P, dtype=torch.float64, device=table.device)
-        grad = torch.empty_like(table) if need_grad else None
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        ext, intr, warp, pairs, flow_ab, flow_ba, weight_ab, weight_ba = arrays
-        solver = module._solver(table.device)
-        with torch.cuda.device(table.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            solver._check(solver._fn("consistency_loss_device")(
-                solver._h, C.byref(desc), ptr(table), ptr(ext), ptr(intr), ptr(warp), ptr(pairs), ptr(flow_ab), ptr(flow_ba),
-                ptr(weight_ab), ptr(weight_ba), ptr(out), C.c_void_p(out.data_ptr() + 8), ptr(grad), C.c_void_p(stream)))
-        ctx.grad_table = grad
-        terms = out[1:].view(P, 3)
-        ctx.mark_non_differentiable(terms)
-        return out[0].to(table.dtype), terms
-
-    @staticmethod
-    def backward(ctx, grad_total, _grad_terms):
-        return ctx.grad_table * grad_total.to(ctx.grad_table.dtype), None, None, None
+from . import torch_common as tc
 
 
 class ConsistencyLoss(torch.nn.Module):
@@ -58,14 +33,7 @@ class ConsistencyLoss(torch.nn.Module):
         self.opt = opt
         if opt.distance_type_static not in api.DISTANCE_TYPES:
             raise KeyError(opt.distance_type_static)
-        self._solvers = {}
         self._pairs = {}
-
-    def _solver(self, device):
-        index = device.index if device.index is not None else torch.cuda.current_device()
-        if index not in self._solvers:
-            self._solvers[index] = api.Solver(index)
-        return self._solvers[index]
 
     def _pair_frames(self, B, device):
         key = (B, device)
@@ -75,29 +43,18 @@ class ConsistencyLoss(torch.nn.Module):
 
     def forward(self, depths, metadata):
         opt = self.opt
-        if not (torch.is_tensor(depths) and depths.is_cuda):
-            raise ValueError("ConsistencyLoss runs on GPU tensors: depths is not on a GPU (there is no CPU path)")
-        if depths.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"ConsistencyLoss: depths must be float32 or float64 (got {depths.dtype})")
+        tc.check_depths("ConsistencyLoss", depths)
         if depths.dim() != 4 or depths.shape[1] != 2:
             raise ValueError(f"ConsistencyLoss: depths must be (B, 2, H, W) (got {tuple(depths.shape)})")
         B, N, H, W = depths.shape
         dev, dt = depths.device, depths.dtype
 
-        def arr(t, shape, name):
-            if not (torch.is_tensor(t) and t.device == dev):
-                raise ValueError(f"ConsistencyLoss: {name} is not a tensor on {dev}")
-            t = t.detach().to(dt).reshape(shape)     # (no copy for a contiguous tensor of this dtype)
-            return t.contiguous()
+        arr = lambda t, shape, name: tc.table("ConsistencyLoss", t, shape, name, depths)
 
         table = depths.contiguous().view(B * N, H, W)
         ext = arr(metadata["extrinsics"], (B * N, 3, 4), "extrinsics")
         intr = arr(metadata["intrinsics"], (B * N, 4), "intrinsics")
-        warp = None
-        if opt.recon != "colmap":
-            # the reference scales metadata["warp"] in place, on every call; here a copy, the caller's tensor stays as it is
-            scale = torch.tensor([W / 2, H / 2], dtype=dt, device=dev).view(1, 2, 1, 1)
-            warp = arr(metadata["warp"], (B * N, 2, H, W), "warp") * scale
+        warp = tc.scaled_warp("ConsistencyLoss", metadata["warp"], B * N, H, W, depths) if opt.recon != "colmap" else None
         geom = metadata["geometry_consistency"]
         flows = [arr(f, (B, 2, H, W), "flows") for f in geom["flows"]]
         masks = [arr(m, (B, H, W), "masks") for m in geom["masks"]]
@@ -106,7 +63,9 @@ class ConsistencyLoss(torch.nn.Module):
         lambdas = (opt.lambda_static_reprojection, opt.lambda_static_disparity, opt.lambda_static_depth_ratio)
         desc = api.consistency_desc(dt == torch.float64, B * N, B, H, W, opt.distance_type_static, opt.distance_scale,
                                     getattr(opt, "distance_alpha", 1.0), lambdas, warp is not None)
-        arrays = (ext, intr, warp, self._pair_frames(B, dev), flows[0], flows[1], masks[0], masks[1])
-        total, terms = _ConsistencyFunction.apply(table, self, desc, arrays)
+        arrays = (table, ext, intr, warp, self._pair_frames(B, dev), flows[0], flows[1], masks[0], masks[1])
+        total, terms = tc.EnqueuedLoss.apply(table, "consistency_loss_device", 1 + 3 * B, lambda result, grad: (
+            C.byref(desc), *map(tc.ptr, arrays), result(0), result(1), grad))
+        terms = terms.view(B, 3)
         batch_losses = {name: terms[:, q].to(dt) for q, name in enumerate(api.CONSISTENCY_TERMS) if lambdas[q] > 0}
         return total, batch_losses

@@ -11,8 +11,7 @@
 //   X_t   = R_t^T (R_r X_r + t_r - t_t)                  formed as M X_r + b with M = R_t^T R_r, b = R_t^T (t_r - t_t)
 //   proj  = (cx_t + fx_t X_t.x / (-X_t.z), cy_t - fy_t X_t.y / (-X_t.z))
 //   m     = pix + flow_k(x, y),   e_rep = |proj - m|
-//   z_w   = -bilinear(D_t; u, v): g = 2 m / (size - 1) - 1, u = ((g + 1) size - 1) / 2 clamped to [0, size - 1] (grid_sample,
-//           bilinear, align_corners = false, border), taps floor / floor + 1, a tap outside the image contributes nothing
+//   z_w   = -bilinear(D_t; m): the tap rule of cvd_loss_common.h (grid_sample, bilinear, align_corners = false, border)
 //   e_dsp = 1 / X_t.z - 1 / z_w,   e_rat = lambda_ratio log(min(|z_w|, |X_t.z|) / max(|z_w|, |X_t.z|))
 //   term(e) = sum_px w rho(e) / max(sum_px w, 1e-6)
 // rho: |e / scale| (l1) or the exact branch of the general robust loss (Barron 2019) at alpha = 2, alpha = 0 or any other finite
@@ -20,41 +19,30 @@
 //
 // k_cons_forward<T, PIX>   grid (blocks, P, 2), 256 threads, PIX = 1 or 4 consecutive pixels of a row per thread (4: W % 4 == 0 and
 //                          16 / 32-byte aligned tables).  The cameras of (pair, direction) are the same for the whole workgroup.
-//                          Every workgroup folds (sum w, sum w rho_rep, sum w rho_dsp, sum w rho_rat) in f64 -- lanes by a shuffle
-//                          tree, waves in index order -- and writes them to its slot of a slab: nothing is accumulated atomically.
-// k_cons_finish_pairs      one wave per pair: sums the pair's slab slots in a fixed order.
+//                          Every workgroup folds (sum w, sum w rho_rep, sum w rho_dsp, sum w rho_rat) in f64 into its slot of a
+//                          slab (lossFoldWorkgroup): nothing is accumulated atomically.
+// k_cons_finish_pairs      one wave per pair: sums the pair's slab slots in a fixed order (lossFinishPairs<2>).
 // k_cons_finish_total      one workgroup: the mean focal lengths, the per-pair terms, the total, and for the backward pass the
 //                          factor d total / d (sum w rho) of every (pair, direction, term).  The forward result repeats bit for bit.
 // k_cons_backward<T, PIX>  the same walk; recomputes the sample and adds d total / d depth to the gradient table [F][H][W] (zero
 //                          before the launch): one hardware float atomic for D_r(x, y), up to four for the bilinear taps of D_t.
 //                          The sampling position depends on no depth.  sign(0) = 0 and the norm of the zero vector has gradient 0.
 // k_cons_backward_det<T>   CVD_DETERMINISTIC: one wave per DESTINATION frame walks the (pair, direction)s that name the frame, in
-//                          pair order; the taps of one lane at a time.  All additions to a frame's table come from one wave in
-//                          program order, so the gradient repeats bit for bit.  Slow; for tests.
+//                          pair order; the taps of one lane at a time (lossOrderedTaps).  All additions to a frame's table come
+//                          from one wave in program order, so the gradient repeats bit for bit.  Slow; for tests.
 // A pair that names a frame outside [0, F), or one frame twice, is never dereferenced: its terms and the total come back NaN.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <type_traits>
-
-#ifndef CVD_DETERMINISTIC
-#define CVD_DETERMINISTIC 0
-#endif
+#include "cvd_loss_common.h"
 
 namespace cvd {
-
-constexpr int kConsThreads = 256;
-constexpr int kConsDetThreads = 64;
-
-enum ConsRho { CONS_RHO_L1 = 0, CONS_RHO_TWO = 1, CONS_RHO_ZERO = 2, CONS_RHO_GENERAL = 3 };
 
 template <typename T>
 struct ConsArgs {
   int F, P, W, H;
-  int rho;                      // ConsRho
   int useRep, useDsp, useRat;   // the term's lambda is > 0
   int nb;                       // workgroups per (pair, direction)
-  T lamRat, scale, alpha;
-  T beta, alphaSafe;            // CONS_RHO_GENERAL: max(eps32, |alpha - 2|), sign(alpha) max(eps32, |alpha|)
+  T lamRat;
+  ConsDistance<T> rho;          // the loss's one distance
   const T* depth;
   const T* ext;
   const T* intr;
@@ -84,10 +72,6 @@ struct ConsCam {
   T fxr, fyr, cxr, cyr, fxt, fyt, cxt, cyt;
 };
 
-__device__ __forceinline__ bool consPairOk(int2 ab, int F) {
-  return ab.x >= 0 && ab.x < F && ab.y >= 0 && ab.y < F && ab.x != ab.y;
-}
-
 template <typename T>
 __device__ __forceinline__ ConsCam<T> consCam(const ConsArgs<T>& A, int r, int t) {
   const T* Er = A.ext + static_cast<size_t>(r) * 12;
@@ -104,59 +88,6 @@ __device__ __forceinline__ ConsCam<T> consCam(const ConsArgs<T>& A, int r, int t
   c.fxr = Ir[0]; c.fyr = Ir[1]; c.cxr = Ir[2]; c.cyr = Ir[3];
   c.fxt = It[0]; c.fyt = It[1]; c.cxt = It[2]; c.cyt = It[3];
   return c;
-}
-
-__device__ __forceinline__ float consAbs(float v) { return fabsf(v); }
-__device__ __forceinline__ double consAbs(double v) { return fabs(v); }
-__device__ __forceinline__ float consSqrt(float v) { return sqrtf(v); }
-__device__ __forceinline__ double consSqrt(double v) { return sqrt(v); }
-__device__ __forceinline__ float consLog(float v) { return logf(v); }
-__device__ __forceinline__ double consLog(double v) { return log(v); }
-__device__ __forceinline__ float consLog1p(float v) { return log1pf(v); }
-__device__ __forceinline__ double consLog1p(double v) { return log1p(v); }
-__device__ __forceinline__ float consPow(float a, float b) { return powf(a, b); }
-__device__ __forceinline__ double consPow(double a, double b) { return pow(a, b); }
-__device__ __forceinline__ float consFloor(float v) { return floorf(v); }
-__device__ __forceinline__ double consFloor(double v) { return floor(v); }
-__device__ __forceinline__ float consClamp(float v, float hi) { return fminf(fmaxf(v, 0.f), hi); }  // (NaN -> 0, as grid_sample)
-__device__ __forceinline__ double consClamp(double v, double hi) { return fmin(fmax(v, 0.0), hi); }
-
-// one robust distance: kind (ConsRho), scale, and the constants of the general branch (beta = max(eps32, |alpha - 2|),
-// alphaSafe = sign(alpha) max(eps32, |alpha|))
-template <typename T>
-struct ConsDistance {
-  int kind;
-  T scale, alpha, beta, alphaSafe;
-};
-
-// rho(e) and d rho / d e of the distance R
-template <typename T>
-__device__ __forceinline__ T consRhoOf(const ConsDistance<T>& R, T e, T& d) {
-  const T q = e / R.scale;
-  if (R.kind == CONS_RHO_L1) {
-    d = (e > T(0) ? T(1) : (e < T(0) ? T(-1) : T(0))) / R.scale;
-    return consAbs(q);
-  }
-  const T s = q * q, hs = T(0.5) * s;
-  if (R.kind == CONS_RHO_TWO) {
-    d = q / R.scale;
-    return hs;
-  }
-  if (R.kind == CONS_RHO_ZERO) {
-    const T cap = T(33e37);
-    d = hs < cap ? (q / R.scale) / (T(1) + hs) : T(0);
-    return consLog1p(hs < cap ? hs : cap);
-  }
-  const T base = s / R.beta + T(1);
-  const T pw = consPow(base, T(0.5) * R.alpha);
-  d = (R.alpha / R.alphaSafe) * (pw / base) * (q / R.scale);
-  return (R.beta / R.alphaSafe) * (pw - T(1));
-}
-
-// the consistency loss's one distance
-template <typename T>
-__device__ __forceinline__ T consRho(const ConsArgs<T>& A, T e, T& d) {
-  return consRhoOf(ConsDistance<T>{A.rho, A.scale, A.alpha, A.beta, A.alphaSafe}, e, d);
 }
 
 // One sample.  Forward (GRAD = false): adds (w, w rho_rep, w rho_dsp, w rho_rat) to acc.  Backward: cf = the three factors
@@ -183,7 +114,7 @@ __device__ __forceinline__ void consSample(const ConsArgs<T>& A, const ConsCam<T
     const T dy = -((Y / nz) * c.fyt) + c.cyt - my;
     const T e = consSqrt(dx * dx + dy * dy);
     T dr;
-    const T r = consRho(A, e, dr);
+    const T r = consRhoOf(A.rho, e, dr);
     if (!GRAD) acc[1] += static_cast<double>(w * r);
     else if (e > T(0)) {
       const T dpx = -c.fxt * (ax * Z - X * az) * iz2, dpy = c.fyt * (ay * Z - Y * az) * iz2;
@@ -191,23 +122,12 @@ __device__ __forceinline__ void consSample(const ConsArgs<T>& A, const ConsCam<T
     }
   }
   if (A.useDsp || A.useRat) {
-    const T gx = T(2) * mx / static_cast<T>(A.W - 1) - T(1), gy = T(2) * my / static_cast<T>(A.H - 1) - T(1);
-    const T u = consClamp(((gx + T(1)) * static_cast<T>(A.W) - T(1)) / T(2), static_cast<T>(A.W - 1));
-    const T v = consClamp(((gy + T(1)) * static_cast<T>(A.H) - T(1)) / T(2), static_cast<T>(A.H - 1));
-    const T fu = consFloor(u), fv = consFloor(v);
-    const int x0 = static_cast<int>(fu), y0 = static_cast<int>(fv);
-    const T tx = u - fu, ex = T(1) - tx, ty = v - fv, ey = T(1) - ty;
-    // after the clamp only the +1 tap at the last column / row can lie outside: it contributes nothing and is read from the
-    // clamped texel
-    const bool xin = x0 + 1 < A.W, yin = y0 + 1 < A.H;
-    const int x1 = xin ? x0 + 1 : x0, y1 = yin ? y0 + 1 : y0;
-    const int i00 = y0 * A.W + x0, i01 = y0 * A.W + x1, i10 = y1 * A.W + x0, i11 = y1 * A.W + x1;
-    const T w00 = ey * ex, w01 = xin ? ey * tx : T(0), w10 = yin ? ty * ex : T(0), w11 = (xin && yin) ? ty * tx : T(0);
-    const T zw = -(Dt[i00] * w00 + Dt[i01] * w01 + Dt[i10] * w10 + Dt[i11] * w11);
+    const LossTaps<T> tp = lossBilinearTaps(A.W, A.H, mx, my);
+    const T zw = -(Dt[tp.idx[0]] * tp.wt[0] + Dt[tp.idx[1]] * tp.wt[1] + Dt[tp.idx[2]] * tp.wt[2] + Dt[tp.idx[3]] * tp.wt[3]);
     if (A.useDsp) {
       const T e = T(1) / Z - T(1) / zw;
       T dr;
-      const T r = consRho(A, e, dr);
+      const T r = consRhoOf(A.rho, e, dr);
       if (!GRAD) acc[2] += static_cast<double>(w * r);
       else {
         const T k = cf[1] * w * dr;
@@ -219,7 +139,7 @@ __device__ __forceinline__ void consSample(const ConsArgs<T>& A, const ConsCam<T
       const T p = consAbs(zw), q = consAbs(Z);
       const T e = A.lamRat * consLog((p < q ? p : q) / (p < q ? q : p));
       T dr;
-      const T r = consRho(A, e, dr);
+      const T r = consRhoOf(A.rho, e, dr);
       if (!GRAD) acc[3] += static_cast<double>(w * r);
       else {
         const T sg = p < q ? T(1) : (p > q ? T(-1) : T(0));
@@ -229,8 +149,11 @@ __device__ __forceinline__ void consSample(const ConsArgs<T>& A, const ConsCam<T
       }
     }
     if (GRAD) {
-      tap[0] = i00; tap[1] = i01; tap[2] = i10; tap[3] = i11;
-      gTap[0] = -w00 * gz; gTap[1] = -w01 * gz; gTap[2] = -w10 * gz; gTap[3] = -w11 * gz;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        tap[j] = tp.idx[j];
+        gTap[j] = -tp.wt[j] * gz;
+      }
     }
   } else if (GRAD) {
     tap[0] = tap[1] = tap[2] = tap[3] = 0;
@@ -238,37 +161,6 @@ __device__ __forceinline__ void consSample(const ConsArgs<T>& A, const ConsCam<T
   }
   if (!GRAD) acc[0] += static_cast<double>(w);
   else gD = g;
-}
-
-// f(k) for k = 0 .. PIX - 1 with k a compile-time constant: the per-pixel arrays stay in registers
-template <int K, int PIX, typename Fn>
-__device__ __forceinline__ void consEachPixel(Fn&& f) {
-  if constexpr (K < PIX) {
-    f(std::integral_constant<int, K>{});
-    consEachPixel<K + 1, PIX>(f);
-  }
-}
-
-template <typename T> struct ConsVec4;
-template <> struct ConsVec4<float> { using type = float4; };
-template <> struct ConsVec4<double> { using type = double4; };
-
-// PIX consecutive values at p[i] (PIX = 4: one 16 / 32-byte aligned vector load), returned by value
-template <typename T, int PIX>
-struct ConsVals {
-  T v[PIX];
-};
-
-template <typename T, int PIX>
-__device__ __forceinline__ ConsVals<T, PIX> consLoad(const T* __restrict__ p, size_t i) {
-  ConsVals<T, PIX> out;
-  if constexpr (PIX == 1) {
-    out.v[0] = p[i];
-  } else {
-    const typename ConsVec4<T>::type q = *reinterpret_cast<const typename ConsVec4<T>::type*>(p + i);
-    out.v[0] = q.x; out.v[1] = q.y; out.v[2] = q.z; out.v[3] = q.w;
-  }
-  return out;
 }
 
 // The inputs of a thread's PIX pixels of (pair, dir); ref frame r.
@@ -300,7 +192,6 @@ __device__ __forceinline__ ConsPixels<T, PIX> consLoadPixels(const ConsArgs<T>& 
 template <typename T, int PIX>
 inline __global__ __launch_bounds__(kConsThreads) void k_cons_forward(ConsArgs<T> A) {
   static_assert(PIX == 1 || PIX == 4, "one pixel or four consecutive pixels of a row per thread");
-  __shared__ double part[kConsThreads / 64][4];
   const int pair = blockIdx.y, dir = blockIdx.z;
   const size_t npx = static_cast<size_t>(A.W) * A.H;
   double* slot = A.slab + ((static_cast<size_t>(pair) * 2 + dir) * A.nb + blockIdx.x) * 4;
@@ -323,50 +214,11 @@ inline __global__ __launch_bounds__(kConsThreads) void k_cons_forward(ConsArgs<T
       consSample<T, false>(A, c, Dt, x + k, y, v.D.v[k], v.wx.v[k], v.wy.v[k], v.fx.v[k], v.fy.v[k], v.w.v[k], nullptr, acc, gD, nullptr, nullptr);
     });
   }
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_down(acc[q], o);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) part[wave][q] = acc[q];
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    double s = part[0][threadIdx.x];
-#pragma unroll
-    for (int k = 1; k < kConsThreads / 64; ++k) s += part[k][threadIdx.x];
-    slot[threadIdx.x] = s;
-  }
+  double s;
+  if (lossFoldWorkgroup(acc, s)) slot[threadIdx.x] = s;
 }
 
-// one wave per pair: sums[pair][dir][q] = the slab's nb slots, lane-strided in index order, then a shuffle tree
-inline __global__ __launch_bounds__(64) void k_cons_finish_pairs(ConsFinishArgs A) {
-  const int pair = blockIdx.x, lane = threadIdx.x;
-#pragma unroll
-  for (int dq = 0; dq < 8; ++dq) {
-    const int dir = dq >> 2, q = dq & 3;
-    const double* s = A.slab + (static_cast<size_t>(pair) * 2 + dir) * A.nb * 4 + q;
-    double a = 0.0;
-    for (int b = lane; b < A.nb; b += 64) a += s[static_cast<size_t>(b) * 4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o);
-    if (lane == 0) A.sums[(static_cast<size_t>(pair) * 2 + dir) * 4 + q] = a;
-  }
-}
-
-// sum of one double per thread over the workgroup, in a fixed order; every thread returns the sum
-__device__ __forceinline__ double consBlockSum(double v, double* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = kConsThreads / 2; o > 0; o >>= 1) {
-    if (static_cast<int>(threadIdx.x) < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  return red[0];
-}
+inline __global__ __launch_bounds__(64) void k_cons_finish_pairs(ConsFinishArgs A) { lossFinishPairs<2>(A.slab, A.sums, A.nb); }
 
 template <typename T>
 inline __global__ __launch_bounds__(kConsThreads) void k_cons_finish_total(ConsFinishArgs A, const T* __restrict__ intr) {
@@ -401,9 +253,6 @@ inline __global__ __launch_bounds__(kConsThreads) void k_cons_finish_total(ConsF
   const double total = consBlockSum(sum, red) / A.P;
   if (threadIdx.x == 0) A.total[0] = total;
 }
-
-__device__ __forceinline__ void consAtomicAdd(float* p, float v) { atomicAdd(p, v); }
-__device__ __forceinline__ void consAtomicAdd(double* p, double v) { atomicAdd(p, v); }
 
 template <typename T, int PIX>
 inline __global__ __launch_bounds__(kConsThreads) void k_cons_backward(ConsArgs<T> A) {
@@ -463,17 +312,8 @@ inline __global__ __launch_bounds__(kConsDetThreads) void k_cons_backward_det(Co
         }
         if (r == f) {  // the lanes' pixels are distinct
           if (gD != T(0)) consAtomicAdd(gf + i, gD);
-        } else {       // taps of different lanes may coincide: one lane at a time, in lane order
-          unsigned long long todo = __ballot(gTap[0] != T(0) || gTap[1] != T(0) || gTap[2] != T(0) || gTap[3] != T(0));
-          while (todo) {
-            const int l = __ffsll(static_cast<long long>(todo)) - 1;
-            todo &= todo - 1;
-            if (lane == l) {
-#pragma unroll
-              for (int j = 0; j < 4; ++j)
-                if (gTap[j] != T(0)) consAtomicAdd(gf + tap[j], gTap[j]);
-            }
-          }
+        } else {
+          lossOrderedTaps(gf, lane, tap, gTap);
         }
       }
     }

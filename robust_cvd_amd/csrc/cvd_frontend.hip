@@ -11,6 +11,7 @@
 #include "cvd_epipolar.h"
 #include "cvd_tracks.h"
 #include "cvd_flowmask.h"
+#include "cvd_loss_common.h"
 #include "cvd_consistency.h"
 #include "cvd_sceneflow.h"
 #include "cvd_spatial.h"
@@ -18,6 +19,8 @@
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 namespace cvd {
+
+constexpr int kLossMaxArrays = 17;  // real input arrays of a fine-tuning loss at most (the scene-flow loss)
 
 // Device state of the operators below.  Nothing is allocated before an operator runs; the staging buffers then keep their
 // high-water size for the life of the handle.
@@ -51,21 +54,17 @@ struct Frontend {
   DevBuf<unsigned char> dTrkKept;
   DevBuf<float2> dTrkLoc;
   long long trkTracks = 0, trkKeptObs = 0;
-  // cvd_consistency.h: per-workgroup partial sums, per-(pair, direction) sums and backward factors; then the staging of the
-  // host-array entry point (inputs in the order of ConsistencyArrays, pair frames, total + terms, gradient)
-  DevBuf<double> dConsSlab, dConsSums, dConsCoef, dConsOut;
-  DevBuf<unsigned char> dConsIn[8], dConsGrad;
-  DevBuf<int2> dConsPairs;
-  // cvd_sceneflow.h: the same; the staging in the order of SceneFlowArrays::real, then pair and neighbour frames, total + terms,
-  // gradient, maps
-  DevBuf<double> dSfSlab, dSfSums, dSfCoef, dSfOut;
-  DevBuf<unsigned char> dSfIn[17], dSfGrad, dSfMaps;
-  DevBuf<int2> dSfPairs;
-  DevBuf<int> dSfNbrs;
-  // cvd_spatial.h: per-workgroup partial sums, per-sample contrast sums; then the staging of the host-array entry point (depth,
-  // depth_orig, image; total + contrast + smooth[B]; gradient)
-  DevBuf<double> dSpSlab, dSpPart, dSpOut;
-  DevBuf<unsigned char> dSpIn[3], dSpGrad;
+  // cvd_consistency.h / cvd_sceneflow.h: per-workgroup partial sums, per-(pair, direction or class) sums and backward factors;
+  // cvd_spatial.h: per-workgroup partial sums, per-sample contrast sums.  Per operator: the device entry points use them on the
+  // caller's stream.
+  DevBuf<double> dConsSlab, dConsSums, dConsCoef;
+  DevBuf<double> dSfSlab, dSfSums, dSfCoef;
+  DevBuf<double> dSpSlab, dSpPart;
+  // staging of the three losses' host-array entry points, which run to completion on the handle's stream one at a time and so
+  // share it (runLossOnHostArrays): real inputs in the loss's own order, pair and neighbour frames, scalar results, gradient, maps
+  DevBuf<unsigned char> dLossIn[kLossMaxArrays], dLossGrad, dLossMaps;
+  DevBuf<int32_t> dLossFrames[2];
+  DevBuf<double> dLossOut;
 };
 
 std::shared_ptr<Frontend> makeFrontend() { return std::make_shared<Frontend>(); }
@@ -833,6 +832,136 @@ void flowConsistencyMasks(cvd_handle* h, int numFrames, int hh, int w, int chann
   timer.collect();
 }
 
+// ---- what the fine-tuning losses share on the host (cvd_loss_common.h on the device) -----------------------------------------
+namespace {
+template <typename Desc> constexpr bool kPairLoss = !std::is_same<Desc, cvd_spatial_desc>::value;
+
+// Checks of the desc fields the three losses share; `op` is the operator's message prefix.  lambdas: every weight, finite and
+// >= 0.  A loss of flow pairs (kPairLoss) also has num_pairs and the robust distances `distances` with their scale and alpha.
+template <typename Desc>
+void checkLossDesc(const char* op, const Desc* d, int minFrames, std::initializer_list<std::pair<const char*, double Desc::*>> lambdas,
+                   std::initializer_list<std::pair<const char*, int32_t Desc::*>> distances) {
+  if (!d) throw std::runtime_error(fmt("%s: null desc", op));
+  if (d->struct_size != CVD_STRUCT_STAMP(Desc))
+    throw std::runtime_error(fmt("%s: desc.struct_size %llu is not this library's %llu (built against another revision of cvd_hip.h)",
+                                 op, static_cast<unsigned long long>(d->struct_size),
+                                 static_cast<unsigned long long>(CVD_STRUCT_STAMP(Desc))));
+  if (d->precision != CVD_PRECISION_F32 && d->precision != CVD_PRECISION_F64)
+    throw std::runtime_error(fmt("%s: precision must be 0 (f32) or 1 (f64) (got %d)", op, d->precision));
+  if (d->width < 2 || d->height < 2)
+    throw std::runtime_error(fmt("%s: width and height must be >= 2 (got %d x %d)", op, d->width, d->height));
+  if (static_cast<size_t>(d->width) * d->height > (size_t(1) << 28))
+    throw std::runtime_error(fmt("%s: image size %d x %d exceeds 2^28 pixels", op, d->width, d->height));
+  if (d->num_frames < minFrames) throw std::runtime_error(fmt("%s: num_frames must be >= %d (got %d)", op, minFrames, d->num_frames));
+  if constexpr (kPairLoss<Desc>) {
+    if (d->num_pairs < 1 || d->num_pairs > 65535)
+      throw std::runtime_error(fmt("%s: num_pairs must lie in [1, 65535] (got %d)", op, d->num_pairs));
+  }
+  for (const auto& l : lambdas)
+    if (!(std::isfinite(d->*l.second) && d->*l.second >= 0.0))
+      throw std::runtime_error(fmt("%s: %s must be finite and >= 0 (got %g)", op, l.first, d->*l.second));
+  if constexpr (kPairLoss<Desc>) {
+    for (const auto& t : distances)
+      if (d->*t.second < CVD_DISTANCE_L1 || d->*t.second > CVD_DISTANCE_GENERAL)
+        throw std::runtime_error(fmt("%s: %s must lie in [0, 4] (got %d)", op, t.first, d->*t.second));
+    if (!(std::isfinite(d->distance_scale) && d->distance_scale > 0.0))
+      throw std::runtime_error(fmt("%s: distance_scale must be finite and > 0 (got %g)", op, d->distance_scale));
+    if (!std::isfinite(d->distance_alpha)) throw std::runtime_error(fmt("%s: distance_alpha must be finite (got %g)", op, d->distance_alpha));
+  }
+}
+
+// host-side check of a pair table [P][2] against F frames
+void checkPairFrames(const char* op, const int32_t* pairFrames, int P, int F) {
+  for (int p = 0; p < P; ++p) {
+    const int a = pairFrames[2 * p], b = pairFrames[2 * p + 1];
+    if (a < 0 || a >= F || b < 0 || b >= F)
+      throw std::runtime_error(fmt("%s: pair_frames[%d] = (%d, %d) outside [0, %d)", op, p, a, b, F));
+    if (a == b) throw std::runtime_error(fmt("%s: pair_frames[%d] = (%d, %d) names one frame twice", op, p, a, b));
+  }
+}
+
+// Pixels per thread of a loss walk: four when the rows are whole 4-pixel groups and every per-pixel table is aligned for the
+// vector accesses (a null table is not read and counts as aligned), else one.
+template <size_t N>
+int lossPixelsPerThread(int width, size_t elemSize, const void* const (&tables)[N]) {
+  bool four = width % 4 == 0;
+  for (const void* p : tables) four = four && reinterpret_cast<uintptr_t>(p) % (4 * elemSize) == 0;
+  return four ? 4 : 1;
+}
+
+// workgroups of kConsThreads threads that cover an image of npx pixels
+int lossWorkgroups(size_t npx, int pix) {
+  return static_cast<int>((npx + static_cast<size_t>(kConsThreads) * pix - 1) / (static_cast<size_t>(kConsThreads) * pix));
+}
+
+// f(T{}) with T the precision's type
+template <typename Fn>
+void withPrecision(int precision, Fn&& f) {
+  if (precision == CVD_PRECISION_F64) f(double{});
+  else f(float{});
+}
+
+// Arrays of a loss's host-array entry point.  in: the real inputs in the loss's own order with their sizes in bytes (null: not
+// read); frames: the int32 frame tables with their element counts (null: none); out: the double results with their counts.
+struct LossHostArrays {
+  int numIn;
+  const void* in[kLossMaxArrays];
+  size_t inBytes[kLossMaxArrays];
+  const int32_t* frames[2];
+  size_t frameCount[2];
+  double* out[3];
+  size_t outCount[3];
+  void* grad;
+  size_t gradBytes;
+  void* maps;
+  size_t mapBytes;
+};
+// their staged copies on the device, null where the host array is null
+struct LossDeviceArrays {
+  const void* in[kLossMaxArrays];
+  const int32_t* frames[2];
+  double* out[3];
+  void* grad;
+  void* maps;
+};
+
+// The host-array entry point of a loss: uploads the inputs into the handle's staging buffers, runs launch(device arrays, stream,
+// timer) on the handle's stream, copies the results back, waits, and collects the timer's `phases` phases into kernelMs (may be
+// null).
+template <typename Launch>
+void runLossOnHostArrays(cvd_handle* h, const LossHostArrays& a, double* kernelMs, int phases, Launch&& launch) {
+  hipStream_t s = h->stream;
+  Frontend& fe = *h->frontend;
+  LossDeviceArrays dv{};
+  for (int k = 0; k < a.numIn; ++k) {
+    if (!a.in[k]) continue;
+    fe.dLossIn[k].upload(static_cast<const unsigned char*>(a.in[k]), a.inBytes[k], s);
+    dv.in[k] = fe.dLossIn[k].p;
+  }
+  for (int k = 0; k < 2; ++k) {
+    if (!a.frames[k]) continue;
+    fe.dLossFrames[k].upload(a.frames[k], a.frameCount[k], s);
+    dv.frames[k] = fe.dLossFrames[k].p;
+  }
+  fe.dLossOut.ensure(a.outCount[0] + a.outCount[1] + a.outCount[2]);
+  dv.out[0] = fe.dLossOut.p;
+  dv.out[1] = dv.out[0] + a.outCount[0];
+  dv.out[2] = dv.out[1] + a.outCount[1];
+  if (a.grad) fe.dLossGrad.ensure(a.gradBytes);
+  if (a.maps) fe.dLossMaps.ensure(a.mapBytes);
+  dv.grad = a.grad ? fe.dLossGrad.p : nullptr;
+  dv.maps = a.maps ? fe.dLossMaps.p : nullptr;
+  KernelTimer timer(s, kernelMs, phases);
+  launch(dv, s, timer);
+  for (int k = 0; k < 3; ++k)
+    if (a.outCount[k]) HIP_CHECK(hipMemcpyAsync(a.out[k], dv.out[k], sizeof(double) * a.outCount[k], hipMemcpyDeviceToHost, s));
+  if (a.grad) fe.dLossGrad.download(static_cast<unsigned char*>(a.grad), a.gradBytes, s);
+  if (a.maps) fe.dLossMaps.download(static_cast<unsigned char*>(a.maps), a.mapBytes, s);
+  HIP_CHECK(hipStreamSynchronize(s));
+  timer.collect();
+}
+}  // namespace
+
 // ---- consistency loss of flow pairs and its depth gradient (reference loss/consistency_loss.py, cvd_consistency.h) ----------
 namespace {
 constexpr int kConsArrays = 8;  // depth, extrinsics, intrinsics, warp, flow a->b, flow b->a, weight a->b, weight b->a
@@ -842,31 +971,9 @@ struct ConsistencyArrays {
 };
 
 void checkConsistency(const cvd_consistency_desc* d, const ConsistencyArrays& in, const double* total, const double* terms) {
-  if (!d) throw std::runtime_error("consistency loss: null desc");
-  if (d->struct_size != CVD_STRUCT_STAMP(cvd_consistency_desc))
-    throw std::runtime_error(fmt("consistency loss: desc.struct_size %llu is not this library's %llu (built against another revision "
-                                 "of cvd_hip.h)", static_cast<unsigned long long>(d->struct_size),
-                                 static_cast<unsigned long long>(CVD_STRUCT_STAMP(cvd_consistency_desc))));
-  if (d->precision != CVD_PRECISION_F32 && d->precision != CVD_PRECISION_F64)
-    throw std::runtime_error(fmt("consistency loss: precision must be 0 (f32) or 1 (f64) (got %d)", d->precision));
-  if (d->width < 2 || d->height < 2)
-    throw std::runtime_error(fmt("consistency loss: width and height must be >= 2 (got %d x %d)", d->width, d->height));
-  if (static_cast<size_t>(d->width) * d->height > (size_t(1) << 28))
-    throw std::runtime_error(fmt("consistency loss: image size %d x %d exceeds 2^28 pixels", d->width, d->height));
-  if (d->num_frames < 2) throw std::runtime_error(fmt("consistency loss: num_frames must be >= 2 (got %d)", d->num_frames));
-  if (d->num_pairs < 1 || d->num_pairs > 65535)
-    throw std::runtime_error(fmt("consistency loss: num_pairs must lie in [1, 65535] (got %d)", d->num_pairs));
-  const double lam[3] = {d->lambda_reprojection, d->lambda_disparity, d->lambda_depth_ratio};
-  const char* lamName[3] = {"lambda_reprojection", "lambda_disparity", "lambda_depth_ratio"};
-  for (int k = 0; k < 3; ++k)
-    if (!(std::isfinite(lam[k]) && lam[k] >= 0.0))
-      throw std::runtime_error(fmt("consistency loss: %s must be finite and >= 0 (got %g)", lamName[k], lam[k]));
-  if (d->distance_type < CVD_DISTANCE_L1 || d->distance_type > CVD_DISTANCE_GENERAL)
-    throw std::runtime_error(fmt("consistency loss: distance_type must lie in [0, 4] (got %d)", d->distance_type));
-  if (!(std::isfinite(d->distance_scale) && d->distance_scale > 0.0))
-    throw std::runtime_error(fmt("consistency loss: distance_scale must be finite and > 0 (got %g)", d->distance_scale));
-  if (!std::isfinite(d->distance_alpha))
-    throw std::runtime_error(fmt("consistency loss: distance_alpha must be finite (got %g)", d->distance_alpha));
+  using D = cvd_consistency_desc;
+  checkLossDesc("consistency loss", d, 2, {{"lambda_reprojection", &D::lambda_reprojection}, {"lambda_disparity", &D::lambda_disparity},
+                                           {"lambda_depth_ratio", &D::lambda_depth_ratio}}, {{"distance_type", &D::distance_type}});
   const void* arr[] = {in.depth, in.ext, in.intr, in.pairs, in.flowAB, in.flowBA, in.weightAB, in.weightBA, total, terms};
   const char* arrName[] = {"depth", "extrinsics", "intrinsics", "pair_frames", "flow_ab", "flow_ba", "weight_ab", "weight_ba",
                            "total", "terms"};
@@ -904,12 +1011,8 @@ void launchConsistency(cvd_handle* h, const cvd_consistency_desc& d, const Consi
     timer.mark();
     return;
   }
-  // four pixels per thread: rows of whole 4-pixel groups and tables aligned for the vector loads
-  const void* vec[] = {in.depth, in.warp, in.flowAB, in.flowBA, in.weightAB, in.weightBA};
-  bool four = d.width % 4 == 0;
-  for (const void* p : vec) four = four && reinterpret_cast<uintptr_t>(p) % (4 * sizeof(T)) == 0;
-  const int pix = four ? 4 : 1;
-  const int nb = static_cast<int>((npx + static_cast<size_t>(kConsThreads) * pix - 1) / (static_cast<size_t>(kConsThreads) * pix));
+  const void* const vec[] = {in.depth, in.warp, in.flowAB, in.flowBA, in.weightAB, in.weightBA};
+  const int pix = lossPixelsPerThread(d.width, sizeof(T), vec), nb = lossWorkgroups(npx, pix);
   fe.dConsSlab.ensure(static_cast<size_t>(P) * 2 * nb * 4);
   fe.dConsSums.ensure(static_cast<size_t>(P) * 8);
   fe.dConsCoef.ensure(static_cast<size_t>(P) * 6);
@@ -918,8 +1021,7 @@ void launchConsistency(cvd_handle* h, const cvd_consistency_desc& d, const Consi
   A.useRep = d.lambda_reprojection > 0.0; A.useDsp = d.lambda_disparity > 0.0; A.useRat = d.lambda_depth_ratio > 0.0;
   A.nb = nb;
   A.lamRat = static_cast<T>(d.lambda_depth_ratio);
-  const ConsDistance<T> rho = robustDistance<T>(d.distance_type, d.distance_scale, d.distance_alpha);
-  A.rho = rho.kind; A.scale = rho.scale; A.alpha = rho.alpha; A.beta = rho.beta; A.alphaSafe = rho.alphaSafe;
+  A.rho = robustDistance<T>(d.distance_type, d.distance_scale, d.distance_alpha);
   A.depth = static_cast<const T*>(in.depth);
   A.ext = static_cast<const T*>(in.ext);
   A.intr = static_cast<const T*>(in.intr);
@@ -963,8 +1065,7 @@ void consistencyLossDevice(cvd_handle* h, const cvd_consistency_desc* d, const v
   const ConsistencyArrays in{depth, ext, intr, warp, flowAB, flowBA, weightAB, weightBA, pairFrames};
   checkConsistency(d, in, total, terms);
   KernelTimer timer(s, nullptr, 2);
-  if (d->precision == CVD_PRECISION_F64) launchConsistency<double>(h, *d, in, total, terms, grad, s, timer);
-  else launchConsistency<float>(h, *d, in, total, terms, grad, s, timer);
+  withPrecision(d->precision, [&](auto t) { launchConsistency<decltype(t)>(h, *d, in, total, terms, grad, s, timer); });
 }
 
 // Host arrays in, host results out.  kernelMs (may be NULL): {forward + finish, backward} HIP-event times.
@@ -972,40 +1073,22 @@ void consistencyLoss(cvd_handle* h, const cvd_consistency_desc* d, const void* d
                      const void* warp, const int32_t* pairFrames, const void* flowAB, const void* flowBA, const void* weightAB,
                      const void* weightBA, double* total, double* terms, void* grad, double* kernelMs) {
   checkConsistency(d, ConsistencyArrays{depth, ext, intr, warp, flowAB, flowBA, weightAB, weightBA, pairFrames}, total, terms);
-  const int P = d->num_pairs, F = d->num_frames;
-  for (int p = 0; p < P; ++p) {
-    const int a = pairFrames[2 * p], b = pairFrames[2 * p + 1];
-    if (a < 0 || a >= F || b < 0 || b >= F)
-      throw std::runtime_error(fmt("consistency loss: pair_frames[%d] = (%d, %d) outside [0, %d)", p, a, b, F));
-    if (a == b) throw std::runtime_error(fmt("consistency loss: pair_frames[%d] = (%d, %d) names one frame twice", p, a, b));
-  }
-  hipStream_t s = h->stream;
-  Frontend& fe = *h->frontend;
+  const size_t P = d->num_pairs, F = d->num_frames;
+  checkPairFrames("consistency loss", pairFrames, d->num_pairs, d->num_frames);
   const size_t es = d->precision == CVD_PRECISION_F64 ? 8 : 4, npx = static_cast<size_t>(d->width) * d->height;
-  const void* src[kConsArrays] = {depth, ext, intr, d->have_warp ? warp : nullptr, flowAB, flowBA, weightAB, weightBA};
-  const size_t count[kConsArrays] = {F * npx, size_t(F) * 12, size_t(F) * 4, F * 2 * npx, P * 2 * npx, P * 2 * npx, P * npx, P * npx};
-  const void* dev[kConsArrays];
-  for (int k = 0; k < kConsArrays; ++k) {
-    if (src[k]) fe.dConsIn[k].upload(static_cast<const unsigned char*>(src[k]), count[k] * es, s);
-    dev[k] = src[k] ? fe.dConsIn[k].p : nullptr;
-  }
-  fe.dConsPairs.upload(reinterpret_cast<const int2*>(pairFrames), P, s);
-  fe.dConsOut.ensure(1 + 3 * static_cast<size_t>(P));
-  if (grad) fe.dConsGrad.ensure(F * npx * es);
-  const ConsistencyArrays in{dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], dev[6], dev[7], reinterpret_cast<const int32_t*>(fe.dConsPairs.p)};
-  KernelTimer timer(s, kernelMs, 2);
-  if (es == 8) launchConsistency<double>(h, *d, in, fe.dConsOut.p, fe.dConsOut.p + 1, grad ? fe.dConsGrad.p : nullptr, s, timer);
-  else launchConsistency<float>(h, *d, in, fe.dConsOut.p, fe.dConsOut.p + 1, grad ? fe.dConsGrad.p : nullptr, s, timer);
-  HIP_CHECK(hipMemcpyAsync(total, fe.dConsOut.p, sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(terms, fe.dConsOut.p + 1, sizeof(double) * 3 * P, hipMemcpyDeviceToHost, s));
-  if (grad) HIP_CHECK(hipMemcpyAsync(grad, fe.dConsGrad.p, F * npx * es, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  timer.collect();
+  const LossHostArrays host{kConsArrays,
+                            {depth, ext, intr, d->have_warp ? warp : nullptr, flowAB, flowBA, weightAB, weightBA},
+                            {F * npx * es, F * 12 * es, F * 4 * es, F * 2 * npx * es, P * 2 * npx * es, P * 2 * npx * es, P * npx * es, P * npx * es},
+                            {pairFrames, nullptr}, {2 * P, 0}, {total, terms, nullptr}, {1, 3 * P, 0}, grad, F * npx * es, nullptr, 0};
+  runLossOnHostArrays(h, host, kernelMs, 2, [&](const LossDeviceArrays& dv, hipStream_t s, KernelTimer& timer) {
+    const ConsistencyArrays in{dv.in[0], dv.in[1], dv.in[2], dv.in[3], dv.in[4], dv.in[5], dv.in[6], dv.in[7], dv.frames[0]};
+    withPrecision(d->precision, [&](auto t) { launchConsistency<decltype(t)>(h, *d, in, dv.out[0], dv.out[1], dv.grad, s, timer); });
+  });
 }
 
 // ---- scene-flow loss of flow pairs and its depth gradient (reference loss/scene_flow_loss.py, cvd_sceneflow.h) --------------
 namespace {
-constexpr int kSfArrays = 17;
+constexpr int kSfArrays = kLossMaxArrays;
 // real[]: depth, extrinsics, intrinsics, warp, flows[2], masks[2], neighbor_flows[4], neighbor_masks[4], valid
 struct SceneFlowArrays {
   const void* real[kSfArrays];
@@ -1025,34 +1108,11 @@ SceneFlowArrays checkSceneFlow(const cvd_scene_flow_desc* d, const void* depth, 
                                const int32_t* pairs, const void* const* flows, const void* const* masks, const int32_t* nbrs,
                                const void* const* nflows, const void* const* nmasks, const void* valid, const double* total,
                                const double* terms) {
-  if (!d) throw std::runtime_error("scene flow loss: null desc");
-  if (d->struct_size != CVD_STRUCT_STAMP(cvd_scene_flow_desc))
-    throw std::runtime_error(fmt("scene flow loss: desc.struct_size %llu is not this library's %llu (built against another revision "
-                                 "of cvd_hip.h)", static_cast<unsigned long long>(d->struct_size),
-                                 static_cast<unsigned long long>(CVD_STRUCT_STAMP(cvd_scene_flow_desc))));
-  if (d->precision != CVD_PRECISION_F32 && d->precision != CVD_PRECISION_F64)
-    throw std::runtime_error(fmt("scene flow loss: precision must be 0 (f32) or 1 (f64) (got %d)", d->precision));
-  if (d->width < 2 || d->height < 2)
-    throw std::runtime_error(fmt("scene flow loss: width and height must be >= 2 (got %d x %d)", d->width, d->height));
-  if (static_cast<size_t>(d->width) * d->height > (size_t(1) << 28))
-    throw std::runtime_error(fmt("scene flow loss: image size %d x %d exceeds 2^28 pixels", d->width, d->height));
-  if (d->num_frames < 2) throw std::runtime_error(fmt("scene flow loss: num_frames must be >= 2 (got %d)", d->num_frames));
-  if (d->num_pairs < 1 || d->num_pairs > 65535)
-    throw std::runtime_error(fmt("scene flow loss: num_pairs must lie in [1, 65535] (got %d)", d->num_pairs));
-  const double lam[4] = {d->lambda_static, d->lambda_smooth_reprojection, d->lambda_smooth_disparity, d->lambda_smooth_depth_ratio};
-  const char* lamName[4] = {"lambda_static", "lambda_smooth_reprojection", "lambda_smooth_disparity", "lambda_smooth_depth_ratio"};
-  for (int k = 0; k < 4; ++k)
-    if (!(std::isfinite(lam[k]) && lam[k] >= 0.0))
-      throw std::runtime_error(fmt("scene flow loss: %s must be finite and >= 0 (got %g)", lamName[k], lam[k]));
-  const int dist[2] = {d->distance_type_static, d->distance_type_smooth};
-  const char* distName[2] = {"distance_type_static", "distance_type_smooth"};
-  for (int k = 0; k < 2; ++k)
-    if (dist[k] < CVD_DISTANCE_L1 || dist[k] > CVD_DISTANCE_GENERAL)
-      throw std::runtime_error(fmt("scene flow loss: %s must lie in [0, 4] (got %d)", distName[k], dist[k]));
-  if (!(std::isfinite(d->distance_scale) && d->distance_scale > 0.0))
-    throw std::runtime_error(fmt("scene flow loss: distance_scale must be finite and > 0 (got %g)", d->distance_scale));
-  if (!std::isfinite(d->distance_alpha))
-    throw std::runtime_error(fmt("scene flow loss: distance_alpha must be finite (got %g)", d->distance_alpha));
+  using D = cvd_scene_flow_desc;
+  checkLossDesc("scene flow loss", d, 2,
+                {{"lambda_static", &D::lambda_static}, {"lambda_smooth_reprojection", &D::lambda_smooth_reprojection},
+                 {"lambda_smooth_disparity", &D::lambda_smooth_disparity}, {"lambda_smooth_depth_ratio", &D::lambda_smooth_depth_ratio}},
+                {{"distance_type_static", &D::distance_type_static}, {"distance_type_smooth", &D::distance_type_smooth}});
   const bool st = sfHasStatic(*d), sm = sfHasSmooth(*d);
   if (st && !flows) throw std::runtime_error("scene flow loss: null flows (lambda_static > 0)");
   if (st && !masks) throw std::runtime_error("scene flow loss: null masks (lambda_static > 0)");
@@ -1100,12 +1160,9 @@ void launchSceneFlow(cvd_handle* h, const cvd_scene_flow_desc& d, const SceneFlo
     timer.mark();
     return;
   }
-  // four pixels per thread: rows of whole 4-pixel groups and every per-pixel table aligned for the vector loads (null: not read)
-  bool four = d.width % 4 == 0;
-  for (int k = 0; k < 16; ++k)
-    if (k != 1 && k != 2) four = four && reinterpret_cast<uintptr_t>(in.real[k]) % (4 * sizeof(T)) == 0;
-  const int pix = four ? 4 : 1;
-  const int nb = static_cast<int>((npx + static_cast<size_t>(kConsThreads) * pix - 1) / (static_cast<size_t>(kConsThreads) * pix));
+  const void* vec[14] = {in.real[0]};   // every per-pixel table: depth, then warp .. neighbor_masks[3]
+  std::copy(in.real + 3, in.real + 16, vec + 1);
+  const int pix = lossPixelsPerThread(d.width, sizeof(T), vec), nb = lossWorkgroups(npx, pix);
   fe.dSfSlab.ensure(static_cast<size_t>(P) * 4 * nb * 4);
   fe.dSfSums.ensure(static_cast<size_t>(P) * 16);
   fe.dSfCoef.ensure(static_cast<size_t>(P) * 12);
@@ -1169,8 +1226,7 @@ void sceneFlowLossDevice(cvd_handle* h, const cvd_scene_flow_desc* d, const void
   const SceneFlowArrays in = checkSceneFlow(d, depth, ext, intr, warp, pairFrames, flows, masks, neighborFrames, nflows, nmasks,
                                             valid, total, terms);
   KernelTimer timer(s, nullptr, 2);
-  if (d->precision == CVD_PRECISION_F64) launchSceneFlow<double>(h, *d, in, total, terms, grad, maps, s, timer);
-  else launchSceneFlow<float>(h, *d, in, total, terms, grad, maps, s, timer);
+  withPrecision(d->precision, [&](auto t) { launchSceneFlow<decltype(t)>(h, *d, in, total, terms, grad, maps, s, timer); });
 }
 
 // Host arrays in, host results out.  kernelMs (may be NULL): {forward + finish, backward} HIP-event times.
@@ -1180,49 +1236,29 @@ void sceneFlowLoss(cvd_handle* h, const cvd_scene_flow_desc* d, const void* dept
                    double* total, double* terms, void* grad, void* maps, double* kernelMs) {
   const SceneFlowArrays host = checkSceneFlow(d, depth, ext, intr, warp, pairFrames, flows, masks, neighborFrames, nflows, nmasks,
                                               valid, total, terms);
-  const int P = d->num_pairs, F = d->num_frames;
-  for (int p = 0; p < P; ++p) {
-    const int a = pairFrames[2 * p], b = pairFrames[2 * p + 1];
-    if (a < 0 || a >= F || b < 0 || b >= F)
-      throw std::runtime_error(fmt("scene flow loss: pair_frames[%d] = (%d, %d) outside [0, %d)", p, a, b, F));
-    if (a == b) throw std::runtime_error(fmt("scene flow loss: pair_frames[%d] = (%d, %d) names one frame twice", p, a, b));
-    for (int j = 0; j < 4 && host.nbrs; ++j) {
-      const int n = host.nbrs[4 * p + j];
-      if (n < 0 || n >= F) throw std::runtime_error(fmt("scene flow loss: neighbor_frames[%d][%d] = %d outside [0, %d)", p, j, n, F));
-    }
-  }
-  hipStream_t s = h->stream;
-  Frontend& fe = *h->frontend;
+  const size_t P = d->num_pairs, F = d->num_frames;
+  checkPairFrames("scene flow loss", pairFrames, d->num_pairs, d->num_frames);
+  for (size_t k = 0; k < 4 * P && host.nbrs; ++k)
+    if (host.nbrs[k] < 0 || host.nbrs[k] >= d->num_frames)
+      throw std::runtime_error(fmt("scene flow loss: neighbor_frames[%d][%d] = %d outside [0, %d)", static_cast<int>(k / 4),
+                                   static_cast<int>(k % 4), host.nbrs[k], d->num_frames));
   const size_t es = d->precision == CVD_PRECISION_F64 ? 8 : 4, npx = static_cast<size_t>(d->width) * d->height;
-  SceneFlowArrays in{};
+  LossHostArrays a{kSfArrays, {}, {}, {pairFrames, host.nbrs}, {2 * P, 4 * P}, {total, terms, nullptr}, {1, 4 * P, 0},
+                   grad, F * npx * es, maps, 6 * P * 3 * npx * es};
   for (int k = 0; k < kSfArrays; ++k) {
-    if (!host.real[k]) continue;
-    const size_t count = k == 0 ? F * npx : k == 1 ? size_t(F) * 12 : k == 2 ? size_t(F) * 4 : k == 3 ? F * 2 * npx
-                         : k == 16 ? size_t(P) * 2 : (k < 6 || (k >= 8 && k < 12)) ? P * 2 * npx : P * npx;
-    fe.dSfIn[k].upload(static_cast<const unsigned char*>(host.real[k]), count * es, s);
-    in.real[k] = fe.dSfIn[k].p;
+    a.in[k] = host.real[k];
+    a.inBytes[k] = es * (k == 0 ? F * npx : k == 1 ? F * 12 : k == 2 ? F * 4 : k == 3 ? F * 2 * npx
+                         : k == 16 ? P * 2 : (k < 6 || (k >= 8 && k < 12)) ? P * 2 * npx : P * npx);
   }
-  fe.dSfPairs.upload(reinterpret_cast<const int2*>(pairFrames), P, s);
-  in.pairs = reinterpret_cast<const int32_t*>(fe.dSfPairs.p);
-  if (host.nbrs) {
-    fe.dSfNbrs.upload(host.nbrs, static_cast<size_t>(P) * 4, s);
-    in.nbrs = fe.dSfNbrs.p;
-  }
-  fe.dSfOut.ensure(1 + 4 * static_cast<size_t>(P));
-  if (grad) fe.dSfGrad.ensure(F * npx * es);
-  const size_t mapBytes = static_cast<size_t>(6) * P * 3 * npx * es;
-  if (maps) fe.dSfMaps.ensure(mapBytes);
-  KernelTimer timer(s, kernelMs, 2);
-  void* dGrad = grad ? fe.dSfGrad.p : nullptr;
-  void* dMaps = maps ? fe.dSfMaps.p : nullptr;
-  if (es == 8) launchSceneFlow<double>(h, *d, in, fe.dSfOut.p, fe.dSfOut.p + 1, dGrad, dMaps, s, timer);
-  else launchSceneFlow<float>(h, *d, in, fe.dSfOut.p, fe.dSfOut.p + 1, dGrad, dMaps, s, timer);
-  HIP_CHECK(hipMemcpyAsync(total, fe.dSfOut.p, sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(terms, fe.dSfOut.p + 1, sizeof(double) * 4 * P, hipMemcpyDeviceToHost, s));
-  if (grad) HIP_CHECK(hipMemcpyAsync(grad, fe.dSfGrad.p, F * npx * es, hipMemcpyDeviceToHost, s));
-  if (maps) HIP_CHECK(hipMemcpyAsync(maps, fe.dSfMaps.p, mapBytes, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  timer.collect();
+  runLossOnHostArrays(h, a, kernelMs, 2, [&](const LossDeviceArrays& dv, hipStream_t s, KernelTimer& timer) {
+    SceneFlowArrays in{};
+    std::copy(dv.in, dv.in + kSfArrays, in.real);
+    in.pairs = dv.frames[0];
+    in.nbrs = dv.frames[1];
+    withPrecision(d->precision, [&](auto t) {
+      launchSceneFlow<decltype(t)>(h, *d, in, dv.out[0], dv.out[1], dv.grad, dv.maps, s, timer);
+    });
+  });
 }
 
 // ---- spatial smoothness and contrast losses and their depth gradient (reference loss/disparity_smooth_loss.py,
@@ -1234,28 +1270,14 @@ bool spHasContrast(const cvd_spatial_desc& d) { return d.lambda_contrast_loss > 
 // checks the desc and the pointers; a table the enabled terms do not read may be NULL (and is then never read)
 void checkSpatial(const cvd_spatial_desc* d, const void* depth, const void* depthOrig, const void* image, const double* total,
                   const double* smooth, const double* contrast) {
-  if (!d) throw std::runtime_error("spatial losses: null desc");
-  if (d->struct_size != CVD_STRUCT_STAMP(cvd_spatial_desc))
-    throw std::runtime_error(fmt("spatial losses: desc.struct_size %llu is not this library's %llu (built against another revision "
-                                 "of cvd_hip.h)", static_cast<unsigned long long>(d->struct_size),
-                                 static_cast<unsigned long long>(CVD_STRUCT_STAMP(cvd_spatial_desc))));
-  if (d->precision != CVD_PRECISION_F32 && d->precision != CVD_PRECISION_F64)
-    throw std::runtime_error(fmt("spatial losses: precision must be 0 (f32) or 1 (f64) (got %d)", d->precision));
-  if (d->width < 2 || d->height < 2)
-    throw std::runtime_error(fmt("spatial losses: width and height must be >= 2 (got %d x %d)", d->width, d->height));
-  if (static_cast<size_t>(d->width) * d->height > (size_t(1) << 28))
-    throw std::runtime_error(fmt("spatial losses: image size %d x %d exceeds 2^28 pixels", d->width, d->height));
-  if (d->num_frames < 1) throw std::runtime_error(fmt("spatial losses: num_frames must be >= 1 (got %d)", d->num_frames));
+  using D = cvd_spatial_desc;
+  checkLossDesc("spatial losses", d, 1, {{"lambda_disparity_smooth", &D::lambda_disparity_smooth},
+                                         {"lambda_contrast_loss", &D::lambda_contrast_loss}}, {});
   if (d->frames_per_sample < 1)
     throw std::runtime_error(fmt("spatial losses: frames_per_sample must be >= 1 (got %d)", d->frames_per_sample));
   if (d->num_frames % d->frames_per_sample != 0)
     throw std::runtime_error(fmt("spatial losses: num_frames %d is not a multiple of frames_per_sample %d", d->num_frames,
                                  d->frames_per_sample));
-  const double lam[2] = {d->lambda_disparity_smooth, d->lambda_contrast_loss};
-  const char* lamName[2] = {"lambda_disparity_smooth", "lambda_contrast_loss"};
-  for (int k = 0; k < 2; ++k)
-    if (!(std::isfinite(lam[k]) && lam[k] >= 0.0))
-      throw std::runtime_error(fmt("spatial losses: %s must be finite and >= 0 (got %g)", lamName[k], lam[k]));
   if (spHasSmooth(*d) && !(std::isfinite(d->sigma_color_grad) && d->sigma_color_grad > 0.0))
     throw std::runtime_error(fmt("spatial losses: sigma_color_grad must be finite and > 0 (got %g)", d->sigma_color_grad));
   if (spHasContrast(*d) && !std::isfinite(d->contrast_thresh))
@@ -1296,12 +1318,8 @@ void launchSpatial(cvd_handle* h, const cvd_spatial_desc& d, const void* depth, 
     timer.mark();
     return;
   }
-  // four pixels per thread: rows of whole 4-pixel groups and every table read or written aligned for the vector accesses
-  bool four = W % 4 == 0;
-  for (const void* p : {depth, ct ? depthOrig : nullptr, sm ? image : nullptr, static_cast<const void*>(grad)})
-    four = four && reinterpret_cast<uintptr_t>(p) % (4 * sizeof(T)) == 0;
-  const int pix = four ? 4 : 1;
-  const int nb = static_cast<int>((npx + static_cast<size_t>(kConsThreads) * pix - 1) / (static_cast<size_t>(kConsThreads) * pix));
+  const void* const vec[] = {depth, ct ? depthOrig : nullptr, sm ? image : nullptr, grad};   // every table read or written
+  const int pix = lossPixelsPerThread(W, sizeof(T), vec), nb = lossWorkgroups(npx, pix);
   fe.dSpSlab.ensure(static_cast<size_t>(F) * nb * 3);
   fe.dSpPart.ensure(static_cast<size_t>(B));
   SpArgs<T> A{};
@@ -1335,38 +1353,25 @@ void spatialLossesDevice(cvd_handle* h, const cvd_spatial_desc* d, const void* d
                          double* total, double* smooth, double* contrast, void* grad, hipStream_t s) {
   checkSpatial(d, depth, depthOrig, image, total, smooth, contrast);
   KernelTimer timer(s, nullptr, 1);
-  if (d->precision == CVD_PRECISION_F64) launchSpatial<double>(h, *d, depth, depthOrig, image, total, smooth, contrast, grad, s, timer);
-  else launchSpatial<float>(h, *d, depth, depthOrig, image, total, smooth, contrast, grad, s, timer);
+  withPrecision(d->precision, [&](auto t) {
+    launchSpatial<decltype(t)>(h, *d, depth, depthOrig, image, total, smooth, contrast, grad, s, timer);
+  });
 }
 
 // Host arrays in, host results out.  kernelMs (may be NULL): {pass + finish} HIP-event time.
 void spatialLosses(cvd_handle* h, const cvd_spatial_desc* d, const void* depth, const void* depthOrig, const void* image,
                    double* total, double* smooth, double* contrast, void* grad, double* kernelMs) {
   checkSpatial(d, depth, depthOrig, image, total, smooth, contrast);
-  hipStream_t s = h->stream;
-  Frontend& fe = *h->frontend;
   const size_t es = d->precision == CVD_PRECISION_F64 ? 8 : 4, npx = static_cast<size_t>(d->width) * d->height;
   const size_t F = d->num_frames, B = F / d->frames_per_sample;
-  const void* host[3] = {depth, spHasContrast(*d) ? depthOrig : nullptr, spHasSmooth(*d) ? image : nullptr};
-  const void* in[3] = {nullptr, nullptr, nullptr};
-  for (int k = 0; k < 3; ++k) {
-    if (!host[k]) continue;
-    fe.dSpIn[k].upload(static_cast<const unsigned char*>(host[k]), F * (k == 2 ? 3 : 1) * npx * es, s);
-    in[k] = fe.dSpIn[k].p;
-  }
-  fe.dSpOut.ensure(2 + B);
-  if (grad) fe.dSpGrad.ensure(F * npx * es);
-  KernelTimer timer(s, kernelMs, 1);
-  void* dGrad = grad ? fe.dSpGrad.p : nullptr;
-  double* out = fe.dSpOut.p;
-  if (es == 8) launchSpatial<double>(h, *d, in[0], in[1], in[2], out, out + 2, out + 1, dGrad, s, timer);
-  else launchSpatial<float>(h, *d, in[0], in[1], in[2], out, out + 2, out + 1, dGrad, s, timer);
-  HIP_CHECK(hipMemcpyAsync(total, out, sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(contrast, out + 1, sizeof(double), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(smooth, out + 2, sizeof(double) * B, hipMemcpyDeviceToHost, s));
-  if (grad) HIP_CHECK(hipMemcpyAsync(grad, fe.dSpGrad.p, F * npx * es, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  timer.collect();
+  const LossHostArrays host{3, {depth, spHasContrast(*d) ? depthOrig : nullptr, spHasSmooth(*d) ? image : nullptr},
+                            {F * npx * es, F * npx * es, F * 3 * npx * es}, {nullptr, nullptr}, {0, 0},
+                            {total, contrast, smooth}, {1, 1, B}, grad, F * npx * es, nullptr, 0};
+  runLossOnHostArrays(h, host, kernelMs, 1, [&](const LossDeviceArrays& dv, hipStream_t s, KernelTimer& timer) {
+    withPrecision(d->precision, [&](auto t) {
+      launchSpatial<decltype(t)>(h, *d, dv.in[0], dv.in[1], dv.in[2], dv.out[0], dv.out[2], dv.out[1], dv.grad, s, timer);
+    });
+  });
 }
 
 // One kernel of this translation unit's code object is looked up at handle creation: the HIP runtime loads a unit's device

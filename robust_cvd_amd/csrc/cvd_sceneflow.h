@@ -1,6 +1,6 @@
 // Scene-flow loss of flow pairs and its gradient with respect to the depth maps: the reference's fine-tuning term SceneFlowLoss,
 // loss/scene_flow_loss.py:31-356 with utils/geometry.py:38-137, 238-245 and utils/loss.py:62-80.  Templated on
-// the precision T (float / double) of every real array.  The sibling of cvd_consistency.h, whose lane / pixel helpers it uses.
+// the precision T (float / double) of every real array.  The sibling of cvd_consistency.h; both build on cvd_loss_common.h.
 //
 // Tables: depth [F][H][W], extrinsics [F][3][4] = [R | t], intrinsics [F][4] = (fx, fy, cx, cy), optional warp [F][2][H][W] (pixel
 // offsets, planar), pairs [P] = (a, b).  Static part, per direction k (0: a -> b on a's raster, 1: b -> a on b's): flow_k
@@ -8,7 +8,7 @@
 // flows nflow_j [P][2][H][W] and masks nmask_j [P][H][W] in that order, valid [P][2].
 //   pix_f(x, y) = (x, y) + warp_f(x, y)
 //   X_f(x, y)   = ray_f(pix_f) D_f(x, y),  ray = ((pix.x - cx) / fx, -(pix.y - cy) / fy, -1);   Xw_f = R_f X_f + t_f
-//   S_f(m)      = bilinear sample of the three-channel map X_f at m (the tap rule of cvd_consistency.h applied to ray(tap) D(tap))
+//   S_f(m)      = bilinear sample of the three-channel map X_f at m (the tap rule of cvd_loss_common.h applied to ray(tap) D(tap))
 //   term(rho, w) = sum_px w rho / max(sum_px w, 1e-6)
 // Static, (pair, direction k), ref r, target t:  Y = R_t S_t(pix_r + flow_k) + t_t,  d = |Xw_r - Y|,  w = mask_k / |D_r|  (the
 // weight depends on the depth and is differentiated),  static = lambda_static mean_k term(rho_s(d), w).
@@ -21,7 +21,7 @@
 //                         cameras of (pair, class) are the same for the whole workgroup.  Per-workgroup f64 sums (sum w and up to
 //                         three sum w rho) go to a slot of a slab; nothing is accumulated atomically.  With A.maps the six
 //                         visualisation maps [6][P][3][H][W] are written (zeros for a class that does not exist).
-// k_sf_finish_pairs       one wave per pair: sums the pair's slab slots in a fixed order.
+// k_sf_finish_pairs       one wave per pair: sums the pair's slab slots in a fixed order (lossFinishPairs<4>).
 // k_sf_finish_total       one workgroup: mean focal lengths, per-pair terms, total, and per (pair, class) the backward factors
 //                         (static: d total / d sum w rho and d total / d sum w; smooth: d total / d sum w rho of the three terms).
 // k_sf_backward<T, PIX>   the same walk; one hardware float atomic for D_r(x, y) (both paths of the static term in one add), one
@@ -29,7 +29,7 @@
 // k_sf_backward_det<T>    CVD_DETERMINISTIC: one wave per DESTINATION frame, (pair, class)s in order, taps one lane at a time.
 // A pair or neighbour index outside [0, F), or a == b, is never dereferenced: its terms and the total come back NaN.
 #pragma once
-#include "cvd_consistency.h"
+#include "cvd_loss_common.h"
 
 namespace cvd {
 
@@ -114,23 +114,15 @@ struct SfTaps {
 template <typename T>
 __device__ __forceinline__ SfVec3<T> sfSample(const SfArgs<T>& A, const SfCam<T>& c, const T* __restrict__ Df,
                                                const T* __restrict__ wf, T mx, T my, SfTaps<T>& tp) {
-  const T gx = T(2) * mx / static_cast<T>(A.W - 1) - T(1), gy = T(2) * my / static_cast<T>(A.H - 1) - T(1);
-  const T u = consClamp(((gx + T(1)) * static_cast<T>(A.W) - T(1)) / T(2), static_cast<T>(A.W - 1));
-  const T v = consClamp(((gy + T(1)) * static_cast<T>(A.H) - T(1)) / T(2), static_cast<T>(A.H - 1));
-  const T fu = consFloor(u), fv = consFloor(v);
-  const int x0 = static_cast<int>(fu), y0 = static_cast<int>(fv);
-  const T tx = u - fu, ex = T(1) - tx, ty = v - fv, ey = T(1) - ty;
-  // after the clamp only the +1 tap at the last column / row can lie outside: weight 0, read from the clamped texel
-  const bool xin = x0 + 1 < A.W, yin = y0 + 1 < A.H;
-  const int x1 = xin ? x0 + 1 : x0, y1 = yin ? y0 + 1 : y0;
-  const int xs[4] = {x0, x1, x0, x1}, ys[4] = {y0, y0, y1, y1};
-  tp.wt[0] = ey * ex; tp.wt[1] = xin ? ey * tx : T(0); tp.wt[2] = yin ? ty * ex : T(0); tp.wt[3] = (xin && yin) ? ty * tx : T(0);
+  const LossTaps<T> bt = lossBilinearTaps(A.W, A.H, mx, my);
+  const int xs[4] = {bt.x[0], bt.x[1], bt.x[0], bt.x[1]}, ys[4] = {bt.y[0], bt.y[0], bt.y[1], bt.y[1]};
   const size_t npx = static_cast<size_t>(A.W) * A.H;
   SfVec3<T> S{T(0), T(0), T(0)};
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int i = ys[j] * A.W + xs[j];
+    const int i = bt.idx[j];
     tp.idx[j] = i;
+    tp.wt[j] = bt.wt[j];
     T px = static_cast<T>(xs[j]), py = static_cast<T>(ys[j]);
     if (wf) {
       px += wf[i];
@@ -345,7 +337,6 @@ __device__ __forceinline__ SfPixels<T, PIX> sfLoadPixels(const SfArgs<T>& A, int
 template <typename T, int PIX>
 inline __global__ __launch_bounds__(kConsThreads) void k_sf_forward(SfArgs<T> A) {
   static_assert(PIX == 1 || PIX == 4, "one pixel or four consecutive pixels of a row per thread");
-  __shared__ double part[kConsThreads / 64][4];
   const int pair = blockIdx.y, cls = blockIdx.z;
   const size_t npx = static_cast<size_t>(A.W) * A.H;
   double* slot = A.slab + ((static_cast<size_t>(pair) * 4 + cls) * A.nb + blockIdx.x) * 4;
@@ -399,38 +390,11 @@ inline __global__ __launch_bounds__(kConsThreads) void k_sf_forward(SfArgs<T> A)
       });
     }
   }
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_down(acc[q], o);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) part[wave][q] = acc[q];
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    double s = part[0][threadIdx.x];
-#pragma unroll
-    for (int k = 1; k < kConsThreads / 64; ++k) s += part[k][threadIdx.x];
-    slot[threadIdx.x] = s;
-  }
+  double s;
+  if (lossFoldWorkgroup(acc, s)) slot[threadIdx.x] = s;
 }
 
-// one wave per pair: sums[pair][class][q] = the slab's nb slots, lane-strided in index order, then a shuffle tree
-inline __global__ __launch_bounds__(64) void k_sf_finish_pairs(SfFinishArgs A) {
-  const int pair = blockIdx.x, lane = threadIdx.x;
-#pragma unroll
-  for (int cq = 0; cq < 16; ++cq) {
-    const int cls = cq >> 2, q = cq & 3;
-    const double* s = A.slab + (static_cast<size_t>(pair) * 4 + cls) * A.nb * 4 + q;
-    double a = 0.0;
-    for (int b = lane; b < A.nb; b += 64) a += s[static_cast<size_t>(b) * 4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o);
-    if (lane == 0) A.sums[(static_cast<size_t>(pair) * 4 + cls) * 4 + q] = a;
-  }
-}
+inline __global__ __launch_bounds__(64) void k_sf_finish_pairs(SfFinishArgs A) { lossFinishPairs<4>(A.slab, A.sums, A.nb); }
 
 template <typename T>
 inline __global__ __launch_bounds__(kConsThreads) void k_sf_finish_total(SfFinishArgs A, const T* __restrict__ intr) {
@@ -540,21 +504,6 @@ inline __global__ __launch_bounds__(kConsThreads) void k_sf_backward(SfArgs<T> A
   });
 }
 
-// the taps of one lane at a time, in lane order (taps of different lanes may coincide)
-template <typename T>
-__device__ __forceinline__ void sfOrderedTaps(T* gf, int lane, const SfTaps<T>& tp, const T* gTap) {
-  unsigned long long todo = __ballot(gTap[0] != T(0) || gTap[1] != T(0) || gTap[2] != T(0) || gTap[3] != T(0));
-  while (todo) {
-    const int l = __ffsll(static_cast<long long>(todo)) - 1;
-    todo &= todo - 1;
-    if (lane == l) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (gTap[j] != T(0)) consAtomicAdd(gf + tp.idx[j], gTap[j]);
-    }
-  }
-}
-
 template <typename T>
 inline __global__ __launch_bounds__(kConsDetThreads) void k_sf_backward_det(SfArgs<T> A) {
   const int f = blockIdx.x, lane = threadIdx.x;
@@ -580,8 +529,8 @@ inline __global__ __launch_bounds__(kConsDetThreads) void k_sf_backward_det(SfAr
                        v.m0.v[0], gD, tp0, gTap0, tp1, gTap1);
         }
         if (fr.r == f && gD != T(0)) consAtomicAdd(gf + i, gD);  // the lanes' pixels are distinct
-        if (fr.s0 == f) sfOrderedTaps(gf, lane, tp0, gTap0);
-        if (cls >= 2 && fr.s1 == f) sfOrderedTaps(gf, lane, tp1, gTap1);
+        if (fr.s0 == f) lossOrderedTaps(gf, lane, tp0.idx, gTap0);
+        if (cls >= 2 && fr.s1 == f) lossOrderedTaps(gf, lane, tp1.idx, gTap1);
       }
     }
   }

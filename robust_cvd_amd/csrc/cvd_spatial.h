@@ -2,7 +2,7 @@
 // DisparitySmoothLoss (loss/disparity_smooth_loss.py:15-56), the edge-aware L1 on the disparity gradient, and ContrastLoss
 // (loss/contrast_loss.py:13-79), which keeps the depth ratio across the original estimator's depth edges above a threshold
 // (DESIGN.md §3.12).  Templated on the precision T (float / double) of every real array.  The lane / vector-load helpers are
-// those of cvd_consistency.h.
+// those of cvd_loss_common.h.
 //
 // Tables, contiguous, F = B N frames, frame f of sample b = f / N: depth [F][H][W], depth_orig [F][H][W] (read only with the
 // contrast term), image [F][3][H][W] (read only with the smoothness term).  With d = 1 / D:
@@ -28,7 +28,7 @@
 // k_sp_finish              one workgroup: a wave per sample sums its frames' slots in a fixed order into S_b; thread 0 then
 //                          forms smooth, contrast and total.
 #pragma once
-#include "cvd_consistency.h"
+#include "cvd_loss_common.h"
 
 namespace cvd {
 
@@ -159,7 +159,6 @@ template <typename T, int PIX, bool GRAD>
 inline __global__ __launch_bounds__(kConsThreads) void k_sp_pass(SpArgs<T> A) {
 #pragma clang fp contract(off)
   static_assert(PIX == 1 || PIX == 4, "one pixel or four consecutive pixels of a row per thread");
-  __shared__ double part[kConsThreads / 64][3];
   const int f = static_cast<int>(blockIdx.x / A.nb), tile = static_cast<int>(blockIdx.x - static_cast<unsigned>(f) * A.nb);
   const size_t npx = static_cast<size_t>(A.W) * A.H;
   const size_t i0 = (static_cast<size_t>(tile) * kConsThreads + threadIdx.x) * PIX;
@@ -238,22 +237,8 @@ inline __global__ __launch_bounds__(kConsThreads) void k_sp_pass(SpArgs<T> A) {
       *reinterpret_cast<typename ConsVec4<T>::type*>(out) = q;
     }
   }
-#pragma unroll
-  for (int q = 0; q < 3; ++q)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_down(acc[q], o);
-  const int wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) part[wave][q] = acc[q];
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double s = part[0][threadIdx.x];
-#pragma unroll
-    for (int k = 1; k < kConsThreads / 64; ++k) s += part[k][threadIdx.x];
-    A.slab[(static_cast<size_t>(f) * A.nb + tile) * 3 + threadIdx.x] = s;
-  }
+  double s;
+  if (lossFoldWorkgroup(acc, s)) A.slab[(static_cast<size_t>(f) * A.nb + tile) * 3 + threadIdx.x] = s;
 }
 
 // One workgroup.  Wave w takes the samples w, w + 16, ...: per frame of the sample, in frame order, the lanes stride over the

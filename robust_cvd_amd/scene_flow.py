@@ -27,37 +27,7 @@ import ctypes as C
 import torch
 
 from . import api
-
-
-class _SceneFlowFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, table, module, desc, arrays, want_maps):
-        """table [F, H, W] contiguous; returns (total, terms [P, 4] float64, maps [6, P, 3, H, W] or an empty tensor).  The gradient
-        table is computed by the same call when `table` needs it and kept for backward."""
-        need_grad = table.requires_grad
-        P = desc.num_pairs
-        F, H, W = table.shape
-        out = torch.empty(1 + 4 * P, dtype=torch.float64, device=table.device)
-        grad = torch.empty_like(table) if need_grad else None
-        maps = torch.empty((6, P, 3, H, W) if want_maps else (0,), dtype=table.dtype, device=table.device)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        group = lambda ts: None if ts is None else (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        ext, intr, warp, pairs, flows, masks, nbrs, nflows, nmasks, valid = arrays
-        solver = module._solver(table.device)
-        with torch.cuda.device(table.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            solver._check(solver._fn("scene_flow_loss_device")(
-                solver._h, C.byref(desc), ptr(table), ptr(ext), ptr(intr), ptr(warp), ptr(pairs), group(flows), group(masks),
-                ptr(nbrs), group(nflows), group(nmasks), ptr(valid), ptr(out), C.c_void_p(out.data_ptr() + 8), ptr(grad),
-                ptr(maps) if want_maps else None, C.c_void_p(stream)))
-        ctx.grad_table = grad
-        terms = out[1:].view(P, 4)
-        ctx.mark_non_differentiable(terms, maps)
-        return out[0].to(table.dtype), terms, maps
-
-    @staticmethod
-    def backward(ctx, grad_total, _grad_terms, _grad_maps):
-        return ctx.grad_table * grad_total.to(ctx.grad_table.dtype), None, None, None, None
+from . import torch_common as tc
 
 
 class SceneFlowLoss(torch.nn.Module):
@@ -68,14 +38,7 @@ class SceneFlowLoss(torch.nn.Module):
         for name in (opt.distance_type_static, opt.distance_type_smooth):
             if name not in api.DISTANCE_TYPES:
                 raise KeyError(name)
-        self._solvers = {}
         self._frames = {}
-
-    def _solver(self, device):
-        index = device.index if device.index is not None else torch.cuda.current_device()
-        if index not in self._solvers:
-            self._solvers[index] = api.Solver(index)
-        return self._solvers[index]
 
     def _frame_tables(self, B, N, device):
         key = (B, N, device)
@@ -88,10 +51,7 @@ class SceneFlowLoss(torch.nn.Module):
 
     def forward(self, depths, metadata):
         opt = self.opt
-        if not (torch.is_tensor(depths) and depths.is_cuda):
-            raise ValueError("SceneFlowLoss runs on GPU tensors: depths is not on a GPU (there is no CPU path)")
-        if depths.dtype not in (torch.float32, torch.float64):
-            raise TypeError(f"SceneFlowLoss: depths must be float32 or float64 (got {depths.dtype})")
+        tc.check_depths("SceneFlowLoss", depths)
         lambdas = (opt.lambda_scene_flow_static, opt.lambda_smooth_reprojection, opt.lambda_smooth_disparity,
                    opt.lambda_smooth_depth_ratio)
         smooth = any(v > 0 for v in lambdas[1:])
@@ -100,20 +60,12 @@ class SceneFlowLoss(torch.nn.Module):
         B, N, H, W = depths.shape
         dev, dt = depths.device, depths.dtype
 
-        def arr(t, shape, name):
-            if not (torch.is_tensor(t) and t.device == dev):
-                raise ValueError(f"SceneFlowLoss: {name} is not a tensor on {dev}")
-            t = t.detach().to(dt).reshape(shape)     # (no copy for a contiguous tensor of this dtype)
-            return t.contiguous()
+        arr = lambda t, shape, name: tc.table("SceneFlowLoss", t, shape, name, depths)
 
         table = depths.contiguous().view(B * N, H, W)
         ext = arr(metadata["extrinsics"], (B * N, 3, 4), "extrinsics")
         intr = arr(metadata["intrinsics"], (B * N, 4), "intrinsics")
-        warp = None
-        if opt.recon != "colmap":
-            # the reference scales metadata["warp"] in place, on every call; here a copy, the caller's tensor stays as it is
-            scale = torch.tensor([W / 2, H / 2], dtype=dt, device=dev).view(1, 2, 1, 1)
-            warp = arr(metadata["warp"], (B * N, 2, H, W), "warp") * scale
+        warp = tc.scaled_warp("SceneFlowLoss", metadata["warp"], B * N, H, W, depths) if opt.recon != "colmap" else None
         flows = masks = nflows = nmasks = valid = None
         if lambdas[0] > 0:
             geom = metadata["geometry_consistency"]
@@ -131,8 +83,13 @@ class SceneFlowLoss(torch.nn.Module):
         pairs, nbrs = self._frame_tables(B, N, dev)
         desc = api.scene_flow_desc(dt == torch.float64, B * N, B, H, W, opt.distance_type_static, opt.distance_type_smooth,
                                    opt.distance_scale, getattr(opt, "distance_alpha", 1.0), lambdas, warp is not None)
-        arrays = (ext, intr, warp, pairs, flows, masks, nbrs if smooth else None, nflows, nmasks, valid)
-        total, terms, maps = _SceneFlowFunction.apply(table, self, desc, arrays, self.scene_flow_maps)
+        # maps [6, B, 3, H, W]: the six visualisation maps, written by the same call on request
+        maps = torch.empty((6, B, 3, H, W), dtype=dt, device=dev) if self.scene_flow_maps else None
+        group = lambda ts: None if ts is None else (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        total, terms = tc.EnqueuedLoss.apply(table, "scene_flow_loss_device", 1 + 4 * B, lambda result, grad: (
+            C.byref(desc), tc.ptr(table), tc.ptr(ext), tc.ptr(intr), tc.ptr(warp), tc.ptr(pairs), group(flows), group(masks),
+            tc.ptr(nbrs if smooth else None), group(nflows), group(nmasks), tc.ptr(valid), result(0), result(1), grad, tc.ptr(maps)))
+        terms = terms.view(B, 4)
         batch_losses = {name: terms[:, q].to(dt) for q, name in enumerate(api.SCENE_FLOW_TERMS) if lambdas[q] > 0}
         scene_flow = None
         if self.scene_flow_maps:

@@ -24,41 +24,8 @@ import ctypes as C
 import torch
 
 from . import api
-
-
-class _SpatialFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, table, solver, desc, depth_orig, image):
-        """table [F, H, W] contiguous; returns (total, smooth [B] float64, contrast).  The gradient table is computed by the same
-        call when `table` needs it and kept for backward."""
-        need_grad = table.requires_grad
-        B = desc.num_frames // desc.frames_per_sample
-        out = torch.empty(2 + B, dtype=torch.float64, device=table.device)      # total, contrast, smooth[B]
-        grad = torch.empty_like(table) if need_grad else None
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        with torch.cuda.device(table.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            solver._check(solver._fn("spatial_losses_device")(
-                solver._h, C.byref(desc), ptr(table), ptr(depth_orig), ptr(image), ptr(out), C.c_void_p(out.data_ptr() + 16),
-                C.c_void_p(out.data_ptr() + 8), ptr(grad), C.c_void_p(stream)))
-        ctx.grad_table = grad
-        smooth, contrast = out[2:], out[1]
-        ctx.mark_non_differentiable(smooth, contrast)
-        return out[0].to(table.dtype), smooth, contrast
-
-    @staticmethod
-    def backward(ctx, grad_total, _grad_smooth, _grad_contrast):
-        return ctx.grad_table * grad_total.to(ctx.grad_table.dtype), None, None, None, None
-
-
-_solvers = {}
-
-
-def _solver(device):
-    index = device.index if device.index is not None else torch.cuda.current_device()
-    if index not in _solvers:
-        _solvers[index] = api.Solver(index)
-    return _solvers[index]
+from . import torch_common as tc
+from .torch_common import solver as _solver     # (the process's handle of a device, as before the modules shared it)
 
 
 def spatial_terms(depths, depth_orig=None, images=None, *, lambda_disparity_smooth=0.0, sigma_color_grad=1.0,
@@ -66,29 +33,26 @@ def spatial_terms(depths, depth_orig=None, images=None, *, lambda_disparity_smoo
     """Both spatial terms of `depths` (B, N, H, W) in one kernel call: (total, smooth (B,), contrast), `total` attached to
     `depths`, the other two detached, all in the dtype of `depths`.  depth_orig (B, N, H, W) is read when lambda_contrast_loss
     > 0, images (B, N, 3, H, W) when lambda_disparity_smooth > 0."""
-    if not (torch.is_tensor(depths) and depths.is_cuda):
-        raise ValueError(f"{who} runs on GPU tensors: depths is not on a GPU (there is no CPU path)")
-    if depths.dtype not in (torch.float32, torch.float64):
-        raise TypeError(f"{who}: depths must be float32 or float64 (got {depths.dtype})")
+    tc.check_depths(who, depths)
     if depths.dim() != 4:
         raise ValueError(f"{who}: depths must be (B, N, H, W) (got {tuple(depths.shape)})")
     B, N, H, W = depths.shape
     dev, dt = depths.device, depths.dtype
 
     def arr(t, shape, name):
-        if not (torch.is_tensor(t) and t.device == dev):
-            raise ValueError(f"{who}: {name} is not a tensor on {dev}")
-        if t.numel() != B * N * H * W * (3 if len(shape) == 4 else 1):
+        if torch.is_tensor(t) and t.device == dev and t.numel() != B * N * H * W * (3 if len(shape) == 4 else 1):
             raise ValueError(f"{who}: {name} has shape {tuple(t.shape)}, expected to view as {shape}")
-        return t.detach().to(dt).reshape(shape).contiguous()     # (no copy for a contiguous tensor of this dtype)
+        return tc.table(who, t, shape, name, depths)
 
     table = depths.contiguous().view(B * N, H, W)
     orig = arr(depth_orig, (B * N, H, W), "depth_orig") if lambda_contrast_loss > 0 else None
     image = arr(images, (B * N, 3, H, W), "images") if lambda_disparity_smooth > 0 else None
     desc = api.spatial_desc(dt == torch.float64, B * N, N, H, W, lambda_disparity_smooth, sigma_color_grad, lambda_contrast_loss,
                             contrast_thresh)
-    total, smooth, contrast = _SpatialFunction.apply(table, _solver(dev), desc, orig, image)
-    return total, smooth.to(dt), contrast.to(dt)
+    # the results: total, contrast, smooth[B]
+    total, rest = tc.EnqueuedLoss.apply(table, "spatial_losses_device", 2 + B, lambda result, grad: (
+        C.byref(desc), tc.ptr(table), tc.ptr(orig), tc.ptr(image), result(0), result(2), result(1), grad))
+    return total, rest[1:].to(dt), rest[0].to(dt)
 
 
 class DisparitySmoothLoss(torch.nn.Module):

@@ -79,9 +79,55 @@ def check_torch_module(solver, golden, dtype):
         raise AssertionError("a CPU tensor was accepted")
 
 
+def check_misaligned_tables(golden, dtype):
+    """Tables that are not aligned to four elements take the one-pixel-per-thread kernels (case `batch`: 24 x 40, four workgroups
+    per image where the aligned run has one): depths, and in a second run one flow tensor, as contiguous views offset by one
+    element.  Total, terms and gradient against the fixture with the bars of test_gpu_consistency.py for this combination: f64
+    1e-10 relative and the gradient 1e-9 x max |g|; f32 total and gradient 8 x the reference's own f32 delta (never below 2^-23;
+    that test sets no f32 bar for the terms, so they are checked in f64)."""
+    combo = cc.COMBOS[11]
+    key, case = cc.combo_key(combo), cc.make_case("batch")
+    td = getattr(torch, dtype)
+    B, H, W = case["P"], case["H"], case["W"]
+    assert W % 4 == 0
+    dev = torch.device("cuda", 0)
+    ref_total, ref_terms, ref_g = float(golden[f"{key}/total"]), golden[f"{key}/terms"], golden[f"{key}/grad"]
+    d_total, d_grad = float(golden[f"{key}/delta_total"]), float(golden[f"{key}/delta_grad"])
+    opt = types.SimpleNamespace(distance_type_static=combo[1], distance_scale=combo[2], distance_alpha=combo[3],
+                                lambda_static_reprojection=combo[4][0], lambda_static_disparity=combo[4][1],
+                                lambda_static_depth_ratio=combo[4][2], recon="i3d")
+    t = lambda a: torch.tensor(np.ascontiguousarray(a), dtype=td, device=dev)
+
+    def shifted(a):
+        flat = torch.zeros(a.size + 1, dtype=td, device=dev)
+        flat[1:] = t(a).ravel()
+        v = flat[1:].view(a.shape)
+        assert v.is_contiguous() and v.data_ptr() % (4 * v.element_size()) != 0
+        return v
+    for which in ("depths", "flow"):
+        depths = (shifted if which == "depths" else t)(case["depth"]).view(B, 2, H, W).detach().requires_grad_(True)
+        assert (depths.data_ptr() % (4 * depths.element_size()) != 0) == (which == "depths")
+        flow_ba = (shifted if which == "flow" else t)(case["flow_ba"])
+        meta = {"extrinsics": t(case["extrinsics"]).view(B, 2, 3, 4), "intrinsics": t(case["intrinsics"]).view(B, 2, 4),
+                "warp": t(case["warp_norm"]).view(B, 2, 2, H, W),
+                "geometry_consistency": {"flows": (t(case["flow_ab"]), flow_ba),
+                                         "masks": (t(case["weight_ab"]).view(B, 1, H, W), t(case["weight_ba"]).view(B, 1, H, W))}}
+        loss, batch = ConsistencyLoss(opt)(depths, meta)
+        loss.backward()
+        g = depths.grad.cpu().numpy().reshape(ref_g.shape).astype(np.float64)
+        what = f"cons misaligned {which} {dtype}"
+        f64 = dtype == "float64"
+        margins.below(f"{what} total", abs(float(loss) - ref_total) / abs(ref_total), 1e-10 if f64 else 8 * max(d_total, EPS32))
+        margins.below(f"{what} grad", np.abs(g - ref_g).max() / np.abs(ref_g).max(), 1e-9 if f64 else 8 * max(d_grad, EPS32))
+        if f64:
+            tt = np.stack([batch[name].cpu().numpy() for name in cr.TERMS], 1)
+            margins.below(f"{what} terms", np.max(np.abs(tt - ref_terms) / np.abs(ref_terms)), 1e-10)
+
+
 if __name__ == "__main__":
     torch.cuda.init()
     s = api.Solver(0)
     check_torch_module(s, np.load(cr.GOLDEN), sys.argv[1])
+    check_misaligned_tables(np.load(cr.GOLDEN), sys.argv[1])
     s.close()
     print("torch module ok")

@@ -101,6 +101,52 @@ def check_bad_frame_index(solver, dtype):
     assert depths.grad[1, 0].any() and depths.grad[0].any()
 
 
+def check_misaligned_tables(golden, dtype):
+    """Tables that are not aligned to four elements take the one-pixel-per-thread kernels (case `batch`: 2 x 6 frames of 16 x 24,
+    two workgroups per image where the aligned run has one): depths, and in a second run one neighbour flow tensor, as
+    contiguous views offset by one element.  Total, terms and gradient against the fixture with the bars of
+    test_gpu_sceneflow.py for this combination: f64 1e-10 relative and the gradient 1e-9 x max |g|; f32 total and gradient 8 x
+    the reference's own f32 delta (never below 2^-23; that test sets no f32 bar for the terms, so they are checked in f64)."""
+    combo = sc.COMBOS[10]
+    key, case = sc.combo_key(combo), sc.make_case("batch")
+    td = getattr(torch, dtype)
+    B, H, W = case["P"], case["H"], case["W"]
+    assert W % 4 == 0 and case["F"] == 6 * B and all(v > 0 for v in combo[5])
+    dev = torch.device("cuda", 0)
+    ref_total, ref_terms, ref_g = float(golden[f"{key}/total"]), golden[f"{key}/terms"], golden[f"{key}/grad"]
+    d_total, d_grad = float(golden[f"{key}/delta_total"]), float(golden[f"{key}/delta_grad"])
+    t = lambda a: torch.tensor(np.ascontiguousarray(a), dtype=td, device=dev)
+
+    def shifted(a):
+        flat = torch.zeros(a.size + 1, dtype=td, device=dev)
+        flat[1:] = t(a).ravel()
+        v = flat[1:].view(a.shape)
+        assert v.is_contiguous() and v.data_ptr() % (4 * v.element_size()) != 0
+        return v
+    for which in ("depths", "flow"):
+        depths = (shifted if which == "depths" else t)(case["depth"]).view(B, 6, H, W).detach().requires_grad_(True)
+        assert (depths.data_ptr() % (4 * depths.element_size()) != 0) == (which == "depths")
+        nflows = [t(f) for f in case["nflows"]]
+        if which == "flow":
+            nflows[2] = shifted(case["nflows"][2])
+        meta = {"extrinsics": t(case["extrinsics"]).view(B, 6, 3, 4), "intrinsics": t(case["intrinsics"]).view(B, 6, 4),
+                "warp": t(case["warp_norm"]).view(B, 6, 2, H, W),
+                "geometry_consistency": {"flows": tuple(t(f) for f in case["flows"]),
+                                         "masks": tuple(t(m).view(B, 1, H, W) for m in case["masks"])},
+                "temporal_smoothness": {"flows": tuple(nflows), "masks": tuple(t(m).view(B, 1, H, W) for m in case["nmasks"]),
+                                        "valid": t(case["valid"]).view(B, 2, 1)}}
+        loss, batch, _ = SceneFlowLoss(options(combo))(depths, meta)
+        loss.backward()
+        g = depths.grad.cpu().numpy().reshape(ref_g.shape).astype(np.float64)
+        what = f"sf misaligned {which} {dtype}"
+        f64 = dtype == "float64"
+        margins.below(f"{what} total", abs(float(loss) - ref_total) / abs(ref_total), 1e-10 if f64 else 8 * max(d_total, EPS32))
+        margins.below(f"{what} grad", np.abs(g - ref_g).max() / np.abs(ref_g).max(), 1e-9 if f64 else 8 * max(d_grad, EPS32))
+        if f64:
+            tt = np.stack([batch[name].cpu().numpy() for name in sr.TERMS], 1)
+            margins.below(f"{what} terms", np.max(np.abs(tt - ref_terms) / np.abs(ref_terms)), 1e-10)
+
+
 if __name__ == "__main__":
     torch.cuda.init()
     s = api.Solver(0)
@@ -108,5 +154,6 @@ if __name__ == "__main__":
     check_torch_module(s, golden, sys.argv[1], sc.COMBOS[10], 6)
     check_torch_module(s, golden, sys.argv[1], sc.COMBOS[12], 2)
     check_bad_frame_index(s, sys.argv[1])
+    check_misaligned_tables(golden, sys.argv[1])
     s.close()
     print("torch module ok")

@@ -10,7 +10,8 @@ from robust_cvd_amd import build
 from tests.codegen_util import CSRC, device_asm, kernel_names
 
 FRONTEND_HEADERS = ["cvd_dense.h", "cvd_sampling.h", "cvd_imageops.h", "cvd_filter.h", "cvd_bilateral.h", "cvd_epipolar.h",
-                    "cvd_tracks.h", "cvd_flowmask.h"]
+                    "cvd_tracks.h", "cvd_flowmask.h", "cvd_consistency.h", "cvd_sceneflow.h", "cvd_spatial.h"]
+# (cvd_loss_common.h, which the three loss headers include, defines device functions only: no kernel to look for)
 
 
 def header_kernels(header):
