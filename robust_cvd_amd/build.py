@@ -4,8 +4,10 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
-# translation units of libcvd_hip.so (compiled in parallel).  Every unit includes cvd_host.h and, through it, the solver's kernel
-# headers; the front-end operators' kernel headers are included by cvd_frontend alone (tests/test_codegen_units.py).
+# translation units of libcvd_hip.so (compiled in parallel).  Every unit includes cvd_host.h, which brings cvd_kernels.h (shared types
+# and device helpers, the pair product: no non-template kernel) and no other kernel header; a unit includes by name the headers of the
+# kernels it launches -- cvd_table.h, cvd_cost.h, cvd_assembly.h, cvd_block_inverse.h, cvd_pcg.h, the side headers, and cvd_frontend
+# alone the front-end operators' (kernel map: cvd_kernels.h; tests/test_codegen_units.py).
 UNITS = ["cvd_api", "cvd_comm", "cvd_setup", "cvd_eval", "cvd_matvec", "cvd_precond", "cvd_temporal", "cvd_solve", "cvd_frontend"]
 LIB = os.path.join(_HERE, "lib", "libcvd_hip.so")
 OBJ = os.path.join(_HERE, "lib", "obj")
@@ -70,8 +72,8 @@ def build_variant(name, defines, units=None, verbose=False):
 
 
 def build_deterministic(verbose=False):
-    """lib/libcvd_hip_det.so: every translation unit with -DCVD_DETERMINISTIC=1 (cvd_kernels.h: accumulations through LDS atomics by
-    ONE wave, folds in index order -- bit-reproducible solves, several times slower).  tests/test_gpu_determinism.py and
+    """lib/libcvd_hip_det.so: every translation unit with -DCVD_DETERMINISTIC=1 (default in cvd_kernels.h, read by every kernel header: accumulations through LDS
+    atomics by ONE wave, folds in index order -- bit-reproducible solves, several times slower).  tests/test_gpu_determinism.py and
     tools/det_check.py load it with api.load_library(variant="det").  Rebuilt when a source is newer than the library."""
     out = os.path.join(_HERE, "lib", "libcvd_hip_det.so")
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))] + [os.path.join(_HERE, "..", "include", "cvd_hip.h"), os.path.join(_HERE, "..", "include", "cvd_hip_debug.h")]

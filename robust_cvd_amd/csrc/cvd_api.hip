@@ -1,5 +1,6 @@
 // cvd_api.hip -- the C ABI of include/cvd_hip.h and the coarse-to-fine schedule above the solve.
 #include "cvd_host.h"
+#include "cvd_coarse.h"
 
 namespace cvd {
 
@@ -350,12 +351,6 @@ int32_t cvd_comm_init_phantom(cvd_handle* h, int32_t rank, int32_t world) {
     h->tableValid = false;
   });
 }
-#ifdef CVD_ASM_PROFILE
-int32_t cvd_debug_asm_profile(unsigned long long* out) {
-  hipDeviceSynchronize();
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(cvd::g_asmProf), sizeof(unsigned long long) * 2048 * 16) == hipSuccess ? 0 : 1;
-}
-#endif
 int32_t cvd_set_generic_kernels(cvd_handle* h, int32_t enabled) { CVD_TRY(h, h->forceGeneric = enabled != 0); }
 
 int32_t cvd_set_video(cvd_handle* h, int32_t numFrames, int32_t width, int32_t height, float aspect, float invAspect) {

@@ -26,9 +26,6 @@
 
 namespace cvd {
 
-constexpr size_t kCoarseMaxUnknowns = 65536;  // 8192 frames (the plan is built on the host in O(F^2))
-constexpr int kCBB = kCB * kCB;   // doubles per coarse block (kCB = 8 coarse unknowns per frame, cvd_device.h)
-
 // LDS hand-off between the lanes of ONE wave (LDS operations of a wave complete in order; the fences only pin
 // the compiler).
 #define CVD_WAVE_SYNC()                                      \
@@ -38,40 +35,6 @@ constexpr int kCBB = kCB * kCB;   // doubles per coarse block (kCB = 8 coarse un
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   \
   } while (0)
 
-// Elimination plan (device pointers, built by the host in buildCoarsePlan).  Indices are elimination POSITIONS
-// unless stated otherwise.  Block ids: [0, F) diagonal block of position j, F + e off-diagonal block e of L.
-struct CoarsePlan {
-  int F, nBlocks, nLevels, nEdges;
-  const int* order;      // position -> frame
-  const int* pos;        // frame -> position
-  const int* levelPtr;   // nLevels + 1, into levelCols
-  const int* levelCols;  // positions grouped by level (columns of one level are mutually independent)
-  const int* lvlBlkPtr;  // nLevels + 1, into lvlBlks: every block (diagonal and below) of the level's columns
-  const int* lvlBlks;    // block ids
-  const int* blkCol;     // block id -> column position j
-  const int* blkRow;     // block id -> row position i (>= j)
-  const int* colPtr;     // F + 1: off-diagonal blocks below the diagonal of column j are ids F + [colPtr[j], colPtr[j+1])
-  const int* rowPtr;     // F + 1: off-diagonal blocks of ROW j (left of the diagonal)
-  const int* rowBlk;     //   their block ids
-  const int* updPtr;     // nBlocks + 1: left-looking update list of block (i, j): pairs L(i,k), L(j,k), k < j
-  const int* updA;       //   block id of L(i, k)
-  const int* updB;       //   block id of L(j, k)
-  const int* edgeBlk;    // nEdges: (block id << 1) | transposed   (edge block is stored rows = fa, cols = fb)
-  const int* edgeFa;     // nEdges
-  const int* edgeFb;     // nEdges
-  // W = L^-1: column j holds blocks at rows path(j) = j, parent(j), parent(parent(j)), ... (W block id = wPtr[j] + t)
-  const int* wPtr;       // F + 1
-  const int* wRow;       // row position of every W block
-  const int* wtPtr;      // F + 1: W blocks of ROW i (transpose structure), ordered by column
-  const int* wtBlk;      //   W block id
-  const int* wtCol;      //   column position
-  const int* wtFrame;    //   frame of that column (order[wtCol])
-  const int* wuPtr;      // nW + 1: gather list of W block (i, j): pairs L(i,k) W(k,j), k on the path below i
-  const int* wuL;        //   block id of L(i, k)
-  const int* wuW;        //   W block id of W(k, j)
-  int nW;                // number of W blocks
-  const int* updBlk;     // per update entry: the block id it belongs to (inverse of updPtr)
-};
 // *flag <- (*flag != 0): the dense level's fail word (bit 0 pivot failure, bit 30 barrier timeout) before it is summed over
 // the ranks of a sharded solve (a sum of bit-30 values could wrap to zero).
 inline __global__ void k_flag_to_bool(int* __restrict__ flag) { *flag = (*flag != 0) ? 1 : 0; }

@@ -20,16 +20,6 @@
 
 namespace cvd {
 
-// Undirected frame pairs of the explicit-block mode: ranges of both directions' pixel slots (either may be empty) and the
-// two rows of the partial-product buffer.
-struct CrossPairs {
-  const int* fa;            // fa < fb
-  const int* fb;
-  const long long* range;   // 4 per pair: [a -> b begin, end, b -> a begin, end) pixel slots
-  const int* slot;          // 2 per pair: rows of the partial buffer (frame-major)
-  int count;
-};
-
 constexpr int kCrossThreads = 512;
 // q rows of one undirected pair from its block: y_a = X p_b, y_b = X^T p_a with p = (z + Z c + beta p_old) * mask (the
 // search direction, formed here exactly as the matrix-free product forms it).  Each wave streams its rows once, fully

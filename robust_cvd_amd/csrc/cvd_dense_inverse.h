@@ -5,7 +5,7 @@
 // it (cvd_temporal.h: n = 8 x nodes = 312 and n = nodes x hats = 495 at 300 frames, 0.12 ms each); the 2400-unknown exact level
 // remains as cvd_solver_options::coarse_over_budget = 1.
 //
-// Algorithm: the symmetric sweep operator of k_block_inverse_mfma (cvd_kernels.h), blocked with 16-wide pivot tiles, spread
+// Algorithm: the symmetric sweep operator of k_block_inverse_mfma (cvd_block_inverse.h), blocked with 16-wide pivot tiles, spread
 // over the device.  Sweeping pivot tile k (P = G_kk^-1) maps
 //     G_kk <- -P,   G_ik <- G_ik P,   G_kj <- P G_kj,   G_ij <- G_ij - G_ik P G_kj      (i, j != k)
 // and after all nT = n / 16 steps G = -A^-1.  n^3 flop like potrf + potri, but ONE uniform step: every tile of the lower
@@ -32,7 +32,7 @@
 // bounded and a timeout raises `fail` and releases all workgroups.
 #pragma once
 
-#include "cvd_kernels.h"
+#include "cvd_block_inverse.h"
 
 namespace cvd {
 

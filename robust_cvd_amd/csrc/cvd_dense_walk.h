@@ -33,7 +33,7 @@
 //   256 + 40 G            sum of rho (the pair's cost)
 #pragma once
 
-#include "cvd_cross.h"
+#include "cvd_kernels.h"
 
 namespace cvd {
 
@@ -45,7 +45,7 @@ constexpr int kDwBlk = 8;            // pixels of a lane's run that are loaded t
 constexpr int kDwIoStride = 9;       // per-run stride of the wave's input tiles [64 runs][8 pixels] (9 is odd: conflict-free by lane)
 // input tiles of a wave: flow (float2, reused for the grid x grid scalars: double) | source depth | target depth | mask
 constexpr int kDwIoBytes = 64 * kDwIoStride * (8 + 4 + 4 + 1);
-// (dwRecordDoubles, DenseRecords: cvd_kernels.h, beside the frame-major kernel that folds the records)
+// (dwRecordDoubles, DenseRecords: cvd_kernels.h; the frame-major kernel that folds the records: k_assemble_fast, cvd_assembly.h)
 constexpr int kDwCols = 15;          // side-block columns of a record
 
 // Lane map of the walks.  A lane's LDS atomics go to the vertices of the cell its pixel lies in: lanes of one wave instruction that

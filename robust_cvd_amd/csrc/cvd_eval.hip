@@ -1,10 +1,14 @@
 // cvd_eval.hip -- cost / gradient / frame-diagonal blocks (and the dense mode's explicit cross blocks) at a point.
 #include "cvd_host.h"
+#include "cvd_cost.h"
+#include "cvd_assembly.h"
+#include "cvd_triplets.h"
+#include "cvd_dense_walk.h"
 
 namespace cvd {
 
 void launchFrameConsts(Ctx& c, const double* x) {
-  hipLaunchKernelGGL(k_frame_consts, dim3((c.L.F + 63) / 64), dim3(64), 0, c.h->stream, c.L, x, c.h->dFc.p);
+  launchFrameConsts(c.L, x, c.h->dFc.p, c.h->stream);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -166,7 +170,7 @@ double evalFull(Ctx& c, const double* x, bool withStats, bool noReadBack) {
   if (fast && fastFits) {
     h->dAsmScratch.ensure(static_cast<size_t>(h->nAsmSlots) * (B * (B + 1) / 2 + B + 4));
     const AsmWork work{h->dAsmParts.p, h->dAsmUnits.p, h->dAsmScratch.p, h->dAsmCount.p};
-    // STAGE: the other frame's parameters in a per-wave LDS buffer whenever the LDS holds 8 B doubles more (cvd_kernels.h)
+    // STAGE: the other frame's parameters in a per-wave LDS buffer whenever the LDS holds 8 B doubles more (cvd_assembly.h)
     const size_t ldsStage = ldsFast + static_cast<size_t>(kAsmThreads / 64) * B * 8;
     const bool stage = ldsStage <= kMaxLds;
 #define CVD_LAUNCH_ASM(DENSEV, STAGEV)                                                                                     \
@@ -277,3 +281,10 @@ void touchModule_eval() {
 }
 
 }  // namespace cvd
+
+#ifdef CVD_ASM_PROFILE
+extern "C" int32_t cvd_debug_asm_profile(unsigned long long* out) {  // (same translation unit as the launches: the symbol is per unit)
+  (void)hipDeviceSynchronize();
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(cvd::g_asmProf), sizeof(unsigned long long) * 2048 * 16) == hipSuccess ? 0 : 1;
+}
+#endif

@@ -1,7 +1,8 @@
 // cvd_host.h -- host-side state shared by the translation units of libcvd_hip.so: error macros, device buffers, the
-// handle (one DepthVideo + depth stream), the per-solve context and the functions the units call across.  It includes the
-// solver's kernel headers, whose types the handle embeds; the front-end operators' headers and device state belong to
-// cvd_frontend.hip alone (cvd::Frontend, an incomplete type here).
+// handle (one DepthVideo + depth stream), the per-solve context and the functions the units call across.  Of the kernel
+// headers it includes cvd_kernels.h alone, for the plain types the handle embeds (that header defines no non-template kernel);
+// every unit includes, by name, the headers of the kernels it launches (kernel map: cvd_kernels.h).  The front-end operators'
+// headers and device state belong to cvd_frontend.hip alone (cvd::Frontend, an incomplete type here).
 // gfx950 only.  There is NO CPU path.
 #pragma once
 
@@ -36,11 +37,6 @@
 
 #include "../../include/cvd_hip_debug.h"
 #include "cvd_kernels.h"
-#include "cvd_coarse.h"
-#include "cvd_temporal.h"
-#include "cvd_cross.h"
-#include "cvd_dense_walk.h"
-#include "cvd_triplets.h"
 
 
 namespace cvd {
@@ -636,7 +632,12 @@ void downloadState(cvd_handle* h, const Layout& L, const DevBuf<double>& src);
 void buildMask(cvd_handle* h, const Layout& L, const cvd_opt_params& p, ProblemKind kind, const std::vector<int>& range);
 void ensureBuffers(Ctx& c);
 void refreshMedians(cvd_handle* h);
-void launchFrameConsts(Ctx& c, const double* x);
+void launchFrameConsts(const Layout& L, const double* x, FrameConst* fc, hipStream_t s);  // k_frame_consts (cvd_setup.hip)
+void launchFrameConsts(Ctx& c, const double* x);   // ... of the solve, into dFc on the main stream
+void launchFlagToBool(int* flag, hipStream_t s);   // k_flag_to_bool (cvd_precond.hip)
+// k_tl_rows_init (cvd_solve.hip): first residual of a level of NT unknowns walked by tlLevelRows, one workgroup per (hat, node range)
+void launchTlRowsInit(cvd_handle* h, const TlStep* tsp, int NT, int groups, int F, unsigned int* counter, int closeScalars, double tol2,
+                      hipStream_t s);
 void spinStream(hipStream_t s);
 void spinEvent(hipEvent_t ev);
 void readScalars(Ctx& c);

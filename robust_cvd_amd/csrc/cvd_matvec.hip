@@ -1,5 +1,8 @@
 // cvd_matvec.hip -- the PCG product q = (J^T J + diag(lam)) p: pair-major partial products, per-frame finish, exchange.
 #include "cvd_host.h"
+#include "cvd_pcg.h"
+#include "cvd_cross.h"
+#include "cvd_triplets.h"
 
 namespace cvd {
 
@@ -229,7 +232,7 @@ void launchMatvec(Ctx& c, const double* x, const double* z, const double* pOld, 
   }
 }
 
-// ---- k_pcg_tail: finish + update of a PCG iteration in one launch (cvd_kernels.h) ----------------------------------------
+// ---- k_pcg_tail: finish + update of a PCG iteration in one launch (cvd_pcg.h) --------------------------------------------
 // Scope and launch geometry: one GPU, frame block <= 256, dense coarse level or none, and every workgroup of the launch
 // resident at once (the kernel has a grid barrier): checked against the kernel's occupancy on this device.
 bool pcgTailScope(Ctx& c, bool coarse, int nThreads, size_t& lds, int& ldsFinish, int& ldsScratch) {

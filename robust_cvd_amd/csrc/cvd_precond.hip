@@ -1,8 +1,14 @@
 // cvd_precond.hip -- the two-level preconditioner: per-frame block inverses and the pose-graph coarse level.
 #include "cvd_host.h"
+#include "cvd_block_inverse.h"
+#include "cvd_coarse.h"
+#include "cvd_cross.h"
+#include "cvd_dense_walk.h"
 #include "cvd_dense_inverse.h"
 
 namespace cvd {
+
+void launchFlagToBool(int* flag, hipStream_t s) { hipLaunchKernelGGL(k_flag_to_bool, dim3(1), dim3(1), 0, s, flag); }
 
 // M_f^-1 = (H_ff + diag(lam_f))^-1 for every frame (f32 output).
 //   variant 0 (default): blocked sweep on the f64 matrix cores (k_block_inverse_mfma, 16-wide pivot blocks);
@@ -212,7 +218,7 @@ void launchCoarseSetup(Ctx& c, const double* x, int side) {
   {
     // off-diagonal blocks of the coarse (pose-graph) matrix at the current linearisation point x (only here: the
     // factor is rebuilt on demand, not at every accepted step)
-    hipLaunchKernelGGL(k_frame_consts, dim3((c.L.F + 63) / 64), dim3(64), 0, s, c.L, x, fcBuf);
+    launchFrameConsts(c.L, x, fcBuf, s);
     HIP_CHECK(hipMemsetAsync(C.edges.p, 0, static_cast<size_t>(std::max(C.nEdges, 1)) * kCBB * sizeof(double), s));
     if (C.sparsified) HIP_CHECK(hipMemsetAsync(C.dropDiag.p, 0, static_cast<size_t>(c.L.F) * kCBB * sizeof(double), s));
     const size_t ldsE = 2 * B * 8 + 2 * sizeof(FrameConst) + 4 * kCBB * 8;  // (x of both frames, their constants, one 8 x 8 slot per wave)
@@ -284,7 +290,7 @@ void launchCoarseSetup(Ctx& c, const double* x, int side) {
       // follows every in-line build, takes the pending request)
       launchPoseTemporalBuild(c, s, failOut, h->temporal.on && !h->dist());
       if (h->dist()) {
-        hipLaunchKernelGGL(k_flag_to_bool, dim3(1), dim3(1), 0, s, failOut);
+        launchFlagToBool(failOut, s);
         const int ct = h->tBegin(KC_COMM_COARSE);
         commAllReduce(h, failOut, 1, CT_I32, s);
         h->tEnd(ct);
@@ -308,7 +314,7 @@ void launchCoarseSetup(Ctx& c, const double* x, int side) {
       // Every rank inverts the same matrix bit-reproducibly, so pivot failures agree by themselves; a barrier TIMEOUT (bit 30)
       // is a property of one device's load.  The ranks must take the same "level on / off" decision -- their PCG iteration
       // counts, hence the collectives they enqueue, depend on it: the flag is reduced to 0 / 1 and summed.
-      hipLaunchKernelGGL(k_flag_to_bool, dim3(1), dim3(1), 0, s, failOut);
+      launchFlagToBool(failOut, s);
       const int ct = h->tBegin(KC_COMM_COARSE);
       commAllReduce(h, failOut, 1, CT_I32, s);
       h->tEnd(ct);

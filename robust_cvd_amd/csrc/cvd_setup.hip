@@ -1,9 +1,17 @@
 // cvd_setup.hip -- problem -> device layout: poses / transforms on the host, the Layout of a solve, the compiled constraint table and
 // work decomposition, the coarse level's symbolic plan, state transfers, buffers, frame medians.
 #include "cvd_host.h"
+#include "cvd_table.h"
+#include "cvd_triplets.h"
+#include "cvd_dense_walk.h"
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 namespace cvd {
+
+// R(w), dR/dw, t, fy of every frame at x: the one launch site of the three units that need them (evaluation, coarse level, third level)
+void launchFrameConsts(const Layout& L, const double* x, FrameConst* fc, hipStream_t s) {
+  hipLaunchKernelGGL(k_frame_consts, dim3((L.F + 63) / 64), dim3(64), 0, s, L, x, fc);
+}
 
 // ---- rotation conversions on the host (ceres/rotation.h + Eigen semantics) -------------
 static void quatToMatrix(const double q[4] /*x,y,z,w*/, double R[3][3]) {

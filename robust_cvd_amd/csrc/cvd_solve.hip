@@ -1,7 +1,17 @@
 // cvd_solve.hip -- the PCG loop, the Levenberg-Marquardt driver (Ceres defaults) and the evaluation hook.
 #include "cvd_host.h"
+#include "cvd_pcg.h"
+#include "cvd_coarse.h"
 
 namespace cvd {
+
+void launchTlRowsInit(cvd_handle* h, const TlStep* tsp, int NT, int groups, int F, unsigned int* counter, int closeScalars, double tol2,
+                      hipStream_t s) {
+  const size_t lds = static_cast<size_t>(tlRowsLds(NT)) * 8;
+  allowLds(k_tl_rows_init, lds);
+  hipLaunchKernelGGL(k_tl_rows_init, dim3(groups), dim3(768), lds, s, tsp, F, h->dScal.p, counter, closeScalars, tol2, h->hPcg);
+  HIP_CHECK(hipGetLastError());
+}
 
 // PCG on (H + diag(lam)) dx = -g with the block-Jacobi preconditioner; returns iterations used.
 // Three launches per iteration (pairs product, per-frame finish, per-frame update).  alpha / beta live on

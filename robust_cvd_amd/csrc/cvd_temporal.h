@@ -20,8 +20,8 @@
 //     products of their temporal weights (k_tl_reduce), the (node, node) blocks gather the groups' sums and the frames'
 //     C_f (k_tl_assemble); A_T is block-banded in the node index (|a - b| <= 2), stored dense, unknown e = s * nn + a.
 //   * inverse              k_dense_spd_inverse (cvd_dense_inverse.h), f64.
-// Per PCG iteration the level lives inside the existing launches (TlStep / CoarseView::tl in cvd_device.h, tlLevelRows in
-// cvd_kernels.h): nothing here.
+// Per PCG iteration the level lives inside the existing launches (TlStep / CoarseView::tl in cvd_device.h, tlLevelRows and
+// k_tl_rows_init in cvd_pcg.h): nothing here.
 #pragma once
 
 #include "cvd_kernels.h"
@@ -447,24 +447,6 @@ inline __global__ __launch_bounds__(256) void k_tl_restrict(Layout L, const doub
     double a = 0.0;
     for (int k = 0; k < ts.width; ++k) a += prod[k * ts.S + tid];
     ts.sq[static_cast<size_t>(f) * ts.S + tid] = a;
-  }
-}
-// t = A_T^-1 P^T r, r_T = P^T r, tl, and the level's part of r^T z added to S_RZPART (k_cg_update(init) left the block-Jacobi part
-// there; the pose-graph level's kernel closes the scalars afterwards)
-inline __global__ __launch_bounds__(1024) void k_tl_rows_init(const TlStep* __restrict__ tsp, int F, double* __restrict__ scal,
-                                                       unsigned int* __restrict__ counter, int closeScalars, double tol2,
-                                                       double* __restrict__ hostMirror) {
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  __shared__ int flag;
-  NoMid mid;
-  double alpha = 0.0;
-  (void)tlLevelRows<false>(tsp, blockIdx.x, F, alpha, 1, 0.0, scal, sm, mid);
-  if (!lastBlockArrivesLite(counter, gridDim.x, &flag)) return;
-  if (threadIdx.x == 0) {
-    double d = 0.0;
-    for (int s = 0; s < tsp->S * tsp->parts; ++s) d += readPartial(tsp->dotPart + s);
-    if (closeScalars) pcgFinishScalars(scal, 1, scal[S_RZPART] + d, scal[S_RR], tol2, hostMirror);
-    else scal[S_RZPART] += d;
   }
 }
 

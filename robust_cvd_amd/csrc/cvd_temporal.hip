@@ -1,6 +1,7 @@
 // cvd_temporal.hip -- host side of the third preconditioner level (cvd_temporal.h): scope, tables and work lists, the build of
 // A_T^-1 per (H, lam, x), the first residual of a PCG solve.  The per-iteration part lives inside the PCG launches.
 #include "cvd_host.h"
+#include "cvd_temporal.h"
 
 namespace cvd {
 
@@ -229,7 +230,7 @@ void launchTemporalSetup(Ctx& c, const double* x, int half) {
     HIP_CHECK(hipEventRecord(T.evIn, h->stream));
     HIP_CHECK(hipStreamWaitEvent(s, T.evIn, 0));
   }
-  hipLaunchKernelGGL(k_frame_consts, dim3((L.F + 63) / 64), dim3(64), 0, s, L, x, fcBuf);
+  launchFrameConsts(L, x, fcBuf, s);
   const size_t ldsD = static_cast<size_t>(L.nD) * T.S * 8 + static_cast<size_t>(T.width) * T.S * 5 + 16;
   allowLds(k_tl_diag, ldsD);
   hipLaunchKernelGGL(k_tl_diag, dim3(L.F), dim3(256), ldsD, s, L, h->dH.p, h->dLam.p, h->dMask.p, tb, T.Cf.p,
@@ -286,7 +287,7 @@ static void temporalInverse(Ctx& c) {
     launchDenseSpdInverse(h, T.NT, T.A.p, T.Ainv.p, T.fail.p, s, T.valid.p, &T.invPanel, &T.invBarrier);
   }
   if (h->dist()) {  // (the ranks must agree on "level on / off": see the dense pose-graph level, launchCoarseSetup)
-    hipLaunchKernelGGL(k_flag_to_bool, dim3(1), dim3(1), 0, s, T.fail.p);
+    launchFlagToBool(T.fail.p, s);
     const int ct = h->tBegin(KC_COMM_COARSE);
     commAllReduce(h, T.fail.p, 1, CT_I32, s);
     h->tEnd(ct);
@@ -313,11 +314,7 @@ void launchTemporalInit(Ctx& c, bool closeScalars, double tol2) {
   if (ts.Ainv == nullptr) return;
   const size_t ldsR = (static_cast<size_t>(c.L.B) + static_cast<size_t>(T.S) * T.width) * 8;
   hipLaunchKernelGGL(k_tl_restrict, dim3(c.L.F), dim3(256), ldsR, s, c.L, h->dR.p, temporalStepDev(h));
-  const size_t ldsI = static_cast<size_t>(tlRowsLds(T.NT)) * 8;
-  allowLds(k_tl_rows_init, ldsI);
-  hipLaunchKernelGGL(k_tl_rows_init, dim3(T.S * tlParts(T.nn)), dim3(768), ldsI, s, temporalStepDev(h), c.L.F, h->dScal.p, T.counter.p,
-                     closeScalars ? 1 : 0, tol2, h->hPcg);
-  HIP_CHECK(hipGetLastError());
+  launchTlRowsInit(h, temporalStepDev(h), T.NT, T.S * tlParts(T.nn), c.L.F, T.counter.p, closeScalars ? 1 : 0, tol2, s);
 }
 
 // ---- temporal pose level (coarse_level 3; k_pt_assemble in cvd_temporal.h) ------------------------------------------------------
@@ -427,11 +424,7 @@ void launchPoseTemporalBuild(Ctx& c, hipStream_t s, int* failOut, bool deferInve
 void launchPoseTemporalInit(Ctx& c, double tol2) {
   cvd_handle* h = c.h;
   auto& C = h->coarse;
-  const size_t lds = static_cast<size_t>(tlRowsLds(C.ptN)) * 8;
-  allowLds(k_tl_rows_init, lds);
-  hipLaunchKernelGGL(k_tl_rows_init, dim3(kCB * tlParts(C.ptNn)), dim3(768), lds, h->stream, C.ptStepDev.p + 1, c.L.F, h->dScal.p, C.ptCounter.p, 1, tol2,
-                     h->hPcg);
-  HIP_CHECK(hipGetLastError());
+  launchTlRowsInit(h, C.ptStepDev.p + 1, C.ptN, kCB * tlParts(C.ptNn), c.L.F, C.ptCounter.p, 1, tol2, h->stream);
 }
 
 const TlStep* poseTemporalStepDev(cvd_handle* h) {

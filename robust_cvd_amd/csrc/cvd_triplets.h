@@ -22,20 +22,6 @@
 
 namespace cvd {
 
-struct TripletTable {
-  const float2* ndc;       // 3 per constraint
-  const float* dsrc;       // 3 per constraint, dsrc[3c] <= 0: constraint inactive
-  const unsigned char* isStatic;
-  const long long* off;    // per group: [2g] begin, [2g+1] end of its constraints
-  const int* center;       // per group: centre frame (frames centre-1, centre, centre+1)
-  const int* slot;         // 3 per group: rows of the partial-product buffer
-  int nGroups;
-  int smoothType;          // cvd_smooth_loss_type
-  double wStaticSqrt, wDynamicSqrt;
-};
-
-enum : int { kSmoothEuclidLaplacian = 0, kSmoothDisparityLaplacian = 1, kSmoothDepthRatio = 2, kSmoothLogDepth = 3 };
-
 template <int KD, int KS>
 struct TripletSample {
   double r[3];

@@ -12,6 +12,9 @@ SOURCE = f'''
 #include <hip/hip_runtime.h>
 #include "{CSRC}/cvd_device.h"
 #include "{CSRC}/cvd_kernels.h"
+#include "{CSRC}/cvd_cost.h"
+#include "{CSRC}/cvd_block_inverse.h"
+#include "{CSRC}/cvd_pcg.h"
 #include "{CSRC}/cvd_coarse.h"
 #include "{CSRC}/cvd_cross.h"
 #include "{CSRC}/cvd_dense_walk.h"

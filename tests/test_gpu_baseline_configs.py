@@ -125,7 +125,7 @@ def test_full_size_cost_gradient_and_blocks_match_the_oracle(Solver):
 
 @pytest.mark.parametrize("robust", ["cauchy", "huber"])
 def test_config4_full_size_cost_gradient_and_blocks_match_the_oracle(Solver, robust):
-    """BASELINE.json configs[4] at full size -- 1000 frames 640x384, hierarchical flow list (4318 directed pairs, 10.4 M
+    """BASELINE.json configs[4] at full size -- 1000 frames 640x384, hierarchical flow list (5958 directed pairs, 10.4 M
     constraints), 16x12 bilinear grid (B = 199: the packed triangle of a frame block just fits the LDS), Cauchy 0.5 (what the
     reference hard-wires) and Huber 0.5 (the stress variant BASELINE names): cost, gradient and every frame-diagonal J^T J
     block of the HIP path against the oracle's block-sparse evaluation at a state away from the minimum."""

@@ -1,4 +1,5 @@
-"""The deterministic build (cvd_kernels.h: CVD_DETERMINISTIC; robust_cvd_amd.build.build_deterministic) reproduces a solve bit for bit.
+"""The deterministic build (CVD_DETERMINISTIC: default and the thread counts derived from it in cvd_kernels.h, read there and by
+the kernel headers that accumulate -- cvd_assembly.h, cvd_pcg.h, cvd_dense_walk.h, cvd_temporal.h; robust_cvd_amd.build.build_deterministic) reproduces a solve bit for bit.
 
 The product build accumulates through LDS f64 atomics issued by several waves of a workgroup: two runs of one solve differ in the
 last bits and the stopping rules turn that into +-1 PCG iteration (what made round 4's GPU record flaky).  The deterministic build

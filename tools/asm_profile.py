@@ -1,4 +1,4 @@
-"""Development aid (GPU, library built with -DCVD_ASM_PROFILE): phase timestamps of k_assemble_fast per frame."""
+"""Development aid (GPU, library built with -DCVD_ASM_PROFILE at least in cvd_eval, the unit of the stamps and their read-out): phase timestamps of k_assemble_fast per frame."""
 import os, sys, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

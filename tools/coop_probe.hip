@@ -3,7 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include "../robust_cvd_amd/csrc/cvd_device.h"
-#include "../robust_cvd_amd/csrc/cvd_kernels.h"
 #include "../robust_cvd_amd/csrc/cvd_dense_inverse.h"
 using namespace cvd;
 

@@ -8,7 +8,7 @@
 #include <cstdlib>
 #include <vector>
 #include "../robust_cvd_amd/csrc/cvd_device.h"
-#include "../robust_cvd_amd/csrc/cvd_kernels.h"
+#include "../robust_cvd_amd/csrc/cvd_block_inverse.h"
 using namespace cvd;
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { std::printf("HIP error %s at %d\n", hipGetErrorString(e_), __LINE__); std::exit(1); } } while (0)
 
