@@ -154,13 +154,6 @@ enum KernelClass { KC_ASSEMBLE = 0, KC_MATVEC_PAIRS, KC_MATVEC_FINISH, KC_CG_UPD
                    // kernels timed on their own beside their class (cvd_get_dense_times): the dense mode's pixel walk and grid x grid kernel
                    KC_DENSE_WALK, KC_DENSE_GG, KC_TOTAL };
 
-struct Ceres {  // ceres::Solver::Options defaults used on this path
-  static constexpr double initial_radius = 1e4, max_radius = 1e16, min_radius = 1e-32;
-  static constexpr double min_relative_decrease = 1e-3;
-  static constexpr double function_tolerance = 1e-6, gradient_tolerance = 1e-10, parameter_tolerance = 1e-8;
-  static constexpr int max_consecutive_invalid = 5;
-};
-
 enum ProblemKind { PK_POSE_STEP = 0, PK_NORMALIZE = 1 };
 
 // exchange layer of the pair-sharded mode (cvd_comm.hip)
@@ -369,7 +362,7 @@ struct cvd_handle_t {
     bool sidePending = false;                     // ... forked and not yet joined (a solve that throws in between joins on its way out)
     double* sqPtr = nullptr; // where the frames' restricted products live: sq, or (pair-sharded, fused exchange) behind [q | Z^T q | p.q]
   } temporal;
-  // measured on this handle (cvd_solve.hip: denseRebuildThreshold): an in-line rebuild of the dense coarse level and a PCG iteration
+  // measured on this handle (cvd_lm.h: denseRebuildThreshold): an in-line rebuild of the dense coarse level and a PCG iteration
   hipEvent_t evRebuild[2] = {nullptr, nullptr};
   bool rebuildTimed = false;
   double coarseRebuildMs = 0.0, pcgIterMs = 0.0;

@@ -1,5 +1,8 @@
 // cvd_solve.hip -- the PCG loop, the Levenberg-Marquardt driver (Ceres defaults) and the evaluation hook.
+#include <optional>
+
 #include "cvd_host.h"
+#include "cvd_lm.h"
 #include "cvd_pcg.h"
 #include "cvd_coarse.h"
 
@@ -276,42 +279,44 @@ void bindTriplets(Ctx& c, const cvd_opt_params& p, ProblemKind kind) {
                       static_cast<int>(p.smooth_loss_type),  // (CVD_SMOOTH_* == kSmooth*)
                       std::sqrt(std::max(0.0, p.smooth_static_weight)), std::sqrt(std::max(0.0, p.smooth_dynamic_weight))};
 }
-void solve(cvd_handle* h, const cvd_opt_params& p, double depthDeformReg, ProblemKind kind) {
-  const double t0 = nowSeconds();
-  if (h->F <= 0) throw std::runtime_error("no video set");
-  if (!h->poseParamsValid) posesToParams(h);
-  const std::vector<int> range = rangeOf(p, h->F);
-  // A coarse rebuild still running on the side stream when the solve ends (or throws) must finish before anything on the
-  // main stream -- the next solve's in-line setup, a table upload -- touches the coarse buffers again.
-  struct PendingGuard {
-    cvd_handle* h;
-    bool pending = false;
-    bool inverseAside = false;   // the block inverses were forked to their own stream and the solve left before the join
-    ~PendingGuard() {
-      if (pending) (void)hipStreamWaitEvent(h->stream, h->evCoarseDone, 0);
-      if (inverseAside) (void)hipStreamWaitEvent(h->stream, h->evInvDone, 0);
-      if (h->temporal.sidePending) {  // (the third level's assembly was forked and the solve left before its join)
-        (void)hipStreamWaitEvent(h->stream, h->temporal.evDone, 0);
-        h->temporal.sidePending = false;
-      }
-    }
-  } pendingGuard{h};
-  const bool dbgSetup = h->opt.verbose >= 3;  // development: where a solve's fixed cost goes
-  double tPhase = nowSeconds();
-  auto phase = [&](const char* what) {
-    if (!dbgSetup) return;
-    const double t = nowSeconds();
-    fprintf(stderr, "[setup] %-14s %8.1f us\n", what, (t - tPhase) * 1e6);
-    tPhase = t;
-  };
+
+namespace {
+
+// verbose >= 3 (development): where a solve's fixed cost goes.  tools/setup_phases.py reads the labels.
+struct SetupPhases {
+  bool on;
+  double t = nowSeconds();
+  void operator()(const char* what) {
+    if (!on) return;
+    const double now = nowSeconds();
+    fprintf(stderr, "[setup] %-14s %8.1f us\n", what, (now - t) * 1e6);
+    t = now;
+  }
+};
+
+// What solve() and evaluate() do differently while they bind a problem.
+struct BindMode {
+  bool checkBlock;    // checkFrameBlock before any state is touched
+  bool staticGuards;  // the dense-list scope and the dense-scope check only for a problem with static constraints (else: always)
+  bool levels;        // the preconditioner's levels per the options, with their tables (else: coarseOn off, their state untouched)
+};
+struct BoundProblem {
   Ctx c;
+  // dense mode outside the fast kernels' scope: the problem runs on the device-materialised list (flipped back when it goes out of scope)
+  std::optional<DenseListScope> denseList;
+};
+
+// Layout through the state upload.  compileTable, DenseListScope and ensureBuffers mutate the handle: the order is behaviour.
+void bindProblem(BoundProblem& b, cvd_handle* h, const cvd_opt_params& p, double depthDeformReg, ProblemKind kind,
+                 const std::vector<int>& range, const BindMode& mode, SetupPhases& phase) {
+  Ctx& c = b.c;
   c.h = h;
   c.L = makeLayout(h, p, depthDeformReg, kind);
-  checkFrameBlock(static_cast<size_t>(c.L.B), "solve");
+  if (mode.checkBlock) checkFrameBlock(static_cast<size_t>(c.L.B), "solve");
   tapCounts(c.L, c.KD, c.KS);
   phase("layout");
-  // dense mode outside the fast kernels' scope: this solve runs on the device-materialised list (flipped back when the solve ends)
-  DenseListScope denseList(h, h->dense && c.L.includeStatic && !denseFastScope(h, c.L, c.KS, wantsTriplets(p, kind)));
+  const bool guarded = !mode.staticGuards || c.L.includeStatic;
+  b.denseList.emplace(h, h->dense && guarded && !denseFastScope(h, c.L, c.KS, wantsTriplets(p, kind)));
   compileTable(h, range, wantsTriplets(p, kind), kind == PK_NORMALIZE && c.L.includeStatic);
   orderTable(h, c.L, c.KD);
   phase("table");
@@ -323,41 +328,184 @@ void solve(cvd_handle* h, const cvd_opt_params& p, double depthDeformReg, Proble
   c.n = static_cast<size_t>(c.L.F) * c.L.B;
   c.boundDepth0 = (kind == PK_NORMALIZE && c.L.N > 0) ? 1 : 0;
   bindTriplets(c, p, kind);
-  if (c.L.includeStatic) checkDenseScope(h, c.L, c.KS, c.trip);
+  if (guarded) checkDenseScope(h, c.L, c.KS, c.trip);
   c.cross = crossScope(h, c);
-  h->coarseOn = h->opt.coarse_level != 0 && h->coarse.valid && c.L.includeStatic && h->coarse.nEdges > 0 && !h->forceGeneric &&
-                kind == PK_POSE_STEP;  // (normalizeDepth's problems have no pose unknowns: the block-Jacobi level alone)
+  h->coarseOn = mode.levels && h->opt.coarse_level != 0 && h->coarse.valid && c.L.includeStatic && h->coarse.nEdges > 0 &&
+                !h->forceGeneric && kind == PK_POSE_STEP;  // (normalizeDepth's problems have no pose unknowns: the block-Jacobi level alone)
   ensureBuffers(c);
   phase("buffers");
-  h->coarse.ptInvPending = false;   // (a request left behind by a solve that threw)
-  h->temporal.on = temporalScope(c);
-  if (h->temporal.on) h->temporal.on = temporalPrepare(c);
-  phase("level 3 tables");
-  if (h->coarseOn && h->coarse.temporalPose) poseTemporalPrepare(c);
-  phase("level 2 tables");
+  if (mode.levels) {
+    h->coarse.ptInvPending = false;   // (a request left behind by a solve that threw)
+    h->temporal.on = temporalScope(c);
+    if (h->temporal.on) h->temporal.on = temporalPrepare(c);
+    phase("level 3 tables");
+    if (h->coarseOn && h->coarse.temporalPose) poseTemporalPrepare(c);
+    phase("level 2 tables");
+  }
   buildMask(h, c.L, p, kind, range);
   phase("mask");
   uploadState(h, c.L, h->dX);
   phase("upload");
+}
+
+// Residual blocks besides the static constraints': the triplets' and the regularisers', as Ceres would count them.
+long long countResidualBlocks(const Ctx& c, const std::vector<int>& range) {
+  const cvd_handle* h = c.h;
+  const long long nr = static_cast<long long>(range.size());
+  long long blocks = c.trip ? h->numValidTrip : 0;
+  if (c.L.scaleRegSqrt > 0.0) blocks += nr * c.L.sregX * c.L.sregY;
+  if (c.L.focalRegSqrt > 0.0) blocks += nr;
+  if (c.L.depthDeformW > 0.0 && c.L.depthType == CVD_DEPTH_GRID) blocks += nr;
+  if (c.L.spatialDeformW > 0.0 && c.L.nS > 0) blocks += nr;
+  if (c.L.positionRegSqrt > 0.0)
+    for (int k = c.L.firstFrame; k < c.L.lastFrame - 1; ++k)
+      blocks += (h->tableRange[k] && h->tableRange[k + 1] && h->tableRange[k + 2]) ? 1 : 0;
+  return blocks;
+}
+
+// A coarse rebuild still running on the side stream when the solve ends (or throws) must finish before anything on the
+// main stream -- the next solve's in-line setup, a table upload -- touches the coarse buffers again.
+struct PendingGuard {
+  cvd_handle* h;
+  const LevelSchedule& schedule;  // (pending: a rebuild is running on the side stream)
+  bool inverseAside = false;      // the block inverses were forked to their own stream and the solve left before the join
+  ~PendingGuard() {
+    if (schedule.pending) (void)hipStreamWaitEvent(h->stream, h->evCoarseDone, 0);
+    if (inverseAside) (void)hipStreamWaitEvent(h->stream, h->evInvDone, 0);
+    if (h->temporal.sidePending) {  // (the third level's assembly was forked and the solve left before its join)
+      (void)hipStreamWaitEvent(h->stream, h->temporal.evDone, 0);
+      h->temporal.sidePending = false;
+    }
+  }
+};
+
+// the depth-grid level by itself, both halves, at the current (H, lam, x)
+void rebuildTemporalLevel(Ctx& c) {
+  cvd_handle* h = c.h;
+  const int slot = h->tBegin(KC_INVERSE);
+  launchTemporalSetup(c, h->dX.p, 0);
+  launchTemporalSetup(c, h->dX.p, 1);
+  h->tEnd(slot);
+}
+
+// Carries out one LM iteration's schedule decision: the block-Jacobi level, which follows lam every LM iteration (lagging it as
+// well is ~4% faster on the benchmark but makes the converged parameters visibly sensitive to rounding noise along the weak gauge
+// directions), and whatever rebuild of the other levels the decision asks for.
+void buildLevels(Ctx& c, const LevelSchedule::Decision& d, PendingGuard& guard) {
+  cvd_handle* h = c.h;
+  hipStream_t s = h->stream;
+  if (d.inverseAside) {
+    // The levels are built in line: the frames' block inverses -- one workgroup per frame, a latency-bound sweep of 0.12 - 0.17 ms
+    // that leaves most of every CU idle, and that only the PCG reads -- run on a stream of their own BESIDE the build instead of
+    // in front of it.
+    HIP_CHECK(hipEventRecord(h->evInvIn, s));
+    HIP_CHECK(hipStreamWaitEvent(h->stream3, h->evInvIn, 0));
+    launchBlockInverse(c, h->stream3);
+    HIP_CHECK(hipEventRecord(h->evInvDone, h->stream3));
+    guard.inverseAside = true;
+  } else {
+    const int slot = h->tBegin(KC_INVERSE);
+    launchBlockInverse(c);
+    h->tEnd(slot);
+  }
+  if (d.coarse == LevelSchedule::SIDE_STREAM) {
+    // The rebuild runs concurrently with this iteration's PCG (which keeps the old factor) and is installed for the next iteration:
+    // its ~0.8 ms leave the critical path.  Its inputs (H, lam, x, mask, the table) are not written before the install; the frame
+    // constants, which the main stream rewrites for the candidate point, are private to the side stream.
+    h->dFc2.ensure(c.L.F);
+    //  the third level is "rebuilt together with the pose-graph level": also when that rebuild runs on the side
+    // stream -- at this linearisation point, for THIS iteration's PCG (it is small: two launches and a 0.1 ms inverse).
+    //  its assembly goes to the side stream BEFORE the pose-graph level's rebuild: queued behind it, the main
+    // stream's wait for the third level would have been a wait for the whole rebuild the side stream exists to hide.
+    // Its inverse (a persistent kernel: gated per device) is enqueued before the rebuild's factorisation as well, so that the
+    // gate's event chain makes the SIDE stream wait for the small inverse and not the solver's stream for the rebuild; the two
+    // levels' inverses have scratch (panel, barrier words) of their own.
+    if (h->temporal.on) rebuildTemporalLevel(c);
+    HIP_CHECK(hipEventRecord(h->evCoarseIn, s));
+    HIP_CHECK(hipStreamWaitEvent(h->stream2, h->evCoarseIn, 0));
+    launchCoarseSetup(c, h->dX.p, 1);
+    HIP_CHECK(hipEventRecord(h->evCoarseDone, h->stream2));
+  } else if (d.coarse == LevelSchedule::IN_LINE) {
+    const int slot = h->tBegin(KC_INVERSE);  // preconditioner construction, same class as the block inverse
+    const bool measure = h->coarse.denseMode && !h->dist() && h->opt.coarse_rebuild_excess_dense < 0;
+    if (measure) {
+      if (!h->evRebuild[0]) for (auto& e : h->evRebuild) HIP_CHECK(hipEventCreate(&e));
+      HIP_CHECK(hipEventRecord(h->evRebuild[0], s));
+    }
+    // (third level: same linearisation point and damping; its assembly runs beside the pose-graph level's build)
+    if (h->temporal.on) launchTemporalSetup(c, h->dX.p, 0);
+    launchCoarseSetup(c, h->dX.p);
+    if (d.inverseAside) {  // (joined before the temporal levels' persistent inverse pair: that kernel keeps the device to itself)
+      HIP_CHECK(hipStreamWaitEvent(s, h->evInvDone, 0));
+      guard.inverseAside = false;
+    }
+    if (h->temporal.on) launchTemporalSetup(c, h->dX.p, 1);
+    if (measure) {
+      HIP_CHECK(hipEventRecord(h->evRebuild[1], s));
+      h->rebuildTimed = true;
+    }
+    h->tEnd(slot);
+  }
+  if (d.temporalOnly) rebuildTemporalLevel(c);
+}
+
+// a factor the side stream finished during this iteration's PCG is swapped in for the next one
+void installPendingCoarse(cvd_handle* h, LevelSchedule& schedule) {
+  if (!schedule.pending) return;
+  HIP_CHECK(hipStreamWaitEvent(h->stream, h->evCoarseDone, 0));  // (device-side wait: the host does not block)
+  std::swap(h->coarse.Wb.p, h->coarse.Wb2.p);
+  std::swap(h->coarse.Wb.n, h->coarse.Wb2.n);
+  std::swap(h->coarse.fail.p, h->coarse.fail2.p);
+  std::swap(h->coarse.fail.n, h->coarse.fail2.n);
+  schedule.installed();
+}
+
+// what denseRebuildThreshold's -1 setting prices a rebuild with: the handle's running averages of an in-line rebuild and a PCG iteration
+void notePcgTime(cvd_handle* h, double seconds, int cgIters) {
+  if (cgIters <= 0 || h->dist()) return;
+  double ms = seconds * 1e3;
+  if (h->rebuildTimed) {  // (the rebuild ran in line right before this PCG: its time is not the iterations')
+    float rb = 0.f;
+    if (hipEventElapsedTime(&rb, h->evRebuild[0], h->evRebuild[1]) == hipSuccess && rb > 0.f) {
+      h->coarseRebuildMs = h->coarseRebuildMs > 0.0 ? 0.5 * (h->coarseRebuildMs + rb) : rb;
+      ms = std::max(0.0, ms - rb);
+    }
+    h->rebuildTimed = false;
+  }
+  const double per = ms / cgIters;
+  h->pcgIterMs = h->pcgIterMs > 0.0 ? 0.75 * h->pcgIterMs + 0.25 * per : per;
+}
+
+// one iteration record at the current point's cost and radius, with its line of the verbose table
+void pushRecord(cvd_handle* h, cvd_iteration_record& rec, double cost, double radius, double gmax, bool tableLine = true) {
+  rec.cost = cost;
+  rec.trust_region_radius = radius;
+  h->records.push_back(rec);
+  if (tableLine && h->opt.verbose)
+    printf("%4d % .6e    % .2e   % .2e   % .2e  % .2e % .2e   %5d\n", rec.iteration, cost, rec.cost_change, gmax, rec.step_norm,
+           rec.relative_decrease, radius, rec.linear_iterations);
+}
+
+}  // namespace
+
+void solve(cvd_handle* h, const cvd_opt_params& p, double depthDeformReg, ProblemKind kind) {
+  const double t0 = nowSeconds();
+  if (h->F <= 0) throw std::runtime_error("no video set");
+  if (!h->poseParamsValid) posesToParams(h);
+  const std::vector<int> range = rangeOf(p, h->F);
+  LevelSchedule schedule;
+  PendingGuard guard{h, schedule};
+  SetupPhases phase{h->opt.verbose >= 3};
+  BoundProblem bound;
+  bindProblem(bound, h, p, depthDeformReg, kind, range, BindMode{/*checkBlock*/ true, /*staticGuards*/ true, /*levels*/ true}, phase);
+  Ctx& c = bound.c;
   hipStream_t s = h->stream;
   HIP_CHECK(hipMemsetAsync(h->dDx.p, 0, c.n * sizeof(double), s));
   HIP_CHECK(hipMemsetAsync(h->dR.p, 0, c.n * sizeof(double), s));
   HIP_CHECK(hipMemsetAsync(h->dFail.p, 0, sizeof(int), s));
 
   cvd_solve_summary sum{};
-  long long regBlocks = 0;
-  {
-    const long long nr = static_cast<long long>(range.size());
-    if (c.L.scaleRegSqrt > 0.0) regBlocks += nr * c.L.sregX * c.L.sregY;
-    if (c.L.focalRegSqrt > 0.0) regBlocks += nr;
-    if (c.L.depthDeformW > 0.0 && c.L.depthType == CVD_DEPTH_GRID) regBlocks += nr;
-    if (c.L.spatialDeformW > 0.0 && c.L.nS > 0) regBlocks += nr;
-    if (c.L.positionRegSqrt > 0.0)
-      for (int k = c.L.firstFrame; k < c.L.lastFrame - 1; ++k)
-        regBlocks += (h->tableRange[k] && h->tableRange[k + 1] && h->tableRange[k + 2]) ? 1 : 0;
-  }
-  sum.num_residual_blocks = static_cast<int>((c.L.includeStatic ? h->numValid : 0) + (c.trip ? h->numValidTrip : 0) + regBlocks);
-
+  sum.num_residual_blocks = static_cast<int>((c.L.includeStatic ? h->numValid : 0) + countResidualBlocks(c, range));
   double tEval = 0.0, tLin = 0.0;
   double te = nowSeconds();
   // first evaluation: cost, |g|_max, |x| and the number of active unknowns arrive with ONE read-back (until round 5: the cost, then the
@@ -371,181 +519,42 @@ void solve(cvd_handle* h, const cvd_opt_params& p, double depthDeformReg, Proble
   sum.num_parameters = static_cast<int>(h->hScal[S_NACTIVE] + 0.5);
   phase("stats");
 
-  double radius = Ceres::initial_radius;
-  double decrease = 2.0;
+  TrustRegion tr;
+  // (sparse factor, rebuilt on the side stream: the option; dense level, built in line: denseRebuildThreshold)
+  const int rebuildExcess = h->coarse.denseMode ? denseRebuildThreshold(h->opt.coarse_rebuild_excess_dense, h->dist(), h->coarseRebuildMs, h->pcgIterMs)
+                                                : h->opt.coarse_rebuild_excess;
+  const LevelSchedule::Config levels{h->opt.coarse_level, h->opt.temporal_level, std::max(0, rebuildExcess), h->coarseOn, h->temporal.on,
+                                     h->coarse.denseMode, h->dist(), h->stream3 != nullptr, c.L.B <= 256};
   // After an accepted step the host does not wait for the new point's |g|_max / |x| (one idle round trip of ~60 us per LM
   // iteration, round 5): the step statistics of the NEXT PCG solve recompute both for the same point (k_step_stats) and arrive
   // with its read-back.  gradPending: the gradient-tolerance test of the last accepted step and its record's gradient norm are
   // still open.  (verbose runs keep the immediate read: the table prints the norm with its iteration)
   bool gradPending = false;
   const bool deferStats = h->opt.verbose == 0;
-  int invalid = 0, iteration = 0, termination = 1;
-  // Rebuild threshold of the coarse level in PCG iterations.  Sparse factor (side stream): the option.  DENSE level, built in
-  // line: coarse_rebuild_excess_dense > 0 fixes it; 0 (default) = 32, a constant: identical inputs must take identical
-  // rebuild decisions on every run and every rank (the wall-clock-derived threshold made PCG counts and end states
-  // depend on host jitter).  -1 opts into pricing a rebuild at what THIS handle measured -- 1.5 x (the rebuild's duration / the
-  // duration of a PCG iteration of the running solves), in steps of 8 (the PCG counts of an LM run grow by themselves as the
-  // trust region opens: a threshold equal to the bare cost ratio, 22 at 300 frames, rebuilt every second LM iteration to save
-  // 0.6 iterations per LM iteration; 1.5 x = 32 there).  Sharded runs ignore -1: every rank must decide alike.
-  auto denseRebuildThreshold = [&]() {
-    if (h->opt.coarse_rebuild_excess_dense > 0) return h->opt.coarse_rebuild_excess_dense;
-    if (h->opt.coarse_rebuild_excess_dense == 0 || h->dist() || h->coarseRebuildMs <= 0.0 || h->pcgIterMs <= 0.0) return 32;
-    const double ratio = 1.5 * h->coarseRebuildMs / h->pcgIterMs;
-    return std::min(256, std::max(8, 8 * static_cast<int>(ratio / 8.0 + 0.5)));
-  };
-  const int kCoarseRebuildIters = std::max(0, h->coarse.denseMode ? denseRebuildThreshold() : h->opt.coarse_rebuild_excess);
-  int coarseAge = -1, cgAfterRefresh = 0, cgExcess = 0;  // coarse level: LM iterations since the last rebuild
-  bool& coarsePending = pendingGuard.pending;  // a rebuild is running on the side stream
-  int factorUses = 0;          // PCG solves done with the factor in use
-  double lastRelChange = 1.0;  // relative cost change of the last accepted step
-  constexpr double asyncMaxChange = 1e-3;
-  bool freshFactor = false;    // the factor was installed right before this iteration's PCG
-  auto installPendingCoarse = [&]() {
-    if (!coarsePending) return;
-    HIP_CHECK(hipStreamWaitEvent(s, h->evCoarseDone, 0));  // (device-side wait: the host does not block)
-    std::swap(h->coarse.Wb.p, h->coarse.Wb2.p);
-    std::swap(h->coarse.Wb.n, h->coarse.Wb2.n);
-    std::swap(h->coarse.fail.p, h->coarse.fail2.p);
-    std::swap(h->coarse.fail.n, h->coarse.fail2.n);
-    coarsePending = false;
-    freshFactor = true;
-    cgExcess = 0;
-    coarseAge = 0;
-    factorUses = 0;
-  };
+  auto gradientConverged = [&]() { return gmax <= Ceres::gradient_tolerance && !h->dbg.force_iterations; };
+  int iteration = 0, termination = 1;
   bool scaleDone = false;
   cvd_iteration_record r0{};
-  r0.cost = xCost;
   r0.gradient_max_norm = gmax;
-  r0.trust_region_radius = radius;
   r0.step_is_successful = 1;
-  h->records.push_back(r0);
-  if (h->opt.verbose)
-    printf("iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius  ls_iter\n"
-           "%4d % .6e    % .2e   % .2e   % .2e  % .2e % .2e   %5d\n", 0, xCost, 0.0, gmax, 0.0, 0.0, radius, 0);
+  if (h->opt.verbose) printf("iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius  ls_iter\n");
+  pushRecord(h, r0, xCost, tr.radius, gmax);
 
-  if (sum.num_parameters == 0 || (gmax <= Ceres::gradient_tolerance && !h->dbg.force_iterations)) {
+  if (sum.num_parameters == 0 || gradientConverged()) {
     termination = 0;
   } else {
     while (true) {
       if (iteration >= p.max_iterations) { termination = 1; break; }
-      if (radius < Ceres::min_radius) { termination = 0; break; }
+      if (tr.belowMinRadius()) { termination = 0; break; }
       ++iteration;
       cvd_iteration_record rec{};
       rec.iteration = iteration;
 
       double tl = nowSeconds();
       hipLaunchKernelGGL(k_lm_diag, dim3((c.n + 255) / 256), dim3(256), 0, s, c.L, h->dHd.p, h->dScale.p,
-                         scaleDone ? 0 : 1, radius, h->dLam.p);
+                         scaleDone ? 0 : 1, tr.radius, h->dLam.p);
       scaleDone = true;
-      // The block-Jacobi level follows lam every LM iteration; the coarse level is rebuilt on demand (below).
-      // (Lagging the block inverse as well is ~4% faster on the benchmark but makes the converged parameters
-      // visibly sensitive to rounding noise along the weak gauge directions.)
-      const bool willRefresh = !coarsePending &&
-                               (!h->coarseOn || h->opt.coarse_level == 2 || coarseAge < 0 || cgExcess >= kCoarseRebuildIters);
-      // This iteration builds the levels in line (the first iteration of a solve, or a rebuild while the iterates still move): the
-      // frames' block inverses -- one workgroup per frame, a latency-bound sweep of 0.12 - 0.17 ms that leaves most of every CU
-      // idle, and that only the PCG reads -- run on a stream of their own BESIDE the build instead of in front of it.
-      // (a rebuild on the side stream, for the NEXT iteration: only in the slowly changing regime, see below)
-      const bool asyncRebuild = lastRelChange < asyncMaxChange && !h->coarse.denseMode && h->opt.coarse_level != 2 && !h->dist();
-      const bool inlineRebuild = h->coarseOn && willRefresh && !asyncRebuild;
-      const bool inverseAside = inlineRebuild && !h->dist() && h->stream3 != nullptr && c.L.B <= 256;
-      if (inverseAside) {
-        HIP_CHECK(hipEventRecord(h->evInvIn, s));
-        HIP_CHECK(hipStreamWaitEvent(h->stream3, h->evInvIn, 0));
-        launchBlockInverse(c, h->stream3);
-        HIP_CHECK(hipEventRecord(h->evInvDone, h->stream3));
-        pendingGuard.inverseAside = true;
-      } else {
-        const int slot = h->tBegin(KC_INVERSE);
-        launchBlockInverse(c);
-        h->tEnd(slot);
-      }
-      if (h->coarseOn) {
-        // The coarse factor is only a preconditioner: any SPD approximation of Z^T A Z serves, so it is kept
-        // across LM iterations (lagged lam and linearisation point).  A rebuild costs about as much as
-        // kCoarseRebuildIters PCG iterations; it is done once the iterations spent beyond the count observed
-        // right after the last rebuild add up to that (coarse_level 2: rebuild every LM iteration).
-        // When a factor already exists the rebuild runs on the side stream, concurrently with this iteration's PCG
-        // (which keeps the old factor), and is installed for the next iteration: its ~0.8 ms leave the critical path.
-        // Its inputs (H, lam, x, mask, the table) are not written before the install below; the frame constants,
-        // which the main stream rewrites for the candidate point, are private to the side stream.
-        if (willRefresh) {
-          // (Only in the slowly changing regime -- the last accepted step changed the cost by less than 0.1 % --: while
-          // the iterates still move a lot a factor that is one iteration late costs more PCG iterations than the
-          // overlap saves, and there the rebuild stays in line.)
-          // (the dense level's inverse is one persistent kernel that wants every CU: always in line)
-          if (asyncRebuild) {
-            h->dFc2.ensure(c.L.F);
-            //  the third level is "rebuilt together with the pose-graph level": also when that rebuild runs on the side
-            // stream -- at this linearisation point, for THIS iteration's PCG (it is small: two launches and a 0.1 ms inverse).
-            //  its assembly goes to the side stream BEFORE the pose-graph level's rebuild: queued behind it, the main
-            // stream's wait for the third level would have been a wait for the whole rebuild the side stream exists to hide.
-            // Its inverse (a persistent kernel: gated per device) is enqueued before the rebuild's factorisation as well, so that the
-            // gate's event chain makes the SIDE stream wait for the small inverse and not the solver's stream for the rebuild; the two
-            // levels' inverses have scratch (panel, barrier words) of their own.
-            if (h->temporal.on) {
-              const int slotT = h->tBegin(KC_INVERSE);
-              launchTemporalSetup(c, h->dX.p, 0);
-              launchTemporalSetup(c, h->dX.p, 1);
-              h->tEnd(slotT);
-            }
-            HIP_CHECK(hipEventRecord(h->evCoarseIn, s));
-            HIP_CHECK(hipStreamWaitEvent(h->stream2, h->evCoarseIn, 0));
-            launchCoarseSetup(c, h->dX.p, 1);
-            HIP_CHECK(hipEventRecord(h->evCoarseDone, h->stream2));
-            coarsePending = true;
-            cgExcess = 0;
-          } else {
-            const int slot = h->tBegin(KC_INVERSE);  // preconditioner construction, same class as the block inverse
-            const bool measure = h->coarse.denseMode && !h->dist() && h->opt.coarse_rebuild_excess_dense < 0;
-            if (measure) {
-              if (!h->evRebuild[0]) for (auto& e : h->evRebuild) HIP_CHECK(hipEventCreate(&e));
-              HIP_CHECK(hipEventRecord(h->evRebuild[0], s));
-            }
-            // (third level: same linearisation point and damping; its assembly runs beside the pose-graph level's build)
-            if (h->temporal.on) launchTemporalSetup(c, h->dX.p, 0);
-            launchCoarseSetup(c, h->dX.p);
-            if (inverseAside) {  // (joined before the temporal levels' persistent inverse pair: that kernel keeps the device to itself)
-              HIP_CHECK(hipStreamWaitEvent(s, h->evInvDone, 0));
-              pendingGuard.inverseAside = false;
-            }
-            if (h->temporal.on) launchTemporalSetup(c, h->dX.p, 1);
-            if (measure) {
-              HIP_CHECK(hipEventRecord(h->evRebuild[1], s));
-              h->rebuildTimed = true;
-            }
-            h->tEnd(slot);
-            coarseAge = 0;
-            cgExcess = 0;
-            freshFactor = true;
-            factorUses = 0;
-          }
-        } else {
-          ++coarseAge;
-          if (h->temporal.on && h->opt.temporal_level == 2) {
-            const int slot = h->tBegin(KC_INVERSE);
-            launchTemporalSetup(c, h->dX.p, 0);
-            launchTemporalSetup(c, h->dX.p, 1);
-            h->tEnd(slot);
-          }
-        }
-      }
-      if (!h->coarseOn && h->temporal.on) {
-        // third level without a pose-graph level (coarse_level 0): rebuilt by the same rule -- at the first iteration, then once
-        // the PCG iterations spent beyond the count seen right after the last build add up to the threshold (level 2: every iteration)
-        if (coarseAge < 0 || h->opt.temporal_level == 2 || cgExcess >= kCoarseRebuildIters) {
-          const int slot = h->tBegin(KC_INVERSE);
-          launchTemporalSetup(c, h->dX.p, 0);
-          launchTemporalSetup(c, h->dX.p, 1);
-          h->tEnd(slot);
-          coarseAge = 0;
-          cgExcess = 0;
-          freshFactor = true;
-        } else {
-          ++coarseAge;
-        }
-      }
+      buildLevels(c, schedule.decide(levels), guard);
       // one read-back for the PCG result, the step statistics and the cost of the candidate point (the
       // candidate is formed speculatively; it is simply not used when the model decrease is invalid)
       const double tPcgStart = nowSeconds();
@@ -556,34 +565,16 @@ void solve(cvd_handle* h, const cvd_opt_params& p, double depthDeformReg, Proble
         HIP_CHECK(hipGetLastError());
         enqueueCost(c, h->dXc.p);
       });
-      {
-        const double tPcg = nowSeconds() - tPcgStart;
-        if (cgIters > 0 && !h->dist()) {
-          double ms = tPcg * 1e3;
-          if (h->rebuildTimed) {  // (the rebuild ran in line right before this PCG: its time is not the iterations')
-            float rb = 0.f;
-            if (hipEventElapsedTime(&rb, h->evRebuild[0], h->evRebuild[1]) == hipSuccess && rb > 0.f) {
-              h->coarseRebuildMs = h->coarseRebuildMs > 0.0 ? 0.5 * (h->coarseRebuildMs + rb) : rb;
-              ms = std::max(0.0, ms - rb);
-            }
-            h->rebuildTimed = false;
-          }
-          const double per = ms / cgIters;
-          h->pcgIterMs = h->pcgIterMs > 0.0 ? 0.75 * h->pcgIterMs + 0.25 * per : per;
-        }
-      }
-      if (freshFactor) cgAfterRefresh = cgIters;
-      else cgExcess += std::max(0, cgIters - cgAfterRefresh);
-      freshFactor = false;
-      ++factorUses;
-      installPendingCoarse();
+      notePcgTime(h, nowSeconds() - tPcgStart, cgIters);
+      schedule.afterPcg(cgIters);
+      installPendingCoarse(h, schedule);
       tLin += nowSeconds() - tl;
       if (gradPending) {
         gradPending = false;
         gmax = h->hScal[S_GMAX];
         xNorm = std::sqrt(h->hScal[S_XX]);
         h->records.back().gradient_max_norm = gmax;
-        if (gmax <= Ceres::gradient_tolerance && !h->dbg.force_iterations) {
+        if (gradientConverged()) {
           // the previous iteration ended the solve (Ceres tests the gradient right after a successful step): this iteration's
           // linear solve was speculative and is dropped -- x, the cost and the records are those of the previous iteration
           --iteration;
@@ -595,76 +586,46 @@ void solve(cvd_handle* h, const cvd_opt_params& p, double depthDeformReg, Proble
       sum.total_linear_iterations += cgIters;
       const double dg = h->hScal[S_DG], dr = h->hScal[S_DR], dld = h->hScal[S_DLD], dd = h->hScal[S_DD];
       const double modelCostChange = -0.5 * dg + 0.5 * dr + 0.5 * dld;
-      bool ok = std::isfinite(modelCostChange) && modelCostChange > 0.0 && std::isfinite(dd);
-      if (!ok) {
-        if (++invalid >= Ceres::max_consecutive_invalid) { termination = 2; break; }
-        radius /= decrease;
-        decrease *= 2.0;
-        rec.cost = xCost;
-        rec.trust_region_radius = radius;
-        h->records.push_back(rec);
+      if (!(std::isfinite(modelCostChange) && modelCostChange > 0.0 && std::isfinite(dd))) {
+        if (!tr.invalidStep()) { termination = 2; break; }
+        pushRecord(h, rec, xCost, tr.radius, gmax, false);
         continue;
       }
-      invalid = 0;
+      tr.validStep();
       double candCost = h->hScal[S_COST];
       if (!std::isfinite(candCost)) candCost = std::numeric_limits<double>::max();
-      const double stepNorm = std::sqrt(dd);
-      rec.step_norm = stepNorm;
+      rec.step_norm = std::sqrt(dd);
       rec.cost_change = xCost - candCost;
       rec.relative_decrease = (xCost - candCost) / modelCostChange;
-      bool stop = false;
-      if (stepNorm <= Ceres::parameter_tolerance * (xNorm + Ceres::parameter_tolerance)) stop = true;
-      if (!stop && std::abs(xCost - candCost) <= Ceres::function_tolerance * xCost) stop = true;
-      if (h->dbg.force_iterations) stop = false;
-      if (stop) {
-        rec.cost = xCost;
-        rec.trust_region_radius = radius;
-        h->records.push_back(rec);
-        if (h->opt.verbose)
-          printf("%4d % .6e    % .2e   % .2e   % .2e  % .2e % .2e   %5d\n", iteration, xCost, rec.cost_change, gmax,
-                 stepNorm, rec.relative_decrease, radius, cgIters);
+      if (!h->dbg.force_iterations &&
+          (TrustRegion::parameterToleranceReached(rec.step_norm, xNorm) || TrustRegion::functionToleranceReached(xCost, candCost))) {
+        pushRecord(h, rec, xCost, tr.radius, gmax);
         termination = 0;
         break;
       }
       if (rec.relative_decrease > Ceres::min_relative_decrease) {
         std::swap(h->dX.p, h->dXc.p);
         std::swap(h->dX.n, h->dXc.n);
-        lastRelChange = std::abs(xCost - candCost) / std::max(std::abs(xCost), 1e-300);
+        schedule.accepted(std::abs(xCost - candCost) / std::max(std::abs(xCost), 1e-300));
         xCost = candCost;
         te = nowSeconds();
         // (the last iteration allowed reads at once: nothing follows that would bring the statistics)
-        const bool defer = deferStats && iteration < p.max_iterations;
-        (void)evalFull(c, h->dX.p, true, defer);
+        gradPending = deferStats && iteration < p.max_iterations;
+        (void)evalFull(c, h->dX.p, true, gradPending);
         tEval += nowSeconds() - te;
-        if (defer) {
-          gradPending = true;   // (gmax / xNorm keep the previous point's values until the next solve's read-back)
-        } else {
+        if (!gradPending) {  // (else gmax / xNorm keep the previous point's values until the next solve's read-back)
           gmax = h->hScal[S_GMAX];
           xNorm = std::sqrt(h->hScal[S_XX]);
         }
         ++sum.num_successful_steps;
         rec.step_is_successful = 1;
-        const double q = rec.relative_decrease;
-        radius = radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * q - 1.0, 3));
-        radius = std::min(Ceres::max_radius, radius);
-        decrease = 2.0;
-        rec.cost = xCost;
+        tr.accept(rec.relative_decrease);
         rec.gradient_max_norm = gmax;
-        rec.trust_region_radius = radius;
-        h->records.push_back(rec);
-        if (h->opt.verbose)
-          printf("%4d % .6e    % .2e   % .2e   % .2e  % .2e % .2e   %5d\n", iteration, xCost, rec.cost_change, gmax,
-                 stepNorm, rec.relative_decrease, radius, cgIters);
-        if (!gradPending && gmax <= Ceres::gradient_tolerance && !h->dbg.force_iterations) { termination = 0; break; }
+        pushRecord(h, rec, xCost, tr.radius, gmax);
+        if (!gradPending && gradientConverged()) { termination = 0; break; }
       } else {
-        radius /= decrease;
-        decrease *= 2.0;
-        rec.cost = xCost;
-        rec.trust_region_radius = radius;
-        h->records.push_back(rec);
-        if (h->opt.verbose)
-          printf("%4d % .6e    % .2e   % .2e   % .2e  % .2e % .2e   %5d\n", iteration, xCost, rec.cost_change, gmax,
-                 stepNorm, rec.relative_decrease, radius, cgIters);
+        tr.reject();
+        pushRecord(h, rec, xCost, tr.radius, gmax);
       }
     }
   }
@@ -673,7 +634,6 @@ void solve(cvd_handle* h, const cvd_opt_params& p, double depthDeformReg, Proble
     enqueueStats(c);
     readScalars(c);
     h->records.back().gradient_max_norm = h->hScal[S_GMAX];
-    gradPending = false;
   }
   phase("LM loop");
   // a barrier timeout of the dense coarse inverse (bit 30) only costs PCG iterations -- but it should never pass unnoticed: its
@@ -707,25 +667,10 @@ void evaluate(cvd_handle* h, const cvd_opt_params& p, double depthDeformReg, con
     posesToParams(h);
   }
   const std::vector<int> range = rangeOf(p, h->F);
-  Ctx c;
-  c.h = h;
-  c.L = makeLayout(h, p, depthDeformReg, PK_POSE_STEP);
-  tapCounts(c.L, c.KD, c.KS);
-  DenseListScope denseList(h, h->dense && !denseFastScope(h, c.L, c.KS, wantsTriplets(p, PK_POSE_STEP)));
-  compileTable(h, range, wantsTriplets(p, PK_POSE_STEP));
-  orderTable(h, c.L, c.KD);
-  refreshMedians(h);
-  c.T = makeTable(h);
-  c.nItems = static_cast<int>(h->itemFa.size());
-  c.it = Items{h->dItemFa.p, h->dItemFb.p, h->dItemRange.p, h->dItemSlot.p, c.nItems};
-  c.n = static_cast<size_t>(c.L.F) * c.L.B;
-  bindTriplets(c, p, PK_POSE_STEP);
-  checkDenseScope(h, c.L, c.KS, c.trip);
-  c.cross = crossScope(h, c);
-  h->coarseOn = false;
-  ensureBuffers(c);
-  buildMask(h, c.L, p, PK_POSE_STEP, range);
-  uploadState(h, c.L, h->dX);
+  SetupPhases quiet{false};
+  BoundProblem bound;
+  bindProblem(bound, h, p, depthDeformReg, PK_POSE_STEP, range, BindMode{/*checkBlock*/ false, /*staticGuards*/ false, /*levels*/ false}, quiet);
+  Ctx& c = bound.c;
   hipStream_t s = h->stream;
   double cst;
   if (!gradient && !hdiag && !hfull) {
@@ -734,18 +679,7 @@ void evaluate(cvd_handle* h, const cvd_opt_params& p, double depthDeformReg, con
     cst = evalFull(c, h->dX.p);
   }
   if (cost) *cost = cst;
-  if (nres) {
-    long long regBlocks = 0;
-    const long long nr = static_cast<long long>(range.size());
-    if (c.L.scaleRegSqrt > 0.0) regBlocks += nr * c.L.sregX * c.L.sregY;
-    if (c.L.focalRegSqrt > 0.0) regBlocks += nr;
-    if (c.L.depthDeformW > 0.0 && c.L.depthType == CVD_DEPTH_GRID) regBlocks += nr;
-    if (c.L.spatialDeformW > 0.0 && c.L.nS > 0) regBlocks += nr;
-    if (c.L.positionRegSqrt > 0.0)
-      for (int k = c.L.firstFrame; k < c.L.lastFrame - 1; ++k)
-        regBlocks += (h->tableRange[k] && h->tableRange[k + 1] && h->tableRange[k + 2]) ? 1 : 0;
-    *nres = static_cast<int32_t>(h->numValid + (c.trip ? h->numValidTrip : 0) + regBlocks);
-  }
+  if (nres) *nres = static_cast<int32_t>(h->numValid + countResidualBlocks(c, range));
   if (gradient) h->dG.download(gradient, c.n, s);
   if (hdiag) {
     if (h->dist()) {  // (parity hook: collect the owners' reduced blocks)
