@@ -530,6 +530,68 @@ int32_t cvd_spatial_losses(cvd_handle* h, const cvd_spatial_desc* desc, const vo
 int32_t cvd_spatial_losses_device(cvd_handle* h, const cvd_spatial_desc* desc, const void* depth, const void* depth_orig,
                                   const void* image, double* total, double* smooth, double* contrast, void* grad, void* stream);
 
+/* ---- parameter regulariser and optimizer step over a list of tensors, DESIGN.md §3.13.  Independent of cvd_set_video.  Each
+ * is ONE kernel launch for any number of tensors: the tensors are cut into chunks of cvd_param_chunk() elements, a chunk whose
+ * addresses are all 16-byte aligned moves 16 bytes per lane, any other goes element by element with the same arithmetic (the
+ * same bits).  desc names the precision of every tensor and their number T (>= 0); a tensor of zero elements is legal (its
+ * address may then be NULL) and contributes nothing.  State and arithmetic are in the tensors' precision; the loss is summed in
+ * double, without atomics: it repeats bit for bit.
+ * Rejected before any device work: a desc of another header revision (struct_size), a precision other than CVD_PRECISION_*,
+ * num_tensors < 0, a NULL address or one that is not a multiple of the element size (of a tensor with elements), a negative
+ * count, a non-finite lambda, beta, eps or step scalar, a beta outside [0, 1), a denom_scale <= 0, an unknown rule; the host
+ * variants also a tensor that leaves the flat arrays. */
+typedef struct cvd_param_desc {
+  uint64_t struct_size;        /* CVD_STRUCT_STAMP(cvd_param_desc), set by the caller */
+  int32_t precision;           /* CVD_PRECISION_* of every tensor */
+  int32_t num_tensors;
+} cvd_param_desc;
+/* cvd_param_record::rule.  Every rule moves the moments: m = beta1 m + (1 - beta1) g, v = beta2 v + (1 - beta2) g g.
+ *   ADAM       torch.optim.Adam (amsgrad = False, maximize = False, no decoupled decay): g += grad_decay p first, then
+ *              p -= step m / (sqrt(v) / denom_scale + eps)
+ *   RADAM      reference optimizer/radam.py:85-90 (N_sma >= 5): p -= param_decay p; p -= step m / (sqrt(v) + eps)
+ *   RADAM_SGD  optimizer/radam.py:91-95 (N_sma < 5, degenerated_to_sgd): p -= param_decay p; p -= step m
+ *   MOMENTS    N_sma < 5 without degenerated_to_sgd: p stays */
+enum { CVD_PARAM_RULE_ADAM = 0, CVD_PARAM_RULE_RADAM = 1, CVD_PARAM_RULE_RADAM_SGD = 2, CVD_PARAM_RULE_MOMENTS = 3 };
+/* One tensor's scalars of one step, formed by the caller in double exactly as the Python of the rule forms them (the kernel casts
+ * them to the tensors' precision) */
+typedef struct cvd_param_record {
+  double beta1, beta2, eps;
+  double grad_decay;           /* ADAM: weight_decay; else 0 */
+  double param_decay;          /* RADAM, RADAM_SGD: weight_decay lr; else 0 */
+  double step;                 /* ADAM: lr / (1 - beta1^t); RADAM, RADAM_SGD: step_size lr (optimizer/radam.py:77-79) */
+  double denom_scale;          /* ADAM: sqrt(1 - beta2^t); else 1 */
+  int32_t rule;                /* CVD_PARAM_RULE_* */
+  int32_t reserved;            /* 0 */
+} cvd_param_record;
+/* Elements per chunk of the tables (CVD_PARAM_CHUNK of the build). */
+int64_t cvd_param_chunk(void);
+/* The reference's ParameterLoss (loss/parameter_loss.py:9-27): total = lambda sum_i sum |p_i - p0_i|, and its subgradient
+ * grad_i (+)= lambda sign(p_i - p0_i) grad_out with sign(0) = 0 (torch.abs's).  Host arrays: tensor i is counts[i] elements at
+ * element offsets[i] of the flat arrays p, p0 (and grad) of flat_count elements.
+ *   total [1]        double
+ *   grad             optional (may be NULL): flat, the tensors' precision; accumulate = 0 overwrites the tensors' elements,
+ *                    1 adds to what the array holds; elements between the tensors stay as they are
+ *   kernel_ms [2]    optional (may be NULL): {value, gradient} kernel time, HIP events */
+int32_t cvd_parameter_l1(cvd_handle* h, const cvd_param_desc* desc, const int64_t* offsets, const int64_t* counts,
+                         int64_t flat_count, const void* p, const void* p0, double lambda, double* total, void* grad,
+                         double grad_out, int32_t accumulate, double* kernel_ms);
+/* The same on DEVICE tensors, enqueued on `stream`: p, p0 and grad are host arrays of T device addresses, total (device, double)
+ * and grad_out (device, one scalar of the tensors' precision) device addresses.  total != NULL computes the value, grad != NULL
+ * the gradient (one launch each; at least one of the two).  No allocation once the table has been seen and no host
+ * synchronisation; the table's static part is rebuilt (one wait for the stream) when the list of counts changes.  One call at a
+ * time per handle. */
+int32_t cvd_parameter_l1_device(cvd_handle* h, const cvd_param_desc* desc, const void* const* p, const void* const* p0,
+                                const int64_t* counts, double lambda, double* total, void* const* grad, const void* grad_out,
+                                int32_t accumulate, void* stream);
+/* One optimizer step of every tensor in one launch: torch.optim.Adam's or the reference's RAdam.step (optimizer/radam.py:31-97),
+ * as records[i].rule says; p, m (exp_avg) and v (exp_avg_sq) are updated in place, g is read.  Host arrays laid out as above;
+ * kernel_ms [1] optional. */
+int32_t cvd_param_step(cvd_handle* h, const cvd_param_desc* desc, const int64_t* offsets, const int64_t* counts, int64_t flat_count,
+                       void* p, const void* g, void* m, void* v, const cvd_param_record* records, double* kernel_ms);
+/* The same on DEVICE tensors (host arrays of T device addresses), enqueued on `stream`; conditions as cvd_parameter_l1_device. */
+int32_t cvd_param_step_device(cvd_handle* h, const cvd_param_desc* desc, void* const* p, const void* const* g, void* const* m,
+                              void* const* v, const int64_t* counts, const cvd_param_record* records, void* stream);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

@@ -116,6 +116,32 @@ class SpatialDesc(C.Structure):
     ]
 
 
+class ParamDesc(C.Structure):
+    """include/cvd_hip.h cvd_param_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("precision", C.c_int32),
+        ("num_tensors", C.c_int32),
+    ]
+
+
+class ParamRecord(C.Structure):
+    """include/cvd_hip.h cvd_param_record"""
+    _fields_ = [
+        ("beta1", C.c_double),
+        ("beta2", C.c_double),
+        ("eps", C.c_double),
+        ("grad_decay", C.c_double),
+        ("param_decay", C.c_double),
+        ("step", C.c_double),
+        ("denom_scale", C.c_double),
+        ("rule", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+PARAM_RULES = {"adam": 0, "radam": 1, "radam_sgd": 2, "moments": 3}  # include/cvd_hip.h CVD_PARAM_RULE_*
+
 DISTANCE_TYPES = {"l1": 0, "l2": 1, "smooth_l1": 2, "cauchy": 3, "general": 4}  # include/cvd_hip.h CVD_DISTANCE_*
 CONSISTENCY_TERMS = ("reproj", "disp", "depth ratio")   # the keys of the reference's batch_losses, in the order of terms[P][3]
 # the keys of the reference's SceneFlowLoss batch_losses, in the order of terms[P][4]
@@ -170,6 +196,52 @@ def spatial_desc(precision, num_frames, frames_per_sample, height, width, lambda
     return d
 
 
+def param_desc(precision, num_tensors):
+    """A stamped cvd_param_desc; precision: 0 / numpy float32 = f32, 1 / float64 = f64."""
+    d = ParamDesc()
+    d.struct_size = C.sizeof(ParamDesc) | (ABI_REVISION << 32)
+    d.precision, d.num_tensors = int(precision), int(num_tensors)
+    return d
+
+
+def adam_record(step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    """The scalars of step number `step` (1, 2, ...) of torch.optim.Adam, in double as torch/optim/adam.py forms them."""
+    beta1, beta2 = betas
+    bias_correction1 = 1 - beta1 ** step
+    bias_correction2 = 1 - beta2 ** step
+    return ParamRecord(beta1=beta1, beta2=beta2, eps=eps, grad_decay=weight_decay, param_decay=0.0, step=lr / bias_correction1,
+                       denom_scale=bias_correction2 ** 0.5, rule=PARAM_RULES["adam"])
+
+
+def radam_record(step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, degenerated_to_sgd=True):
+    """The scalars of step number `step` of the reference's RAdam, in double as optimizer/radam.py:70-95 forms them: the rule is
+    picked by N_sma (rectified from 5 on), the rectification is folded into step_size."""
+    import math
+    beta1, beta2 = betas
+    beta2_t = beta2 ** step
+    N_sma_max = 2 / (1 - beta2) - 1
+    N_sma = N_sma_max - 2 * step * beta2_t / (1 - beta2_t)
+    if N_sma >= 5:
+        rule = "radam"
+        step_size = math.sqrt((1 - beta2_t) * (N_sma - 4) / (N_sma_max - 4) * (N_sma - 2) / N_sma * N_sma_max / (N_sma_max - 2)) / (1 - beta1 ** step)
+    elif degenerated_to_sgd:
+        rule = "radam_sgd"
+        step_size = 1.0 / (1 - beta1 ** step)
+    else:
+        rule, step_size = "moments", 0.0
+    decay = weight_decay * lr if rule != "moments" and weight_decay != 0 else 0.0
+    return ParamRecord(beta1=beta1, beta2=beta2, eps=eps, grad_decay=0.0, param_decay=decay, step=step_size * lr, denom_scale=1.0,
+                       rule=PARAM_RULES[rule])
+
+
+def __getattr__(name):
+    if name == "PARAM_CHUNK":   # elements per chunk of the multi-tensor tables: CVD_PARAM_CHUNK of the loaded library
+        lib = load_library()
+        lib.cvd_param_chunk.restype = C.c_int64
+        return int(lib.cvd_param_chunk())
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def load_library(variant=None):
     """dlopen the in-tree libcvd_hip.so. Raises ImportError (never falls back) when it is not built.  Nothing is read from the
     environment.  `variant` (development tools only, before anything else loaded the library): a profile build
@@ -213,7 +285,7 @@ EXPORTED_SYMBOLS = [
     "cvd_reset_poses", "cvd_reset_depth_xforms", "cvd_reset_spatial_xforms", "cvd_grid_xform_split",
     "cvd_get_xform_desc", "cvd_num_xform_params", "cvd_get_xform_params", "cvd_set_xform_params",
     "cvd_get_pose_params", "cvd_set_pose_params", "cvd_block_size", "cvd_normalize_depth", "cvd_pose_optimization",
-    "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_scene_flow_loss", "cvd_scene_flow_loss_device", "cvd_spatial_losses", "cvd_spatial_losses_device", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
+    "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_scene_flow_loss", "cvd_scene_flow_loss_device", "cvd_spatial_losses", "cvd_spatial_losses_device", "cvd_param_chunk", "cvd_parameter_l1", "cvd_parameter_l1_device", "cvd_param_step", "cvd_param_step_device", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
     "cvd_get_kernel_times", "cvd_get_comm_times", "cvd_get_dense_times", "cvd_set_kernel_timing", "cvd_num_active_constraints", "cvd_coarse_debug", "cvd_temporal_debug", "cvd_path_info", "cvd_abi_revision",
     "cvd_block_inverse_debug", "cvd_dense_inverse_debug", "cvd_epipolar_debug", "cvd_flow_masks_debug",
 ]
@@ -505,6 +577,77 @@ class Solver(Binding):
         if timing:
             out += (ms[0],)
         return out
+
+    @staticmethod
+    def _param_layout(who, arrays, counts, offsets):
+        """The flat arrays of a parameter table, all of one dtype (float32 or float64), with their counts and offsets (default:
+        back to back) as int64."""
+        import numpy as np
+        flat = [np.ascontiguousarray(a).reshape(-1) for a in arrays]
+        dt = flat[0].dtype
+        if dt not in (np.float32, np.float64):
+            raise TypeError(f"{who}: the arrays must be float32 or float64 (got {dt})")
+        for a in flat[1:]:
+            if a.dtype != dt or a.size != flat[0].size:
+                raise ValueError(f"{who}: flat arrays of {a.dtype} x {a.size} and {dt} x {flat[0].size}")
+        counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+        if offsets is None:
+            offsets = np.concatenate([[0], np.cumsum(counts)[:-1]]) if counts.size else np.zeros(0)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if offsets.size != counts.size:
+            raise ValueError(f"{who}: {offsets.size} offsets for {counts.size} counts")
+        return flat, dt, counts, offsets
+
+    def parameter_l1(self, p, p0, counts, lam, *, offsets=None, grad=None, grad_out=1.0, timing=False):
+        """The reference's ParameterLoss (loss/parameter_loss.py) over a list of tensors in one launch, and its subgradient
+        (include/cvd_hip.h cvd_parameter_l1).  p, p0: flat numpy arrays, float32 or float64; tensor i is
+        counts[i] elements at offsets[i] (default: back to back).  grad: None (value only), True (the gradient lam sign(p - p0)
+        grad_out, zero between the tensors) or a flat array the gradient is ADDED to (a copy: the argument stays).  Returns
+        total, then the flat gradient when grad, then {"forward", "backward"} kernel ms when timing."""
+        import numpy as np
+        (p, p0), dt, counts, offsets = self._param_layout("parameter_l1", (p, p0), counts, offsets)
+        accumulate = grad is not None and grad is not True
+        g = None
+        if accumulate:
+            g = np.array(grad, dtype=dt).reshape(-1)
+            if g.size != p.size:
+                raise ValueError(f"parameter_l1: grad has {g.size} elements, the flat arrays {p.size}")
+        elif grad:
+            g = np.zeros(p.size, dt)
+        desc = param_desc(dt == np.float64, counts.size)
+        total = C.c_double(0.0)
+        ms = (C.c_double * 2)()
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        self._check(self._fn("parameter_l1")(self._h, C.byref(desc), ip(offsets), ip(counts), C.c_int64(p.size), vp(p), vp(p0),
+                                             C.c_double(lam), C.byref(total), vp(g), C.c_double(grad_out),
+                                             C.c_int32(int(accumulate)), ms if timing else None))
+        out = (total.value,)
+        if g is not None:
+            out += (g,)
+        if timing:
+            out += ({"forward": ms[0], "backward": ms[1]},)
+        return out if len(out) > 1 else out[0]
+
+    def param_step(self, p, g, m, v, counts, records, *, offsets=None, timing=False):
+        """One optimizer step of a list of tensors in one launch (include/cvd_hip.h cvd_param_step): flat numpy
+        arrays laid out as in parameter_l1, records: one ParamRecord per tensor (adam_record / radam_record), or one for all.
+        Returns the new (p, m, v) (copies: the arguments stay), then the kernel ms when timing."""
+        import numpy as np
+        (p, g, m, v), dt, counts, offsets = self._param_layout("param_step", (p, g, m, v), counts, offsets)
+        p, m, v = p.copy(), m.copy(), v.copy()
+        if isinstance(records, ParamRecord):
+            records = [records] * counts.size
+        if len(records) != counts.size:
+            raise ValueError(f"param_step: {len(records)} records for {counts.size} tensors")
+        rec = (ParamRecord * max(counts.size, 1))(*records)
+        desc = param_desc(dt == np.float64, counts.size)
+        ms = (C.c_double * 1)()
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))
+        self._check(self._fn("param_step")(self._h, C.byref(desc), ip(offsets), ip(counts), C.c_int64(p.size), vp(p), vp(g), vp(m),
+                                           vp(v), rec, ms if timing else None))
+        return (p, m, v, ms[0]) if timing else (p, m, v)
 
     def num_active_constraints(self):
         return int(self._lib.cvd_num_active_constraints(self._h))

@@ -771,6 +771,25 @@ int32_t cvd_spatial_losses_device(cvd_handle* h, const cvd_spatial_desc* desc, c
   CVD_TRY(h, spatialLossesDevice(h, desc, depth, depth_orig, image, total, smooth, contrast, grad,
                                  static_cast<hipStream_t>(stream)));
 }
+int64_t cvd_param_chunk(void) { return paramChunkElements(); }
+int32_t cvd_parameter_l1(cvd_handle* h, const cvd_param_desc* desc, const int64_t* offsets, const int64_t* counts, int64_t flat_count,
+                         const void* p, const void* p0, double lambda, double* total, void* grad, double grad_out,
+                         int32_t accumulate, double* kernel_ms) {
+  CVD_TRY(h, parameterL1(h, desc, offsets, counts, flat_count, p, p0, lambda, total, grad, grad_out, accumulate, kernel_ms));
+}
+int32_t cvd_parameter_l1_device(cvd_handle* h, const cvd_param_desc* desc, const void* const* p, const void* const* p0,
+                                const int64_t* counts, double lambda, double* total, void* const* grad, const void* grad_out,
+                                int32_t accumulate, void* stream) {
+  CVD_TRY(h, parameterL1Device(h, desc, p, p0, counts, lambda, total, grad, grad_out, accumulate, static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_param_step(cvd_handle* h, const cvd_param_desc* desc, const int64_t* offsets, const int64_t* counts, int64_t flat_count,
+                       void* p, const void* g, void* m, void* v, const cvd_param_record* records, double* kernel_ms) {
+  CVD_TRY(h, paramStep(h, desc, offsets, counts, flat_count, p, g, m, v, records, kernel_ms));
+}
+int32_t cvd_param_step_device(cvd_handle* h, const cvd_param_desc* desc, void* const* p, const void* const* g, void* const* m,
+                              void* const* v, const int64_t* counts, const cvd_param_record* records, void* stream) {
+  CVD_TRY(h, paramStepDevice(h, desc, p, g, m, v, counts, records, static_cast<hipStream_t>(stream)));
+}
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {

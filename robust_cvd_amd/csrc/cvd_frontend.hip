@@ -1,6 +1,6 @@
 // cvd_frontend.hip -- the steps either side of the solve: constraint sampling, epipolar RANSAC flags, image operators, dense
 // consumers, flow-guided and bilateral filters, feature tracks, flow consistency masks, the fine-tuning consistency,
-// scene-flow and spatial losses.  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
+// scene-flow and spatial losses, the parameter regulariser and the optimizer step.  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
 // through a pointer to the incomplete type).
 #include "cvd_host.h"
 #include "cvd_dense.h"
@@ -15,12 +15,42 @@
 #include "cvd_consistency.h"
 #include "cvd_sceneflow.h"
 #include "cvd_spatial.h"
+#include "cvd_paramstep.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 namespace cvd {
 
 constexpr int kLossMaxArrays = 17;  // real input arrays of a fine-tuning loss at most (the scene-flow loss)
+
+// A multi-tensor table of cvd_paramstep.h on the device, kept between calls.  The static part (counts, chunk list) is rebuilt only
+// when the list of element counts changes.  The dynamic part (the K pointer arrays and the records: gradients are reallocated
+// between steps, the step scalars change every step) is written into one of kParamSlots slots of pinned staging and copied with
+// one asynchronous copy per call; a slot is rewritten only after the event recorded behind its last copy has completed.
+constexpr int kParamSlots = 4;
+struct ParamTableState {
+  std::vector<long long> counts;       // the tensor list the static part was built for
+  bool built = false;
+  int numChunks = 0;
+  std::vector<int> chunkTensor;        // (outlive their uploads: a rebuild waits for the stream)
+  std::vector<long long> chunkStart;
+  DevBuf<long long> dCounts, dChunkStart;
+  DevBuf<int> dChunkTensor;
+  DevBuf<unsigned char> dDynamic;      // [K][T] addresses, then [T] ParamRecord
+  unsigned char* staging = nullptr;    // pinned, kParamSlots slots of slotBytes
+  size_t slotBytes = 0;
+  hipEvent_t copied[kParamSlots] = {};
+  bool pending[kParamSlots] = {};
+  int next = 0;
+  ParamTableState() = default;
+  ParamTableState(const ParamTableState&) = delete;
+  ParamTableState& operator=(const ParamTableState&) = delete;
+  ~ParamTableState() {
+    for (auto& e : copied)
+      if (e) (void)hipEventDestroy(e);
+    if (staging) (void)hipHostFree(staging);
+  }
+};
 
 // Device state of the operators below.  Nothing is allocated before an operator runs; the staging buffers then keep their
 // high-water size for the life of the handle.
@@ -60,6 +90,9 @@ struct Frontend {
   DevBuf<double> dConsSlab, dConsSums, dConsCoef;
   DevBuf<double> dSfSlab, dSfSums, dSfCoef;
   DevBuf<double> dSpSlab, dSpPart;
+  // cvd_paramstep.h: the tables of the regulariser [0] and of the step [1] per precision, the regulariser's per-workgroup sums
+  ParamTableState paramTable[2][2];
+  DevBuf<double> dParamSlab;
   // staging of the three losses' host-array entry points, which run to completion on the handle's stream one at a time and so
   // share it (runLossOnHostArrays): real inputs in the loss's own order, pair and neighbour frames, scalar results, gradient, maps
   DevBuf<unsigned char> dLossIn[kLossMaxArrays], dLossGrad, dLossMaps;
@@ -1373,6 +1406,307 @@ void spatialLosses(cvd_handle* h, const cvd_spatial_desc* d, const void* depth, 
     });
   });
 }
+
+// ---- parameter regulariser and optimizer step over a multi-tensor table (reference loss/parameter_loss.py,
+// optimizer/radam.py, torch.optim.Adam; cvd_paramstep.h) ----------------------------------------------------------------------
+namespace {
+// checks the desc; returns the element size
+size_t checkParamDesc(const char* op, const cvd_param_desc* d) {
+  if (!d) throw std::runtime_error(fmt("%s: null desc", op));
+  if (d->struct_size != CVD_STRUCT_STAMP(cvd_param_desc))
+    throw std::runtime_error(fmt("%s: desc.struct_size %llu is not this library's %llu (built against another revision of cvd_hip.h)",
+                                 op, static_cast<unsigned long long>(d->struct_size),
+                                 static_cast<unsigned long long>(CVD_STRUCT_STAMP(cvd_param_desc))));
+  if (d->precision != CVD_PRECISION_F32 && d->precision != CVD_PRECISION_F64)
+    throw std::runtime_error(fmt("%s: precision must be 0 (f32) or 1 (f64) (got %d)", op, d->precision));
+  if (d->num_tensors < 0) throw std::runtime_error(fmt("%s: num_tensors must be >= 0 (got %d)", op, d->num_tensors));
+  return d->precision == CVD_PRECISION_F64 ? 8 : 4;
+}
+
+void checkParamCounts(const char* op, int T, const int64_t* counts) {
+  if (T && !counts) throw std::runtime_error(fmt("%s: null counts", op));
+  long long chunks = 0;
+  for (int t = 0; t < T; ++t) {
+    if (counts[t] < 0) throw std::runtime_error(fmt("%s: counts[%d] = %lld is negative", op, t, static_cast<long long>(counts[t])));
+    chunks += counts[t] / kParamChunk + (counts[t] % kParamChunk != 0);   // (no rounding up by addition: a count near 2^63 would wrap)
+    if (chunks >= (1ll << 31)) break;
+  }
+  if (chunks >= (1ll << 31)) throw std::runtime_error(fmt("%s: %lld chunks exceed the chunk list", op, chunks));
+}
+
+// one array of T device addresses: none may be null or off the element size unless its tensor is empty
+void checkParamAddresses(const char* op, const char* name, int T, const void* const* a, const int64_t* counts, size_t es) {
+  if (T && !a) throw std::runtime_error(fmt("%s: null %s", op, name));
+  for (int t = 0; t < T; ++t) {
+    if (counts[t] == 0) continue;
+    if (!a[t]) throw std::runtime_error(fmt("%s: %s[%d] is a null pointer", op, name, t));
+    if (reinterpret_cast<uintptr_t>(a[t]) % es)
+      throw std::runtime_error(fmt("%s: %s[%d] = %p is misaligned for %zu-byte elements", op, name, t, a[t], es));
+  }
+}
+
+void checkParamLambda(const char* op, double lambda) {
+  if (!std::isfinite(lambda)) throw std::runtime_error(fmt("%s: lambda must be finite (got %g)", op, lambda));
+}
+
+void checkParamRecords(const char* op, int T, const cvd_param_record* r) {
+  if (T && !r) throw std::runtime_error(fmt("%s: null records", op));
+  for (int t = 0; t < T; ++t) {
+    const std::pair<const char*, double> scalars[] = {{"beta1", r[t].beta1}, {"beta2", r[t].beta2}, {"eps", r[t].eps},
+                                                      {"grad_decay", r[t].grad_decay}, {"param_decay", r[t].param_decay},
+                                                      {"step", r[t].step}, {"denom_scale", r[t].denom_scale}};
+    for (const auto& v : scalars)
+      if (!std::isfinite(v.second)) throw std::runtime_error(fmt("%s: records[%d].%s must be finite (got %g)", op, t, v.first, v.second));
+    for (int k = 0; k < 2; ++k)
+      if (!(scalars[k].second >= 0.0 && scalars[k].second < 1.0))
+        throw std::runtime_error(fmt("%s: records[%d].%s must lie in [0, 1) (got %g)", op, t, scalars[k].first, scalars[k].second));
+    if (!(r[t].denom_scale > 0.0))
+      throw std::runtime_error(fmt("%s: records[%d].denom_scale must be > 0 (got %g)", op, t, r[t].denom_scale));
+    if (r[t].rule < CVD_PARAM_RULE_ADAM || r[t].rule > CVD_PARAM_RULE_MOMENTS)
+      throw std::runtime_error(fmt("%s: records[%d].rule %d is not a CVD_PARAM_RULE_*", op, t, r[t].rule));
+  }
+}
+
+// The table of T tensors with K pointer arrays (arrays[k] NULL: zeros) on the device, ready for a launch on s.
+ParamTable paramTable(ParamTableState& st, int T, int K, const void* const* const* arrays, const int64_t* counts,
+                      const cvd_param_record* records, hipStream_t s) {
+  ParamTable tab{};
+  tab.numTensors = T;
+  if (T == 0) return tab;
+  const bool same = st.built && st.counts.size() == static_cast<size_t>(T) && std::equal(st.counts.begin(), st.counts.end(), counts);
+  const size_t slotBytes = static_cast<size_t>(T) * (kParamStepArrays * sizeof(unsigned long long) + sizeof(ParamRecord));
+  if (!same) {
+    // the uploads below read host vectors this rewrites, and the staging may move: nothing of the last table may be in flight
+    HIP_CHECK(hipStreamSynchronize(s));
+    for (int k = 0; k < kParamSlots; ++k) {
+      if (st.pending[k]) HIP_CHECK(hipEventSynchronize(st.copied[k]));
+      st.pending[k] = false;
+      if (!st.copied[k]) HIP_CHECK(hipEventCreateWithFlags(&st.copied[k], hipEventDisableTiming));
+    }
+    st.built = false;
+    st.counts.assign(counts, counts + T);
+    st.chunkTensor.clear();
+    st.chunkStart.clear();
+    for (int t = 0; t < T; ++t)
+      for (long long at = 0; at < counts[t]; at += kParamChunk) {
+        st.chunkTensor.push_back(t);
+        st.chunkStart.push_back(at);
+      }
+    st.numChunks = static_cast<int>(st.chunkTensor.size());
+    st.dCounts.upload(st.counts.data(), st.counts.size(), s);
+    st.dChunkTensor.upload(st.chunkTensor.data(), st.chunkTensor.size(), s);
+    st.dChunkStart.upload(st.chunkStart.data(), st.chunkStart.size(), s);
+    st.dDynamic.ensure(slotBytes);
+    if (slotBytes > st.slotBytes) {
+      if (st.staging) HIP_CHECK(hipHostFree(st.staging));
+      st.staging = nullptr;
+      st.slotBytes = 0;
+      HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&st.staging), slotBytes * kParamSlots, hipHostMallocDefault));
+      st.slotBytes = slotBytes;
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    st.built = true;
+  }
+  const int slot = st.next;
+  st.next = (slot + 1) % kParamSlots;
+  if (st.pending[slot]) HIP_CHECK(hipEventSynchronize(st.copied[slot]));   // (kParamSlots calls ago: long complete)
+  unsigned char* stage = st.staging + static_cast<size_t>(slot) * st.slotBytes;
+  auto* addr = reinterpret_cast<unsigned long long*>(stage);
+  for (int k = 0; k < kParamStepArrays; ++k)
+    for (int t = 0; t < T; ++t)
+      addr[static_cast<size_t>(k) * T + t] = k < K && arrays[k] ? reinterpret_cast<uintptr_t>(arrays[k][t]) : 0ull;
+  auto* rec = reinterpret_cast<ParamRecord*>(stage + static_cast<size_t>(T) * kParamStepArrays * sizeof(unsigned long long));
+  for (int t = 0; t < T; ++t) {
+    ParamRecord r{};
+    if (records) {
+      const cvd_param_record& c = records[t];
+      r = ParamRecord{c.beta1, 1.0 - c.beta1, c.beta2, 1.0 - c.beta2, c.eps, c.grad_decay, c.param_decay, c.step, c.denom_scale,
+                      c.rule, 0};
+    }
+    rec[t] = r;
+  }
+  HIP_CHECK(hipMemcpyAsync(st.dDynamic.p, stage, slotBytes, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipEventRecord(st.copied[slot], s));
+  st.pending[slot] = true;
+  tab.numChunks = st.numChunks;
+  tab.ptrs = reinterpret_cast<const unsigned long long*>(st.dDynamic.p);
+  tab.counts = st.dCounts.p;
+  tab.chunkTensor = st.dChunkTensor.p;
+  tab.chunkStart = st.dChunkStart.p;
+  tab.records = reinterpret_cast<const ParamRecord*>(st.dDynamic.p + static_cast<size_t>(T) * kParamStepArrays * sizeof(unsigned long long));
+  return tab;
+}
+
+dim3 paramGrid(const ParamTable& tab) { return dim3(static_cast<unsigned>(std::min(tab.numChunks, kParamMaxGrid))); }
+
+// value (total != null) and gradient (grad != null) of the regulariser on device tensors, on s; the timer's phases: value, gradient
+template <typename T>
+void launchParameterL1(cvd_handle* h, int numTensors, const void* const* p, const void* const* p0, const int64_t* counts,
+                       double lambda, double* total, void* const* grad, const void* gradOut, bool accumulate, hipStream_t s,
+                       KernelTimer& timer) {
+  Frontend& fe = *h->frontend;
+  const void* const* arrays[kParamL1Arrays] = {p, p0, grad};
+  const ParamTable tab = paramTable(fe.paramTable[0][sizeof(T) == 8], numTensors, kParamL1Arrays, arrays, counts, nullptr, s);
+  timer.mark();
+  if (total) {
+    fe.dParamSlab.ensure(kParamMaxGrid);
+    const dim3 grid = paramGrid(tab);
+    if (tab.numChunks) hipLaunchKernelGGL((k_param_l1<T>), grid, dim3(kConsThreads), 0, s, tab, fe.dParamSlab.p);
+    hipLaunchKernelGGL(k_param_l1_finish, dim3(1), dim3(kConsThreads), 0, s, fe.dParamSlab.p, static_cast<int>(tab.numChunks ? grid.x : 0),
+                       lambda, total);
+    HIP_CHECK(hipGetLastError());
+  }
+  timer.mark();
+  if (grad) {
+    if (tab.numChunks) {
+      if (accumulate) hipLaunchKernelGGL((k_param_l1_grad<T, true>), paramGrid(tab), dim3(kConsThreads), 0, s, tab, lambda, static_cast<const T*>(gradOut));
+      else hipLaunchKernelGGL((k_param_l1_grad<T, false>), paramGrid(tab), dim3(kConsThreads), 0, s, tab, lambda, static_cast<const T*>(gradOut));
+      HIP_CHECK(hipGetLastError());
+    }
+    timer.mark();
+  }
+}
+
+template <typename T>
+void launchParamStep(cvd_handle* h, int numTensors, void* const* p, const void* const* g, void* const* m, void* const* v,
+                     const int64_t* counts, const cvd_param_record* records, hipStream_t s, KernelTimer& timer) {
+  Frontend& fe = *h->frontend;
+  const void* const* arrays[kParamStepArrays] = {p, g, m, v};
+  const ParamTable tab = paramTable(fe.paramTable[1][sizeof(T) == 8], numTensors, kParamStepArrays, arrays, counts, records, s);
+  timer.mark();
+  if (tab.numChunks) {
+    hipLaunchKernelGGL((k_param_step<T>), paramGrid(tab), dim3(kConsThreads), 0, s, tab);
+    HIP_CHECK(hipGetLastError());
+  }
+  timer.mark();
+}
+
+void checkParameterL1(const char* op, const cvd_param_desc* d, const int64_t* counts, double lambda) {
+  checkParamDesc(op, d);
+  checkParamCounts(op, d->num_tensors, counts);
+  checkParamLambda(op, lambda);
+}
+
+// device addresses of the tensors inside a staged flat array
+std::vector<const void*> paramAddresses(const unsigned char* base, int T, const int64_t* offsets, size_t es) {
+  std::vector<const void*> a(T);
+  for (int t = 0; t < T; ++t) a[t] = base + static_cast<size_t>(offsets[t]) * es;
+  return a;
+}
+
+void checkParamFlat(const char* op, int T, const int64_t* offsets, const int64_t* counts, int64_t flatCount) {
+  if (flatCount < 0) throw std::runtime_error(fmt("%s: flat_count %lld is negative", op, static_cast<long long>(flatCount)));
+  if (T && !offsets) throw std::runtime_error(fmt("%s: null offsets", op));
+  for (int t = 0; t < T; ++t)
+    if (offsets[t] < 0 || offsets[t] > flatCount || counts[t] > flatCount - offsets[t])
+      throw std::runtime_error(fmt("%s: tensor %d (%lld elements at %lld) leaves the flat arrays of %lld elements", op, t,
+                                   static_cast<long long>(counts[t]), static_cast<long long>(offsets[t]),
+                                   static_cast<long long>(flatCount)));
+}
+}  // namespace
+
+void parameterL1Device(cvd_handle* h, const cvd_param_desc* d, const void* const* p, const void* const* p0, const int64_t* counts,
+                       double lambda, double* total, void* const* grad, const void* gradOut, int accumulate, hipStream_t s) {
+  const char* op = "parameter l1";
+  checkParameterL1(op, d, counts, lambda);
+  const size_t es = d->precision == CVD_PRECISION_F64 ? 8 : 4;
+  checkParamAddresses(op, "p", d->num_tensors, p, counts, es);
+  checkParamAddresses(op, "p0", d->num_tensors, p0, counts, es);
+  if (!total && !grad) throw std::runtime_error(fmt("%s: neither total nor grad is asked for", op));
+  if (grad) {
+    checkParamAddresses(op, "grad", d->num_tensors, grad, counts, es);
+    if (!gradOut) throw std::runtime_error(fmt("%s: null grad_out", op));
+  }
+  KernelTimer timer(s, nullptr, 2);
+  withPrecision(d->precision, [&](auto t) {
+    launchParameterL1<decltype(t)>(h, d->num_tensors, p, p0, counts, lambda, total, grad, gradOut, accumulate != 0, s, timer);
+  });
+}
+
+// Host arrays in, host results out.  kernelMs (may be NULL): {value, gradient} HIP-event times.
+void parameterL1(cvd_handle* h, const cvd_param_desc* d, const int64_t* offsets, const int64_t* counts, int64_t flatCount,
+                 const void* p, const void* p0, double lambda, double* total, void* grad, double gradOut, int accumulate,
+                 double* kernelMs) {
+  const char* op = "parameter l1";
+  checkParameterL1(op, d, counts, lambda);
+  const int T = d->num_tensors;
+  const size_t es = d->precision == CVD_PRECISION_F64 ? 8 : 4;
+  checkParamFlat(op, T, offsets, counts, flatCount);
+  if (flatCount && !p) throw std::runtime_error(fmt("%s: null p", op));
+  if (flatCount && !p0) throw std::runtime_error(fmt("%s: null p0", op));
+  if (!total) throw std::runtime_error(fmt("%s: null total", op));
+  if (!std::isfinite(gradOut)) throw std::runtime_error(fmt("%s: grad_out must be finite (got %g)", op, gradOut));
+  hipStream_t s = h->stream;
+  Frontend& fe = *h->frontend;
+  const size_t bytes = static_cast<size_t>(flatCount) * es;
+  fe.dLossIn[0].upload(static_cast<const unsigned char*>(p), bytes, s);
+  fe.dLossIn[1].upload(static_cast<const unsigned char*>(p0), bytes, s);
+  if (grad) fe.dLossGrad.upload(static_cast<const unsigned char*>(grad), bytes, s);
+  fe.dLossOut.ensure(2);   // the total, the scalar grad_out
+  const float go32 = static_cast<float>(gradOut);
+  HIP_CHECK(hipMemcpyAsync(fe.dLossOut.p + 1, es == 8 ? static_cast<const void*>(&gradOut) : static_cast<const void*>(&go32), es,
+                           hipMemcpyHostToDevice, s));
+  const auto ap = paramAddresses(fe.dLossIn[0].p, T, offsets, es), ap0 = paramAddresses(fe.dLossIn[1].p, T, offsets, es);
+  const auto ag = grad ? paramAddresses(fe.dLossGrad.p, T, offsets, es) : std::vector<const void*>();
+  KernelTimer timer(s, kernelMs, 2);
+  withPrecision(d->precision, [&](auto t) {
+    launchParameterL1<decltype(t)>(h, T, ap.data(), ap0.data(), counts, lambda, fe.dLossOut.p,
+                                   grad ? const_cast<void* const*>(ag.data()) : nullptr, fe.dLossOut.p + 1, accumulate != 0, s, timer);
+  });
+  HIP_CHECK(hipMemcpyAsync(total, fe.dLossOut.p, sizeof(double), hipMemcpyDeviceToHost, s));
+  if (grad) fe.dLossGrad.download(static_cast<unsigned char*>(grad), bytes, s);
+  HIP_CHECK(hipStreamSynchronize(s));
+  timer.collect();
+}
+
+void paramStepDevice(cvd_handle* h, const cvd_param_desc* d, void* const* p, const void* const* g, void* const* m, void* const* v,
+                     const int64_t* counts, const cvd_param_record* records, hipStream_t s) {
+  const char* op = "param step";
+  const size_t es = checkParamDesc(op, d);
+  const int T = d->num_tensors;
+  checkParamCounts(op, T, counts);
+  checkParamAddresses(op, "p", T, p, counts, es);
+  checkParamAddresses(op, "g", T, g, counts, es);
+  checkParamAddresses(op, "m", T, m, counts, es);
+  checkParamAddresses(op, "v", T, v, counts, es);
+  checkParamRecords(op, T, records);
+  KernelTimer timer(s, nullptr, 1);
+  withPrecision(d->precision, [&](auto t) { launchParamStep<decltype(t)>(h, T, p, g, m, v, counts, records, s, timer); });
+}
+
+// Host arrays in, p / m / v updated in place.  kernelMs (may be NULL): the launch's HIP-event time.
+void paramStep(cvd_handle* h, const cvd_param_desc* d, const int64_t* offsets, const int64_t* counts, int64_t flatCount, void* p,
+               const void* g, void* m, void* v, const cvd_param_record* records, double* kernelMs) {
+  const char* op = "param step";
+  const size_t es = checkParamDesc(op, d);
+  const int T = d->num_tensors;
+  checkParamCounts(op, T, counts);
+  checkParamFlat(op, T, offsets, counts, flatCount);
+  const std::pair<const char*, const void*> flat[] = {{"p", p}, {"g", g}, {"m", m}, {"v", v}};
+  for (const auto& a : flat)
+    if (flatCount && !a.second) throw std::runtime_error(fmt("%s: null %s", op, a.first));
+  checkParamRecords(op, T, records);
+  hipStream_t s = h->stream;
+  Frontend& fe = *h->frontend;
+  const size_t bytes = static_cast<size_t>(flatCount) * es;
+  std::vector<const void*> dev[kParamStepArrays];
+  for (int k = 0; k < kParamStepArrays; ++k) {
+    fe.dLossIn[k].upload(static_cast<const unsigned char*>(flat[k].second), bytes, s);
+    dev[k] = paramAddresses(fe.dLossIn[k].p, T, offsets, es);
+  }
+  KernelTimer timer(s, kernelMs, 1);
+  withPrecision(d->precision, [&](auto t) {
+    launchParamStep<decltype(t)>(h, T, const_cast<void* const*>(dev[0].data()), dev[1].data(), const_cast<void* const*>(dev[2].data()),
+                                 const_cast<void* const*>(dev[3].data()), counts, records, s, timer);
+  });
+  fe.dLossIn[0].download(static_cast<unsigned char*>(p), bytes, s);
+  fe.dLossIn[2].download(static_cast<unsigned char*>(m), bytes, s);
+  fe.dLossIn[3].download(static_cast<unsigned char*>(v), bytes, s);
+  HIP_CHECK(hipStreamSynchronize(s));
+  timer.collect();
+}
+
+long long paramChunkElements() { return kParamChunk; }
 
 // One kernel of this translation unit's code object is looked up at handle creation: the HIP runtime loads a unit's device
 // code at its first use, ~20 ms per unit that would otherwise land in the first solve of a process (cvd_create: loadDeviceCode).

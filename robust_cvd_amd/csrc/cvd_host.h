@@ -742,5 +742,15 @@ void spatialLosses(cvd_handle* h, const cvd_spatial_desc* d, const void* depth, 
                    double* total, double* smooth, double* contrast, void* grad, double* kernelMs);
 void spatialLossesDevice(cvd_handle* h, const cvd_spatial_desc* d, const void* depth, const void* depthOrig, const void* image,
                          double* total, double* smooth, double* contrast, void* grad, hipStream_t s);
+void parameterL1(cvd_handle* h, const cvd_param_desc* d, const int64_t* offsets, const int64_t* counts, int64_t flatCount,
+                 const void* p, const void* p0, double lambda, double* total, void* grad, double gradOut, int accumulate,
+                 double* kernelMs);
+void parameterL1Device(cvd_handle* h, const cvd_param_desc* d, const void* const* p, const void* const* p0, const int64_t* counts,
+                       double lambda, double* total, void* const* grad, const void* gradOut, int accumulate, hipStream_t s);
+void paramStep(cvd_handle* h, const cvd_param_desc* d, const int64_t* offsets, const int64_t* counts, int64_t flatCount, void* p,
+               const void* g, void* m, void* v, const cvd_param_record* records, double* kernelMs);
+void paramStepDevice(cvd_handle* h, const cvd_param_desc* d, void* const* p, const void* const* g, void* const* m, void* const* v,
+                     const int64_t* counts, const cvd_param_record* records, hipStream_t s);
+long long paramChunkElements();   // CVD_PARAM_CHUNK of cvd_frontend.hip's build
 
 }  // namespace cvd

@@ -11,7 +11,9 @@
 scene_flow.py) live on one GPU; N = 2, or 6 when a temporally smooth lambda is > 0.  With N = 6 the consistency term gets frames
 0 and 1 of every sample (slices of depths, extrinsics, intrinsics and warp), as the reference's own loop over the two flow
 directions does.  When both spatial terms are on they run in ONE kernel call.  ParameterLoss is plain torch
-(lambda sum |p - p_init| over a list of arbitrary tensors; off by default).
+(lambda sum |p - p_init| over a list of arbitrary tensors; off by default); JointLoss(..., fused_parameter_loss=True) uses
+robust_cvd_amd.parameter_loss.ParameterLoss instead: one launch over all tensors, and one for their gradients (DESIGN.md §3.13;
+contiguous float32 / float64 parameters on one GPU).
 
 Differences from the reference:
   * nothing is printed (the reference prints every term, one host synchronisation each);
@@ -27,6 +29,7 @@ Import this module (torch) before anything loads libcvd_hip.so, as robust_cvd_am
 """
 import torch
 
+from . import parameter_loss as fused
 from .consistency import ConsistencyLoss
 from .scene_flow import SceneFlowLoss
 from .spatial_losses import ContrastLoss, DisparitySmoothLoss, spatial_terms
@@ -54,12 +57,12 @@ def _has_scene_flow(opt):
 
 
 class JointLoss(torch.nn.Module):
-    def __init__(self, opt, parameters_init=None, scene_flow_maps=False):
+    def __init__(self, opt, parameters_init=None, scene_flow_maps=False, fused_parameter_loss=False):
         super().__init__()
         self.opt = opt
         if opt.lambda_parameter > 0:
             assert parameters_init is not None
-            self.parameter_loss = ParameterLoss(parameters_init, opt)
+            self.parameter_loss = (fused.ParameterLoss if fused_parameter_loss else ParameterLoss)(parameters_init, opt)
         if _has_consistency(opt):
             self.consistency_loss = ConsistencyLoss(opt)
         if _has_scene_flow(opt):
