@@ -592,6 +592,86 @@ int32_t cvd_param_step(cvd_handle* h, const cvd_param_desc* desc, const int64_t*
 int32_t cvd_param_step_device(cvd_handle* h, const cvd_param_desc* desc, void* const* p, const void* const* g, void* const* m,
                               void* const* v, const int64_t* counts, const cvd_param_record* records, void* stream);
 
+/* ---- fine-tuning batches from a device-resident dataset, DESIGN.md §3.14.  Independent of cvd_set_video.  Replaces the
+ * reference's loaders/video_dataset.py::VideoDataset behind a DataLoader and to_device: the colour, flow and mask images of a
+ * video are uploaded ONCE, in their file layout, and every batch is then ONE kernel launch that writes all its tensors in the
+ * layout the losses read.  Every output element is a copy of a store element or the constant 0 / 1.
+ * The store belongs to the handle: calls on it are ordered on one stream (or synchronised across streams) by the caller; the
+ * set_* calls and cvd_dataset_create / _clear wait for the device, the batch entry points do not allocate once their staging
+ * has its size.  cvd_destroy frees the store. */
+typedef struct cvd_dataset_desc {
+  uint64_t struct_size;          /* CVD_STRUCT_STAMP(cvd_dataset_desc), set by the caller */
+  int32_t num_frames;            /* F: frames of the store */
+  int32_t height, width;
+  int32_t num_pairs;             /* Q: directed pairs whose flow and mask the store holds */
+  int32_t num_samples;           /* S */
+  int32_t temporal;              /* 0: a sample is its pair (N = 2 frames); 1: and the four neighbours (N = 6) */
+  int32_t has_depth_orig;        /* 1: the store also holds an initial depth per frame (cvd_dataset_set_depth_orig) */
+  int32_t neighbor_rule_frames;  /* the reference's self.num_frames = len(frames) of its rule for real neighbours, 0 < k <
+                                    num_frames - 1, and of the clamp of the neighbour indices; 0 = num_frames, never more */
+} cvd_dataset_desc;
+/* Allocates the store (zeroed) and builds the device-resident sample table (reference loaders/video_dataset.py:223-256, 309-328,
+ * 358-367).  pair_frames [Q][2]: the directed pairs (source, target), slot = position; samples [S][2]: the frame pair (a, b) of
+ * every sample.  A sample reads the flows of (a, b) and (b, a) and, with `temporal`, of (k, k-1) and (k, k+1) for k = a, b where k
+ * is an interior frame (else the reference's dummies: images 0, cameras, flows and masks 1, valid 0).  Rejected before any device
+ * work: a desc of another header revision, a shape or count below its minimum, a frame outside [0, F), a directed pair listed
+ * twice, a sample one of whose directions is not in the pair list, a temporal sample whose interior frame lacks a neighbour flow.
+ * Replaces the store of an earlier call. */
+int32_t cvd_dataset_create(cvd_handle* h, const cvd_dataset_desc* desc, const int32_t* pair_frames, const int32_t* samples);
+/* Frees the store. */
+int32_t cvd_dataset_clear(cvd_handle* h);
+/* Uploads, in chunks of the caller's choice (a caller streams from disk).  Colour of frames [first, first + count): host f32
+ * [count][H][W][3] in the channel order the batch returns (the reference's load_color, loaders/video_dataset.py:49-60: raw files
+ * flipped BGR -> RGB, other files / 255).  Flow and mask of pair slots [first, first + count) in their file layout: flow f32
+ * [count][H][W][2] pixels, mask u8 [count][H][W], any nonzero value counts as 1 (load_flow / load_mask, :63-78).  Initial depth of
+ * frames [first, first + count): f32 [count][H][W], already 1 / disparity (reference depth_fine_tuning.py:457-471). */
+int32_t cvd_dataset_set_colors(cvd_handle* h, int32_t first, int32_t count, const float* hwc3);
+int32_t cvd_dataset_set_flows(cvd_handle* h, int32_t first, int32_t count, const float* flow, const uint8_t* mask);
+int32_t cvd_dataset_set_depth_orig(cvd_handle* h, int32_t first, int32_t count, const float* depth);
+/* Cameras of all frames as update_poses forms them (reference loaders/video_dataset.py:177-189): extrinsics f32 [F][3][4] with
+ * columns right, up, backward, position; intrinsics f32 [F][4] = (fx, fy, cx, cy) in pixels. */
+int32_t cvd_dataset_set_cameras(cvd_handle* h, const float* extrinsics, const float* intrinsics);
+/* The per-frame tables of update_poses (reference loaders/video_dataset.py:191-217) from the transforms' parameters, on the
+ * device, one launch per table: scales = GridDepthXform::paramMap as f32 [F][H][W] for a 2-D grid, [F] scalars 1.0 for Identity
+ * and params[0] for Global; warp = SpatialXform::warp(H, W) as f32 [F][2][H][W] (planar) for the five spatial families.
+ * depth_params [F][nD], spatial_params [F][nS] doubles (NULL where the count is 0).  Refused as the reference refuses them: a value
+ * transform other than Scale when the depth type is not Identity ("We only support scale-based transforms at the moment."), other
+ * depth / spatial types ("Unsupported depth / spatial transform type").  A depth-wise grid (grid z > 1), whose map needs the source
+ * depth, is refused too: evaluate it on the host and use cvd_dataset_set_maps. */
+int32_t cvd_dataset_set_xforms(cvd_handle* h, const cvd_xform_desc* depth_desc, const double* depth_params,
+                               const cvd_xform_desc* spatial_desc, const double* spatial_params);
+/* The same tables from host arrays: scales f32 [F][H][W] (scale_is_map != 0) or [F], NULL = no scales; warp f32 [F][2][H][W],
+ * NULL = no warp. */
+int32_t cvd_dataset_set_maps(cvd_handle* h, const float* scales, int32_t scale_is_map, const float* warp);
+/* Where a batch of B samples goes; f32 and contiguous unless noted, N = 6 with `temporal`, else 2.  The ts_* members are written
+ * with `temporal` only (else ignored); scales, warp and depth_orig are optional (NULL: not written) and need their table. */
+typedef struct cvd_dataset_batch_out {
+  uint64_t struct_size;        /* CVD_STRUCT_STAMP(cvd_dataset_batch_out), set by the caller */
+  void* images;                /* (B, N, 3, H, W): colour of the pair, then of the four neighbours (0 for a dummy) */
+  void* extrinsics;            /* (B, N, 3, 4); dummies are 1 */
+  void* intrinsics;            /* (B, N, 4); dummies are 1 */
+  void* gc_indices;            /* (B, 2) int64: the pair */
+  void* gc_flows[2];           /* (B, 2, H, W): a -> b, b -> a, planar */
+  void* gc_masks[2];           /* (B, 1, H, W): 0 or 1 */
+  void* ts_indices;            /* (B, 4) int64: (a-1, a+1, b-1, b+1) clamped */
+  void* ts_flows[4];           /* (B, 2, H, W): a -> a-1, a -> a+1, b -> b-1, b -> b+1; dummies are 1 */
+  void* ts_masks[4];           /* (B, 1, H, W); dummies are 1 */
+  void* ts_valid;              /* (B, 2, 1): 1 where a / b is an interior frame */
+  void* scales;                /* (B, N, H, W) or (B, N, 1, 1): of the pair and the clamped neighbours (real frames, dummies or not) */
+  void* warp;                  /* (B, N, 2, H, W): frames as for scales */
+  void* depth_orig;            /* (B, 2, H, W): of the pair */
+} cvd_dataset_batch_out;
+/* One batch: host indices (int64 [B], each in [0, S): checked before any device work) and host arrays.  kernel_ms [1] optional. */
+int32_t cvd_dataset_batch(cvd_handle* h, int32_t batch_size, const int64_t* indices, const cvd_dataset_batch_out* out,
+                          double* kernel_ms);
+/* The same with DEVICE indices and DEVICE outputs, one launch enqueued on `stream`: no copy, no allocation and no host
+ * synchronisation.  The indices cannot be checked here: the kernel clamps an index outside [0, S) into it -- it never reads
+ * outside the store -- and counts it in a device word. */
+int32_t cvd_dataset_batch_device(cvd_handle* h, int32_t batch_size, const int64_t* indices, const cvd_dataset_batch_out* out,
+                                 void* stream);
+/* Indices the device entry point has clamped since cvd_dataset_create.  Waits for the device: for tests and debugging. */
+int32_t cvd_dataset_bad_indices(cvd_handle* h, int64_t* count);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

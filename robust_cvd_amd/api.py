@@ -140,6 +140,41 @@ class ParamRecord(C.Structure):
     ]
 
 
+class DatasetDesc(C.Structure):
+    """include/cvd_hip.h cvd_dataset_desc"""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("num_frames", C.c_int32),
+        ("height", C.c_int32),
+        ("width", C.c_int32),
+        ("num_pairs", C.c_int32),
+        ("num_samples", C.c_int32),
+        ("temporal", C.c_int32),
+        ("has_depth_orig", C.c_int32),
+        ("neighbor_rule_frames", C.c_int32),
+    ]
+
+
+class DatasetBatchOut(C.Structure):
+    """include/cvd_hip.h cvd_dataset_batch_out: addresses of a batch's tensors (host or device, as the entry point says)"""
+    _fields_ = [
+        ("struct_size", C.c_uint64),
+        ("images", C.c_void_p),
+        ("extrinsics", C.c_void_p),
+        ("intrinsics", C.c_void_p),
+        ("gc_indices", C.c_void_p),
+        ("gc_flows", C.c_void_p * 2),
+        ("gc_masks", C.c_void_p * 2),
+        ("ts_indices", C.c_void_p),
+        ("ts_flows", C.c_void_p * 4),
+        ("ts_masks", C.c_void_p * 4),
+        ("ts_valid", C.c_void_p),
+        ("scales", C.c_void_p),
+        ("warp", C.c_void_p),
+        ("depth_orig", C.c_void_p),
+    ]
+
+
 PARAM_RULES = {"adam": 0, "radam": 1, "radam_sgd": 2, "moments": 3}  # include/cvd_hip.h CVD_PARAM_RULE_*
 
 DISTANCE_TYPES = {"l1": 0, "l2": 1, "smooth_l1": 2, "cauchy": 3, "general": 4}  # include/cvd_hip.h CVD_DISTANCE_*
@@ -202,6 +237,90 @@ def param_desc(precision, num_tensors):
     d.struct_size = C.sizeof(ParamDesc) | (ABI_REVISION << 32)
     d.precision, d.num_tensors = int(precision), int(num_tensors)
     return d
+
+
+def dataset_desc(num_frames, height, width, num_pairs, num_samples, temporal, has_depth_orig=False, neighbor_rule_frames=0):
+    """A stamped cvd_dataset_desc."""
+    d = DatasetDesc()
+    d.struct_size = C.sizeof(DatasetDesc) | (ABI_REVISION << 32)
+    d.num_frames, d.height, d.width = int(num_frames), int(height), int(width)
+    d.num_pairs, d.num_samples = int(num_pairs), int(num_samples)
+    d.temporal, d.has_depth_orig = int(bool(temporal)), int(bool(has_depth_orig))
+    d.neighbor_rule_frames = int(neighbor_rule_frames)
+    return d
+
+
+def dataset_batch_shapes(B, N, H, W, scale_mode=0, warp=False, depth_orig=False):
+    """{name: (shape, dtype name)} of the tensors of a batch of B samples, in the order of cvd_dataset_batch_out; the lists
+    gc_flows .. ts_masks are named `gc_flows0` ...  scale_mode: 0 no scales, 1 scalars (B, N, 1, 1), 2 maps (B, N, H, W)."""
+    out = {"images": ((B, N, 3, H, W), "float32"), "extrinsics": ((B, N, 3, 4), "float32"), "intrinsics": ((B, N, 4), "float32"),
+           "gc_indices": ((B, 2), "int64")}
+    out.update({f"gc_flows{d}": ((B, 2, H, W), "float32") for d in range(2)})
+    out.update({f"gc_masks{d}": ((B, 1, H, W), "float32") for d in range(2)})
+    if N > 2:
+        out["ts_indices"] = ((B, 4), "int64")
+        out.update({f"ts_flows{d}": ((B, 2, H, W), "float32") for d in range(4)})
+        out.update({f"ts_masks{d}": ((B, 1, H, W), "float32") for d in range(4)})
+        out["ts_valid"] = ((B, 2, 1), "float32")
+    if scale_mode:
+        out["scales"] = ((B, N, H, W) if scale_mode == 2 else (B, N, 1, 1), "float32")
+    if warp:
+        out["warp"] = ((B, N, 2, H, W), "float32")
+    if depth_orig:
+        out["depth_orig"] = ((B, 2, H, W), "float32")
+    return out
+
+
+def dataset_batch_out(addresses):
+    """A stamped cvd_dataset_batch_out from {name of dataset_batch_shapes: address}."""
+    o = DatasetBatchOut()
+    o.struct_size = C.sizeof(DatasetBatchOut) | (ABI_REVISION << 32)
+    for name, a in addresses.items():
+        if name[-1].isdigit():
+            getattr(o, name[:-1])[int(name[-1])] = a
+        else:
+            setattr(o, name, a)
+    return o
+
+
+def nest_batch(flat):
+    """The flat tensors of dataset_batch_shapes as (images, metadata) with the nesting and key names of the reference's
+    VideoDataset (loaders/video_dataset.py:330-398)."""
+    meta = {"extrinsics": flat["extrinsics"], "intrinsics": flat["intrinsics"],
+            "geometry_consistency": {"indices": flat["gc_indices"], "flows": [flat["gc_flows0"], flat["gc_flows1"]],
+                                     "masks": [flat["gc_masks0"], flat["gc_masks1"]]}}
+    if "ts_indices" in flat:
+        meta["temporal_smoothness"] = {"indices": flat["ts_indices"], "flows": [flat[f"ts_flows{d}"] for d in range(4)],
+                                       "masks": [flat[f"ts_masks{d}"] for d in range(4)], "valid": flat["ts_valid"]}
+    for k in ("scales", "warp", "depth_orig"):
+        if k in flat:
+            meta[k] = flat[k]
+    return flat["images"], meta
+
+
+_hip = None
+
+
+def _hip_runtime():
+    """The HIP runtime this process already holds (libcvd_hip.so's dependency), for the few raw device buffers the numpy mirror
+    of a `*_device` entry point needs (Solver.dataset_batch(device_entry=True)); torch callers use torch's tensors instead."""
+    global _hip
+    if _hip is None:
+        load_library()
+        path = None
+        with open("/proc/self/maps") as f:
+            for line in f:
+                if "libamdhip64" in line:
+                    path = line.split()[-1]
+                    break
+        if path is None:
+            raise RuntimeError("the HIP runtime is not loaded in this process")
+        lib = C.CDLL(path)
+        lib.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        lib.hipFree.argtypes = [C.c_void_p]
+        lib.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        _hip = lib
+    return _hip
 
 
 def adam_record(step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
@@ -285,7 +404,7 @@ EXPORTED_SYMBOLS = [
     "cvd_reset_poses", "cvd_reset_depth_xforms", "cvd_reset_spatial_xforms", "cvd_grid_xform_split",
     "cvd_get_xform_desc", "cvd_num_xform_params", "cvd_get_xform_params", "cvd_set_xform_params",
     "cvd_get_pose_params", "cvd_set_pose_params", "cvd_block_size", "cvd_normalize_depth", "cvd_pose_optimization",
-    "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_scene_flow_loss", "cvd_scene_flow_loss_device", "cvd_spatial_losses", "cvd_spatial_losses_device", "cvd_param_chunk", "cvd_parameter_l1", "cvd_parameter_l1_device", "cvd_param_step", "cvd_param_step_device", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
+    "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_scene_flow_loss", "cvd_scene_flow_loss_device", "cvd_spatial_losses", "cvd_spatial_losses_device", "cvd_param_chunk", "cvd_parameter_l1", "cvd_parameter_l1_device", "cvd_param_step", "cvd_param_step_device", "cvd_dataset_create", "cvd_dataset_clear", "cvd_dataset_set_colors", "cvd_dataset_set_flows", "cvd_dataset_set_depth_orig", "cvd_dataset_set_cameras", "cvd_dataset_set_xforms", "cvd_dataset_set_maps", "cvd_dataset_batch", "cvd_dataset_batch_device", "cvd_dataset_bad_indices", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
     "cvd_get_kernel_times", "cvd_get_comm_times", "cvd_get_dense_times", "cvd_set_kernel_timing", "cvd_num_active_constraints", "cvd_coarse_debug", "cvd_temporal_debug", "cvd_path_info", "cvd_abi_revision",
     "cvd_block_inverse_debug", "cvd_dense_inverse_debug", "cvd_epipolar_debug", "cvd_flow_masks_debug",
 ]
@@ -648,6 +767,146 @@ class Solver(Binding):
         self._check(self._fn("param_step")(self._h, C.byref(desc), ip(offsets), ip(counts), C.c_int64(p.size), vp(p), vp(g), vp(m),
                                            vp(v), rec, ms if timing else None))
         return (p, m, v, ms[0]) if timing else (p, m, v)
+
+    # -- fine-tuning batches from a device-resident dataset (include/cvd_hip.h cvd_dataset_*) ---------------
+    def dataset_create(self, num_frames, height, width, pair_frames, samples, temporal, has_depth_orig=False,
+                       neighbor_rule_frames=0, desc=None):
+        """Allocates the store and builds its sample table: pair_frames [Q, 2] directed pairs (slot = position), samples [S, 2].
+        desc: a cvd_dataset_desc to pass as it is (tests)."""
+        import numpy as np
+        pf = np.ascontiguousarray(pair_frames, dtype=np.int32).reshape(-1, 2)
+        sm = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, 2)
+        if desc is None:
+            desc = dataset_desc(num_frames, height, width, pf.shape[0], sm.shape[0], temporal, has_depth_orig, neighbor_rule_frames)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._fn("dataset_create")(self._h, C.byref(desc), ip(pf), ip(sm)))
+        self._dataset = {"F": int(num_frames), "H": int(height), "W": int(width), "Q": pf.shape[0], "S": sm.shape[0],
+                         "N": 6 if temporal else 2, "depth_orig": bool(has_depth_orig), "scale_mode": 0, "warp": False}
+
+    def dataset_clear(self):
+        self._check(self._fn("dataset_clear")(self._h))
+        self._dataset = None
+
+    def _dataset_info(self):
+        info = getattr(self, "_dataset", None)
+        if info is None:   # (the library names the missing store)
+            info = {"F": 0, "H": 1, "W": 1, "Q": 0, "S": 0, "N": 2, "depth_orig": False, "scale_mode": 0, "warp": False}
+        return info
+
+    def dataset_set_colors(self, first, hwc3):
+        """Colour of frames first, first + 1, ...: float32 [n, H, W, 3], in the channel order the batch returns."""
+        import numpy as np
+        d = self._dataset_info()
+        a = np.ascontiguousarray(hwc3, dtype=np.float32)
+        assert a.ndim == 4 and a.shape[1:] == (d["H"], d["W"], 3), a.shape
+        self._check(self._fn("dataset_set_colors")(self._h, C.c_int32(first), C.c_int32(a.shape[0]), a.ctypes.data_as(C.c_void_p)))
+
+    def dataset_set_flows(self, first, flow, mask):
+        """Flow float32 [n, H, W, 2] and mask uint8 [n, H, W] (file layout) of pair slots first, first + 1, ..."""
+        import numpy as np
+        d = self._dataset_info()
+        fl = np.ascontiguousarray(flow, dtype=np.float32)
+        mk = np.ascontiguousarray(mask, dtype=np.uint8)
+        assert fl.ndim == 4 and fl.shape[1:] == (d["H"], d["W"], 2) and mk.shape == fl.shape[:3], (fl.shape, mk.shape)
+        self._check(self._fn("dataset_set_flows")(self._h, C.c_int32(first), C.c_int32(fl.shape[0]), fl.ctypes.data_as(C.c_void_p),
+                                                  mk.ctypes.data_as(C.c_void_p)))
+
+    def dataset_set_depth_orig(self, first, depth):
+        """Initial depth (1 / disparity) float32 [n, H, W] of frames first, first + 1, ..."""
+        import numpy as np
+        d = self._dataset_info()
+        a = np.ascontiguousarray(depth, dtype=np.float32)
+        assert a.ndim == 3 and a.shape[1:] == (d["H"], d["W"]), a.shape
+        self._check(self._fn("dataset_set_depth_orig")(self._h, C.c_int32(first), C.c_int32(a.shape[0]), a.ctypes.data_as(C.c_void_p)))
+
+    def dataset_set_cameras(self, extrinsics, intrinsics):
+        import numpy as np
+        d = self._dataset_info()
+        ext = np.ascontiguousarray(extrinsics, dtype=np.float32)
+        intr = np.ascontiguousarray(intrinsics, dtype=np.float32)
+        assert ext.shape == (d["F"], 3, 4) and intr.shape == (d["F"], 4), (ext.shape, intr.shape)
+        self._check(self._fn("dataset_set_cameras")(self._h, ext.ctypes.data_as(C.c_void_p), intr.ctypes.data_as(C.c_void_p)))
+
+    def dataset_set_xforms(self, depth_desc, depth_params, spatial_desc, spatial_params):
+        """The store's scale and warp tables from the transforms' parameters, on the device: depth_params [F, nD], spatial_params
+        [F, nS] float64 (None or empty where the transform has none)."""
+        import numpy as np
+        d = self._dataset_info()
+        conv = lambda p: None if p is None or np.size(p) == 0 else np.ascontiguousarray(p, dtype=np.float64).reshape(d["F"], -1)
+        dp, sp = conv(depth_params), conv(spatial_params)
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        self._check(self._fn("dataset_set_xforms")(self._h, C.byref(depth_desc), vp(dp), C.byref(spatial_desc), vp(sp)))
+        d["scale_mode"] = 2 if int(depth_desc.depth_type) == 3 else 1
+        d["warp"] = True
+
+    def dataset_set_maps(self, scales=None, warp=None):
+        """The same tables from host arrays: scales float32 [F, H, W] (maps) or F values (anything that reshapes to [F]), warp
+        float32 [F, 2, H, W]; None = not set."""
+        import numpy as np
+        d = self._dataset_info()
+        sc = wp = None
+        is_map = False
+        if scales is not None:
+            sc = np.ascontiguousarray(scales, dtype=np.float32)
+            is_map = sc.size != d["F"]
+            assert sc.size == (d["F"] * d["H"] * d["W"] if is_map else d["F"]), sc.shape
+        if warp is not None:
+            wp = np.ascontiguousarray(warp, dtype=np.float32)
+            assert wp.shape == (d["F"], 2, d["H"], d["W"]), wp.shape
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        self._check(self._fn("dataset_set_maps")(self._h, vp(sc), C.c_int32(int(is_map)), vp(wp)))
+        d["scale_mode"] = 0 if sc is None else (2 if is_map else 1)
+        d["warp"] = wp is not None
+
+    def dataset_batch(self, indices, timing=False, device_entry=False, nested=True):
+        """One batch as numpy arrays: (images, metadata) with the reference's nesting (nested=False: the flat dict of
+        dataset_batch_shapes), plus the kernel ms when timing.  device_entry=True goes through cvd_dataset_batch_device with
+        indices and outputs in raw device buffers, on the null stream (tests: that entry point checks no index)."""
+        import numpy as np
+        d = self._dataset_info()
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        B = idx.size
+        shapes = dataset_batch_shapes(max(B, 1), d["N"], d["H"], d["W"], d["scale_mode"], d["warp"], d["depth_orig"])
+        flat = {k: np.zeros(shape, dtype) for k, (shape, dtype) in shapes.items()}
+        ip = idx.ctypes.data_as(C.POINTER(C.c_int64))
+        if not device_entry:
+            ms = (C.c_double * 1)()
+            out = dataset_batch_out({k: a.ctypes.data for k, a in flat.items()})
+            self._check(self._fn("dataset_batch")(self._h, C.c_int32(B), ip, C.byref(out), ms if timing else None))
+        else:
+            if timing:
+                raise ValueError("dataset_batch: the device entry point is not timed")
+            hip = _hip_runtime()
+            bufs = {}
+
+            def alloc(name, nbytes):
+                p = C.c_void_p()
+                if hip.hipMalloc(C.byref(p), max(nbytes, 1)) != 0:
+                    raise RuntimeError("hipMalloc failed")
+                bufs[name] = p
+                return p
+            try:
+                dev_idx = alloc("indices", idx.nbytes)
+                if hip.hipMemcpy(dev_idx, idx.ctypes.data_as(C.c_void_p), idx.nbytes, 1) != 0:
+                    raise RuntimeError("hipMemcpy failed")
+                out = dataset_batch_out({k: alloc(k, a.nbytes).value for k, a in flat.items()})
+                self._check(self._fn("dataset_batch_device")(self._h, C.c_int32(B), C.cast(dev_idx, C.POINTER(C.c_int64)), C.byref(out),
+                                                             None))
+                for k, a in flat.items():   # (a blocking copy on the null stream: behind the launch)
+                    if hip.hipMemcpy(a.ctypes.data_as(C.c_void_p), bufs[k], a.nbytes, 2) != 0:
+                        raise RuntimeError("hipMemcpy failed")
+            finally:
+                for p in bufs.values():
+                    hip.hipFree(p)
+        flat = {k: a[:B] for k, a in flat.items()}
+        res = nest_batch(flat) if nested else (flat,)
+        return res + (ms[0],) if timing else (res if nested else res[0])
+
+    def dataset_bad_indices(self):
+        """Indices the device entry point has clamped since dataset_create (waits for the device)."""
+        n = C.c_int64(0)
+        self._check(self._fn("dataset_bad_indices")(self._h, C.byref(n)))
+        return int(n.value)
 
     def num_active_constraints(self):
         return int(self._lib.cvd_num_active_constraints(self._h))

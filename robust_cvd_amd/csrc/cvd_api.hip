@@ -790,6 +790,38 @@ int32_t cvd_param_step_device(cvd_handle* h, const cvd_param_desc* desc, void* c
                               void* const* v, const int64_t* counts, const cvd_param_record* records, void* stream) {
   CVD_TRY(h, paramStepDevice(h, desc, p, g, m, v, counts, records, static_cast<hipStream_t>(stream)));
 }
+int32_t cvd_dataset_create(cvd_handle* h, const cvd_dataset_desc* desc, const int32_t* pair_frames, const int32_t* samples) {
+  CVD_TRY(h, datasetCreate(h, desc, pair_frames, samples));
+}
+int32_t cvd_dataset_clear(cvd_handle* h) { CVD_TRY(h, datasetClear(h)); }
+int32_t cvd_dataset_set_colors(cvd_handle* h, int32_t first, int32_t count, const float* hwc3) {
+  CVD_TRY(h, datasetSetColors(h, first, count, hwc3));
+}
+int32_t cvd_dataset_set_flows(cvd_handle* h, int32_t first, int32_t count, const float* flow, const uint8_t* mask) {
+  CVD_TRY(h, datasetSetFlows(h, first, count, flow, mask));
+}
+int32_t cvd_dataset_set_depth_orig(cvd_handle* h, int32_t first, int32_t count, const float* depth) {
+  CVD_TRY(h, datasetSetDepthOrig(h, first, count, depth));
+}
+int32_t cvd_dataset_set_cameras(cvd_handle* h, const float* extrinsics, const float* intrinsics) {
+  CVD_TRY(h, datasetSetCameras(h, extrinsics, intrinsics));
+}
+int32_t cvd_dataset_set_xforms(cvd_handle* h, const cvd_xform_desc* depth_desc, const double* depth_params,
+                               const cvd_xform_desc* spatial_desc, const double* spatial_params) {
+  CVD_TRY(h, datasetSetXforms(h, depth_desc, depth_params, spatial_desc, spatial_params));
+}
+int32_t cvd_dataset_set_maps(cvd_handle* h, const float* scales, int32_t scale_is_map, const float* warp) {
+  CVD_TRY(h, datasetSetMaps(h, scales, scale_is_map, warp));
+}
+int32_t cvd_dataset_batch_device(cvd_handle* h, int32_t batch_size, const int64_t* indices, const cvd_dataset_batch_out* out,
+                                 void* stream) {
+  CVD_TRY(h, datasetBatchDevice(h, batch_size, indices, out, static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_dataset_batch(cvd_handle* h, int32_t batch_size, const int64_t* indices, const cvd_dataset_batch_out* out,
+                          double* kernel_ms) {
+  CVD_TRY(h, datasetBatch(h, batch_size, indices, out, kernel_ms));
+}
+int32_t cvd_dataset_bad_indices(cvd_handle* h, int64_t* count) { CVD_TRY(h, *count = datasetBadIndices(h)); }
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {

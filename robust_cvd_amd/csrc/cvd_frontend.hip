@@ -1,6 +1,6 @@
 // cvd_frontend.hip -- the steps either side of the solve: constraint sampling, epipolar RANSAC flags, image operators, dense
 // consumers, flow-guided and bilateral filters, feature tracks, flow consistency masks, the fine-tuning consistency,
-// scene-flow and spatial losses, the parameter regulariser and the optimizer step.  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
+// scene-flow and spatial losses, the parameter regulariser and the optimizer step, the fine-tuning batches.  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
 // through a pointer to the incomplete type).
 #include "cvd_host.h"
 #include "cvd_dense.h"
@@ -16,6 +16,7 @@
 #include "cvd_sceneflow.h"
 #include "cvd_spatial.h"
 #include "cvd_paramstep.h"
+#include "cvd_batch.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -49,6 +50,31 @@ struct ParamTableState {
     for (auto& e : copied)
       if (e) (void)hipEventDestroy(e);
     if (staging) (void)hipHostFree(staging);
+  }
+};
+
+// The device-resident fine-tuning dataset of cvd_batch.h (cvd_dataset_create .. cvd_dataset_clear): images in their file layout,
+// cameras, per-frame tables, the sample table and the word that counts out-of-range indices of the device entry point.
+struct DatasetState {
+  bool created = false;
+  int F = 0, H = 0, W = 0, Q = 0, S = 0, N = 2;
+  bool hasDepthOrig = false;
+  int scaleMode = 0;      // 0: no scales, 1: [F] scalars, 2: [F][H][W] maps
+  bool haveWarp = false;
+  DevBuf<float> color, flow, depthOrig, ext, intr, scales, warp;
+  DevBuf<unsigned char> mask;
+  DevBuf<DatasetSample> samples;
+  DevBuf<unsigned int> bad;
+  DevBuf<double> params;              // staging of cvd_dataset_set_xforms
+  DevBuf<unsigned char> stage;        // staging of the host-array batch: indices, then every output
+  size_t npx() const { return static_cast<size_t>(H) * W; }
+  void clear() {
+    for (DevBuf<float>* b : {&color, &flow, &depthOrig, &ext, &intr, &scales, &warp}) b->release();
+    mask.release(); samples.release(); bad.release(); params.release(); stage.release();
+    created = false;
+    F = H = W = Q = S = 0; N = 2;
+    hasDepthOrig = haveWarp = false;
+    scaleMode = 0;
   }
 };
 
@@ -93,6 +119,7 @@ struct Frontend {
   // cvd_paramstep.h: the tables of the regulariser [0] and of the step [1] per precision, the regulariser's per-workgroup sums
   ParamTableState paramTable[2][2];
   DevBuf<double> dParamSlab;
+  DatasetState dataset;      // cvd_batch.h
   // staging of the three losses' host-array entry points, which run to completion on the handle's stream one at a time and so
   // share it (runLossOnHostArrays): real inputs in the loss's own order, pair and neighbour frames, scalar results, gradient, maps
   DevBuf<unsigned char> dLossIn[kLossMaxArrays], dLossGrad, dLossMaps;
@@ -1707,6 +1734,376 @@ void paramStep(cvd_handle* h, const cvd_param_desc* d, const int64_t* offsets, c
 }
 
 long long paramChunkElements() { return kParamChunk; }
+
+// ---- fine-tuning batches from a device-resident store (reference loaders/video_dataset.py; cvd_batch.h) ---------------------------
+namespace {
+const char* kDsOp = "dataset";
+
+DatasetState& datasetStore(cvd_handle* h, const char* what) {
+  DatasetState& ds = h->frontend->dataset;
+  if (!ds.created) throw std::runtime_error(fmt("%s %s: no store (cvd_dataset_create first)", kDsOp, what));
+  return ds;
+}
+
+void checkDatasetRange(const char* what, int first, int count, int total, const char* unit) {
+  if (first < 0 || count < 0 || first > total || count > total - first)
+    throw std::runtime_error(fmt("%s %s: %s [%d, %d + %d) leave the store's %d", kDsOp, what, unit, first, first, count, total));
+}
+
+// the gather-relevant part of a Layout from the two transform descriptors (makeLayout's statement of it, without a video)
+Layout datasetLayout(int F, const cvd_xform_desc& dd, const cvd_xform_desc& sd) {
+  Layout L{};
+  L.F = F;
+  L.depthType = dd.depth_type;
+  L.N = xformBlockSize(dd);
+  L.cubic = dd.cubic_interpolation ? 1 : 0;
+  L.gx = dd.depth_type == CVD_DEPTH_GRID ? dd.grid_size[0] : 1;
+  L.gy = dd.depth_type == CVD_DEPTH_GRID ? dd.grid_size[1] : 1;
+  L.maxcx = std::nextafter(static_cast<double>(L.gx - 1), 0.0);
+  L.maxcy = std::nextafter(static_cast<double>(L.gy - 1), 0.0);
+  L.gz = 1;
+  L.maxcz = 0.0;
+  L.dispMin = 0.0;
+  L.dispInterval = 1.0;
+  L.nD = xformNumBlocks(dd) * xformBlockSize(dd);
+  L.spatialType = sd.spatial_type;
+  L.sgx = sd.grid_size[0];
+  L.sgy = sd.grid_size[1];
+  L.smaxcx = std::nextafter(static_cast<double>(L.sgx - 1), 0.0);
+  L.smaxcy = std::nextafter(static_cast<double>(L.sgy - 1), 0.0);
+  L.nS = xformNumBlocks(sd) * xformBlockSize(sd);
+  L.B = 7 + L.nD + L.nS;
+  return L;
+}
+
+// the outputs of a batch in the order of cvd_dataset_batch_out's members: kBatchRequired that the shape of the store decides, then
+// the optional scales, warp and depth_orig
+constexpr int kBatchRequired = 18, kBatchOutputs = 21;
+const char* const kBatchOutNames[kBatchOutputs] = {"images", "extrinsics", "intrinsics", "gc_indices", "gc_flows[0]", "gc_flows[1]",
+                                                   "gc_masks[0]", "gc_masks[1]", "ts_indices", "ts_flows[0]", "ts_flows[1]", "ts_flows[2]",
+                                                   "ts_flows[3]", "ts_masks[0]", "ts_masks[1]", "ts_masks[2]", "ts_masks[3]", "ts_valid",
+                                                   "scales", "warp", "depth_orig"};
+void batchOutMembers(const cvd_dataset_batch_out* o, void** list) {
+  void* m[kBatchOutputs] = {o->images, o->extrinsics, o->intrinsics, o->gc_indices, o->gc_flows[0], o->gc_flows[1], o->gc_masks[0],
+                            o->gc_masks[1], o->ts_indices, o->ts_flows[0], o->ts_flows[1], o->ts_flows[2], o->ts_flows[3],
+                            o->ts_masks[0], o->ts_masks[1], o->ts_masks[2], o->ts_masks[3], o->ts_valid, o->scales, o->warp,
+                            o->depth_orig};
+  std::copy(m, m + kBatchOutputs, list);
+}
+
+// checks a batch request against the store (before any device work); fills the bytes of every output (0: not written)
+void checkBatch(const DatasetState& ds, const char* what, int B, const int64_t* indices, const cvd_dataset_batch_out* o,
+                size_t* bytes) {
+  if (B < 1) throw std::runtime_error(fmt("%s %s: batch size must be >= 1 (got %d)", kDsOp, what, B));
+  if (ds.S < 1) throw std::runtime_error(fmt("%s %s: the store has no samples", kDsOp, what));
+  if (!indices) throw std::runtime_error(fmt("%s %s: null indices", kDsOp, what));
+  if (!o) throw std::runtime_error(fmt("%s %s: null out", kDsOp, what));
+  if (o->struct_size != CVD_STRUCT_STAMP(cvd_dataset_batch_out))
+    throw std::runtime_error(fmt("%s %s: out.struct_size %llu is not this library's %llu (built against another revision of cvd_hip.h)",
+                                 kDsOp, what, static_cast<unsigned long long>(o->struct_size),
+                                 static_cast<unsigned long long>(CVD_STRUCT_STAMP(cvd_dataset_batch_out))));
+  const size_t npx = ds.npx(), b = static_cast<size_t>(B), N = static_cast<size_t>(ds.N), f = sizeof(float);
+  const bool ts = ds.N > 2;
+  const size_t flowB = b * 2 * npx * f, maskB = b * npx * f;
+  const size_t sizes[kBatchRequired] = {b * N * 3 * npx * f, b * N * 12 * f, b * N * 4 * f, b * 2 * sizeof(int64_t), flowB, flowB, maskB, maskB,
+                            ts ? b * 4 * sizeof(int64_t) : 0, ts ? flowB : 0, ts ? flowB : 0, ts ? flowB : 0, ts ? flowB : 0,
+                            ts ? maskB : 0, ts ? maskB : 0, ts ? maskB : 0, ts ? maskB : 0, ts ? b * 2 * f : 0};
+  void* members[kBatchOutputs];
+  batchOutMembers(o, members);
+  for (int k = 0; k < kBatchRequired; ++k) {
+    bytes[k] = sizes[k];
+    if (sizes[k] && !members[k]) throw std::runtime_error(fmt("%s %s: null output %s", kDsOp, what, kBatchOutNames[k]));
+  }
+  if (o->scales && ds.scaleMode == 0) throw std::runtime_error(fmt("%s %s: scales asked for, but no scale table is set", kDsOp, what));
+  if (o->warp && !ds.haveWarp) throw std::runtime_error(fmt("%s %s: warp asked for, but no warp table is set", kDsOp, what));
+  if (o->depth_orig && !ds.hasDepthOrig)
+    throw std::runtime_error(fmt("%s %s: depth_orig asked for, but the store was created without it", kDsOp, what));
+  bytes[18] = o->scales ? b * N * (ds.scaleMode == 2 ? npx : 1) * f : 0;
+  bytes[19] = o->warp ? b * N * 2 * npx * f : 0;
+  bytes[20] = o->depth_orig ? b * 2 * npx * f : 0;
+}
+
+// one launch for the whole batch, on s; `o` holds DEVICE addresses
+void launchDatasetBatch(DatasetState& ds, int B, const long long* indices, const cvd_dataset_batch_out& o, hipStream_t s) {
+  DatasetStore st{ds.color.p, ds.flow.p, ds.mask.p, ds.hasDepthOrig ? ds.depthOrig.p : nullptr, ds.ext.p, ds.intr.p,
+                  ds.scaleMode ? ds.scales.p : nullptr, ds.haveWarp ? ds.warp.p : nullptr, ds.samples.p, ds.S,
+                  static_cast<int>(ds.npx()), ds.N, ds.scaleMode};
+  DatasetBatch out{};
+  auto fp = [](void* p) { return static_cast<float*>(p); };
+  out.images = fp(o.images); out.ext = fp(o.extrinsics); out.intr = fp(o.intrinsics);
+  out.gcIndices = static_cast<long long*>(o.gc_indices);
+  out.tsIndices = static_cast<long long*>(o.ts_indices);
+  for (int d = 0; d < 2; ++d) { out.gcFlow[d] = fp(o.gc_flows[d]); out.gcMask[d] = fp(o.gc_masks[d]); }
+  for (int d = 0; d < 4; ++d) { out.tsFlow[d] = fp(o.ts_flows[d]); out.tsMask[d] = fp(o.ts_masks[d]); }
+  out.tsValid = fp(o.ts_valid); out.scales = fp(o.scales); out.warp = fp(o.warp); out.depthOrig = fp(o.depth_orig);
+  const int ts = ds.N > 2 ? 4 : 0;
+  out.segGcFlow = ds.N;
+  out.segGcMask = out.segGcFlow + 2;
+  out.segTsFlow = out.segGcMask + 2;
+  out.segTsMask = out.segTsFlow + ts;
+  out.segScale = out.segTsMask + ts;
+  out.segWarp = out.segScale + (o.scales && ds.scaleMode == 2 ? ds.N : 0);
+  out.segDepth = out.segWarp + (o.warp ? ds.N : 0);
+  out.segSmall = out.segDepth + (o.depth_orig ? 2 : 0);
+  const bool vec = ds.npx() % 4 == 0;   // every plane then starts 16-byte aligned from an aligned base
+  const size_t lanes = vec ? ds.npx() / 4 : ds.npx();
+  const dim3 grid(static_cast<unsigned>((lanes + kBatchThreads - 1) / kBatchThreads), out.segSmall + 1, B);
+  if (vec) hipLaunchKernelGGL((k_dataset_batch<true>), grid, dim3(kBatchThreads), 0, s, st, out, indices, B, ds.bad.p);
+  else hipLaunchKernelGGL((k_dataset_batch<false>), grid, dim3(kBatchThreads), 0, s, st, out, indices, B, ds.bad.p);
+  HIP_CHECK(hipGetLastError());
+}
+}  // namespace
+
+// Builds the store and its sample table (reference loaders/video_dataset.py:223-256, 309-367: which flows a sample reads, the
+// rule 0 < k < num_frames - 1 for real neighbours, the clamped neighbour indices).  pairFrames [Q][2]: the directed pairs whose
+// flow and mask the store holds, slot = position; samples [S][2].
+void datasetCreate(cvd_handle* h, const cvd_dataset_desc* d, const int32_t* pairFrames, const int32_t* samples) {
+  const char* what = "create";
+  if (!d) throw std::runtime_error(fmt("%s %s: null desc", kDsOp, what));
+  if (d->struct_size != CVD_STRUCT_STAMP(cvd_dataset_desc))
+    throw std::runtime_error(fmt("%s %s: desc.struct_size %llu is not this library's %llu (built against another revision of cvd_hip.h)",
+                                 kDsOp, what, static_cast<unsigned long long>(d->struct_size),
+                                 static_cast<unsigned long long>(CVD_STRUCT_STAMP(cvd_dataset_desc))));
+  const int F = d->num_frames, Q = d->num_pairs, S = d->num_samples;
+  if (F < 1 || d->height < 1 || d->width < 1)
+    throw std::runtime_error(fmt("%s %s: invalid shape (%d frames of %d x %d)", kDsOp, what, F, d->height, d->width));
+  if (static_cast<long long>(d->height) * d->width > (1ll << 30)) throw std::runtime_error(fmt("%s %s: frame too large", kDsOp, what));
+  if (Q < 0 || S < 0) throw std::runtime_error(fmt("%s %s: negative count (%d pairs, %d samples)", kDsOp, what, Q, S));
+  if ((Q && !pairFrames) || (S && !samples)) throw std::runtime_error(fmt("%s %s: null pair or sample list", kDsOp, what));
+  if (d->temporal != 0 && d->temporal != 1) throw std::runtime_error(fmt("%s %s: temporal must be 0 or 1 (got %d)", kDsOp, what, d->temporal));
+  const int ruleF = d->neighbor_rule_frames > 0 ? d->neighbor_rule_frames : F;
+  if (ruleF > F)
+    throw std::runtime_error(fmt("%s %s: neighbor_rule_frames %d exceeds the store's %d frames", kDsOp, what, ruleF, F));
+  std::map<std::pair<int, int>, int> slotOf;
+  for (int q = 0; q < Q; ++q) {
+    const int a = pairFrames[2 * q], b = pairFrames[2 * q + 1];
+    for (int f : {a, b})
+      if (f < 0 || f >= F) throw std::runtime_error(fmt("%s %s: frame %d of pair %d is out of range [0, %d)", kDsOp, what, f, q, F));
+    if (!slotOf.emplace(std::make_pair(a, b), q).second)
+      throw std::runtime_error(fmt("%s %s: directed pair (%d, %d) is listed twice", kDsOp, what, a, b));
+  }
+  std::vector<DatasetSample> table(S);
+  for (int i = 0; i < S; ++i) {
+    const int ab[2] = {samples[2 * i], samples[2 * i + 1]};
+    DatasetSample& sm = table[i];
+    for (int k = 0; k < 2; ++k)
+      if (ab[k] < 0 || ab[k] >= F)
+        throw std::runtime_error(fmt("%s %s: frame %d of sample %d is out of range [0, %d)", kDsOp, what, ab[k], i, F));
+    for (int k = 0; k < 2; ++k) {
+      const auto it = slotOf.find({ab[k], ab[1 - k]});
+      if (it == slotOf.end())
+        throw std::runtime_error(fmt("%s %s: sample %d (%d, %d): direction (%d, %d) is not in the pair list", kDsOp, what, i, ab[0],
+                                     ab[1], ab[k], ab[1 - k]));
+      sm.frame[k] = ab[k];
+      sm.slot[k] = it->second;
+    }
+    for (int k = 0; k < 2; ++k) {
+      const bool interior = 0 < ab[k] && ab[k] < ruleF - 1;
+      sm.valid[k] = interior ? 1 : 0;
+      for (int j = 0; j < 2; ++j) {
+        const int nb = ab[k] + (j ? 1 : -1);
+        sm.frame[2 + 2 * k + j] = std::max(0, std::min(nb, ruleF - 1));
+        sm.slot[2 + 2 * k + j] = -1;
+        if (d->temporal && interior) {
+          const auto it = slotOf.find({ab[k], nb});
+          if (it == slotOf.end())
+            throw std::runtime_error(fmt("%s %s: temporal sample %d: neighbour flow (%d, %d) of interior frame %d is not in the pair list",
+                                         kDsOp, what, i, ab[k], nb, ab[k]));
+          sm.slot[2 + 2 * k + j] = it->second;
+        }
+      }
+    }
+  }
+  // (validated: device work from here)
+  DatasetState& ds = h->frontend->dataset;
+  hipStream_t s = h->stream;
+  HIP_CHECK(hipDeviceSynchronize());   // a batch of the previous store may be in flight on a caller's stream
+  ds.clear();
+  ds.F = F; ds.H = d->height; ds.W = d->width; ds.Q = Q; ds.S = S; ds.N = d->temporal ? 6 : 2;
+  ds.hasDepthOrig = d->has_depth_orig != 0;
+  const size_t npx = ds.npx();
+  auto zeroed = [&](auto& buf, size_t n) {
+    buf.ensure(std::max<size_t>(n, 1));
+    HIP_CHECK(hipMemsetAsync(buf.p, 0, std::max<size_t>(n, 1) * sizeof(*buf.p), s));
+  };
+  zeroed(ds.color, static_cast<size_t>(F) * npx * 3);
+  zeroed(ds.flow, static_cast<size_t>(Q) * npx * 2);
+  zeroed(ds.mask, static_cast<size_t>(Q) * npx);
+  if (ds.hasDepthOrig) zeroed(ds.depthOrig, static_cast<size_t>(F) * npx);
+  zeroed(ds.ext, static_cast<size_t>(F) * 12);
+  zeroed(ds.intr, static_cast<size_t>(F) * 4);
+  zeroed(ds.bad, 1);
+  ds.samples.upload(table.data(), table.size(), s);
+  HIP_CHECK(hipStreamSynchronize(s));
+  ds.created = true;
+}
+
+void datasetClear(cvd_handle* h) {
+  HIP_CHECK(hipDeviceSynchronize());
+  h->frontend->dataset.clear();
+}
+
+// host f32 [count][H][W][3], in the channel order the batch returns (reference load_color, loaders/video_dataset.py:49-60)
+void datasetSetColors(cvd_handle* h, int first, int count, const float* hwc3) {
+  DatasetState& ds = datasetStore(h, "set_colors");
+  checkDatasetRange("set_colors", first, count, ds.F, "frames");
+  if (count == 0) return;
+  if (!hwc3) throw std::runtime_error(fmt("%s set_colors: null input", kDsOp));
+  HIP_CHECK(hipMemcpyAsync(ds.color.p + static_cast<size_t>(first) * ds.npx() * 3, hwc3, static_cast<size_t>(count) * ds.npx() * 3 * sizeof(float),
+                           hipMemcpyHostToDevice, h->stream));
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+}
+
+// file layout: flow f32 [count][H][W][2], mask u8 [count][H][W] (reference load_flow / load_mask, loaders/video_dataset.py:63-78)
+void datasetSetFlows(cvd_handle* h, int first, int count, const float* flow, const uint8_t* mask) {
+  DatasetState& ds = datasetStore(h, "set_flows");
+  checkDatasetRange("set_flows", first, count, ds.Q, "pairs");
+  if (count == 0) return;
+  if (!flow || !mask) throw std::runtime_error(fmt("%s set_flows: null input", kDsOp));
+  const size_t npx = ds.npx();
+  HIP_CHECK(hipMemcpyAsync(ds.flow.p + static_cast<size_t>(first) * npx * 2, flow, static_cast<size_t>(count) * npx * 2 * sizeof(float),
+                           hipMemcpyHostToDevice, h->stream));
+  HIP_CHECK(hipMemcpyAsync(ds.mask.p + static_cast<size_t>(first) * npx, mask, static_cast<size_t>(count) * npx, hipMemcpyHostToDevice, h->stream));
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+}
+
+// f32 [count][H][W], already 1 / disparity (reference depth_fine_tuning.py:457-471)
+void datasetSetDepthOrig(cvd_handle* h, int first, int count, const float* depth) {
+  DatasetState& ds = datasetStore(h, "set_depth_orig");
+  if (!ds.hasDepthOrig) throw std::runtime_error(fmt("%s set_depth_orig: the store was created without depth_orig", kDsOp));
+  checkDatasetRange("set_depth_orig", first, count, ds.F, "frames");
+  if (count == 0) return;
+  if (!depth) throw std::runtime_error(fmt("%s set_depth_orig: null input", kDsOp));
+  HIP_CHECK(hipMemcpyAsync(ds.depthOrig.p + static_cast<size_t>(first) * ds.npx(), depth, static_cast<size_t>(count) * ds.npx() * sizeof(float),
+                           hipMemcpyHostToDevice, h->stream));
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+}
+
+// f32 [F][3][4] and [F][4], as update_poses forms them (reference loaders/video_dataset.py:177-189)
+void datasetSetCameras(cvd_handle* h, const float* ext, const float* intr) {
+  DatasetState& ds = datasetStore(h, "set_cameras");
+  if (!ext || !intr) throw std::runtime_error(fmt("%s set_cameras: null input", kDsOp));
+  ds.ext.upload(ext, static_cast<size_t>(ds.F) * 12, h->stream);
+  ds.intr.upload(intr, static_cast<size_t>(ds.F) * 4, h->stream);
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+}
+
+// The per-frame tables from the transforms' parameters, one launch per table (reference loaders/video_dataset.py:191-217).
+void datasetSetXforms(cvd_handle* h, const cvd_xform_desc* dd, const double* dparams, const cvd_xform_desc* sd, const double* sparams) {
+  DatasetState& ds = datasetStore(h, "set_xforms");
+  if (!dd || !sd) throw std::runtime_error(fmt("%s set_xforms: null descriptor", kDsOp));
+  if (dd->type != CVD_XFORM_DEPTH || sd->type != CVD_XFORM_SPATIAL)
+    throw std::runtime_error(fmt("%s set_xforms: a depth and a spatial descriptor are expected, in this order", kDsOp));
+  // what the reference refuses (:195-217), before any device work
+  if (dd->depth_type != CVD_DEPTH_IDENTITY && dd->value_xform != CVD_VALUE_SCALE)
+    throw std::runtime_error("We only support scale-based transforms at the moment.");
+  if (dd->depth_type != CVD_DEPTH_IDENTITY && dd->depth_type != CVD_DEPTH_GLOBAL && dd->depth_type != CVD_DEPTH_GRID)
+    throw std::runtime_error(fmt("Unsupported depth transform type '%d'.", dd->depth_type));
+  if (sd->spatial_type < CVD_SPATIAL_IDENTITY || sd->spatial_type > CVD_SPATIAL_BICUBIC_GRID)
+    throw std::runtime_error(fmt("Unsupported spatial transform type '%d'.", sd->spatial_type));
+  if (dd->depth_type == CVD_DEPTH_GRID && dd->grid_size[2] > 1)
+    throw std::runtime_error(fmt("%s set_xforms: a depth-wise grid (grid z = %d) needs the source depth for its map: evaluate it on the "
+                                 "host and use cvd_dataset_set_maps", kDsOp, dd->grid_size[2]));
+  if (ds.W < 2 || ds.H < 2) throw std::runtime_error(fmt("%s set_xforms: raster too small", kDsOp));
+  const Layout L = datasetLayout(ds.F, *dd, *sd);   // (throws what the transforms' own constructors throw for a bad grid)
+  if ((L.nD && !dparams) || (L.nS && !sparams)) throw std::runtime_error(fmt("%s set_xforms: null parameters", kDsOp));
+  int KD, KS;
+  tapCounts(L, KD, KS);
+  hipStream_t s = h->stream;
+  const size_t F = ds.F, npx = ds.npx();
+  HIP_CHECK(hipDeviceSynchronize());   // the tables may be read by a batch in flight on a caller's stream
+  ds.params.ensure(F * (L.nD + L.nS));
+  if (L.nD) HIP_CHECK(hipMemcpyAsync(ds.params.p, dparams, F * L.nD * sizeof(double), hipMemcpyHostToDevice, s));
+  if (L.nS) HIP_CHECK(hipMemcpyAsync(ds.params.p + F * L.nD, sparams, F * L.nS * sizeof(double), hipMemcpyHostToDevice, s));
+  const dim3 grid(static_cast<unsigned>((npx + 255) / 256), 1, ds.F), block(256);
+  if (L.depthType == CVD_DEPTH_GRID) {
+    ds.scales.ensure(F * npx);
+    if (KD == 16) hipLaunchKernelGGL((k_dataset_scale_map<16>), grid, block, 0, s, L, ds.W, ds.H, ds.params.p, ds.scales.p);
+    else hipLaunchKernelGGL((k_dataset_scale_map<4>), grid, block, 0, s, L, ds.W, ds.H, ds.params.p, ds.scales.p);
+    ds.scaleMode = 2;
+  } else {
+    ds.scales.ensure(F);
+    hipLaunchKernelGGL(k_dataset_scale_scalars, dim3((ds.F + 255) / 256), block, 0, s, ds.F, L.nD, ds.params.p, ds.scales.p);
+    ds.scaleMode = 1;
+  }
+  HIP_CHECK(hipGetLastError());
+  ds.warp.ensure(F * 2 * npx);
+  const double* sp = ds.params.p + F * L.nD;
+  if (KS == 0) hipLaunchKernelGGL((k_dataset_warp_map<0>), grid, block, 0, s, L, ds.W, ds.H, sp, ds.warp.p);
+  else if (KS == 4) hipLaunchKernelGGL((k_dataset_warp_map<4>), grid, block, 0, s, L, ds.W, ds.H, sp, ds.warp.p);
+  else hipLaunchKernelGGL((k_dataset_warp_map<16>), grid, block, 0, s, L, ds.W, ds.H, sp, ds.warp.p);
+  HIP_CHECK(hipGetLastError());
+  ds.haveWarp = true;
+  HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// The same tables from host arrays: scales f32 [F][H][W] (scaleIsMap) or [F], or NULL (no scales); warp f32 [F][2][H][W] or NULL.
+void datasetSetMaps(cvd_handle* h, const float* scales, int scaleIsMap, const float* warp) {
+  DatasetState& ds = datasetStore(h, "set_maps");
+  const size_t F = ds.F, npx = ds.npx();
+  HIP_CHECK(hipDeviceSynchronize());
+  ds.scaleMode = scales ? (scaleIsMap ? 2 : 1) : 0;
+  if (scales) ds.scales.upload(scales, scaleIsMap ? F * npx : F, h->stream);
+  ds.haveWarp = warp != nullptr;
+  if (warp) ds.warp.upload(warp, F * 2 * npx, h->stream);
+  HIP_CHECK(hipStreamSynchronize(h->stream));
+}
+
+// Device indices in, device outputs out, one launch on the caller's stream: no copy and no host wait.  An index outside [0, S)
+// cannot be seen here: the kernel clamps and counts it (datasetBadIndices).
+void datasetBatchDevice(cvd_handle* h, int B, const int64_t* indices, const cvd_dataset_batch_out* out, hipStream_t s) {
+  DatasetState& ds = datasetStore(h, "batch");
+  size_t bytes[kBatchOutputs];
+  checkBatch(ds, "batch", B, indices, out, bytes);
+  launchDatasetBatch(ds, B, reinterpret_cast<const long long*>(indices), *out, s);
+}
+
+// Host indices in, host outputs out.  kernelMs (may be NULL): the launch's HIP-event time.
+void datasetBatch(cvd_handle* h, int B, const int64_t* indices, const cvd_dataset_batch_out* out, double* kernelMs) {
+  DatasetState& ds = datasetStore(h, "batch");
+  size_t sizes[kBatchOutputs];
+  checkBatch(ds, "batch", B, indices, out, sizes);
+  for (int b = 0; b < B; ++b)
+    if (indices[b] < 0 || indices[b] >= ds.S)
+      throw std::runtime_error(fmt("%s batch: indices[%d] = %lld is outside the store's %d samples", kDsOp, b,
+                                   static_cast<long long>(indices[b]), ds.S));
+  hipStream_t s = h->stream;
+  void* hostMembers[kBatchOutputs];
+  batchOutMembers(out, hostMembers);
+  // staging: the indices, then every output at a 256-byte boundary
+  auto pad = [](size_t n) { return (n + 255) / 256 * 256; };
+  size_t total = pad(static_cast<size_t>(B) * sizeof(int64_t));
+  size_t offset[kBatchOutputs];
+  for (int k = 0; k < kBatchOutputs; ++k) { offset[k] = total; total += pad(sizes[k]); }
+  ds.stage.ensure(total);
+  HIP_CHECK(hipMemcpyAsync(ds.stage.p, indices, static_cast<size_t>(B) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  auto dev = [&](int k) -> void* { return sizes[k] ? ds.stage.p + offset[k] : nullptr; };
+  cvd_dataset_batch_out d{};
+  d.struct_size = out->struct_size;
+  d.images = dev(0); d.extrinsics = dev(1); d.intrinsics = dev(2); d.gc_indices = dev(3);
+  d.gc_flows[0] = dev(4); d.gc_flows[1] = dev(5); d.gc_masks[0] = dev(6); d.gc_masks[1] = dev(7);
+  d.ts_indices = dev(8);
+  for (int k = 0; k < 4; ++k) { d.ts_flows[k] = dev(9 + k); d.ts_masks[k] = dev(13 + k); }
+  d.ts_valid = dev(17); d.scales = dev(18); d.warp = dev(19); d.depth_orig = dev(20);
+  KernelTimer timer(s, kernelMs, 1);
+  timer.mark();
+  launchDatasetBatch(ds, B, reinterpret_cast<const long long*>(ds.stage.p), d, s);
+  timer.mark();
+  for (int k = 0; k < kBatchOutputs; ++k)
+    if (sizes[k]) HIP_CHECK(hipMemcpyAsync(hostMembers[k], ds.stage.p + offset[k], sizes[k], hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  timer.collect();
+}
+
+// Out-of-range indices the device entry point has clamped since cvd_dataset_create.  Waits for the device.
+long long datasetBadIndices(cvd_handle* h) {
+  DatasetState& ds = datasetStore(h, "bad_indices");
+  HIP_CHECK(hipDeviceSynchronize());
+  unsigned int n = 0;
+  HIP_CHECK(hipMemcpy(&n, ds.bad.p, sizeof(n), hipMemcpyDeviceToHost));
+  return n;
+}
+
 
 // One kernel of this translation unit's code object is looked up at handle creation: the HIP runtime loads a unit's device
 // code at its first use, ~20 ms per unit that would otherwise land in the first solve of a process (cvd_create: loadDeviceCode).

@@ -752,5 +752,16 @@ void paramStep(cvd_handle* h, const cvd_param_desc* d, const int64_t* offsets, c
 void paramStepDevice(cvd_handle* h, const cvd_param_desc* d, void* const* p, const void* const* g, void* const* m, void* const* v,
                      const int64_t* counts, const cvd_param_record* records, hipStream_t s);
 long long paramChunkElements();   // CVD_PARAM_CHUNK of cvd_frontend.hip's build
+void datasetCreate(cvd_handle* h, const cvd_dataset_desc* d, const int32_t* pairFrames, const int32_t* samples);
+void datasetClear(cvd_handle* h);
+void datasetSetColors(cvd_handle* h, int first, int count, const float* hwc3);
+void datasetSetFlows(cvd_handle* h, int first, int count, const float* flow, const uint8_t* mask);
+void datasetSetDepthOrig(cvd_handle* h, int first, int count, const float* depth);
+void datasetSetCameras(cvd_handle* h, const float* ext, const float* intr);
+void datasetSetXforms(cvd_handle* h, const cvd_xform_desc* dd, const double* dparams, const cvd_xform_desc* sd, const double* sparams);
+void datasetSetMaps(cvd_handle* h, const float* scales, int scaleIsMap, const float* warp);
+void datasetBatchDevice(cvd_handle* h, int B, const int64_t* indices, const cvd_dataset_batch_out* out, hipStream_t s);
+void datasetBatch(cvd_handle* h, int B, const int64_t* indices, const cvd_dataset_batch_out* out, double* kernelMs);
+long long datasetBadIndices(cvd_handle* h);
 
 }  // namespace cvd
