@@ -74,6 +74,11 @@ int32_t cvd_coarse_debug(cvd_handle* h, int32_t* num_unknowns, double* a_c, doub
  * matrix (NT x NT, unknown s * nn + a, diagonal shifted by coarse_dense_shift), a_t_inverse = the inverse in use, lam = the LM
  * damping vector (frames x block) of the last LM iteration.  Any output pointer but dims6 may be NULL. */
 int32_t cvd_temporal_debug(cvd_handle* h, int32_t* dims6, double* a_t, double* a_t_inverse, double* lam, int32_t* failed);
+/* Test hook: what the handle's last product launch (PCG product, J^T J hook of cvd_evaluate) was.  out6 = {threads per workgroup,
+ * SPEC (1 / 2: the compile-time ReproDisparity Cauchy / Huber variant, 0: runtime loss branches), KD (depth taps per side: 1, 4, 16),
+ * kind (0: generic list kernel, 1: fast list kernel, 2: fast dense-mode kernel, 3: explicit cross blocks; -1: no product yet),
+ * work items (= workgroups of the launch), compute units the workgroup-size rule counted}. */
+int32_t cvd_product_launch_debug(cvd_handle* h, int32_t* out6);
 
 #ifdef __cplusplus
 }

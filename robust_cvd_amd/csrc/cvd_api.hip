@@ -972,6 +972,11 @@ int32_t cvd_path_info(cvd_handle* h, int32_t* out8) {
     out8[7] = h->lastCross ? 1 : 0;
   });
 }
+int32_t cvd_product_launch_debug(cvd_handle* h, int32_t* out6) {
+  CVD_TRY(h, {
+    for (int i = 0; i < 6; ++i) out6[i] = h->lastProduct[i];
+  });
+}
 int32_t cvd_coarse_debug(cvd_handle* h, int32_t* num_unknowns, double* a_c, double* a_c_inverse, int32_t* failed) {
   CVD_TRY(h, {
     auto& C = h->coarse;

@@ -73,6 +73,11 @@ void launchMatvec(Ctx& c, const double* x, const double* z, const double* pOld, 
   hipStream_t s = h->stream;
   const CoarseView cF = coarseView(h, withCoarse, coarseFusedConsumers());  // z + Z c: the coarse part of the preconditioned residual
   const size_t B = c.L.B;
+  // (cvd_product_launch_debug: called with the template arguments of the instantiation that is launched)
+  auto recordLaunch = [h](int threads, int spec, int kd, int kind, int items) {
+    const int launched[6] = {threads, spec, kd, kind, items, h->numCU};
+    std::copy(launched, launched + 6, h->lastProduct);
+  };
   if (c.cross) {
     // explicit cross blocks (dense mode): one workgroup per undirected pair streams its B x B block
     hipEvent_t evStart, evStop;
@@ -81,6 +86,7 @@ void launchMatvec(Ctx& c, const double* x, const double* z, const double* pOld, 
     // (+ one workgroup per frame for its own block H_ff: see k_cross_matvec)
     const unsigned nP = static_cast<unsigned>(h->xFa.size()) + (h->xDiagRows ? static_cast<unsigned>(c.L.F) : 0u);
     const int* diagSlot = h->xDiagRows ? h->dXDiagSlot.p : nullptr;
+    recordLaunch(kCrossThreads, 0, c.KD, 3, static_cast<int>(nP));
     if (evStart)
       hipExtLaunchKernelGGL(k_cross_matvec, dim3(nP), dim3(kCrossThreads), ldsX, s, evStart, evStop, 0, c.L, crossPairs(h),
                             h->dXBlocks.p, h->dH.p, diagSlot, h->dMask.p, z, pOld, h->dScal.p, useBeta, h->dQPart.p, cF);
@@ -99,10 +105,11 @@ void launchMatvec(Ctx& c, const double* x, const double* z, const double* pOld, 
     const double* maskp = h->dMask.p;
     const double* scalp = h->dScal.p;
     if (fast) {
-      // Workgroup size: a work item keeps its slot for ~20 us at 256 threads and the register budget allows two
-      // waves per SIMD, i.e. 2 x CUs slots of 256 threads or 4 x CUs slots of 128.  When the items need more than one
-      // round at 256 threads but fit into one round of 128-thread workgroups the launch has no ragged second round
-      // (benchmark: 883 items, 44 -> 39.5 us).
+      // Workgroup size: 256 threads when the items fit into one round of 256-thread workgroups (nItems <= slots256, below) or
+      // need more than one round even at 128 threads (nItems > slots128); 128 threads in between, where the launch then has no
+      // ragged second round.  On 256 CUs the 128-thread windows are (1024, 2048] items for SPEC 1 / 2 with KD <= 4, (768, 1536]
+      // for SPEC 1 / 2 with KD = 16 and (512, 1024] for SPEC 0: the benchmarked lists (2070 and 883 items, SPEC 1, KD <= 4) lie
+      // outside theirs and run 256 threads.
       // SPEC = 1 / 2: the default pipeline's variant (one value parameter, ReproDisparity; Cauchy / Huber) fixed at compile time
       const int spec = (c.L.N == 1 && c.L.lossType == CVD_STATIC_REPRO_DISPARITY) ? (c.L.robustKind == 0 ? 1 : 2) : 0;
       // Slots of 256-thread workgroups on the device: waves per SIMD the variant is compiled for (cvd_kernels.h) x CUs; 128-thread
@@ -118,6 +125,7 @@ void launchMatvec(Ctx& c, const double* x, const double* z, const double* pOld, 
                                     : (c.nItems > 2 * h->numCU && c.nItems <= 4 * h->numCU ? 128 : 256);
 #define CVD_LAUNCH_PAIRS_FAST_S(NTV, SPECV)                                                                              \
       CVD_DISPATCH_KD(c.KD, {                                                                                            \
+        recordLaunch(NTV, SPECV, KD, 1, c.nItems);                                                                       \
         allowLds((k_matvec_pairs_fast<KD, NTV, SPECV>), ldsFast);                                                        \
         if (evStart)                                                                                                     \
           hipExtLaunchKernelGGL((k_matvec_pairs_fast<KD, NTV, SPECV>), dim3(c.nItems), dim3(NTV), ldsFast, s, evStart, evStop, 0, \
@@ -133,6 +141,7 @@ void launchMatvec(Ctx& c, const double* x, const double* z, const double* pOld, 
 #define CVD_LAUNCH_PAIRS_DENSE(SPECV)                                                                                     \
         CVD_DISPATCH_KD(c.KD, {                                                                                          \
           if constexpr (KD <= 4) { /* (dense mode: Global and bilinear grids) */                                         \
+            recordLaunch(256, SPECV, KD, 2, c.nItems);                                                                   \
             allowLds((k_matvec_pairs_fast<KD, 256, SPECV, true>), ldsDense);                                             \
             if (evStart)                                                                                                 \
               hipExtLaunchKernelGGL((k_matvec_pairs_fast<KD, 256, SPECV, true>), dim3(c.nItems), dim3(256), ldsDense, s, evStart, \
@@ -156,6 +165,7 @@ void launchMatvec(Ctx& c, const double* x, const double* z, const double* pOld, 
 #undef CVD_LAUNCH_PAIRS_FAST_S
 #undef CVD_LAUNCH_PAIRS_FAST
     } else {
+      recordLaunch(256, 0, c.KD, 0, c.nItems);
       CVD_DISPATCH(c.KD, c.KS, {
         allowLds(k_matvec_pairs<KD, KS>, lds);
         if (evStart)

@@ -31,7 +31,8 @@ def test_header_symbols_are_exported():
     # the product header holds no test hook: debug options, simulated ranks and parity hooks of internal solves live in cvd_hip_debug.h
     product = declared_symbols(("cvd_hip.h",))
     for n in ("cvd_set_debug_options", "cvd_comm_init_local_group", "cvd_comm_init_phantom", "cvd_set_generic_kernels",
-              "cvd_block_inverse_debug", "cvd_dense_inverse_debug", "cvd_coarse_debug", "cvd_temporal_debug"):
+              "cvd_block_inverse_debug", "cvd_dense_inverse_debug", "cvd_coarse_debug", "cvd_temporal_debug",
+              "cvd_product_launch_debug"):
         assert n not in product and n in names
     text = open(os.path.join(ROOT, "include", "cvd_hip.h")).read()
     for hook in ("force_iterations", "force_sharded_path", "pcg_lockstep", "stall_fused_tail_once"):
