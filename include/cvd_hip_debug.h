@@ -79,6 +79,12 @@ int32_t cvd_temporal_debug(cvd_handle* h, int32_t* dims6, double* a_t, double* a
  * kind (0: generic list kernel, 1: fast list kernel, 2: fast dense-mode kernel, 3: explicit cross blocks; -1: no product yet),
  * work items (= workgroups of the launch), compute units the workgroup-size rule counted}. */
 int32_t cvd_product_launch_debug(cvd_handle* h, int32_t* out6);
+/* Test hook: what the handle's last assembly launch (gradient and frame blocks of cvd_evaluate or of an LM iteration) was.  out6 =
+ * {threads per workgroup, SPEC (as above), KD, kind (0: generic kernel, 1: fast list kernel, 2: fast dense-mode kernel, 3: fold of the
+ * dense walk's records; -1: no assembly yet), workgroups of the launch (list mode: parts of the work list), parts that belong to
+ * frames split into several parts (0: no frame is split)}.  cost_frame (optional, one double per frame): the per-frame costs that
+ * launch left behind -- a frame's regularisers and the constraints of the pairs it is the source of; their sum is the cost. */
+int32_t cvd_assembly_launch_debug(cvd_handle* h, int32_t* out6, double* cost_frame);
 
 #ifdef __cplusplus
 }

@@ -407,7 +407,7 @@ EXPORTED_SYMBOLS = [
     "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_scene_flow_loss", "cvd_scene_flow_loss_device", "cvd_spatial_losses", "cvd_spatial_losses_device", "cvd_param_chunk", "cvd_parameter_l1", "cvd_parameter_l1_device", "cvd_param_step", "cvd_param_step_device", "cvd_dataset_create", "cvd_dataset_clear", "cvd_dataset_set_colors", "cvd_dataset_set_flows", "cvd_dataset_set_depth_orig", "cvd_dataset_set_cameras", "cvd_dataset_set_xforms", "cvd_dataset_set_maps", "cvd_dataset_batch", "cvd_dataset_batch_device", "cvd_dataset_bad_indices", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
     "cvd_get_kernel_times", "cvd_get_comm_times", "cvd_get_dense_times", "cvd_set_kernel_timing", "cvd_num_active_constraints", "cvd_coarse_debug", "cvd_temporal_debug", "cvd_path_info", "cvd_abi_revision",
     "cvd_block_inverse_debug", "cvd_dense_inverse_debug", "cvd_epipolar_debug", "cvd_flow_masks_debug",
-    "cvd_product_launch_debug",
+    "cvd_product_launch_debug", "cvd_assembly_launch_debug",
 ]
 
 KERNEL_CLASSES = ["evaluate_assemble", "matvec_pairs", "matvec_finish", "cg_update", "block_inverse", "cost"]
@@ -971,6 +971,17 @@ class Solver(Binding):
         kind = {-1: "none", 0: "generic list", 1: "fast list", 2: "fast dense", 3: "cross blocks"}[out[3]]
         return {"threads": out[0], "spec": out[1], "kd": out[2], "kind": out[3], "kind_name": kind, "work_items": out[4],
                 "num_cu": out[5]}
+
+    def assembly_launch_debug(self):
+        """The handle's last assembly launch (cvd_assembly_launch_debug): workgroup size, kernel variant, workgroups, parts of split
+        frames, and the per-frame costs it wrote (their sum is the cost of the evaluation)."""
+        import numpy as np
+        out = (C.c_int32 * 6)()
+        cost = np.zeros(self.num_frames, dtype=np.float64)
+        self._check(self._fn("assembly_launch_debug")(self._h, out, cost.ctypes.data_as(C.POINTER(C.c_double))))
+        kind = {-1: "none", 0: "generic", 1: "fast list", 2: "fast dense", 3: "dense fold"}[out[3]]
+        return {"threads": out[0], "spec": out[1], "kd": out[2], "kind": out[3], "kind_name": kind, "workgroups": out[4],
+                "split_parts": out[5], "cost_frame": cost}
 
     def coarse_debug(self):
         """(A_c, A_c^-1 as applied, pivot failures) of the coarse preconditioner level after the last solve."""

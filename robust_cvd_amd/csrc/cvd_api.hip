@@ -977,6 +977,16 @@ int32_t cvd_product_launch_debug(cvd_handle* h, int32_t* out6) {
     for (int i = 0; i < 6; ++i) out6[i] = h->lastProduct[i];
   });
 }
+int32_t cvd_assembly_launch_debug(cvd_handle* h, int32_t* out6, double* cost_frame) {
+  CVD_TRY(h, {
+    for (int i = 0; i < 6; ++i) out6[i] = h->lastAssembly[i];
+    const size_t F = static_cast<size_t>(h->F);
+    if (cost_frame && h->lastAssembly[3] >= 0 && h->dCostFrame.n >= F) {  // (kind -1: nothing to read, cost_frame is left as it is)
+      h->dCostFrame.download(cost_frame, F, h->stream);
+      HIP_CHECK(hipStreamSynchronize(h->stream));
+    }
+  });
+}
 int32_t cvd_coarse_debug(cvd_handle* h, int32_t* num_unknowns, double* a_c, double* a_c_inverse, int32_t* failed) {
   CVD_TRY(h, {
     auto& C = h->coarse;

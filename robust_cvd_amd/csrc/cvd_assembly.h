@@ -284,9 +284,12 @@ inline __global__ void k_extract_diag(Layout L, const double* __restrict__ hBloc
 // =====================================================================================================
 // Fast path of the frame-major assembly (same scope as k_matvec_pairs_fast: identity spatial transform,
 // reprojection losses, Identity / Global / bilinear depth transform).  Only the OWN side's Jacobian is formed
-// (3x7 pose-like columns + the 3-vector d r / d D); taps are unrolled, nothing is indexed dynamically, so the
-// kernel needs neither scratch nor 256 VGPRs.  Accumulation: 7x7 + gradient in registers (wave-reduced at
-// the end), pose x grid and grid x grid through LDS f64 atomics into the packed lower triangle.
+// (3x7 pose-like columns + the 3-vector d r / d D); taps are unrolled, nothing is indexed dynamically.
+// Accumulation: 7x7 + gradient in registers (wave-reduced at the end), pose x grid and grid x grid through LDS
+// f64 atomics into the packed lower triangle.
+// Register state (KD = 4, list mode, STAGE; DESIGN_LOG has the history): the runtime-variant walk (SPEC = 0) sits at
+// its 256-VGPR budget with a few spilled values; the specialised walk (SPEC = 1 / 2, asmWalkSpec below) needs no
+// scratch -- tests/test_codegen_assembly.py pins that.
 // =====================================================================================================
 
 #ifdef CVD_ASM_PROFILE
@@ -295,6 +298,287 @@ __device__ unsigned long long g_asmProf[2048 * 16];
 #else
 #define ASM_STAMP(slot) do {} while (0)
 #endif
+// Every instantiation runs kAsmThreads per workgroup.  The packed triangle leaves room for ONE workgroup per CU, so the waves per
+// SIMD are the workgroup's waves / 4: 8 waves need <= 256 VGPRs, 12 would need <= 168 (the specialised walk then spills 102), 16 <= 128.
+
+// The walk of one unit with the variant fixed at compile time (k_assemble_fast's SPEC = 1 / 2: one value parameter per vertex,
+// ReproDisparity, Cauchy / Huber -- the rule of k_matvec_pairs_fast).  `side` is the own frame's role in the pair (0: the source,
+// 1: the target): wave-uniform, a scalar branch where the two Jacobians differ.  (Two copies of the loop, one per role, were tried: the
+// register allocator then keeps the 35 accumulators twice and the kernel spills.)
+//  * Frame constants are scalars for the whole unit (R_a, R_b, t_a - t_b, the focals and their reciprocals): nothing of FrameConst is
+//    read inside the constraint loop.
+//  * Rotation columns in the frame's LOCAL basis.  dR/dw_i = [a_i]x R (a_i = row i of FrameConst::Jl), so with G = M R_b^T, the rows
+//    of the translation columns,
+//      source:  G_rr . dR_a,i (D_a c_a) = a_i . (X x G_rr),  X = D_a R_a c_a
+//      target:  M_rr . dR_b,i^T v       = a_i . (G_rr x v)
+//    i.e. every rotation column is Jl applied to ONE cross product per residual row.  The loop accumulates with that 3-vector in
+//    columns 3..5 (no dR, no Jl) and the kernel applies T = diag(I_3, Jl^T, I) to the sums afterwards: H <- T^T H T, g <- T^T g
+//    (asmLocalToAxisAngle).
+//  * Hardware reciprocals with two Newton steps (rcpFast / rsqrtFast) instead of IEEE divisions; rho and rho' written out.
+//  * The next trip's table record is in flight during this trip's arithmetic (RecordStream, primed by the caller before it stages).
+template <int KD, int SPEC>
+__device__ __forceinline__ void asmWalkSpec(const Layout& L, const Table& T, RecordStream<false>& rs, long long cBegin, int n,
+                                            int lane, const bool side, const FrameConst& Fa, const FrameConst& Fb,
+                                            const double* __restrict__ xa, const double* __restrict__ xb, double* Hs,
+                                            double* gs, double (&PP)[28], double (&gp)[7], double (&GD)[19], double& cost) {
+  constexpr double eps = 1e-6;
+  const double A = L.aspect;
+  double RaU[9], RbU[9], dTU[3];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) { RaU[i] = uniformValue(Fa.R[i]); RbU[i] = uniformValue(Fb.R[i]); }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) dTU[i] = uniformValue(Fa.t[i] - Fb.t[i]);
+  const double fya = uniformValue(Fa.fy), fxa = fya * A;
+  const double fyb = uniformValue(Fb.fy);
+  const double ifyb = uniformValue(1.0 / fyb), ifxb = uniformValue(1.0 / (fyb * A));
+  for (int ci = lane; ci < n; ci += 64) {
+    float4 nd;
+    float2 d;
+    if (!rs.take(T, cBegin, ci, 64, n, 0, 0, 0, nd, d)) continue;
+    const double da = static_cast<double>(d.x), db = static_cast<double>(d.y);
+    FastTaps<KD> ta, tb;
+    fastGather<KD>(L, nd.x, nd.y, ta);
+    fastGather<KD>(L, nd.z, nd.w, tb);
+    double Da = 0.0, Db = 0.0;
+#pragma unroll
+    for (int k = 0; k < KD; ++k) {
+      if (ta.ok(k)) Da += xa[7 + ta.I(k)] * ta.Wt(k);
+      if (tb.ok(k)) Db += xb[7 + tb.I(k)] * tb.Wt(k);
+    }
+    Da *= da;
+    Db *= db;
+    const double pax = static_cast<double>(nd.x), pay = static_cast<double>(nd.y);
+    const double pbx = static_cast<double>(nd.z), pby = static_cast<double>(nd.w);
+    const double ca[3] = {pax * fxa, pay * fya, -1.0};
+    const double Rca[3] = {dot3(RaU, ca), dot3(RaU + 3, ca), dot3(RaU + 6, ca)};
+    const double v[3] = {dTU[0] + Rca[0] * Da, dTU[1] + Rca[1] * Da, dTU[2] + Rca[2] * Da};
+    const double q0 = RbU[0] * v[0] + RbU[3] * v[1] + RbU[6] * v[2];
+    const double q1 = RbU[1] * v[0] + RbU[4] * v[1] + RbU[7] * v[2];
+    const double q2 = RbU[2] * v[0] + RbU[5] * v[1] + RbU[8] * v[2];
+    const double zz = -q2;
+    const double iz = rcpFast(zz);
+    const double u = q0 * iz * ifxb;
+    const double vv = q1 * iz * ifyb;
+    double r[3];
+    r[0] = (u - pbx) * L.ws;
+    r[1] = (vv - pby) * L.ws;
+    const bool zo = !(zz < eps), bo = !(Db < eps);
+    const double izc = zo ? iz : 1.0 / eps, ibc = rcpFast(bo ? Db : eps);
+    r[2] = (izc - ibc) * L.wd;
+    const double dr2dA = zo ? (-L.wd * izc * izc) : 0.0;
+    const double dr2dDb = bo ? (L.wd * ibc * ibc) : 0.0;
+    const double sq = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+    double w;  // rho'; rho goes to the cost on the source visit (every constraint is counted once)
+    if constexpr (SPEC == 1) {
+      const double sum = 1.0 + sq * L.cauchyC;
+      w = rcpFast(sum);
+      if (!side) cost += L.cauchyB * log(sum);
+    } else {
+      const bool outer = sq > L.cauchyB;
+      const double irt = rsqrtFast(outer ? sq : 1.0);
+      w = outer ? fmax(2.2250738585072014e-308, L.robustA * irt) : 1.0;
+      if (!side) cost += outer ? (2.0 * L.robustA * (sq * irt) - L.cauchyB) : sq;
+    }
+
+    // d r / d q (rows): M0 = (m00, 0, m02), M1 = (0, m11, m12), M2 = (0, 0, m22);  G = M R_b^T
+    const double wiz = L.ws * iz;
+    const double m00 = wiz * ifxb, m11 = wiz * ifyb, m02 = wiz * u, m12 = wiz * vv, m22 = -dr2dA;
+    double G[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      G[0][i] = m00 * RbU[i * 3 + 0] + m02 * RbU[i * 3 + 2];
+      G[1][i] = m11 * RbU[i * 3 + 1] + m12 * RbU[i * 3 + 2];
+      G[2][i] = m22 * RbU[i * 3 + 2];
+    }
+    double Jp[3][7];  // columns 3..5: local basis (see above)
+    double JD[3];
+    if (!side) {
+      const double X[3] = {Da * Rca[0], Da * Rca[1], Da * Rca[2]};
+      const double cf0 = pax * A, cf1 = pay;
+      const double dXdf[3] = {Da * (RaU[0] * cf0 + RaU[1] * cf1), Da * (RaU[3] * cf0 + RaU[4] * cf1),
+                              Da * (RaU[6] * cf0 + RaU[7] * cf1)};
+#pragma unroll
+      for (int rr = 0; rr < 3; ++rr) {
+        Jp[rr][0] = G[rr][0]; Jp[rr][1] = G[rr][1]; Jp[rr][2] = G[rr][2];
+        Jp[rr][3] = X[1] * G[rr][2] - X[2] * G[rr][1];
+        Jp[rr][4] = X[2] * G[rr][0] - X[0] * G[rr][2];
+        Jp[rr][5] = X[0] * G[rr][1] - X[1] * G[rr][0];
+        Jp[rr][6] = dot3(G[rr], dXdf);
+        JD[rr] = dot3(G[rr], Rca);
+      }
+    } else {
+#pragma unroll
+      for (int rr = 0; rr < 3; ++rr) {
+        Jp[rr][0] = -G[rr][0]; Jp[rr][1] = -G[rr][1]; Jp[rr][2] = -G[rr][2];
+        Jp[rr][3] = G[rr][1] * v[2] - G[rr][2] * v[1];
+        Jp[rr][4] = G[rr][2] * v[0] - G[rr][0] * v[2];
+        Jp[rr][5] = G[rr][0] * v[1] - G[rr][1] * v[0];
+      }
+      Jp[0][6] = -L.ws * u * ifyb;
+      Jp[1][6] = -L.ws * vv * ifyb;
+      Jp[2][6] = 0.0;
+      JD[0] = 0.0; JD[1] = 0.0; JD[2] = dr2dDb;
+    }
+    // ---- accumulate
+    int qi = 0;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+      gp[i] += w * (Jp[0][i] * r[0] + Jp[1][i] * r[1] + Jp[2][i] * r[2]);
+#pragma unroll
+      for (int j = 0; j <= i; ++j) {
+        PP[qi] += w * (Jp[0][i] * Jp[0][j] + Jp[1][i] * Jp[1][j] + Jp[2][i] * Jp[2][j]);
+        ++qi;
+      }
+    }
+    double v7[7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) v7[i] = w * (Jp[0][i] * JD[0] + Jp[1][i] * JD[1] + Jp[2][i] * JD[2]);
+    const double sDD = w * (JD[0] * JD[0] + JD[1] * JD[1] + JD[2] * JD[2]);
+    const double sDr = w * (JD[0] * r[0] + JD[1] * r[1] + JD[2] * r[2]);
+    const FastTaps<KD>& tm = side ? tb : ta;
+    const double dm = side ? db : da;  // d D / d theta_k = w_k d
+    if constexpr (KD == 1) {
+      // (Global / Identity: the single depth block is hit by every sample -> the kernel's register accumulators)
+      const double fac = tm.Wt(0) * dm;
+#pragma unroll
+      for (int i = 0; i < 7; ++i) GD[i] += v7[i] * fac;
+      GD[17] += sDr * fac;
+      GD[14] += sDD * fac * fac;
+    } else {
+#pragma unroll
+      for (int ka = 0; ka < KD; ++ka) {
+        if (!tm.ok(ka)) continue;
+        const double fa = tm.Wt(ka) * dm;
+        const int ct = 7 + tm.I(ka);
+        const int rowBase = ct * (ct + 1) / 2;
+        atomicAdd(&gs[ct], sDr * fa);
+#pragma unroll
+        for (int i = 0; i < 7; ++i) atomicAdd(&Hs[rowBase + i], v7[i] * fa);
+        const double sfa = sDD * fa;
+#pragma unroll
+        for (int kb = 0; kb <= ka; ++kb) {
+          if (!tm.ok(kb)) continue;
+          const int c2 = 7 + tm.I(kb);
+          // (bilinear taps at gx = 1 are not in index order: order the pair; the bicubic taps are)
+          const int hi = (KD == 16 || ct > c2) ? ct : c2, lo = (KD == 16 || ct > c2) ? c2 : ct;
+          atomicAdd(&Hs[packedIdx(hi, lo)], sfa * (tm.Wt(kb) * dm));
+        }
+      }
+    }
+  }
+}
+
+// Rotation rows / columns of a frame's sums from the local basis of asmWalkSpec to the axis-angle parameters: with J = Jl (row i =
+// a_i) every triple (H[3][j], H[4][j], H[5][j]), j outside 3..5, becomes J times itself, the 3 x 3 block S becomes J S J^T and the
+// gradient triple J g.  Linear, so it commutes with the fold of a split frame's parts: every part transforms its own sums, BEFORE
+// the regularisers (which are in axis-angle terms) are added.  Each entry is read and written by one thread; the caller's barriers
+// separate it from the accumulation before and the regularisers after.
+template <int NT>
+__device__ __forceinline__ void asmLocalToAxisAngle(const double* __restrict__ Jl, int B, int tid, double* Hs, double* gs) {
+  double J[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) J[i] = Jl[i];
+  for (int j = tid; j < B; j += NT) {
+    if (j >= 3 && j <= 5) continue;
+    const int i0 = j < 3 ? packedIdx(3, j) : packedIdx(j, 3);
+    const int i1 = j < 3 ? packedIdx(4, j) : packedIdx(j, 4);
+    const int i2 = j < 3 ? packedIdx(5, j) : packedIdx(j, 5);
+    const double h0 = Hs[i0], h1 = Hs[i1], h2 = Hs[i2];
+    Hs[i0] = J[0] * h0 + J[1] * h1 + J[2] * h2;
+    Hs[i1] = J[3] * h0 + J[4] * h1 + J[5] * h2;
+    Hs[i2] = J[6] * h0 + J[7] * h1 + J[8] * h2;
+  }
+  if (tid == NT - 1) {
+    double S[3][3], JS[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) S[a][b] = Hs[a >= b ? packedIdx(3 + a, 3 + b) : packedIdx(3 + b, 3 + a)];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) JS[a][b] = J[a * 3] * S[0][b] + J[a * 3 + 1] * S[1][b] + J[a * 3 + 2] * S[2][b];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b <= a; ++b)
+        Hs[packedIdx(3 + a, 3 + b)] = JS[a][0] * J[b * 3] + JS[a][1] * J[b * 3 + 1] + JS[a][2] * J[b * 3 + 2];
+    const double g0 = gs[3], g1 = gs[4], g2 = gs[5];
+    gs[3] = J[0] * g0 + J[1] * g1 + J[2] * g2;
+    gs[4] = J[3] * g0 + J[4] * g1 + J[5] * g2;
+    gs[5] = J[6] * g0 + J[7] * g1 + J[8] * g2;
+  }
+}
+
+// The frame's regularisers for the specialised walk (N = 1, 2-D grid or Global): same residuals as regResidual, with nothing indexed
+// dynamically.  The scale regulariser's taps are unrolled (FastTaps); the others (focal, grid deformation, spatial: one or two columns)
+// go through regResidual with the scale term switched off, which leaves only constant indices into its column arrays.  Returns
+// this thread's sum of squared residuals.
+template <int KD, int NT>
+__device__ __forceinline__ double asmRegularisersSpec(const Layout& L, int f, int tid, const double* __restrict__ xf, float median,
+                                                      double* Hs, double* gs) {
+  constexpr double eps = 1e-6;
+  double regCost = 0.0;
+  if (L.scaleRegSqrt > 0.0) {
+    const int ns = L.sregX * L.sregY;
+    const bool taps = KD > 1 || L.depthType == kDepthGlobal;  // (depthGather: one tap exists for the Global transform only)
+    for (int i = tid; i < ns; i += NT) {
+      const int y = i / L.sregX, x = i - y * L.sregX;
+      // float arithmetic of reference lib/PoseOptimizer.cpp:1384-1385
+      const float lx = __fadd_rn(-1.f, __fdiv_rn(__fmul_rn(2.f, static_cast<float>(x)), static_cast<float>(L.sregX - 1)));
+      const float ly = __fadd_rn(-1.f, __fdiv_rn(__fmul_rn(2.f, static_cast<float>(y)), static_cast<float>(L.sregY - 1)));
+      FastTaps<KD> t;
+      fastGather<KD>(L, lx, ly, t);
+      const double d = static_cast<double>(median);
+      double D = (L.depthType == kDepthIdentity) ? d : 0.0;
+#pragma unroll
+      for (int k = 0; k < KD; ++k)
+        if (taps && t.ok(k)) D += d * xf[7 + t.I(k)] * t.Wt(k);
+      const bool o = !(D < eps);
+      const double dd = o ? D : eps;
+      const double r = L.scaleRegSqrt * (1.0 / dd - 1.0);
+      const double drdD = o ? (-L.scaleRegSqrt / (dd * dd)) : 0.0;
+      regCost += r * r;
+#pragma unroll
+      for (int ka = 0; ka < KD; ++ka) {
+        if (!(taps && t.ok(ka))) continue;
+        const int ca = 7 + t.I(ka);
+        const double ja = drdD * t.Wt(ka) * d;
+        atomicAdd(&gs[ca], ja * r);
+#pragma unroll
+        for (int kb = 0; kb <= ka; ++kb) {
+          if (!t.ok(kb)) continue;
+          const int cb = 7 + t.I(kb);
+          const int hi = ca > cb ? ca : cb, lo = ca > cb ? cb : ca;
+          atomicAdd(&Hs[packedIdx(hi, lo)], ja * (drdD * t.Wt(kb) * d));
+        }
+      }
+    }
+  }
+  Layout Lr = L;
+  Lr.scaleRegSqrt = 0.0;
+  const int nr = numRegResiduals<KD>(Lr);
+  for (int i = tid; i < nr; i += NT) {
+    double r;
+    int n;
+    int cols[2 * KD + 2];
+    double jac[2 * KD + 2];
+    regResidual<KD>(Lr, f, i, xf, median, r, n, cols, jac);
+    regCost += r * r;
+    if (n >= 1) {
+      atomicAdd(&gs[cols[0]], jac[0] * r);
+      atomicAdd(&Hs[packedIdx(cols[0], cols[0])], jac[0] * jac[0]);
+    }
+    if (n >= 2) {
+      atomicAdd(&gs[cols[1]], jac[1] * r);
+      const int hi = cols[1] > cols[0] ? cols[1] : cols[0], lo = cols[1] > cols[0] ? cols[0] : cols[1];
+      atomicAdd(&Hs[packedIdx(hi, lo)], jac[1] * jac[0]);
+      atomicAdd(&Hs[packedIdx(cols[1], cols[1])], jac[1] * jac[1]);
+    }
+  }
+  return regCost;
+}
+
 // STAGE (round 5): the OTHER frame's parameters of the unit a wave walks are copied into a per-wave LDS buffer first.  Without it
 // the taps of the other side are 4-tap gathers from global memory -- a dependent round trip in every trip of a kernel that runs
 // two waves per SIMD -- and, since `side` selects between an LDS and a global pointer at run time, every parameter read of the
@@ -302,7 +586,10 @@ __device__ unsigned long long g_asmProf[2048 * 16];
 // FOLD (round 6, dense mode inside the explicit-block scope): the constraints were walked by k_dense_walk (cvd_dense_walk.h); a
 // frame's workgroup sums its records -- a gather over (pair, side) entries, no atomics -- in place of the walk, and continues with
 // the regularisers and the write-out as ever.  One workgroup per frame (blockIdx.x = frame; the work list is not used).
-template <int KD, bool DENSE = false, bool STAGE = false, bool FOLD = false>
+// SPEC (as on k_matvec_pairs_fast, chosen by the same rule): 1 = one value parameter per vertex, ReproDisparity, Cauchy; 2 = the same
+// with Huber; 0 = the runtime-variant walk below (everything else, shared intrinsics -- their extra focal column sits in the loop --
+// and the DENSE / FOLD instantiations).  SPEC != 0 walks its units through asmWalkSpec.
+template <int KD, bool DENSE = false, bool STAGE = false, bool FOLD = false, int SPEC = 0>
 inline __global__ __launch_bounds__(kAsmThreads) void k_assemble_fast(Layout L, Table T, const double* __restrict__ x,
                                                        const FrameConst* __restrict__ fc,
                                                        const double* __restrict__ mask, const float* __restrict__ median,
@@ -323,10 +610,11 @@ inline __global__ __launch_bounds__(kAsmThreads) void k_assemble_fast(Layout L, 
   double* gs = Hs + npk;
   double* xf = gs + B;
   double* red = xf + B;  // 36 workgroup sums (LDS atomics, one set per wave) + scratch
-  double* xstage = red + 4 * 36;  // STAGE: kAsmThreads / 64 x B doubles
+  double* xstage = red + 4 * 36;  // STAGE: NT / 64 x B doubles
   const AsmPart me = FOLD ? AsmPart{static_cast<int>(blockIdx.x), 0, 0, 0, 1, 0} : work.parts[blockIdx.x];
   const int f = me.frame;
   const int tid = threadIdx.x;
+  static_assert(SPEC == 0 || (!DENSE && !FOLD), "the specialised walk is list mode only");
   constexpr int NT = kAsmThreads;
   // wave-uniform wave index (scalar register: the per-entry frame constants below become scalar loads)
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -353,7 +641,7 @@ inline __global__ __launch_bounds__(kAsmThreads) void k_assemble_fast(Layout L, 
   for (int i = 0; i < 28; ++i) PP[i] = 0.0;
 #pragma unroll
   for (int i = 0; i < 7; ++i) gp[i] = 0.0;
-  const int N = L.N;
+  const int N = SPEC ? 1 : L.N;
   const double A = L.aspect;
 
   if constexpr (FOLD) {
@@ -417,6 +705,23 @@ inline __global__ __launch_bounds__(kAsmThreads) void k_assemble_fast(Layout L, 
       const FrameConst& Fa = side ? fc[o] : fc[f];
       const FrameConst& Fb = side ? fc[f] : fc[o];
       double* xw = xstage + wv * B;
+      if constexpr (SPEC != 0) {
+        const long long pOff = T.pairOff[p];
+        const long long cb = pOff + __builtin_amdgcn_readfirstlane(unit.y);
+        const long long pEnd = T.pairOff[p + 1];
+        const int n = static_cast<int>((cb + kAsmUnit < pEnd ? cb + kAsmUnit : pEnd) - cb);
+        RecordStream<false> rs;
+        rs.prime(T, cb, lane, n);
+        // (the unit's first record is requested before the staging copy: one round trip for both; LDS ordering as below)
+        if constexpr (STAGE) {
+          for (int i = lane; i < B; i += 64) xw[i] = xo[i];
+          asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        }
+        const double* xov = STAGE ? xw : xo;
+        asmWalkSpec<KD, SPEC>(L, T, rs, cb, n, lane, side != 0, Fa, Fb, side ? xov : xf,
+                              side ? xf : xov, Hs, gs, PP, gp, GD, cost);
+        continue;
+      }
       if constexpr (STAGE) {
         // (a wave's LDS operations execute in order: its own earlier reads of the buffer are done before these writes land, and
         // the reads below see them -- no workgroup barrier, the waves walk their units independently)
@@ -729,6 +1034,10 @@ inline __global__ __launch_bounds__(kAsmThreads) void k_assemble_fast(Layout L, 
   __syncthreads();
   const double staticCost = 0.5 * red[35];
   __syncthreads();
+  if constexpr (SPEC != 0) {
+    asmLocalToAxisAngle<NT>(fc[f].Jl, B, tid, Hs, gs);
+    __syncthreads();
+  }
   if (tid == 0) ASM_STAMP(13);
   if (L.intrOpt == kIntrShared) {
     // The focal column of every constraint belongs to frame 0's slot: publish this frame's static focal
@@ -757,6 +1066,9 @@ inline __global__ __launch_bounds__(kAsmThreads) void k_assemble_fast(Layout L, 
 
   if (tid == 0) ASM_STAMP(14);
   double regCost = 0.0;
+  if constexpr (SPEC != 0) {
+    if (regOwner[f] && me.part == 0) regCost = asmRegularisersSpec<KD, NT>(L, f, tid, xf, median[f], Hs, gs);
+  } else
   if (regOwner[f] && me.part == 0) {
     const int nr = numRegResiduals<KD>(L);
     for (int i = tid; i < nr; i += NT) {

@@ -167,19 +167,30 @@ double evalFull(Ctx& c, const double* x, bool withStats, bool noReadBack) {
   const size_t ldsRest = 3 * B * 8 + 2 * sizeof(FrameConst) + 4 * 36 * 8;
   int panelCap = 0;
   const bool fastFits = ldsFast <= kMaxLds;
+  auto recordAsm = [h](int threads, int spec, int kd, int kind, int groups, int splitParts) {  // (cvd_assembly_launch_debug)
+    const int v[6] = {threads, spec, kd, kind, groups, splitParts};
+    for (int i = 0; i < 6; ++i) h->lastAssembly[i] = v[i];
+  };
   if (fast && fastFits) {
     h->dAsmScratch.ensure(static_cast<size_t>(h->nAsmSlots) * (B * (B + 1) / 2 + B + 4));
     const AsmWork work{h->dAsmParts.p, h->dAsmUnits.p, h->dAsmScratch.p, h->dAsmCount.p};
     // STAGE: the other frame's parameters in a per-wave LDS buffer whenever the LDS holds 8 B doubles more (cvd_assembly.h)
+    // SPEC: the default pipeline's variant fixed at compile time, by the rule of the pair product (cvd_matvec.hip); shared
+    // intrinsics (an extra focal column inside the loop) and the dense mode stay on the runtime-variant walk.
+    const int spec = (!h->dense && c.L.N == 1 && c.L.lossType == CVD_STATIC_REPRO_DISPARITY && c.L.intrOpt != CVD_INTR_SHARED)
+                         ? (c.L.robustKind == 0 ? 1 : 2) : 0;
     const size_t ldsStage = ldsFast + static_cast<size_t>(kAsmThreads / 64) * B * 8;
     const bool stage = ldsStage <= kMaxLds;
-#define CVD_LAUNCH_ASM(DENSEV, STAGEV)                                                                                     \
+#define CVD_LAUNCH_ASM_S(DENSEV, STAGEV, SPECV)                                                                            \
     CVD_DISPATCH_KD(c.KD, {                                                                                              \
-      allowLds((k_assemble_fast<KD, DENSEV, STAGEV>), STAGEV ? ldsStage : ldsFast);                                        \
-      hipLaunchKernelGGL((k_assemble_fast<KD, DENSEV, STAGEV>), dim3(h->nAsmParts), dim3(kAsmThreads), STAGEV ? ldsStage : ldsFast, s, \
+      recordAsm(kAsmThreads, SPECV, KD, DENSEV ? 2 : 1, h->nAsmParts, h->nAsmSlots);                                       \
+      allowLds((k_assemble_fast<KD, DENSEV, STAGEV, false, SPECV>), STAGEV ? ldsStage : ldsFast);                          \
+      hipLaunchKernelGGL((k_assemble_fast<KD, DENSEV, STAGEV, false, SPECV>), dim3(h->nAsmParts),                          \
+                         dim3(kAsmThreads), STAGEV ? ldsStage : ldsFast, s,                                                \
                          c.L, c.T, x, h->dFc.p, h->dMask.p, h->dMedian.p, h->dRegOwner.p, h->dInRange.p, work, h->dG.p, h->dH.p,  \
                          h->dCostFrame.p, h->dFocal.p, h->dFocal.p + c.L.F);                                             \
     })
+#define CVD_LAUNCH_ASM(DENSEV, STAGEV) CVD_LAUNCH_ASM_S(DENSEV, STAGEV, 0)
 #ifndef CVD_ASM_STAGE
 #define CVD_ASM_STAGE 1
 #endif
@@ -189,6 +200,7 @@ double evalFull(Ctx& c, const double* x, bool withStats, bool noReadBack) {
       // are the one-tap instantiation's.  Until round 6 that level ran matrix-free: 1.6 ms per PCG product over the 144 M pixels
       // for an 8 x 8 block per pair, more than half of the dense pipeline's time.)
       launchDenseWalk(c, x);
+      recordAsm(kAsmThreads, 0, c.KD, 3, c.L.F, 0);
       if (c.KD == 1) {
         allowLds((k_assemble_fast<1, true, false, true>), ldsFast);
         hipLaunchKernelGGL((k_assemble_fast<1, true, false, true>), dim3(c.L.F), dim3(kAsmThreads), ldsFast, s, c.L, c.T, x, h->dFc.p,
@@ -201,12 +213,16 @@ double evalFull(Ctx& c, const double* x, bool withStats, bool noReadBack) {
                            h->dFocal.p, h->dFocal.p + c.L.F, denseRecords(h));
       }
     } else if (h->dense) { if (stage && CVD_ASM_STAGE) CVD_LAUNCH_ASM(true, true); else CVD_LAUNCH_ASM(true, false); }
+    else if (spec == 1) { if (stage && CVD_ASM_STAGE) CVD_LAUNCH_ASM_S(false, true, 1); else CVD_LAUNCH_ASM_S(false, false, 1); }
+    else if (spec == 2) { if (stage && CVD_ASM_STAGE) CVD_LAUNCH_ASM_S(false, true, 2); else CVD_LAUNCH_ASM_S(false, false, 2); }
     else { if (stage && CVD_ASM_STAGE) CVD_LAUNCH_ASM(false, true); else CVD_LAUNCH_ASM(false, false); }
 #undef CVD_LAUNCH_ASM
+#undef CVD_LAUNCH_ASM_S
   } else {
     if (h->dense && c.L.includeStatic) throw std::logic_error("dense mode: the generic assembly has no images to read (DenseListScope should have taken this solve)");
     const AsmPanels panels = makePanels(static_cast<int>(B), (kMaxLds - ldsRest) / 8, panelCap);
     const size_t lds = static_cast<size_t>(panelCap) * 8 + ldsRest;
+    recordAsm(256, 0, c.KD, 0, c.L.F, 0);
     CVD_DISPATCH(c.KD, c.KS, {
       allowLds(k_assemble<KD, KS>, lds);
       hipLaunchKernelGGL((k_assemble<KD, KS>), dim3(c.L.F), dim3(256), lds, s, c.L, c.T, x, h->dFc.p, h->dMask.p,

@@ -391,6 +391,8 @@ struct cvd_handle_t {
   int lastKD = 0;
   // cvd_product_launch_debug: {threads per workgroup, SPEC, KD, kind, work items, numCU} of the last launchMatvec (kind -1: none yet)
   int lastProduct[6] = {0, 0, 0, -1, 0, 0};
+  // cvd_assembly_launch_debug: {threads per workgroup, SPEC, KD, kind, workgroups, parts of split frames} of the last evalFull (kind -1: none yet)
+  int lastAssembly[6] = {0, 0, 0, -1, 0, 0};
   bool tailDisabled = false;  // k_pcg_tail abandoned its grid barrier once on this handle: two-launch tail from then on (runPcg)
   bool forceGeneric = false;  // test hook: route the products through the generic (all-variants) kernel
 
