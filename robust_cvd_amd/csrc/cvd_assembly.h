@@ -321,7 +321,6 @@ __device__ __forceinline__ void asmWalkSpec(const Layout& L, const Table& T, Rec
                                             int lane, const bool side, const FrameConst& Fa, const FrameConst& Fb,
                                             const double* __restrict__ xa, const double* __restrict__ xb, double* Hs,
                                             double* gs, double (&PP)[28], double (&gp)[7], double (&GD)[19], double& cost) {
-  constexpr double eps = 1e-6;
   const double A = L.aspect;
   double RaU[9], RbU[9], dTU[3];
 #pragma unroll
@@ -349,40 +348,20 @@ __device__ __forceinline__ void asmWalkSpec(const Layout& L, const Table& T, Rec
     Db *= db;
     const double pax = static_cast<double>(nd.x), pay = static_cast<double>(nd.y);
     const double pbx = static_cast<double>(nd.z), pby = static_cast<double>(nd.w);
-    const double ca[3] = {pax * fxa, pay * fya, -1.0};
-    const double Rca[3] = {dot3(RaU, ca), dot3(RaU + 3, ca), dot3(RaU + 6, ca)};
+    double ca[3], Rca[3];
+    fastRay(RaU, pax, pay, fxa, fya, ca, Rca);
     const double v[3] = {dTU[0] + Rca[0] * Da, dTU[1] + Rca[1] * Da, dTU[2] + Rca[2] * Da};
-    const double q0 = RbU[0] * v[0] + RbU[3] * v[1] + RbU[6] * v[2];
-    const double q1 = RbU[1] * v[0] + RbU[4] * v[1] + RbU[7] * v[2];
-    const double q2 = RbU[2] * v[0] + RbU[5] * v[1] + RbU[8] * v[2];
-    const double zz = -q2;
-    const double iz = rcpFast(zz);
-    const double u = q0 * iz * ifxb;
-    const double vv = q1 * iz * ifyb;
-    double r[3];
-    r[0] = (u - pbx) * L.ws;
-    r[1] = (vv - pby) * L.ws;
-    const bool zo = !(zz < eps), bo = !(Db < eps);
-    const double izc = zo ? iz : 1.0 / eps, ibc = rcpFast(bo ? Db : eps);
-    r[2] = (izc - ibc) * L.wd;
-    const double dr2dA = zo ? (-L.wd * izc * izc) : 0.0;
-    const double dr2dDb = bo ? (L.wd * ibc * ibc) : 0.0;
+    double zz, iz, u, vv, r[3], dr2dA, dr2dDb;
+    fastProject<true>(L, RbU, v, ifxb, ifyb, pbx, pby, zz, iz, u, vv, r[0], r[1]);
+    fastDepthResidual<true>(L, kLossDisparity, zz, iz, Db, r[2], dr2dA, dr2dDb);
     const double sq = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-    double w;  // rho'; rho goes to the cost on the source visit (every constraint is counted once)
-    if constexpr (SPEC == 1) {
-      const double sum = 1.0 + sq * L.cauchyC;
-      w = rcpFast(sum);
-      if (!side) cost += L.cauchyB * log(sum);
-    } else {
-      const bool outer = sq > L.cauchyB;
-      const double irt = rsqrtFast(outer ? sq : 1.0);
-      w = outer ? fmax(2.2250738585072014e-308, L.robustA * irt) : 1.0;
-      if (!side) cost += outer ? (2.0 * L.robustA * (sq * irt) - L.cauchyB) : sq;
-    }
+    const double w = fastRobustRho1<SPEC>(L, sq);     // rho'
+    if (!side) cost += fastRobustRho0<SPEC>(L, sq);  // rho: on the source visit (every constraint is counted once)
 
-    // d r / d q (rows): M0 = (m00, 0, m02), M1 = (0, m11, m12), M2 = (0, 0, m22);  G = M R_b^T
-    const double wiz = L.ws * iz;
-    const double m00 = wiz * ifxb, m11 = wiz * ifyb, m02 = wiz * u, m12 = wiz * vv, m22 = -dr2dA;
+    // d r / d q (rows, fastRows);  G = M R_b^T
+    double m00, m11, m02, m12;
+    fastRows(L, iz, u, vv, ifxb, ifyb, m00, m11, m02, m12);
+    const double m22 = -dr2dA;
     double G[3][3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {

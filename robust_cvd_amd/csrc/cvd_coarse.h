@@ -145,7 +145,6 @@ inline __global__ __launch_bounds__(256) void k_coarse_edges_fast(Layout L, Tabl
                                                            const int* __restrict__ itemEdge, double* __restrict__ edgeOut,
                                                            double* __restrict__ dropDiag) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  constexpr double eps = 1e-6;
   const int B = L.B;
   double* xa = sm;
   double* xb = sm + B;
@@ -216,44 +215,16 @@ inline __global__ __launch_bounds__(256) void k_coarse_edges_fast(Layout L, Tabl
       }
       const double pax = static_cast<double>(nd.x), pay = static_cast<double>(nd.y);
       const double pbx = static_cast<double>(nd.z), pby = static_cast<double>(nd.w);
-      const double ca[3] = {pax * fxa, pay * fya, -1.0};
-      const double Rca[3] = {dot3(Fa.R, ca), dot3(Fa.R + 3, ca), dot3(Fa.R + 6, ca)};
+      double ca[3], Rca[3];
+      fastRay(Fa.R, pax, pay, fxa, fya, ca, Rca);
       const double v[3] = {Fa.t[0] + Rca[0] * Da - Fb.t[0], Fa.t[1] + Rca[1] * Da - Fb.t[1], Fa.t[2] + Rca[2] * Da - Fb.t[2]};
-      const double q0 = Fb.R[0] * v[0] + Fb.R[3] * v[1] + Fb.R[6] * v[2];
-      const double q1 = Fb.R[1] * v[0] + Fb.R[4] * v[1] + Fb.R[7] * v[2];
-      const double q2 = Fb.R[2] * v[0] + Fb.R[5] * v[1] + Fb.R[8] * v[2];
-      const double zz = -q2;
-      const double iz = 1.0 / zz;
-      const double u = q0 * iz * ifxb;
-      const double vv = q1 * iz * ifyb;
-      const double r0 = (u - pbx) * L.ws;
-      const double r1 = (vv - pby) * L.ws;
-      double r2, dr2dA, dr2dDb;
-      if (L.lossType == kLossDisparity) {
-        const bool zo = !(zz < eps), bo = !(Db < eps);
-        const double izc = zo ? iz : 1.0 / eps, ibc = 1.0 / (bo ? Db : eps);
-        r2 = (izc - ibc) * L.wd;
-        dr2dA = zo ? (-L.wd * izc * izc) : 0.0;
-        dr2dDb = bo ? (L.wd * ibc * ibc) : 0.0;
-      } else {
-        const bool zIsMax = !(zz < Db), zIsMin = !(Db < zz);
-        const double mx = zIsMax ? zz : Db, mn = zIsMin ? zz : Db;
-        if (L.lossType == kLossRatio) {
-          r2 = (mx / mn - 1.0) * L.wd;
-          const double dmx = 1.0 / mn, dmn = -mx / (mn * mn);
-          dr2dA = ((zIsMax ? dmx : 0.0) + (zIsMin ? dmn : 0.0)) * L.wd;
-          dr2dDb = ((zIsMax ? 0.0 : dmx) + (zIsMin ? 0.0 : dmn)) * L.wd;
-        } else {
-          r2 = log(mn / mx) * L.wd;
-          const double dmn = 1.0 / mn, dmx = -1.0 / mx;
-          dr2dA = ((zIsMax ? dmx : 0.0) + (zIsMin ? dmn : 0.0)) * L.wd;
-          dr2dDb = ((zIsMax ? 0.0 : dmx) + (zIsMin ? 0.0 : dmn)) * L.wd;
-        }
-      }
+      double zz, iz, u, vv, r0, r1, r2, dr2dA, dr2dDb;
+      fastProject<false>(L, Fb.R, v, ifxb, ifyb, pbx, pby, zz, iz, u, vv, r0, r1);
+      fastDepthResidual<false>(L, L.lossType, zz, iz, Db, r2, dr2dA, dr2dDb);
       const double w = robustRho1(L, r0 * r0 + r1 * r1 + r2 * r2);
-      // d r / d q (rows): M0 = (m00, 0, m02), M1 = (0, m11, m12), M2 = (0, 0, m22)
-      const double wiz = L.ws * iz;
-      const double m00 = wiz * ifxb, m11 = wiz * ifyb, m02 = wiz * u, m12 = wiz * vv, m22 = -dr2dA;
+      double m00, m11, m02, m12;
+      fastRows(L, iz, u, vv, ifxb, ifyb, m00, m11, m02, m12);
+      const double m22 = -dr2dA;
       // Z-projected Jacobians: 7 pose columns + the uniform depth-scale column (d r / d scale_k = JD w_k d_src and the
       // interpolation weights sum to one) of the source side (Js) and of the target side (Jt)
       double Js[3][kCB], Jt[3][kCB];

@@ -114,7 +114,6 @@ template <int KD, bool DENSE = false>
 inline __global__ __launch_bounds__(256) void k_cost_items_fast(Layout L, Table T, Items it, const double* __restrict__ x,
                                                          const FrameConst* __restrict__ fc, double* __restrict__ costItem) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  constexpr double eps = 1e-6;
   const int B = L.B;
   double* xa = sm;
   double* xb = sm + B;
@@ -182,25 +181,12 @@ inline __global__ __launch_bounds__(256) void k_cost_items_fast(Layout L, Table 
       }
       const double pax = static_cast<double>(nd.x), pay = static_cast<double>(nd.y);
       const double pbx = static_cast<double>(nd.z), pby = static_cast<double>(nd.w);
-      const double ca[3] = {pax * fxa, pay * fya, -1.0};
-      const double Rca[3] = {dot3(Fa.R, ca), dot3(Fa.R + 3, ca), dot3(Fa.R + 6, ca)};
+      double ca[3], Rca[3];
+      fastRay(Fa.R, pax, pay, fxa, fya, ca, Rca);
       const double v[3] = {Fa.t[0] + Rca[0] * Da - Fb.t[0], Fa.t[1] + Rca[1] * Da - Fb.t[1], Fa.t[2] + Rca[2] * Da - Fb.t[2]};
-      const double q0 = Fb.R[0] * v[0] + Fb.R[3] * v[1] + Fb.R[6] * v[2];
-      const double q1 = Fb.R[1] * v[0] + Fb.R[4] * v[1] + Fb.R[7] * v[2];
-      const double q2 = Fb.R[2] * v[0] + Fb.R[5] * v[1] + Fb.R[8] * v[2];
-      const double zz = -q2;
-      const double iz = 1.0 / zz;
-      const double r0 = (q0 * iz * ifxb - pbx) * L.ws;
-      const double r1 = (q1 * iz * ifyb - pby) * L.ws;
-      double r2;
-      if (L.lossType == kLossDisparity) {
-        const double zc = !(zz < eps) ? zz : eps, bc = !(Db < eps) ? Db : eps;
-        r2 = (1.0 / zc - 1.0 / bc) * L.wd;
-      } else {
-        const bool zIsMax = !(zz < Db), zIsMin = !(Db < zz);
-        const double mx = zIsMax ? zz : Db, mn = zIsMin ? zz : Db;
-        r2 = (L.lossType == kLossRatio ? (mx / mn - 1.0) : log(mn / mx)) * L.wd;
-      }
+      double zz, iz, u, vv, r0, r1, r2, dr2dA, dr2dDb;
+      fastProject<false>(L, Fb.R, v, ifxb, ifyb, pbx, pby, zz, iz, u, vv, r0, r1);
+      fastDepthResidual<false>(L, L.lossType, zz, iz, Db, r2, dr2dA, dr2dDb);  // (value only: the derivatives drop out)
       double rho0, rho1;
       robustRho(L, r0 * r0 + r1 * r1 + r2 * r2, rho0, rho1);
       acc += rho0;

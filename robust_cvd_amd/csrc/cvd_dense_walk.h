@@ -142,7 +142,6 @@ struct DwPairConst {
 __device__ __forceinline__ void dwChain(const Layout& L, const DwPairConst& P, const double* __restrict__ xs,
                                         const double* __restrict__ xt, const float4& nd, double da, double db, const DwTaps& ts,
                                         const DwTaps& tt, DwState& o) {
-  constexpr double eps = 1e-6;
   const int gx = L.gx, gMax = L.nD - 1;
   // (the same tap order and summation order as fastGather / the other fast kernels)
   double Da = 0.0, Db = 0.0;
@@ -157,42 +156,14 @@ __device__ __forceinline__ void dwChain(const Layout& L, const DwPairConst& P, c
   const double ca[3] = {pax * P.fxs, pay * P.fys, -1.0};
   double v[3];
 #pragma unroll
-  for (int i = 0; i < 3; ++i) {
+  for (int i = 0; i < 3; ++i) {  // (R_s c row by row with v: the order the walk's schedule was tuned in)
     o.Rca[i] = dot3(P.Rs + 3 * i, ca);
     v[i] = P.dT[i] + o.Rca[i] * Da;
   }
-  const double q0 = P.Rt[0] * v[0] + P.Rt[3] * v[1] + P.Rt[6] * v[2];
-  const double q1 = P.Rt[1] * v[0] + P.Rt[4] * v[1] + P.Rt[7] * v[2];
-  const double q2 = P.Rt[2] * v[0] + P.Rt[5] * v[1] + P.Rt[8] * v[2];
-  const double zz = -q2;
-  const double iz = rcpFast(zz);   // (1 - 2 ulp: cvd_kernels.h; the IEEE division sequence is twice the instructions)
-  const double u = q0 * iz * P.ifxt;
-  const double vv = q1 * iz * P.ifyt;
-  o.zz = zz;
-  o.r[0] = (u - pbx) * L.ws;
-  o.r[1] = (vv - pby) * L.ws;
-  double dr2dA, dr2dDb;
-  if (L.lossType == kLossDisparity) {
-    const bool zo = !(zz < eps), bo = !(Db < eps);
-    const double izc = zo ? iz : 1.0 / eps, ibc = rcpFast(bo ? Db : eps);
-    o.r[2] = (izc - ibc) * L.wd;
-    dr2dA = zo ? (-L.wd * izc * izc) : 0.0;
-    dr2dDb = bo ? (L.wd * ibc * ibc) : 0.0;
-  } else {
-    const bool zIsMax = !(zz < Db), zIsMin = !(Db < zz);
-    const double mx = zIsMax ? zz : Db, mn = zIsMin ? zz : Db;
-    if (L.lossType == kLossRatio) {
-      o.r[2] = (mx / mn - 1.0) * L.wd;
-      const double dmx = 1.0 / mn, dmn = -mx / (mn * mn);
-      dr2dA = ((zIsMax ? dmx : 0.0) + (zIsMin ? dmn : 0.0)) * L.wd;
-      dr2dDb = ((zIsMax ? 0.0 : dmx) + (zIsMin ? 0.0 : dmn)) * L.wd;
-    } else {
-      o.r[2] = log(mn / mx) * L.wd;
-      const double dmn = 1.0 / mn, dmx = -1.0 / mx;
-      dr2dA = ((zIsMax ? dmx : 0.0) + (zIsMin ? dmn : 0.0)) * L.wd;
-      dr2dDb = ((zIsMax ? 0.0 : dmx) + (zIsMin ? 0.0 : dmn)) * L.wd;
-    }
-  }
+  // (the reciprocals in their fast form, 1 - 2 ulp: the IEEE division sequence is twice the instructions)
+  double iz, u, vv, dr2dA;
+  fastProject<true>(L, P.Rt, v, P.ifxt, P.ifyt, pbx, pby, o.zz, iz, u, vv, o.r[0], o.r[1]);
+  fastDepthResidual<true>(L, L.lossType, o.zz, iz, Db, o.r[2], dr2dA, o.JDT2);
   {
     const double sq = o.r[0] * o.r[0] + o.r[1] * o.r[1] + o.r[2] * o.r[2];
     if (L.robustKind == kRobustCauchy) {   // (robustRho with the reciprocal and the square root of rho' in their fast forms)
@@ -205,13 +176,8 @@ __device__ __forceinline__ void dwChain(const Layout& L, const DwPairConst& P, c
       o.sw = sqrt(o.w);
     }
   }
-  const double wiz = L.ws * iz;
-  o.m00 = wiz * P.ifxt;
-  o.m11 = wiz * P.ifyt;
-  o.m02 = wiz * u;
-  o.m12 = wiz * vv;
+  fastRows(L, iz, u, vv, P.ifxt, P.ifyt, o.m00, o.m11, o.m02, o.m12);
   o.m22 = -dr2dA;
-  o.JDT2 = dr2dDb;
 }
 
 // The Jacobian row that d r / d q = mu stands for, in FEATURE form.  With g = R_t mu, y = D_s R_s c, n = y x g, v = dT + y the 15

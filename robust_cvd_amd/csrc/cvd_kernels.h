@@ -1,6 +1,7 @@
 // cvd_kernels.h -- what every solver kernel header shares, and the hot kernel: the plain types the host hands to the kernels
 // (Table, Items, AsmWork, DenseRecords, RegCache, CoarsePlan, CrossPairs, TripletTable, ...), the device helpers more than one
-// header needs (dense pixel geometry, loadConstraint / RecordStream, FastTaps, the inter-workgroup hand-offs, pcgFinishScalars),
+// header needs (dense pixel geometry, loadConstraint / RecordStream, FastTaps, the fast scope's constraint model -- fastRay ...
+// fastRows, the one statement every fast kernel calls --, the inter-workgroup hand-offs, pcgFinishScalars),
 // the CVD_DETERMINISTIC default and the CVD_MV_* knobs, and the pair product (k_matvec_pairs_fast, k_matvec_pairs).
 // cvd_host.h includes this header and no other kernel header: NO non-template __global__ function may be defined here (a unit
 // emits device code for every non-template kernel it parses; tests/test_codegen_units.py).
@@ -686,7 +687,8 @@ __device__ __forceinline__ void fastGather(const Layout& L, float lx, float ly, 
 }
 
 // 1 / x to f64 accuracy (1-2 ulp; not correctly rounded): hardware estimate + two Newton steps, 5 instructions instead of the
-// ~10 of the IEEE division sequence (div_scale x2, rcp, fma chain, div_fmas, div_fixup).  For the hot product's loop only.
+// ~10 of the IEEE division sequence (div_scale x2, rcp, fma chain, div_fmas, div_fixup).  For the specialised constraint loops
+// (the FAST policy of the constraint model below).
 __device__ __forceinline__ double rcpFast(double x) {
   double r = __builtin_amdgcn_rcp(x);
   double e = __builtin_fma(-x, r, 1.0);
@@ -708,6 +710,120 @@ __device__ __forceinline__ double rsqrtFast(double x) {
 // A wave-uniform double as a scalar (SGPR pair): the compiler cannot prove that an LDS load is uniform.
 __device__ __forceinline__ double uniformValue(double v) {
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
+// =====================================================================================================
+// The constraint model of the fast scope, stated ONCE.  A constraint a -> b with interpolated depths D_a, D_b:
+//   q = R_b^T v, v = t_a + D_a R_a c_a - t_b;   z' = -q_z, (u, v') = (q_x / (z' fx_b), q_y / (z' fy_b));
+//   r = (ws (u - p_b.x), ws (v' - p_b.y), wd r_depth(z', D_b)),   weight rho'(|r|^2)
+// and the rows M = d r / d q of its Jacobian.  Users: k_cost_items_fast (value only), k_coarse_edges_fast, k_tl_edges,
+// k_matvec_pairs_fast, the specialised walk of k_assemble_fast (asmWalkSpec) and dwChain of k_dense_walk.  The generic evalSample
+// (cvd_device.h) is the independent statement the tests hold these against.  What differs between the users in the last bits
+// stays at the call site: how v is summed (t_a - t_b pre-combined or not), the interpolated depths and the pose columns built
+// on M.  The runtime-variant walk of k_assemble_fast (SPEC = 0) keeps its own text of the whole chain: through these functions
+// its multiply-adds contracted differently and the bicubic variant's gradient moved in the last bits.  The one numeric policy
+// here is FAST: hardware reciprocals + two Newton steps (rcpFast) for IEEE divisions.
+// =====================================================================================================
+template <bool FAST>
+__device__ __forceinline__ double fastRcp(double x) {
+  if constexpr (FAST) return rcpFast(x);
+  else return 1.0 / x;
+}
+
+// the source ray c_a = (p_a.x fx_a, p_a.y fy_a, -1) and R_a c_a
+__device__ __forceinline__ void fastRay(const double* Ra, double pax, double pay, double fxa, double fya, double (&ca)[3],
+                                        double (&Rca)[3]) {
+  ca[0] = pax * fxa;
+  ca[1] = pay * fya;
+  ca[2] = -1.0;
+  Rca[0] = dot3(Ra, ca);
+  Rca[1] = dot3(Ra + 3, ca);
+  Rca[2] = dot3(Ra + 6, ca);
+}
+
+// projection into the target frame: z' (zz), 1 / z' (iz), the normalised image point (u, vv) and the two reprojection residuals
+template <bool FAST>
+__device__ __forceinline__ void fastProject(const Layout& L, const double* Rb, const double (&v)[3], double ifxb, double ifyb,
+                                            double pbx, double pby, double& zz, double& iz, double& u, double& vv, double& r0,
+                                            double& r1) {
+  const double q0 = Rb[0] * v[0] + Rb[3] * v[1] + Rb[6] * v[2];
+  const double q1 = Rb[1] * v[0] + Rb[4] * v[1] + Rb[7] * v[2];
+  const double q2 = Rb[2] * v[0] + Rb[5] * v[1] + Rb[8] * v[2];
+  zz = -q2;
+  iz = fastRcp<FAST>(zz);
+  u = q0 * iz * ifxb;
+  vv = q1 * iz * ifyb;
+  r0 = (u - pbx) * L.ws;
+  r1 = (vv - pby) * L.ws;
+}
+
+// depth residual r2 of the three reprojection losses with d r2 / d z' (dr2dA) and d r2 / d D_b.  Disparity: 1 / max(z', eps) -
+// 1 / max(D_b, eps), a clamped side has no derivative; Ratio: max / min - 1; LogRatio: log(min / max); at a tie z' = D_b both
+// one-sided derivatives count (zIsMax and zIsMin).  A value-only user drops the derivatives.
+template <bool FAST>
+__device__ __forceinline__ void fastDepthResidual(const Layout& L, int lossType, double zz, double iz, double Db, double& r2,
+                                                  double& dr2dA, double& dr2dDb) {
+  constexpr double eps = 1e-6;
+  if (lossType == kLossDisparity) {
+    const bool zo = !(zz < eps), bo = !(Db < eps);
+    const double bc = bo ? Db : eps;
+    const double izc = zo ? iz : 1.0 / eps, ibc = fastRcp<FAST>(bc);
+    r2 = (izc - ibc) * L.wd;
+    dr2dA = zo ? (-L.wd * izc * izc) : 0.0;
+    dr2dDb = bo ? (L.wd * ibc * ibc) : 0.0;
+  } else {
+    const bool zIsMax = !(zz < Db), zIsMin = !(Db < zz);
+    const double mx = zIsMax ? zz : Db, mn = zIsMin ? zz : Db;
+    if (lossType == kLossRatio) {
+      r2 = (mx / mn - 1.0) * L.wd;
+      const double dmx = 1.0 / mn, dmn = -mx / (mn * mn);
+      dr2dA = ((zIsMax ? dmx : 0.0) + (zIsMin ? dmn : 0.0)) * L.wd;
+      dr2dDb = ((zIsMax ? 0.0 : dmx) + (zIsMin ? 0.0 : dmn)) * L.wd;
+    } else {
+      r2 = log(mn / mx) * L.wd;
+      const double dmn = 1.0 / mn, dmx = -1.0 / mx;
+      dr2dA = ((zIsMax ? dmx : 0.0) + (zIsMin ? dmn : 0.0)) * L.wd;
+      dr2dDb = ((zIsMax ? 0.0 : dmx) + (zIsMin ? 0.0 : dmn)) * L.wd;
+    }
+  }
+}
+
+// rho' with the robustifier fixed at compile time.  SPEC 1: Cauchy, what the reference hard-wires; SPEC 2: Huber, BASELINE
+// configs[4]'s stress variant -- rho' = a / sqrt(s) beyond s = a^2, clamped like ceres::HuberLoss; SPEC 0: the runtime choice.
+// (Huber: the reciprocal root is a statement of its own, on an argument that is valid on both sides of s = a^2 -- selects, no
+// branch, in a loop that sits at its register budget.)
+template <int SPEC>
+__device__ __forceinline__ double fastRobustRho1(const Layout& L, double sq) {
+  if constexpr (SPEC == 1) return rcpFast(1.0 + sq * L.cauchyC);
+  else if constexpr (SPEC == 2) {
+    const bool outer = sq > L.cauchyB;
+    const double irt = rsqrtFast(outer ? sq : 1.0);
+    return outer ? fmax(2.2250738585072014e-308, L.robustA * irt) : 1.0;
+  }
+  else return robustRho1(L, sq);
+}
+// ... and rho itself for the two compile-time forms, written out on the same intermediates (a user of both pays for them once;
+// a separate function so that the caller can keep the logarithm under its own condition)
+template <int SPEC>
+__device__ __forceinline__ double fastRobustRho0(const Layout& L, double sq) {
+  static_assert(SPEC == 1 || SPEC == 2, "the runtime choice goes through robustRho");
+  if constexpr (SPEC == 1) {
+    return L.cauchyB * log(1.0 + sq * L.cauchyC);
+  } else {
+    const bool outer = sq > L.cauchyB;
+    const double irt = rsqrtFast(outer ? sq : 1.0);
+    return outer ? (2.0 * L.robustA * (sq * irt) - L.cauchyB) : sq;
+  }
+}
+
+// d r / d q (rows): M0 = (m00, 0, m02), M1 = (0, m11, m12), M2 = (0, 0, m22) with m22 = -dr2dA (the caller's)
+__device__ __forceinline__ void fastRows(const Layout& L, double iz, double u, double vv, double ifxb, double ifyb, double& m00,
+                                         double& m11, double& m02, double& m12) {
+  const double wiz = L.ws * iz;
+  m00 = wiz * ifxb;
+  m11 = wiz * ifyb;
+  m02 = wiz * u;
+  m12 = wiz * vv;
 }
 
 #ifdef CVD_MV_PROFILE  // tools/mv_profile.py: wall-clock (100 MHz) stamps of the hot product's workgroups
@@ -746,7 +862,6 @@ inline __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SPEC 
   const double sDone = scal[S_DONE];
   extern __shared__ __attribute__((aligned(16))) double sm[];
   constexpr int NV = KD == 1 ? kRedVals : 11;  // the depth-block sums exist only with one tap per side
-  constexpr double eps = 1e-6;
   const int B = L.B;
   if (threadIdx.x == 0) MV_STAMP(0);
   double* xa = sm;
@@ -977,47 +1092,13 @@ inline __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SPEC 
     }
     const double pax = static_cast<double>(nd.x), pay = static_cast<double>(nd.y);
     const double pbx = static_cast<double>(nd.z), pby = static_cast<double>(nd.w);
-    const double ca[3] = {pax * fxa, pay * fya, -1.0};
-    const double Rca[3] = {dot3(RaU, ca), dot3(RaU + 3, ca), dot3(RaU + 6, ca)};
+    double ca[3], Rca[3];
+    fastRay(RaU, pax, pay, fxa, fya, ca, Rca);
     const double v[3] = {dTU[0] + Rca[0] * Da, dTU[1] + Rca[1] * Da, dTU[2] + Rca[2] * Da};
-    const double q0 = RbU[0] * v[0] + RbU[3] * v[1] + RbU[6] * v[2];
-    const double q1 = RbU[1] * v[0] + RbU[4] * v[1] + RbU[7] * v[2];
-    const double q2 = RbU[2] * v[0] + RbU[5] * v[1] + RbU[8] * v[2];
-    const double zz = -q2;
-    const double iz = SPEC ? rcpFast(zz) : 1.0 / zz;
-    const double u = q0 * iz * ifxb;
-    const double vv = q1 * iz * ifyb;
-    const double r0 = (u - pbx) * L.ws;
-    const double r1 = (vv - pby) * L.ws;
-    double r2, dr2dA, dr2dDb;
-    if (lossType == kLossDisparity) {
-      const bool zo = !(zz < eps), bo = !(Db < eps);
-      const double zc = zo ? zz : eps, bc = bo ? Db : eps;
-      const double izc = zo ? iz : 1.0 / eps, ibc = SPEC ? rcpFast(bc) : 1.0 / bc;
-      r2 = (izc - ibc) * L.wd;
-      dr2dA = zo ? (-L.wd * izc * izc) : 0.0;
-      dr2dDb = bo ? (L.wd * ibc * ibc) : 0.0;
-    } else {
-      const bool zIsMax = !(zz < Db), zIsMin = !(Db < zz);
-      const double mx = zIsMax ? zz : Db, mn = zIsMin ? zz : Db;
-      if (lossType == kLossRatio) {
-        r2 = (mx / mn - 1.0) * L.wd;
-        const double dmx = 1.0 / mn, dmn = -mx / (mn * mn);
-        dr2dA = ((zIsMax ? dmx : 0.0) + (zIsMin ? dmn : 0.0)) * L.wd;
-        dr2dDb = ((zIsMax ? 0.0 : dmx) + (zIsMin ? 0.0 : dmn)) * L.wd;
-      } else {
-        r2 = log(mn / mx) * L.wd;
-        const double dmn = 1.0 / mn, dmx = -1.0 / mx;
-        dr2dA = ((zIsMax ? dmx : 0.0) + (zIsMin ? dmn : 0.0)) * L.wd;
-        dr2dDb = ((zIsMax ? 0.0 : dmx) + (zIsMin ? 0.0 : dmn)) * L.wd;
-      }
-    }
-    const double sq = r0 * r0 + r1 * r1 + r2 * r2;
-    // (SPEC 1: Cauchy, what the reference hard-wires; SPEC 2: Huber, BASELINE configs[4]'s stress variant -- rho' = a / sqrt(s)
-    // beyond s = a^2, clamped like ceres::HuberLoss)
-    const double rho1 = SPEC == 1 ? rcpFast(1.0 + sq * L.cauchyC)
-                                  : (SPEC == 2 ? (sq > L.cauchyB ? fmax(2.2250738585072014e-308, L.robustA * rsqrtFast(sq)) : 1.0)
-                                               : robustRho1(L, sq));
+    double zz, iz, u, vv, r0, r1, r2, dr2dA, dr2dDb;
+    fastProject<SPEC != 0>(L, RbU, v, ifxb, ifyb, pbx, pby, zz, iz, u, vv, r0, r1);
+    fastDepthResidual<SPEC != 0>(L, lossType, zz, iz, Db, r2, dr2dA, dr2dDb);
+    const double rho1 = fastRobustRho1<SPEC>(L, r0 * r0 + r1 * r1 + r2 * r2);
 
     // ---- forward: dX, dq, t
     // R c_f, c_f = d c_a / d fy = (c_a + e_z) / fy: the rotated ray plus R's third column (the 1 / fy sits in pfaU and, for the
@@ -1031,8 +1112,8 @@ inline __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SPEC 
     const double dq0 = RbU[0] * w3[0] + RbU[3] * w3[1] + RbU[6] * w3[2];
     const double dq1 = RbU[1] * w3[0] + RbU[4] * w3[1] + RbU[7] * w3[2];
     const double dq2 = RbU[2] * w3[0] + RbU[5] * w3[1] + RbU[8] * w3[2];
-    const double wiz = L.ws * iz;
-    const double m00 = wiz * ifxb, m11 = wiz * ifyb, m02 = wiz * u, m12 = wiz * vv;
+    double m00, m11, m02, m12;
+    fastRows(L, iz, u, vv, ifxb, ifyb, m00, m11, m02, m12);
     double t0 = (m00 * dq0 + m02 * dq2 - u * pfrU) * rho1;
     double t1 = (m11 * dq1 + m12 * dq2 - vv * pfrU) * rho1;
     double t2 = (-dr2dA * dq2 + dr2dDb * sDb) * rho1;

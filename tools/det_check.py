@@ -1,16 +1,25 @@
 #!/usr/bin/env python3
 """GPU: repeat the benchmark's solve of the final level from the same start state (fresh set_pose_params / set_xform_params every time)
-and print, per repeat, the PCG iterations of every LM iteration and the final cost as a hex float.  With the deterministic build
-(--variant det: lib/libcvd_hip_det.so, robust_cvd_amd.build.build_deterministic) every line must be identical bit for bit; with the
-product build the counts differ by an iteration here and there and the costs in the last digits (LDS atomics of several waves).
+and print, per repeat, the PCG iterations of every LM iteration, the final cost as a hex float and sha256 prefixes of the results
+(comparable across processes and commits).  With the deterministic build (--variant det: lib/libcvd_hip_det.so,
+robust_cvd_amd.build.build_deterministic) every line must be identical bit for bit; with the product build the counts differ by an
+iteration here and there and the costs in the last digits (LDS atomics of several waves).
 usage: det_check.py [--variant det] [--frames 300] [--level 6] [--reps 5] [--iterations 8]"""
 import argparse
+import hashlib
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 torch.cuda.init()
 from robust_cvd_amd import api, synth
+
+
+def digest(a):
+    """sha256 prefix of an array's bytes: the same in every process (hash() of bytes is salted per process), so two runs -- or two
+    commits -- can be compared by it."""
+    return hashlib.sha256(a.tobytes()).hexdigest()[:12]
+
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--variant", default=None)
@@ -38,8 +47,7 @@ if args.pipeline:
         s.pose_optimization(p)
         sm = s.summary()
         print("rep", r, "LM", sm["num_iterations"], "pcg", sm["total_linear_iterations"], "cost", float(sm["final_cost"]).hex(),
-              "pose-digest", hex(hash(s.get_pose_params().tobytes()) & 0xFFFFFFFFFFFF),
-              "theta-digest", hex(hash(s.get_xform_params().tobytes()) & 0xFFFFFFFFFFFF), flush=True)
+              "pose-sha256", digest(s.get_pose_params()), "theta-sha256", digest(s.get_xform_params()), flush=True)
         s.close()
     sys.exit(0)
 s = api.Solver(0)
@@ -56,4 +64,4 @@ for r in range(args.reps):
     sm = s.summary()
     x = s.get_pose_params()
     print("rep", r, "pcg", [int(q["linear_iterations"]) for q in recs[1:]], "cost", float(sm["final_cost"]).hex(),
-          "pose-digest", hex(hash(x.tobytes()) & 0xFFFFFFFFFFFF), flush=True)
+          "pose-sha256", digest(x), flush=True)
