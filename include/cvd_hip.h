@@ -672,6 +672,40 @@ int32_t cvd_dataset_batch_device(cvd_handle* h, int32_t batch_size, const int64_
 /* Indices the device entry point has clamped since cvd_dataset_create.  Waits for the device: for tests and debugging. */
 int32_t cvd_dataset_bad_indices(cvd_handle* h, int64_t* count);
 
+/* ---- RAFT's correlation pyramid, windowed lookup and convex upsampling, DESIGN.md §3.15.  Independent of cvd_set_video.  The two
+ * stages of the reference's flow network (raft/core/raft.py) that are neither a convolution nor a matmul; f32, forward only (RAFT
+ * runs under no_grad).  DEVICE arrays, enqueued on `stream` (a hipStream_t of the handle's device): ONE kernel launch each, no
+ * copy, no host synchronisation, no scratch of the handle -- calls need no ordering among themselves beyond the data's.  No
+ * atomics: every result repeats bit for bit.  Each call rejects, before any device work and with an error that names the value:
+ * sizes < 1, num_levels outside [1, 4], radius outside [1, 4], a coarsest level below 2 x 2 (the reference divides by size - 1:
+ * NaN), null arrays, an array that must be 16-byte aligned and is not.
+ *
+ * Pyramid -- reference raft/core/corr.py:15-23 and :48-56, what CorrBlock.__init__ does after its matmul:
+ *   raw        [Q][height][width]   fmap1^T fmap2, Q = B h1 w1 queries, (height, width) = (h2, w2) of frame 2; 16-byte aligned
+ *   levels     host array of num_levels device arrays, 16-byte aligned; levels[l] is [Q][height >> l][width >> l]
+ *   levels[0] = raw / sqrtf((float)dim), an IEEE f32 division (bit for bit torch's); levels[0] may BE raw (scaled in place).
+ *   levels[l + 1] = mean of the 2 x 2 cells of levels[l] (avg_pool2d(2, stride = 2): an odd last row or column is dropped). */
+int32_t cvd_raft_corr_pyramid_device(cvd_handle* h, int64_t num_queries, int32_t height, int32_t width, int32_t dim,
+                                     int32_t num_levels, const float* raw, float* const* levels, void* stream);
+/* Lookup -- reference raft/core/corr.py:25-46 (CorrBlock.__call__) with raft/core/utils/utils.py:56-70 (bilinear_sampler):
+ *   coords     [batch][2][h1][w1]   channel 0 = x, 1 = y, in level-0 pixels of frame 2
+ *   levels     as above, (h2, w2) the level-0 size
+ *   out        [batch][num_levels n^2][h1][w1], n = 2 radius + 1
+ * out channel l n^2 + a n + b = levels[l] of the query sampled at (x / 2^l + a - radius, y / 2^l + b - radius): the FIRST window
+ * index moves x (the reference's meshgrid(dy, dx) order; the trained weights depend on it).  Bilinear, pixel centres at integers
+ * (align_corners = True), corners by floor, corners outside the map count 0 (padding_mode = "zeros").  The n^2 taps of a query
+ * share one pair of fractions (the reference rounds each tap through a normalise / unnormalise round trip: last-bit differences).
+ * Any finite coordinate, however large, gives zeros; a non-finite one gives unspecified values; neither reads out of range. */
+int32_t cvd_raft_corr_lookup_device(cvd_handle* h, int32_t batch, int32_t h1, int32_t w1, int32_t h2, int32_t w2,
+                                    int32_t num_levels, int32_t radius, const float* const* levels, const float* coords,
+                                    float* out, void* stream);
+/* Convex upsampling -- reference raft/core/raft.py:49-60 (RAFT.upsample_flow):
+ *   flow [n][2][height][width], mask [n][576][height][width], out [n][2][8 height][8 width] (16-byte aligned)
+ *   out[n][c][8 y + i][8 x + j] = sum_k softmax_k(mask[n][64 k + 8 i + j][y][x]) 8 flow[n][c][y + k / 3 - 1][x + k % 3 - 1],
+ * flow outside the image counting 0 (unfold with padding 1); the softmax subtracts the maximum (stable for logits of +-100). */
+int32_t cvd_raft_upsample_flow_device(cvd_handle* h, int32_t n, int32_t height, int32_t width, const float* flow,
+                                      const float* mask, float* out, void* stream);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

@@ -323,6 +323,79 @@ def _hip_runtime():
     return _hip
 
 
+RAFT_MAX_LEVELS = 4   # kRaftMaxLevels / kRaftMaxRadius of csrc/cvd_raftops.h
+RAFT_MAX_RADIUS = 4
+
+
+def raft_level_shapes(h2, w2, levels):
+    """The (height, width) of the `levels` correlation maps over an h2 x w2 frame: each floor(half) of the one above.  ValueError
+    (before any device work) outside the operators' domain: 1..4 levels, the coarsest at least 2 x 2 -- the reference's sampler
+    divides by (size - 1), a 1-wide level is NaN there."""
+    if not 1 <= int(levels) <= RAFT_MAX_LEVELS:
+        raise ValueError(f"RAFT correlation: num_levels must be 1..{RAFT_MAX_LEVELS} (got {levels})")
+    shapes = [(int(h2) >> l, int(w2) >> l) for l in range(int(levels))]
+    if min(shapes[-1]) < 2:
+        raise ValueError(f"RAFT correlation: level {levels - 1} of a {h2} x {w2} map is {shapes[-1][0]} x {shapes[-1][1]}, below "
+                         "2 x 2 (the reference's lookup is NaN there)")
+    return shapes
+
+
+def raft_check_radius(radius):
+    if not 1 <= int(radius) <= RAFT_MAX_RADIUS:
+        raise ValueError(f"RAFT correlation: radius must be 1..{RAFT_MAX_RADIUS} (got {radius})")
+    return int(radius)
+
+
+def raft_check_dim(dim):
+    if int(dim) < 1:
+        raise ValueError(f"RAFT correlation: dim must be >= 1 (got {dim})")
+    return int(dim)
+
+
+def raft_check_upsample(flow_shape, mask_shape):
+    """(N, H, W) of flow [N, 2, H, W] and mask [N, 576, H, W]; ValueError for anything else."""
+    if len(flow_shape) != 4 or flow_shape[1] != 2 or min(flow_shape) < 1:
+        raise ValueError(f"RAFT upsampling: flow must be (N, 2, H, W) (got {tuple(flow_shape)})")
+    N, _, H, W = (int(v) for v in flow_shape)
+    if tuple(mask_shape) != (N, 576, H, W):
+        raise ValueError(f"RAFT upsampling: mask must be {(N, 576, H, W)} (got {tuple(mask_shape)})")
+    return N, H, W
+
+
+class _DeviceArrays:
+    """Raw device buffers of the numpy mirror of a `*_device` entry point (null stream, blocking copies); freed on exit."""
+
+    def __init__(self):
+        self._hip = _hip_runtime()
+        self._bufs = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for p in self._bufs:
+            self._hip.hipFree(p)
+        self._bufs = []
+
+    def alloc(self, nbytes):
+        p = C.c_void_p()
+        if self._hip.hipMalloc(C.byref(p), max(int(nbytes), 1)) != 0:
+            raise RuntimeError("hipMalloc failed")
+        self._bufs.append(p)
+        return p
+
+    def upload(self, a):
+        p = self.alloc(a.nbytes)
+        if a.nbytes and self._hip.hipMemcpy(p, a.ctypes.data_as(C.c_void_p), a.nbytes, 1) != 0:
+            raise RuntimeError("hipMemcpy failed")
+        return p
+
+    def download(self, p, a):
+        if a.nbytes and self._hip.hipMemcpy(a.ctypes.data_as(C.c_void_p), p, a.nbytes, 2) != 0:
+            raise RuntimeError("hipMemcpy failed")
+        return a
+
+
 def adam_record(step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
     """The scalars of step number `step` (1, 2, ...) of torch.optim.Adam, in double as torch/optim/adam.py forms them."""
     beta1, beta2 = betas
@@ -404,7 +477,8 @@ EXPORTED_SYMBOLS = [
     "cvd_reset_poses", "cvd_reset_depth_xforms", "cvd_reset_spatial_xforms", "cvd_grid_xform_split",
     "cvd_get_xform_desc", "cvd_num_xform_params", "cvd_get_xform_params", "cvd_set_xform_params",
     "cvd_get_pose_params", "cvd_set_pose_params", "cvd_block_size", "cvd_normalize_depth", "cvd_pose_optimization",
-    "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_scene_flow_loss", "cvd_scene_flow_loss_device", "cvd_spatial_losses", "cvd_spatial_losses_device", "cvd_param_chunk", "cvd_parameter_l1", "cvd_parameter_l1_device", "cvd_param_step", "cvd_param_step_device", "cvd_dataset_create", "cvd_dataset_clear", "cvd_dataset_set_colors", "cvd_dataset_set_flows", "cvd_dataset_set_depth_orig", "cvd_dataset_set_cameras", "cvd_dataset_set_xforms", "cvd_dataset_set_maps", "cvd_dataset_batch", "cvd_dataset_batch_device", "cvd_dataset_bad_indices", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
+    "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_scene_flow_loss", "cvd_scene_flow_loss_device", "cvd_spatial_losses", "cvd_spatial_losses_device", "cvd_param_chunk", "cvd_parameter_l1", "cvd_parameter_l1_device", "cvd_param_step", "cvd_param_step_device", "cvd_dataset_create", "cvd_dataset_clear", "cvd_dataset_set_colors", "cvd_dataset_set_flows", "cvd_dataset_set_depth_orig", "cvd_dataset_set_cameras", "cvd_dataset_set_xforms", "cvd_dataset_set_maps", "cvd_dataset_batch", "cvd_dataset_batch_device", "cvd_dataset_bad_indices",
+    "cvd_raft_corr_pyramid_device", "cvd_raft_corr_lookup_device", "cvd_raft_upsample_flow_device", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
     "cvd_get_kernel_times", "cvd_get_comm_times", "cvd_get_dense_times", "cvd_set_kernel_timing", "cvd_num_active_constraints", "cvd_coarse_debug", "cvd_temporal_debug", "cvd_path_info", "cvd_abi_revision",
     "cvd_block_inverse_debug", "cvd_dense_inverse_debug", "cvd_epipolar_debug", "cvd_flow_masks_debug",
     "cvd_product_launch_debug", "cvd_assembly_launch_debug",
@@ -908,6 +982,80 @@ class Solver(Binding):
         n = C.c_int64(0)
         self._check(self._fn("dataset_bad_indices")(self._h, C.byref(n)))
         return int(n.value)
+
+    # -- RAFT's correlation pyramid, lookup and convex upsampling (include/cvd_hip.h) on numpy arrays: each goes
+    #    through its `*_device` entry point with raw device buffers on the null stream.  Domain errors are ValueErrors, raised
+    #    before any device work (api.raft_level_shapes, raft_check_*). ------------------------------------------------------------
+    def raft_corr_pyramid(self, raw, dim, levels=4):
+        """CorrBlock.__init__ after its matmul: raw [Q, h2, w2] f32 (fmap1^T fmap2) -> the list of `levels` arrays
+        [Q, h2 >> l, w2 >> l]; level 0 = raw / sqrt(dim) bit for bit, the others 2 x 2 means."""
+        import numpy as np
+        raw = np.asarray(raw)
+        if raw.dtype != np.float32:
+            raise TypeError(f"raft_corr_pyramid: raw must be float32 (got {raw.dtype})")
+        if raw.ndim != 3 or min(raw.shape) < 1:
+            raise ValueError(f"raft_corr_pyramid: raw must be (Q, h2, w2) (got {raw.shape})")
+        raw = np.ascontiguousarray(raw)
+        Q, h2, w2 = raw.shape
+        shapes = raft_level_shapes(h2, w2, levels)
+        dim = raft_check_dim(dim)
+        out = [np.zeros((Q, h, w), np.float32) for h, w in shapes]
+        with _DeviceArrays() as dev:
+            ptrs = [dev.upload(raw)] + [dev.alloc(a.nbytes) for a in out[1:]]
+            table = (C.c_void_p * len(ptrs))(*[p.value for p in ptrs])
+            self._check(self._fn("raft_corr_pyramid_device")(self._h, C.c_int64(Q), C.c_int32(h2), C.c_int32(w2), C.c_int32(dim),
+                                                             C.c_int32(len(shapes)), ptrs[0], table, None))
+            for p, a in zip(ptrs, out):
+                dev.download(p, a)
+        return out
+
+    def raft_corr_lookup(self, levels_list, coords, radius=4):
+        """CorrBlock.__call__: levels_list = the pyramid (arrays [Q, h2 >> l, w2 >> l] f32, Q = B h1 w1), coords [B, 2, h1, w1]
+        f32 (channel 0 = x) -> [B, L (2 radius + 1)^2, h1, w1] f32."""
+        import numpy as np
+        lv = [np.asarray(a) for a in levels_list]
+        coords = np.asarray(coords)
+        if coords.dtype != np.float32 or any(a.dtype != np.float32 for a in lv):
+            raise TypeError("raft_corr_lookup: levels and coords must be float32")
+        if coords.ndim != 4 or coords.shape[1] != 2 or min(coords.shape) < 1:
+            raise ValueError(f"raft_corr_lookup: coords must be (B, 2, h1, w1) (got {coords.shape})")
+        if not lv or lv[0].ndim != 3:
+            raise ValueError("raft_corr_lookup: levels_list must hold arrays (Q, h, w)")
+        radius = raft_check_radius(radius)
+        B, _, h1, w1 = coords.shape
+        Q, h2, w2 = lv[0].shape
+        shapes = raft_level_shapes(h2, w2, len(lv))
+        if Q != B * h1 * w1:
+            raise ValueError(f"raft_corr_lookup: {Q} correlation maps for {B} x {h1} x {w1} queries")
+        for a, (h, w) in zip(lv, shapes):
+            if a.shape != (Q, h, w):
+                raise ValueError(f"raft_corr_lookup: a level has shape {a.shape}, expected {(Q, h, w)}")
+        n = 2 * radius + 1
+        out = np.zeros((B, len(lv) * n * n, h1, w1), np.float32)
+        with _DeviceArrays() as dev:
+            ptrs = [dev.upload(np.ascontiguousarray(a)) for a in lv]
+            table = (C.c_void_p * len(ptrs))(*[p.value for p in ptrs])
+            dc = dev.upload(np.ascontiguousarray(coords))
+            do = dev.alloc(out.nbytes)
+            self._check(self._fn("raft_corr_lookup_device")(self._h, C.c_int32(B), C.c_int32(h1), C.c_int32(w1), C.c_int32(h2),
+                                                            C.c_int32(w2), C.c_int32(len(lv)), C.c_int32(radius), table, dc, do, None))
+            dev.download(do, out)
+        return out
+
+    def raft_upsample_flow(self, flow, mask):
+        """RAFT.upsample_flow: flow [N, 2, H, W], mask [N, 576, H, W] f32 -> [N, 2, 8 H, 8 W] f32."""
+        import numpy as np
+        flow, mask = np.asarray(flow), np.asarray(mask)
+        if flow.dtype != np.float32 or mask.dtype != np.float32:
+            raise TypeError("raft_upsample_flow: flow and mask must be float32")
+        N, H, W = raft_check_upsample(flow.shape, mask.shape)
+        out = np.zeros((N, 2, 8 * H, 8 * W), np.float32)
+        with _DeviceArrays() as dev:
+            df, dm = dev.upload(np.ascontiguousarray(flow)), dev.upload(np.ascontiguousarray(mask))
+            do = dev.alloc(out.nbytes)
+            self._check(self._fn("raft_upsample_flow_device")(self._h, C.c_int32(N), C.c_int32(H), C.c_int32(W), df, dm, do, None))
+            dev.download(do, out)
+        return out
 
     def num_active_constraints(self):
         return int(self._lib.cvd_num_active_constraints(self._h))

@@ -822,6 +822,23 @@ int32_t cvd_dataset_batch(cvd_handle* h, int32_t batch_size, const int64_t* indi
   CVD_TRY(h, datasetBatch(h, batch_size, indices, out, kernel_ms));
 }
 int32_t cvd_dataset_bad_indices(cvd_handle* h, int64_t* count) { CVD_TRY(h, *count = datasetBadIndices(h)); }
+// reference raft/core/corr.py:15-23, 48-56 (CorrBlock.__init__ after the matmul: the scaling and the three avg_pool2d)
+int32_t cvd_raft_corr_pyramid_device(cvd_handle* h, int64_t num_queries, int32_t height, int32_t width, int32_t dim,
+                                     int32_t num_levels, const float* raw, float* const* levels, void* stream) {
+  CVD_TRY(h, raftCorrPyramidDevice(h, num_queries, height, width, dim, num_levels, raw, levels, static_cast<hipStream_t>(stream)));
+}
+// reference raft/core/corr.py:25-46 (CorrBlock.__call__) with raft/core/utils/utils.py:56-70 (bilinear_sampler)
+int32_t cvd_raft_corr_lookup_device(cvd_handle* h, int32_t batch, int32_t h1, int32_t w1, int32_t h2, int32_t w2,
+                                    int32_t num_levels, int32_t radius, const float* const* levels, const float* coords,
+                                    float* out, void* stream) {
+  CVD_TRY(h, raftCorrLookupDevice(h, batch, h1, w1, h2, w2, num_levels, radius, levels, coords, out,
+                                  static_cast<hipStream_t>(stream)));
+}
+// reference raft/core/raft.py:49-60 (RAFT.upsample_flow)
+int32_t cvd_raft_upsample_flow_device(cvd_handle* h, int32_t n, int32_t height, int32_t width, const float* flow,
+                                      const float* mask, float* out, void* stream) {
+  CVD_TRY(h, raftUpsampleFlowDevice(h, n, height, width, flow, mask, out, static_cast<hipStream_t>(stream)));
+}
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {

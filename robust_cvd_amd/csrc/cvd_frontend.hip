@@ -1,6 +1,7 @@
 // cvd_frontend.hip -- the steps either side of the solve: constraint sampling, epipolar RANSAC flags, image operators, dense
 // consumers, flow-guided and bilateral filters, feature tracks, flow consistency masks, the fine-tuning consistency,
-// scene-flow and spatial losses, the parameter regulariser and the optimizer step, the fine-tuning batches.  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
+// scene-flow and spatial losses, the parameter regulariser and the optimizer step, the fine-tuning batches, RAFT's correlation pyramid / lookup and convex
+// upsampling (cvd_raftops.h: k_corr_pyramid, k_corr_lookup, k_convex_upsample).  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
 // through a pointer to the incomplete type).
 #include "cvd_host.h"
 #include "cvd_dense.h"
@@ -17,6 +18,7 @@
 #include "cvd_spatial.h"
 #include "cvd_paramstep.h"
 #include "cvd_batch.h"
+#include "cvd_raftops.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -2102,6 +2104,101 @@ long long datasetBadIndices(cvd_handle* h) {
   unsigned int n = 0;
   HIP_CHECK(hipMemcpy(&n, ds.bad.p, sizeof(n), hipMemcpyDeviceToHost));
   return n;
+}
+
+// ---- RAFT's correlation pyramid, lookup and convex upsampling (reference raft/core/corr.py, raft/core/raft.py:49-60;
+// cvd_raftops.h).  Device arrays on the caller's stream: one launch each, no copy, no host wait, no scratch. -----
+namespace {
+void checkRaftPyramidShape(const char* who, int h2, int w2, int levels) {
+  if (levels < 1 || levels > kRaftMaxLevels)
+    throw std::runtime_error(fmt("%s: num_levels must be 1..%d (got %d)", who, kRaftMaxLevels, levels));
+  if (h2 < 1 || w2 < 1) throw std::runtime_error(fmt("%s: the correlation maps must be at least 1 x 1 (got %d x %d)", who, h2, w2));
+  // (the reference divides by (size - 1) of every level it samples: a 1-wide level is NaN there)
+  if ((h2 >> (levels - 1)) < 2 || (w2 >> (levels - 1)) < 2)
+    throw std::runtime_error(fmt("%s: level %d of a %d x %d map is %d x %d, below 2 x 2", who, levels - 1, h2, w2,
+                                 h2 >> (levels - 1), w2 >> (levels - 1)));
+}
+void checkAligned16(const char* who, const char* name, const void* p) {
+  if (!p) throw std::runtime_error(fmt("%s: null %s", who, name));
+  if (reinterpret_cast<uintptr_t>(p) & 15) throw std::runtime_error(fmt("%s: %s is not 16-byte aligned", who, name));
+}
+unsigned raftGrid(const char* who, long long threads) {
+  const long long blocks = (threads + kRaftThreads - 1) / kRaftThreads;
+  if (blocks > 0x7fffffffll) throw std::runtime_error(fmt("%s: %lld workgroups exceed the grid", who, blocks));
+  return static_cast<unsigned>(blocks);
+}
+}  // namespace
+
+void raftCorrPyramidDevice(cvd_handle*, long long Q, int h2, int w2, int dim, int levels, const float* raw, float* const* level,
+                           hipStream_t s) {
+  const char* who = "raft corr pyramid";
+  if (Q < 1) throw std::runtime_error(fmt("%s: num_queries must be >= 1 (got %lld)", who, Q));
+  if (dim < 1) throw std::runtime_error(fmt("%s: dim must be >= 1 (got %d)", who, dim));
+  checkRaftPyramidShape(who, h2, w2, levels);
+  checkAligned16(who, "raw", raw);
+  if (!level) throw std::runtime_error(fmt("%s: null levels", who));
+  CorrPyramidArgs A{};
+  A.raw = raw;
+  for (int l = 0; l < levels; ++l) {
+    checkAligned16(who, "level", level[l]);
+    A.level[l] = level[l];
+  }
+  A.Q = Q; A.h = h2; A.w = w2; A.levels = levels;
+  A.nbx = (w2 + 7) / 8; A.nby = (h2 + 7) / 8;
+  A.scale = sqrtf(static_cast<float>(dim));
+  const unsigned grid = raftGrid(who, corrPyramidThreads(A));
+  hipLaunchKernelGGL(k_corr_pyramid, dim3(grid), dim3(kRaftThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+}
+
+namespace {
+template <int R>
+void launchCorrLookup(const CorrLookupArgs& A, unsigned tiles, hipStream_t s) {
+  hipLaunchKernelGGL((k_corr_lookup<R>), dim3(tiles, A.levels), dim3(kRaftThreads), 0, s, A);
+}
+}  // namespace
+
+void raftCorrLookupDevice(cvd_handle*, int B, int h1, int w1, int h2, int w2, int levels, int radius, const float* const* level,
+                          const float* coords, float* out, hipStream_t s) {
+  const char* who = "raft corr lookup";
+  if (B < 1 || h1 < 1 || w1 < 1) throw std::runtime_error(fmt("%s: batch, h1 and w1 must be >= 1 (got %d, %d, %d)", who, B, h1, w1));
+  if (radius < 1 || radius > kRaftMaxRadius)
+    throw std::runtime_error(fmt("%s: radius must be 1..%d (got %d)", who, kRaftMaxRadius, radius));
+  checkRaftPyramidShape(who, h2, w2, levels);
+  if (static_cast<long long>(h1) * w1 > 0x7fffffffll) throw std::runtime_error(fmt("%s: %d x %d queries per image exceed 2^31", who, h1, w1));
+  if (!level || !coords || !out) throw std::runtime_error(fmt("%s: null array", who));
+  CorrLookupArgs A{};
+  for (int l = 0; l < levels; ++l) {
+    if (!level[l]) throw std::runtime_error(fmt("%s: null level %d", who, l));
+    A.level[l] = level[l];
+  }
+  A.coords = coords; A.out = out;
+  A.hw1 = h1 * w1;
+  A.Q = static_cast<long long>(B) * A.hw1;
+  A.h2 = h2; A.w2 = w2; A.levels = levels;
+  const long long tiles = (A.Q + kRaftTileQueries - 1) / kRaftTileQueries;
+  if (tiles > 0x7fffffffll) throw std::runtime_error(fmt("%s: %lld workgroups exceed the grid", who, tiles));
+  switch (radius) {
+    case 1: launchCorrLookup<1>(A, static_cast<unsigned>(tiles), s); break;
+    case 2: launchCorrLookup<2>(A, static_cast<unsigned>(tiles), s); break;
+    case 3: launchCorrLookup<3>(A, static_cast<unsigned>(tiles), s); break;
+    default: launchCorrLookup<4>(A, static_cast<unsigned>(tiles), s); break;
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+void raftUpsampleFlowDevice(cvd_handle*, int N, int H, int W, const float* flow, const float* mask, float* out, hipStream_t s) {
+  const char* who = "raft upsample flow";
+  if (N < 1 || H < 1 || W < 1) throw std::runtime_error(fmt("%s: n, height and width must be >= 1 (got %d, %d, %d)", who, N, H, W));
+  if (!flow || !mask) throw std::runtime_error(fmt("%s: null array", who));
+  checkAligned16(who, "out", out);
+  ConvexUpsampleArgs A{};
+  A.flow = flow; A.mask = mask; A.out = out;
+  A.H = H; A.W = W;
+  A.total = static_cast<long long>(N) * H * 8 * W;
+  const unsigned grid = raftGrid(who, A.total);
+  hipLaunchKernelGGL(k_convex_upsample, dim3(grid), dim3(kRaftThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
 }
 
 

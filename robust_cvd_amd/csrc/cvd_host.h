@@ -767,5 +767,10 @@ void datasetSetMaps(cvd_handle* h, const float* scales, int scaleIsMap, const fl
 void datasetBatchDevice(cvd_handle* h, int B, const int64_t* indices, const cvd_dataset_batch_out* out, hipStream_t s);
 void datasetBatch(cvd_handle* h, int B, const int64_t* indices, const cvd_dataset_batch_out* out, double* kernelMs);
 long long datasetBadIndices(cvd_handle* h);
+void raftCorrPyramidDevice(cvd_handle* h, long long Q, int h2, int w2, int dim, int levels, const float* raw, float* const* level,
+                           hipStream_t s);
+void raftCorrLookupDevice(cvd_handle* h, int B, int h1, int w1, int h2, int w2, int levels, int radius, const float* const* level,
+                          const float* coords, float* out, hipStream_t s);
+void raftUpsampleFlowDevice(cvd_handle* h, int N, int H, int W, const float* flow, const float* mask, float* out, hipStream_t s);
 
 }  // namespace cvd
