@@ -706,6 +706,34 @@ int32_t cvd_raft_corr_lookup_device(cvd_handle* h, int32_t batch, int32_t h1, in
 int32_t cvd_raft_upsample_flow_device(cvd_handle* h, int32_t n, int32_t height, int32_t width, const float* flow,
                                       const float* mask, float* out, void* stream);
 
+/* ---- SepConvGRU of RAFT's update block, DESIGN.md §3.16 -- reference raft/core/update.py:37-75 (SepConvGRU.forward with
+ * hidden_dim = 128, input_dim = 256, the only sizes BasicUpdateBlock builds).  Independent of cvd_set_video.  f32, forward only.
+ * Per half (1 x 5 with padding (0, 2), then 5 x 1 with padding (2, 0)):
+ *   z = sigmoid(conv_z([h, x])), r = sigmoid(conv_r([h, x])), q = tanh(conv_q([r h, x])), h = (1 - z) h + z q.
+ * DEVICE arrays, enqueued on `stream`: four kernel launches, no copy, no host synchronisation, no atomics; results repeat bit for
+ * bit and do not depend on how x is segmented.  Scratch (3 x 128 batch height width floats) belongs to the handle and keeps its
+ * high-water size: calls on one device must be ordered on one stream (the rule of the *_loss_device entry points), and a call
+ * that has to grow the scratch allocates (every call after the first of a shape does not).
+ *   hidden            [batch][128][height][width]
+ *   segments          host array of num_segments (1..3) device arrays; segments[i] is [batch][segment_channels[i]][height][width].
+ *                     x is their concatenation along the channels, which is never formed.
+ *   segment_channels  host array; positive multiples of 32 that sum to 256
+ *   weights, biases   host arrays of six device arrays in the order convz1, convr1, convq1, convz2, convr2, convq2, in torch's
+ *                     layout: weight [128][384][1][5] resp. [128][384][5][1] (the same memory order, k = 5 c + t), 16-byte
+ *                     aligned; bias [128]
+ *   out               [batch][128][height][width]; must not overlap hidden or a segment
+ * Rejected before any device work, with an error that names the value: sizes < 1, a wrong segment table, null arrays, a weight that
+ * is not 16-byte aligned, an output that overlaps an input. */
+int32_t cvd_raft_sepconv_gru_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, const float* hidden,
+                                    int32_t num_segments, const float* const* segments, const int32_t* segment_channels,
+                                    const float* const* weights, const float* const* biases, float* out, void* stream);
+/* The same call for measurement (tools/raftgru_bench.py): HIP events around the four launches on `stream`, then a host wait;
+ * kernel_ms[4] = {z and r of the 1 x 5 half, q and gate of it, z and r of the 5 x 1 half, q and gate of it} in milliseconds. */
+int32_t cvd_raft_sepconv_gru_timed(cvd_handle* h, int32_t batch, int32_t height, int32_t width, const float* hidden,
+                                   int32_t num_segments, const float* const* segments, const int32_t* segment_channels,
+                                   const float* const* weights, const float* const* biases, float* out, void* stream,
+                                   double* kernel_ms);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

@@ -362,6 +362,48 @@ def raft_check_upsample(flow_shape, mask_shape):
     return N, H, W
 
 
+GRU_HIDDEN = 128     # kGruHidden / kGruInput / kGruBlockChannels / kGruMaxSegments of csrc/cvd_raftgru.h
+GRU_INPUT = 256
+GRU_SEGMENT_MULTIPLE = 32
+GRU_MAX_SEGMENTS = 3
+GRU_PARAMETERS = ("convz1", "convr1", "convq1", "convz2", "convr2", "convq2")    # the entry point's order
+
+
+def raft_gru_weight_shape(name):
+    """Shape of `<name>.weight` of the reference's SepConvGRU(128, 256): 1 x 5 for the first half, 5 x 1 for the second."""
+    return (GRU_HIDDEN, GRU_HIDDEN + GRU_INPUT) + ((1, 5) if name.endswith("1") else (5, 1))
+
+
+def raft_check_gru(h_shape, x_shapes, weight_shapes, bias_shapes):
+    """(B, H, W) of h [B, 128, H, W] and the segments of x, each [B, C_i, H, W] with C_i a multiple of 32 and sum 256; the six
+    weight and six bias shapes in GRU_PARAMETERS order.  ValueError (before any device work) for anything else."""
+    who = "RAFT SepConvGRU"
+    h_shape = tuple(int(v) for v in h_shape)
+    if len(h_shape) != 4 or h_shape[1] != GRU_HIDDEN:
+        raise ValueError(f"{who}: h must be (B, {GRU_HIDDEN}, H, W) (got {h_shape}); hidden_dim is fixed at {GRU_HIDDEN}")
+    B, _, H, W = h_shape
+    if B * H * W == 0:
+        raise ValueError(f"{who}: B H W = 0 (h is {h_shape})")
+    x_shapes = [tuple(int(v) for v in s) for s in x_shapes]
+    if not 1 <= len(x_shapes) <= GRU_MAX_SEGMENTS:
+        raise ValueError(f"{who}: x must be one tensor or a tuple of up to {GRU_MAX_SEGMENTS} (got {len(x_shapes)})")
+    for s in x_shapes:
+        if len(s) != 4 or (s[0], s[2], s[3]) != (B, H, W):
+            raise ValueError(f"{who}: a segment of x has shape {s}, expected ({B}, C, {H}, {W})")
+        if s[1] < GRU_SEGMENT_MULTIPLE or s[1] % GRU_SEGMENT_MULTIPLE:
+            raise ValueError(f"{who}: a segment of x has {s[1]} channels, not a positive multiple of {GRU_SEGMENT_MULTIPLE}")
+    if sum(s[1] for s in x_shapes) != GRU_INPUT:
+        raise ValueError(f"{who}: x has {sum(s[1] for s in x_shapes)} channels; input_dim is fixed at {GRU_INPUT}")
+    if len(weight_shapes) != 6 or len(bias_shapes) != 6:
+        raise ValueError(f"{who}: six weights and six biases are expected, in the order {GRU_PARAMETERS}")
+    for name, ws, bs in zip(GRU_PARAMETERS, weight_shapes, bias_shapes):
+        if tuple(ws) != raft_gru_weight_shape(name):
+            raise ValueError(f"{who}: {name}.weight must be {raft_gru_weight_shape(name)} (got {tuple(ws)})")
+        if tuple(bs) != (GRU_HIDDEN,):
+            raise ValueError(f"{who}: {name}.bias must be ({GRU_HIDDEN},) (got {tuple(bs)})")
+    return B, H, W
+
+
 class _DeviceArrays:
     """Raw device buffers of the numpy mirror of a `*_device` entry point (null stream, blocking copies); freed on exit."""
 
@@ -478,7 +520,7 @@ EXPORTED_SYMBOLS = [
     "cvd_get_xform_desc", "cvd_num_xform_params", "cvd_get_xform_params", "cvd_set_xform_params",
     "cvd_get_pose_params", "cvd_set_pose_params", "cvd_block_size", "cvd_normalize_depth", "cvd_pose_optimization",
     "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_scene_flow_loss", "cvd_scene_flow_loss_device", "cvd_spatial_losses", "cvd_spatial_losses_device", "cvd_param_chunk", "cvd_parameter_l1", "cvd_parameter_l1_device", "cvd_param_step", "cvd_param_step_device", "cvd_dataset_create", "cvd_dataset_clear", "cvd_dataset_set_colors", "cvd_dataset_set_flows", "cvd_dataset_set_depth_orig", "cvd_dataset_set_cameras", "cvd_dataset_set_xforms", "cvd_dataset_set_maps", "cvd_dataset_batch", "cvd_dataset_batch_device", "cvd_dataset_bad_indices",
-    "cvd_raft_corr_pyramid_device", "cvd_raft_corr_lookup_device", "cvd_raft_upsample_flow_device", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
+    "cvd_raft_corr_pyramid_device", "cvd_raft_corr_lookup_device", "cvd_raft_upsample_flow_device", "cvd_raft_sepconv_gru_device", "cvd_raft_sepconv_gru_timed", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
     "cvd_get_kernel_times", "cvd_get_comm_times", "cvd_get_dense_times", "cvd_set_kernel_timing", "cvd_num_active_constraints", "cvd_coarse_debug", "cvd_temporal_debug", "cvd_path_info", "cvd_abi_revision",
     "cvd_block_inverse_debug", "cvd_dense_inverse_debug", "cvd_epipolar_debug", "cvd_flow_masks_debug",
     "cvd_product_launch_debug", "cvd_assembly_launch_debug",
@@ -1054,6 +1096,35 @@ class Solver(Binding):
             df, dm = dev.upload(np.ascontiguousarray(flow)), dev.upload(np.ascontiguousarray(mask))
             do = dev.alloc(out.nbytes)
             self._check(self._fn("raft_upsample_flow_device")(self._h, C.c_int32(N), C.c_int32(H), C.c_int32(W), df, dm, do, None))
+            dev.download(do, out)
+        return out
+
+    def raft_sepconv_gru(self, h, x, weights, biases):
+        """SepConvGRU.forward (raft/core/update.py:37-75): h [B, 128, H, W] f32, x [B, 256, H, W] f32 or a tuple
+        of up to three arrays whose channel counts are multiples of 32 and sum to 256 (never concatenated), weights / biases = the
+        six of convz1, convr1, convq1, convz2, convr2, convq2 in torch's shapes -> the new h [B, 128, H, W] f32."""
+        import numpy as np
+        segs = [np.asarray(a) for a in (x if isinstance(x, (tuple, list)) else (x,))]
+        h = np.asarray(h)
+        weights, biases = [np.asarray(a) for a in weights], [np.asarray(a) for a in biases]
+        for a in [h] + segs + weights + biases:
+            if a.dtype != np.float32:
+                raise TypeError(f"raft_sepconv_gru: every array must be float32 (got {a.dtype})")
+        B, H, W = raft_check_gru(h.shape, [a.shape for a in segs], [a.shape for a in weights], [a.shape for a in biases])
+        out = np.zeros((B, GRU_HIDDEN, H, W), np.float32)
+        with _DeviceArrays() as dev:
+            dh = dev.upload(np.ascontiguousarray(h))
+            ds = [dev.upload(np.ascontiguousarray(a)) for a in segs]
+            dw = [dev.upload(np.ascontiguousarray(a)) for a in weights]
+            db = [dev.upload(np.ascontiguousarray(a)) for a in biases]
+            do = dev.alloc(out.nbytes)
+            seg_table = (C.c_void_p * len(ds))(*[p.value for p in ds])
+            seg_channels = (C.c_int32 * len(ds))(*[a.shape[1] for a in segs])
+            w_table, b_table = (C.c_void_p * 6)(*[p.value for p in dw]), (C.c_void_p * 6)(*[p.value for p in db])
+            self._check(self._fn("raft_sepconv_gru_device")(self._h, C.c_int32(B), C.c_int32(H), C.c_int32(W), dh, C.c_int32(len(ds)),
+                                                            seg_table, seg_channels, w_table, b_table, do, None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("raft_sepconv_gru: the device reported an error")
             dev.download(do, out)
         return out
 

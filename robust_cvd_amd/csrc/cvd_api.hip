@@ -839,6 +839,20 @@ int32_t cvd_raft_upsample_flow_device(cvd_handle* h, int32_t n, int32_t height, 
                                       const float* mask, float* out, void* stream) {
   CVD_TRY(h, raftUpsampleFlowDevice(h, n, height, width, flow, mask, out, static_cast<hipStream_t>(stream)));
 }
+// reference raft/core/update.py:37-75 (SepConvGRU.forward)
+int32_t cvd_raft_sepconv_gru_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, const float* hidden,
+                                    int32_t num_segments, const float* const* segments, const int32_t* segment_channels,
+                                    const float* const* weights, const float* const* biases, float* out, void* stream) {
+  CVD_TRY(h, raftSepConvGruDevice(h, batch, height, width, hidden, num_segments, segments, segment_channels, weights, biases, out,
+                                  static_cast<hipStream_t>(stream), nullptr));
+}
+int32_t cvd_raft_sepconv_gru_timed(cvd_handle* h, int32_t batch, int32_t height, int32_t width, const float* hidden,
+                                   int32_t num_segments, const float* const* segments, const int32_t* segment_channels,
+                                   const float* const* weights, const float* const* biases, float* out, void* stream,
+                                   double* kernel_ms) {
+  CVD_TRY(h, raftSepConvGruDevice(h, batch, height, width, hidden, num_segments, segments, segment_channels, weights, biases, out,
+                                  static_cast<hipStream_t>(stream), kernel_ms));
+}
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {

@@ -1,7 +1,8 @@
 // cvd_frontend.hip -- the steps either side of the solve: constraint sampling, epipolar RANSAC flags, image operators, dense
 // consumers, flow-guided and bilateral filters, feature tracks, flow consistency masks, the fine-tuning consistency,
 // scene-flow and spatial losses, the parameter regulariser and the optimizer step, the fine-tuning batches, RAFT's correlation pyramid / lookup and convex
-// upsampling (cvd_raftops.h: k_corr_pyramid, k_corr_lookup, k_convex_upsample).  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
+// upsampling (cvd_raftops.h: k_corr_pyramid, k_corr_lookup, k_convex_upsample), the SepConvGRU of RAFT's update block
+// (cvd_raftgru.h: k_gru_gemm).  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
 // through a pointer to the incomplete type).
 #include "cvd_host.h"
 #include "cvd_dense.h"
@@ -19,6 +20,7 @@
 #include "cvd_paramstep.h"
 #include "cvd_batch.h"
 #include "cvd_raftops.h"
+#include "cvd_raftgru.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -127,6 +129,9 @@ struct Frontend {
   DevBuf<unsigned char> dLossIn[kLossMaxArrays], dLossGrad, dLossMaps;
   DevBuf<int32_t> dLossFrames[2];
   DevBuf<double> dLossOut;
+  // cvd_raftgru.h: sigmoid(z), r h and the state between the halves, 128 B H W floats each.  The device entry point uses them on
+  // the caller's stream (the loss operators' rule: calls on one device are ordered on one stream).
+  DevBuf<float> dGru;
 };
 
 std::shared_ptr<Frontend> makeFrontend() { return std::make_shared<Frontend>(); }
@@ -2201,6 +2206,86 @@ void raftUpsampleFlowDevice(cvd_handle*, int N, int H, int W, const float* flow,
   HIP_CHECK(hipGetLastError());
 }
 
+
+// ---- SepConvGRU of RAFT's update block (reference raft/core/update.py:37-75; cvd_raftgru.h).  Device arrays on
+// the caller's stream: four launches, no copy, no host wait once the handle's scratch has its size. ---------------------------------
+void raftSepConvGruDevice(cvd_handle* h, int B, int H, int W, const float* hidden, int numSegments, const float* const* segments,
+                          const int32_t* segmentChannels, const float* const* weights, const float* const* biases, float* out,
+                          hipStream_t s, double* kernelMs) {
+  const char* who = "raft sepconv gru";
+  if (B < 1 || H < 1 || W < 1) throw std::runtime_error(fmt("%s: batch, height and width must be >= 1 (got %d, %d, %d)", who, B, H, W));
+  const long long HW = static_cast<long long>(H) * W;
+  if (HW > 0x7fffffffll) throw std::runtime_error(fmt("%s: %d x %d pixels per image exceed 2^31", who, H, W));
+  const long long M = HW * B;
+  const long long tiles = (M + kGruTile - 1) / kGruTile;
+  if (tiles > 0x7fffffffll) throw std::runtime_error(fmt("%s: %lld workgroups exceed the grid", who, tiles));
+  if (numSegments < 1 || numSegments > kGruMaxSegments)
+    throw std::runtime_error(fmt("%s: num_segments must be 1..%d (got %d)", who, kGruMaxSegments, numSegments));
+  if (!hidden || !segments || !segmentChannels || !weights || !biases || !out) throw std::runtime_error(fmt("%s: null array", who));
+  int sum = 0;
+  for (int i = 0; i < numSegments; ++i) {
+    const int c = segmentChannels[i];
+    if (c < kGruBlockChannels || c % kGruBlockChannels)
+      throw std::runtime_error(fmt("%s: segment %d has %d channels, not a positive multiple of %d", who, i, c, kGruBlockChannels));
+    if (!segments[i]) throw std::runtime_error(fmt("%s: null segment %d", who, i));
+    sum += c;
+  }
+  if (sum != kGruInput) throw std::runtime_error(fmt("%s: the segments hold %d channels, input_dim is %d", who, sum, kGruInput));
+  for (int i = 0; i < 6; ++i) {
+    if (!biases[i]) throw std::runtime_error(fmt("%s: null bias %d", who, i));
+    checkAligned16(who, "weight", weights[i]);
+  }
+  // the output is written while the neighbours of x are still being read by other workgroups
+  const auto overlaps = [&](const float* a, long long channels) {
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(a), hi = lo + static_cast<uintptr_t>(channels) * M * sizeof(float);
+    const uintptr_t olo = reinterpret_cast<uintptr_t>(out), ohi = olo + static_cast<uintptr_t>(kGruHidden) * M * sizeof(float);
+    return lo < ohi && olo < hi;
+  };
+  if (overlaps(hidden, kGruHidden)) throw std::runtime_error(fmt("%s: out aliases h", who));
+  for (int i = 0; i < numSegments; ++i)
+    if (overlaps(segments[i], segmentChannels[i])) throw std::runtime_error(fmt("%s: out aliases segment %d of x", who, i));
+
+  Frontend& fe = *h->frontend;
+  const size_t plane = static_cast<size_t>(kGruHidden) * M;
+  fe.dGru.ensure(3 * plane);
+  float* z = fe.dGru.p;
+  float* rh = z + plane;
+  float* mid = rh + plane;
+
+  GruArgs A{};
+  int nb = kGruHidden / kGruBlockChannels;
+  for (int i = 0; i < numSegments; ++i)
+    for (int c = 0; c < segmentChannels[i]; c += kGruBlockChannels) A.blk[nb++] = GruBlock{segments[i], c, segmentChannels[i]};
+  A.M = M; A.HW = static_cast<int>(HW); A.W = W;
+  A.zOut = z; A.rhOut = rh; A.z = z;
+  KernelTimer timer(s, kernelMs, 4);   // (measurement only: tools/raftgru_bench.py; nothing is recorded with a null kernelMs)
+  timer.mark();
+  for (int half = 0; half < 2; ++half) {
+    const float* state = half == 0 ? hidden : mid;
+    A.len = half == 0 ? W : H;
+    A.stride = half == 0 ? 1 : W;
+    A.vertical = half;
+    A.h = state;
+    for (int c = 0; c < kGruHidden / kGruBlockChannels; ++c) A.blk[c] = GruBlock{state, c * kGruBlockChannels, kGruHidden};
+    A.w[0] = weights[3 * half]; A.w[1] = weights[3 * half + 1];
+    A.bias[0] = biases[3 * half]; A.bias[1] = biases[3 * half + 1];
+    A.out = nullptr;
+    hipLaunchKernelGGL((k_gru_gemm<false>), dim3(static_cast<unsigned>(tiles), 2 * kGruHidden / kGruTile), dim3(kGruThreads), 0, s, A);
+    HIP_CHECK(hipGetLastError());
+    timer.mark();
+    for (int c = 0; c < kGruHidden / kGruBlockChannels; ++c) A.blk[c] = GruBlock{rh, c * kGruBlockChannels, kGruHidden};
+    A.w[0] = weights[3 * half + 2]; A.w[1] = nullptr;
+    A.bias[0] = biases[3 * half + 2]; A.bias[1] = nullptr;
+    A.out = half == 0 ? mid : out;
+    hipLaunchKernelGGL((k_gru_gemm<true>), dim3(static_cast<unsigned>(tiles), kGruHidden / kGruTile), dim3(kGruThreads), 0, s, A);
+    HIP_CHECK(hipGetLastError());
+    timer.mark();
+  }
+  if (kernelMs) {
+    timer.wait();
+    timer.collect();
+  }
+}
 
 // One kernel of this translation unit's code object is looked up at handle creation: the HIP runtime loads a unit's device
 // code at its first use, ~20 ms per unit that would otherwise land in the first solve of a process (cvd_create: loadDeviceCode).

@@ -772,5 +772,8 @@ void raftCorrPyramidDevice(cvd_handle* h, long long Q, int h2, int w2, int dim, 
 void raftCorrLookupDevice(cvd_handle* h, int B, int h1, int w1, int h2, int w2, int levels, int radius, const float* const* level,
                           const float* coords, float* out, hipStream_t s);
 void raftUpsampleFlowDevice(cvd_handle* h, int N, int H, int W, const float* flow, const float* mask, float* out, hipStream_t s);
+void raftSepConvGruDevice(cvd_handle* h, int B, int H, int W, const float* hidden, int numSegments, const float* const* segments,
+                          const int32_t* segmentChannels, const float* const* weights, const float* const* biases, float* out,
+                          hipStream_t s, double* kernelMs);
 
 }  // namespace cvd

@@ -14,6 +14,11 @@ Raised before any device work: a CPU tensor, a dtype other than float32, an inpu
 (ValueError / TypeError / RuntimeError), and the domain errors of the operators (ValueError): 1..4 levels, radius 1..4, a coarsest
 level below 2 x 2 (NaN in the reference).
 
+SepConvGRU is the recurrent core of the update block (raft/core/update.py:37-75) with the reference's parameter names, on
+csrc/cvd_raftgru.h: `from robust_cvd_amd.raft_ops import SepConvGRU` in raft/core/update.py.  It refuses, with
+ValueError / TypeError and before any device work, other sizes than (128, 256), segments of x that are not multiples of 32
+channels, CPU tensors, other dtypes, and an input or parameter that requires grad while grad mode is on.
+
 Import this module (torch) before anything loads libcvd_hip.so.
 """
 import ctypes as C
@@ -78,6 +83,55 @@ class CorrBlock:
         out = torch.empty((batch, self.num_levels * n * n, ht, wd), dtype=torch.float32, device=coords.device)
         _call(coords.device, "raft_corr_lookup_device", C.c_int32(batch), C.c_int32(ht), C.c_int32(wd), C.c_int32(ht), C.c_int32(wd),
               C.c_int32(self.num_levels), C.c_int32(self.radius), self._table, tc.ptr(coords), tc.ptr(out))
+        return out
+
+
+class SepConvGRU(torch.nn.Module):
+    """The reference's SepConvGRU(hidden_dim=128, input_dim=256) (raft/core/update.py:37-75) with its parameter names and shapes,
+    so the update block's part of a RAFT state dict loads unchanged; forward(h, x) is four launches of csrc/cvd_raftgru.h
+    (DESIGN.md §3.16).  x is one [B, 256, H, W] tensor or a tuple of up to three whose channel counts are multiples of 32 and sum
+    to 256: the tuple is read where its tensors lie, no cat is formed.  Forward only, float32, GPU tensors; the result is a new
+    tensor.  The scratch is the device handle's: calls on one device are ordered on one stream."""
+
+    def __init__(self, hidden_dim=128, input_dim=256):
+        super().__init__()
+        if (hidden_dim, input_dim) != (api.GRU_HIDDEN, api.GRU_INPUT):
+            raise ValueError(f"SepConvGRU: hidden_dim = {api.GRU_HIDDEN} and input_dim = {api.GRU_INPUT} are the only sizes of the "
+                             f"kernel (BasicUpdateBlock's); got {hidden_dim}, {input_dim}")
+        for name in api.GRU_PARAMETERS:
+            kernel = api.raft_gru_weight_shape(name)[2:]
+            # (a Conv2d for the parameter names, shapes and default initialisation of the reference; its forward is never called)
+            setattr(self, name, torch.nn.Conv2d(hidden_dim + input_dim, hidden_dim, kernel, padding=(kernel[0] // 2, kernel[1] // 2)))
+
+    def forward(self, h, x):
+        who = "SepConvGRU"
+        segs = tuple(x) if isinstance(x, (tuple, list)) else (x,)
+        weights = [getattr(self, n).weight for n in api.GRU_PARAMETERS]
+        biases = [getattr(self, n).bias for n in api.GRU_PARAMETERS]
+        named = {"h": h, **{f"x[{i}]": t for i, t in enumerate(segs)},
+                 **{f"{n}.weight": w for n, w in zip(api.GRU_PARAMETERS, weights)},
+                 **{f"{n}.bias": b for n, b in zip(api.GRU_PARAMETERS, biases)}}
+        for name, t in named.items():
+            if not (torch.is_tensor(t) and t.is_cuda):
+                raise ValueError(f"{who} runs on GPU tensors: {name} is not on a GPU (there is no CPU path)")
+            if t.dtype != torch.float32:
+                raise TypeError(f"{who}: {name} must be float32 (got {t.dtype})")
+            if torch.is_grad_enabled() and t.requires_grad:
+                raise ValueError(f"{who} is forward only: {name} requires grad (call it under torch.no_grad())")
+        if len({t.device for t in named.values()}) != 1:
+            raise ValueError(f"{who}: the tensors are on different devices")
+        B, H, W = api.raft_check_gru(h.shape, [t.shape for t in segs], [w.shape for w in weights], [b.shape for b in biases])
+        h = h.detach().contiguous()
+        segs = [t.detach().contiguous() for t in segs]
+        weights = [w.detach().contiguous() for w in weights]
+        biases = [b.detach().contiguous() for b in biases]
+        out = torch.empty((B, api.GRU_HIDDEN, H, W), dtype=torch.float32, device=h.device)
+        seg_table = (C.c_void_p * len(segs))(*[t.data_ptr() for t in segs])
+        seg_channels = (C.c_int32 * len(segs))(*[t.shape[1] for t in segs])
+        w_table = (C.c_void_p * 6)(*[t.data_ptr() for t in weights])
+        b_table = (C.c_void_p * 6)(*[t.data_ptr() for t in biases])
+        _call(h.device, "raft_sepconv_gru_device", C.c_int32(B), C.c_int32(H), C.c_int32(W), tc.ptr(h), C.c_int32(len(segs)),
+              seg_table, seg_channels, w_table, b_table, tc.ptr(out))
         return out
 
 
