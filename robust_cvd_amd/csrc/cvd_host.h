@@ -254,6 +254,7 @@ struct cvd_handle_t {
   hipEvent_t evInvIn = nullptr, evInvDone = nullptr;
   DevBuf<FrameConst> dFc2;                             // its own frame constants (the main stream rewrites dFc)
   DevBuf<long long> dItemRange;
+  DevBuf<ItemRecord> dItemRec;                         // the same per item in one 64-byte record (the pair product's one scalar load)
   // explicit cross blocks of the dense mode (cvd_cross.h): undirected pairs, their rows, the blocks
   std::vector<int> xFa, xFb;
   DevBuf<int> dXFa, dXFb, dXSlot, dXFiOff, dXPairEdge, dXDiagSlot;

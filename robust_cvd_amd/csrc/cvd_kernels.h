@@ -127,6 +127,14 @@ struct RecordStream {
     dNext = make_float2(0.f, 0.f);
     if (i < n) { dNext = (T.dsrc + base)[i]; ndNext = (T.ndc + base)[i]; }
   }
+  // The same without a branch, for a kernel prologue whose loads are all requested before its first wait: a lane outside [0, n)
+  // -- an empty direction included, whose base may be the table's end -- reads record 0, which exists whenever an item does.
+  __device__ __forceinline__ void primeClamped(const Table& T, long long base, int i, int n) {
+    const long long c = i < n ? base + i : 0;
+    dNext = T.dsrc[c];
+    ndNext = T.ndc[c];
+    if (i >= n) { dNext = make_float2(0.f, 0.f); ndNext = make_float4(0.f, 0.f, 0.f, 0.f); }
+  }
   // record base + i (false: skipped); requests record base + i + step
   __device__ __forceinline__ bool take(const Table& T, long long base, int i, int step, int n, long long, int, int, float4& nd,
                                        float2& d) {
@@ -148,6 +156,7 @@ struct RecordStream<true> {
     mNext = 0u;
     if (i < n) { mNext = (T.fmask + base)[i]; fNext = (T.flow + base)[i]; }
   }
+  __device__ __forceinline__ void primeClamped(const Table& T, long long base, int i, int n) { prime(T, base, i, n); }
   __device__ __forceinline__ bool take(const Table& T, long long base, int i, int step, int n, long long pixBase, int fa, int fb,
                                        float4& nd, float2& d) {
     const unsigned int m = mNext;
@@ -197,12 +206,23 @@ struct DenseStreamAhead {
 // Work items of the pair-major kernels: one UNDIRECTED frame pair {fa < fb} with a chunk of the constraints
 // of the directed pair fa->fb (range[0..1]) and of fb->fa (range[2..3]); either may be empty.  Both directions
 // share the two frames' parameter blocks, so one workgroup prologue / epilogue serves both.
+// The same per item as ONE 64-byte record: k_matvec_pairs_fast reads it with a single scalar load at its top (four arrays were
+// four dependent-address scalar loads in front of the prologue, and `range` / `slot` came back as loads behind barriers).
+struct alignas(64) ItemRecord {
+  int fa, fb;
+  int slotA, slotB;        // rows of the partial-product buffer of frame fa / fb
+  long long b0, e0;        // constraints of fa -> fb
+  long long b1, e1;        // constraints of fb -> fa
+  long long pad[2];
+};
+static_assert(sizeof(ItemRecord) == 64, "one record per 64-byte line");
 struct Items {
   const int* fa;
   const int* fb;
   const long long* range;  // 4 per item
   const int* slot;         // 2 per item: rows of the partial-product buffer (frame-major, see k_matvec_finish)
   int count;
+  const ItemRecord* rec;   // [count] the arrays above packed per item (the pair product reads only this)
 };
 
 // Work list of k_assemble_fast: a frame's (pair, side) entries are cut into units of at most kAsmUnit constraints
@@ -843,10 +863,6 @@ constexpr int kRedStride = 4 * 33 + 1;     // 128 columns (lane pairs pre-summed
 #define CVD_MV_WAVES 4   // waves per SIMD the specialised list-mode product (Global / bilinear) is compiled for (round 5: 129 -> 128
                          // VGPRs; 3 = rounds 2-4 and still the bicubic and dense variants, which spill at 128)
 #endif
-#ifndef CVD_MV_SLOAD
-#define CVD_MV_SLOAD 1   // 1: frame constants by scalar loads from global memory; 0: staged in LDS, v_readfirstlane per direction
-                         // (same box, 4140-pair set: 39.6 us against 41.4 / 41.9; without the early request below 40.8)
-#endif
 #ifndef CVD_MV_EARLY
 #define CVD_MV_EARLY 1   // 1: direction 0's first table record is requested at the top of the kernel
 #endif
@@ -870,8 +886,8 @@ inline __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SPEC 
   double* pb = pa + B;
   double* qa = pb + B;
   double* qb = qa + B;
-  FrameConst* fcs = reinterpret_cast<FrameConst*>(qb + B);   // (CVD_MV_SLOAD = 0: both frames' constants)
-  double* red = reinterpret_cast<double*>(fcs + 2);          // the reduced accumulators
+  double* fix = qb + B;                            // t, fy, J_l of both frames for the epilogue (2 x 13 of the 2 x 49 doubles reserved)
+  double* red = fix + 2 * sizeof(FrameConst) / 8;  // the reduced accumulators
   double* W = red + 32;                            // transposed reduction scratch: kRedVals rows x kRedStride
   // Dense mode: neighbouring lanes are neighbouring pixels and hit the SAME grid vertices -- 64-way same-address LDS
   // atomics.  The grid columns are therefore accumulated into kPriv lane-keyed private copies (after W) and folded
@@ -882,68 +898,109 @@ inline __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SPEC 
   double* cl = W;                                  // prologue only: 2 x kCB coarse corrections
   const int item = blockIdx.x;
   const int tid = threadIdx.x;
-  const int fa = it.fa[item], fb = it.fb[item];
+  // frames, constraint ranges and output rows of the item: ONE scalar load (four arrays were four, and `range` / `slot` were
+  // loaded again behind the barriers of the loop and of the write-out)
+  const ItemRecord* __restrict__ recp = it.rec + item;
+  const int fa = recp->fa, fb = recp->fb;
+  const int slotA = recp->slotA, slotB = recp->slotB;
+  const long long cbD[2] = {recp->b0, recp->b1}, ceD[2] = {recp->e0, recp->e1};
   const double beta = useBeta ? scal[S_BETA] : 0.0;
   // The frame constants (R, t, fy, J_l of both frames) are wave-uniform READ-ONLY global data at an address that depends on
   // blockIdx only: the compiler fetches them with scalar loads straight into SGPRs (round 5; rounds 2-4 staged the two structs in
   // LDS and moved 26 doubles per direction into SGPRs through v_readfirstlane: ~200 instructions per wave and direction).
-#if CVD_MV_SLOAD
+  // (Staged in LDS instead, same box, 4140-pair set: 41.4 / 41.9 us against 39.6; without the early request below 40.8.)
   const FrameConst* __restrict__ fcF[2] = {fc + fa, fc + fb};
-#else
-  const FrameConst* fcF[2] = {fcs, fcs + 1};
-  {
-    constexpr int FCW = sizeof(FrameConst) / 8;
-    if (tid >= NT - 2 * FCW) {  // (the last waves: the first ones carry the coarse loads)
-      const int t = tid - (NT - 2 * FCW);
-      const int which = t / FCW, k = t % FCW;
-      reinterpret_cast<double*>(fcs + which)[k] = reinterpret_cast<const double*>(fc + (which ? fb : fa))[k];
-    }
-  }
-#endif
   // The first table record of direction 0 is requested before anything else: it is back when the prologue's barriers are.
-  const long long cb0 = it.range[item * 4], ce0 = it.range[item * 4 + 1];
   // (not the bicubic variant: six more live registers through the prologue spill at its budget)
   constexpr bool kEarlyPrime = KD <= 4 && CVD_MV_EARLY;
   RecordStream<DENSE> rs;   // (list mode: the next trip's table record is in flight during this trip's arithmetic)
-  if constexpr (kEarlyPrime) rs.prime(T, cb0, (tid >> 6) * 64 + (tid & 63), static_cast<int>(ce0 - cb0));
+  if constexpr (kEarlyPrime) rs.primeClamped(T, cbD[0], tid, static_cast<int>(ceD[0] - cbD[0]));
   // Prologue in ONE global round trip (the workgroup lives ~5 us, a dependent load costs ~1 us of it): every thread
-  // issues its loads of x / z / p_old / mask for both frames and the coarse correction c_f (see CoarseView) in the same phase,
-  // and the search direction is formed after the barrier.  B <= 256: one element per thread.
-  if (V.Wb != nullptr) {  // (fused coarse variant: the correction is gathered here, one wave per frame)
-    if (tid < 64) coarseFrameCorrection(V, fa, tid, cl);
-    if (NT == 64) coarseFrameCorrection(V, fb, tid, cl + kCB);   // (one-wave workgroups of the deterministic build)
-    else if (tid >= 64 && tid < 128) coarseFrameCorrection(V, fb, tid - 64, cl + kCB);
-  } else if (tid < 2 * kCB) {
-    cl[tid] = (V.cF != nullptr) ? V.cF[(tid < kCB ? fa : fb) * kCB + (tid & (kCB - 1))] : 0.0;
-  }
+  // issues its loads of x / z / p_old / mask for both frames, the coarse correction c_f (see CoarseView), the third level's
+  // coefficients and taps and the epilogue's frame constants in the same phase, and the search direction is formed after the
+  // barrier.  B <= 256: one element per thread (two / four at 128 / 64 threads).
+  // Every load below is issued UNCONDITIONALLY, into registers, from an address that is clamped or replaced so that it lies
+  // inside its buffer (thread beyond B: element 0 of the frame's row; level off / first product of a solve: x, which always
+  // holds F x B >= 2 doubles); the LDS stores follow the one wait and are predicated instead.  A load in a divergent block in
+  // front of its own LDS store is waited for inside that block: the phases used to run one after the other, four round trips.
   constexpr int EPT = 256 / NT;  // elements of a frame block per thread (B <= 256)
-  double vza[EPT], vzb[EPT], vpa[EPT], vpb[EPT], vma[EPT], vmb[EPT];
+  constexpr int TLE = (2 * kTlMaxS + NT - 1) / NT;  // third-level coefficients per thread (2 x tlS <= 2 kTlMaxS)
+  const bool fusedCoarse = V.Wb != nullptr;
+  const bool tlOn = V.tl != nullptr;
+  const size_t rowA = static_cast<size_t>(fa) * B, rowB = static_cast<size_t>(fb) * B;
+  double vcf;   // coarse correction c_f of both frames (threads < 2 kCB keep it)
+  {
+    const int k = tid & (2 * kCB - 1);
+    vcf = *(V.cF != nullptr ? V.cF + static_cast<size_t>(k < kCB ? fa : fb) * kCB + (k & (kCB - 1)) : x);
+  }
   // third level (CoarseView::tl): the two frames' coefficients go to LDS behind the coarse corrections, the thread's vertex
   // taps to registers -- same round trip as everything else here
-  const bool tlOn = V.tl != nullptr;
   double* tls = cl + 2 * kCB;
-  TlTaps tt[EPT];
-  if (tlOn) {
-    for (int i = tid; i < 2 * V.tlS; i += NT) {
-      const int which = i >= V.tlS ? 1 : 0;
-      tls[i] = V.tl[static_cast<size_t>(which ? fb : fa) * V.tlS + (i - which * V.tlS)];
-    }
+  double vtl[TLE];
 #pragma unroll
-    for (int e = 0; e < EPT; ++e) tlLoadTaps(V, tid + e * NT, L.nD, tt[e]);
+  for (int e = 0; e < TLE; ++e) {
+    const int i = tid + e * NT;
+    const int ic = (tlOn && i < 2 * V.tlS) ? i : 0;
+    const int which = ic >= V.tlS ? 1 : 0;
+    vtl[e] = *(tlOn ? V.tl + static_cast<size_t>(which ? fb : fa) * V.tlS + (ic - which * V.tlS) : x);
   }
+  TlTaps tt[EPT];
 #pragma unroll
   for (int e = 0; e < EPT; ++e) {
     const int i = tid + e * NT;
-    vza[e] = vzb[e] = vpa[e] = vpb[e] = vma[e] = vmb[e] = 0.0;
+    const bool in = i >= 7 && i < 7 + L.nD;
+    const int v = in ? i - 7 : 0;
+    tt[e].w = *(tlOn ? V.tlW + v : reinterpret_cast<const float4*>(x));
+    tt[e].idx = *(tlOn ? V.tlIdx + v : reinterpret_cast<const unsigned int*>(x));
+    if (!in) tt[e].w = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  // what the epilogue's pose-row fix-up needs of the two frames' constants (t, fy, J_l: 13 consecutive doubles of FrameConst)
+  // is staged in LDS here: read there, behind the reduction's barrier, it was a global round trip of its own
+  constexpr int kFix = 13;
+  static_assert(offsetof(FrameConst, fy) == offsetof(FrameConst, t) + 24 && offsetof(FrameConst, Jl) == offsetof(FrameConst, t) + 32,
+                "t, fy, Jl are consecutive");
+  const int fixK = NT - 1 - tid;   // (the last threads: the first ones keep the coarse correction)
+  double vfix;
+  {
+    const int k = fixK < 2 * kFix ? fixK : 0;
+    vfix = (reinterpret_cast<const double*>(fc + (k >= kFix ? fb : fa)) + offsetof(FrameConst, t) / 8)[k >= kFix ? k - kFix : k];
+  }
+  double vxa[EPT], vxb[EPT], vza[EPT], vzb[EPT], vpa[EPT], vpb[EPT], vma[EPT], vmb[EPT];
+  const double* __restrict__ pOldOrZ = useBeta ? pOld : z;   // (useBeta = 0: pOld may be unset and is not read)
+#pragma unroll
+  for (int e = 0; e < EPT; ++e) {
+    const int i = tid + e * NT;
+    const size_t ia = rowA + (i < B ? i : 0), ib = rowB + (i < B ? i : 0);
+    vxa[e] = x[ia];
+    vxb[e] = x[ib];
+    vza[e] = z[ia];
+    vzb[e] = z[ib];
+    vpa[e] = pOldOrZ[ia];
+    vpb[e] = pOldOrZ[ib];
+    vma[e] = mask[ia];
+    vmb[e] = mask[ib];
+  }
+  // (shared intrinsics: frame 0's focal slot, wave-uniform)
+  const double z6 = z[6], po6 = pOldOrZ[6], m6 = mask[6];
+  if (fusedCoarse) {  // (fused coarse variant, off by default: the correction is gathered here, one wave per frame)
+    if (tid < 64) coarseFrameCorrection(V, fa, tid, cl);
+    if (NT == 64) coarseFrameCorrection(V, fb, tid, cl + kCB);   // (one-wave workgroups of the deterministic build)
+    else if (tid >= 64 && tid < 128) coarseFrameCorrection(V, fb, tid - 64, cl + kCB);
+  }
+  // ---- the one wait; from here on the prologue touches LDS only
+  if (!fusedCoarse && tid < 2 * kCB) cl[tid] = (V.cF != nullptr) ? vcf : 0.0;
+#pragma unroll
+  for (int e = 0; e < TLE; ++e) {
+    const int i = tid + e * NT;
+    if (tlOn && i < 2 * V.tlS) tls[i] = vtl[e];
+  }
+  if (fixK < 2 * kFix) fix[fixK] = vfix;
+#pragma unroll
+  for (int e = 0; e < EPT; ++e) {
+    const int i = tid + e * NT;
     if (i < B) {
-      const size_t ia = static_cast<size_t>(fa) * B + i, ib = static_cast<size_t>(fb) * B + i;
-      xa[i] = x[ia];
-      xb[i] = x[ib];
-      vza[e] = z[ia];
-      vzb[e] = z[ib];
-      if (useBeta) { vpa[e] = pOld[ia]; vpb[e] = pOld[ib]; }
-      vma[e] = mask[ia];
-      vmb[e] = mask[ib];
+      xa[i] = vxa[e];
+      xb[i] = vxb[e];
       qa[i] = 0.0;
       qb[i] = 0.0;
     }
@@ -969,7 +1026,7 @@ inline __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SPEC 
     // every constraint's focal column is frame 0's slot (reference lib/PoseOptimizer.cpp:1226)
     __syncthreads();
     if (tid == 0) {
-      const double p06 = (z[6] + (useBeta ? beta * pOld[6] : 0.0)) * mask[6];
+      const double p06 = (z6 + (useBeta ? beta * po6 : 0.0)) * m6;
       pa[6] = p06;
       pb[6] = p06;
     }
@@ -994,9 +1051,9 @@ inline __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SPEC 
   double Cx[3] = {0, 0, 0};
   double aFa = 0.0, aFb = 0.0;  // (unnormalised: x 1 / fy of the frame in the epilogue)
   double gDa[2] = {0.0, 0.0}, gDb[2] = {0.0, 0.0};  // KD == 1: every sample hits the one depth block -> registers
-  const long long units0 = (it.range[item * 4 + 1] - it.range[item * 4] + 63) >> 6;  // wave-units of direction 0
+  const long long units0 = (ceD[0] - cbD[0] + 63) >> 6;  // wave-units of direction 0
   for (int dir = 0; dir < 2; ++dir) {
-  const long long cb = it.range[item * 4 + dir * 2], ce = it.range[item * 4 + dir * 2 + 1];
+  const long long cb = cbD[dir], ce = ceD[dir];
   // role swap for the reverse pair (source = fb, target = fa): swap every per-frame pointer
   const FrameConst& Fa = *fcF[dir];
   const FrameConst& Fb = *fcF[dir ^ 1];
@@ -1178,8 +1235,9 @@ inline __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SPEC 
   // Lane pairs store their values transposed into LDS (row = accumulator, column = lane pair, 33-padded 32-column
   // segments), then 4 threads per accumulator sum one segment each: ~25 LDS ops per thread instead of 11 x 6
   // cross-lane butterfly steps.
-  const FrameConst& Fa = *fcF[1];
-  const FrameConst& Fb = *fcF[0];
+  // (t, fy, J_l of the two frames from the prologue's LDS copy: [0..2] t, [3] fy, [4..12] J_l)
+  const double* fixFa = fix + kFix;   // frame fb, the source of direction 1
+  const double* fixFb = fix;
   {
     double vals[NV];
 #pragma unroll
@@ -1224,18 +1282,18 @@ inline __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SPEC 
   } else if (tid < 9) {
     const bool tgt = tid >= 6;
     const int i = tgt ? tid - 6 : tid - 3;
-    const double dT[3] = {Fa.t[0] - Fb.t[0], Fa.t[1] - Fb.t[1], Fa.t[2] - Fb.t[2]};
+    const double dT[3] = {fixFa[0] - fixFb[0], fixFa[1] - fixFb[1], fixFa[2] - fixFb[2]};
     const double* y = red + (tgt ? 3 : 0);
     const double m[3] = {red[6] - (dT[1] * y[2] - dT[2] * y[1]), red[7] - (dT[2] * y[0] - dT[0] * y[2]),
                          red[8] - (dT[0] * y[1] - dT[1] * y[0])};
-    const double* a = (tgt ? Fb.Jl : Fa.Jl) + 3 * i;   // (frame fb is the source of direction 1)
+    const double* a = (tgt ? fixFb : fixFa) + 4 + 3 * i;   // (frame fb is the source of direction 1)
     const double sdot = a[0] * m[0] + a[1] * m[1] + a[2] * m[2];
     if (tgt) qb[3 + i] -= sdot;
     else qa[3 + i] += sdot;
   } else if (tid == 9) {
-    qa[6] += red[9] / Fa.fy;
+    qa[6] += red[9] / fixFa[3];
   } else if (tid == 10) {
-    qb[6] += red[10] / Fb.fy;
+    qb[6] += red[10] / fixFb[3];
   } else if (KD == 1 && tid < 15) {
     const int n = (tid - 11) & 1;
     if (n < N) {
@@ -1261,8 +1319,8 @@ inline __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SPEC 
     __syncthreads();
   }
   // rows are grouped by frame (slot = position in the frame's item list) so that k_matvec_finish streams them
-  double* outA = qPart + static_cast<size_t>(it.slot[item * 2]) * B;
-  double* outB = qPart + static_cast<size_t>(it.slot[item * 2 + 1]) * B;
+  double* outA = qPart + static_cast<size_t>(slotA) * B;
+  double* outB = qPart + static_cast<size_t>(slotB) * B;
   for (int i = tid; i < B; i += NT) {
     outA[i] = qa[i];
     outB[i] = qb[i];

@@ -1062,6 +1062,13 @@ void compileTable(cvd_handle* h, const std::vector<int>& range, bool withTriplet
   for (size_t e = 0; e < fiList.size(); ++e) itemSlot[fiList[e]] = static_cast<int>(e);
   h->qRows = static_cast<int>(fiList.size());
   h->dItemSlot.upload(itemSlot.data(), itemSlot.size(), s);
+  {  // the pair product's view of an item: frames, row slots and ranges in ONE record (Items::rec)
+    std::vector<ItemRecord> rec(std::max<size_t>(1, h->itemFa.size()), ItemRecord{});
+    for (size_t i = 0; i < h->itemFa.size(); ++i)
+      rec[i] = ItemRecord{h->itemFa[i], h->itemFb[i], itemSlot[2 * i], itemSlot[2 * i + 1], h->itemRange[4 * i], h->itemRange[4 * i + 1],
+                          h->itemRange[4 * i + 2], h->itemRange[4 * i + 3], {0, 0}};
+    h->dItemRec.upload(rec.data(), rec.size(), s);
+  }
   if (withTriplets) {
     // compact per-rank group arrays in tripActive order: offsets / centre / rows; per-frame (group, role) lists
     const size_t nG = h->tripActive.size();

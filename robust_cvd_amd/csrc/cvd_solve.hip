@@ -324,7 +324,7 @@ void bindProblem(BoundProblem& b, cvd_handle* h, const cvd_opt_params& p, double
   phase("medians");
   c.T = makeTable(h);
   c.nItems = static_cast<int>(h->itemFa.size());
-  c.it = Items{h->dItemFa.p, h->dItemFb.p, h->dItemRange.p, h->dItemSlot.p, c.nItems};
+  c.it = Items{h->dItemFa.p, h->dItemFb.p, h->dItemRange.p, h->dItemSlot.p, c.nItems, h->dItemRec.p};
   c.n = static_cast<size_t>(c.L.F) * c.L.B;
   c.boundDepth0 = (kind == PK_NORMALIZE && c.L.N > 0) ? 1 : 0;
   bindTriplets(c, p, kind);
