@@ -759,8 +759,10 @@ int32_t cvd_set_kernel_timing(cvd_handle* h, int32_t enabled);
 int64_t cvd_num_active_constraints(cvd_handle* h);
 /* Diagnostics (no counterpart in the reference): which variant of the linear solver the LAST solve of the handle ran --
  * out8 = { pose-graph level on, its form (0 exact sparse factor, 1 exact dense inverse, 2 temporal pose level), depth-grid
- * temporal level on, PCG tail fused into one launch (k_pcg_tail), fused tail disabled after an abandoned barrier, depth taps per
- * sample (1 / 4 / 16), work items of the pair-major kernels, explicit cross blocks (dense mode) }.  tools/defaults_sweep.py. */
+ * temporal level on, PCG tail (bit field), fused tail disabled after an abandoned barrier, depth taps per
+ * sample (1 / 4 / 16), work items of the pair-major kernels, explicit cross blocks (dense mode) }.  tools/defaults_sweep.py.
+ * out8[3], PCG tail: bit 0 = fused into one launch (k_pcg_tail); bit 1 = that launch's temporal-level workgroups staged their rows
+ * of the inverse in LDS (set only together with bit 0).  Test bit 0, not == 1, for "fused". */
 int32_t cvd_path_info(cvd_handle* h, int32_t* out8);
 
 #ifdef __cplusplus

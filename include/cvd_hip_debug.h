@@ -23,6 +23,9 @@ typedef struct cvd_debug_options {
                                     that per-launch counter averages contain no early-exit launches */
   int32_t stall_fused_tail_once; /* 1: the host treats the third PCG iteration of the handle's first solve as a stalled grid barrier
                                     of k_pcg_tail (exercises the fall-back to the two-launch tail; until round 5: pcg_fused_tail = 2) */
+  int32_t tail_no_row_staging;   /* 1: the temporal levels' workgroups of k_pcg_tail read their rows of the inverse from memory behind
+                                    the grid barrier (the path a launch takes when the staged rows would not fit the LDS or the device)
+                                    instead of staging them in LDS in front of it; cvd_path_info reports which ran */
 } cvd_debug_options;
 void cvd_debug_options_default(cvd_debug_options* o);
 int32_t cvd_set_debug_options(cvd_handle* h, const cvd_debug_options* o);

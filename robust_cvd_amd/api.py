@@ -55,6 +55,7 @@ class DebugOptions(C.Structure):
         ("force_sharded_path", C.c_int32),
         ("pcg_lockstep", C.c_int32),
         ("stall_fused_tail_once", C.c_int32),
+        ("tail_no_row_staging", C.c_int32),
     ]
 
 
@@ -542,7 +543,7 @@ class Solver(Binding):
     def set_options(self, pcg_relative_tolerance=None, pcg_max_iterations=None, verbose=None,
                     coarse_level=None, robust_loss=None, **variants):
         """Options persist per handle: only the fields given change (robust_loss: 0 Cauchy = reference, 1 Huber).  Names of
-        cvd_debug_options (force_iterations, force_sharded_path, pcg_lockstep, stall_fused_tail_once: test / measurement hooks,
+        cvd_debug_options (force_iterations, force_sharded_path, pcg_lockstep, stall_fused_tail_once, tail_no_row_staging: test / measurement hooks,
         include/cvd_hip_debug.h) are routed to cvd_set_debug_options."""
         debug = {k: variants.pop(k) for k in list(variants) if k in dict(DebugOptions._fields_) and k != "struct_size"}
         if debug:
@@ -1180,7 +1181,8 @@ class Solver(Binding):
         out = (C.c_int32 * 8)()
         self._check(self._fn("path_info")(self._h, out))
         form = {-1: "none", 0: "exact sparse factor", 1: "exact dense inverse", 2: "temporal pose level"}[out[1]]
-        return {"pose_graph_level": form, "depth_grid_level": bool(out[2]), "fused_tail": bool(out[3]), "tail_disabled": bool(out[4]),
+        return {"pose_graph_level": form, "depth_grid_level": bool(out[2]), "fused_tail": bool(out[3] & 1), "tail_rows_staged": bool(out[3] & 2),
+                "tail_disabled": bool(out[4]),
                 "taps": out[5], "work_items": out[6], "cross_blocks": bool(out[7])}
 
     def product_launch_debug(self):

@@ -389,6 +389,7 @@ struct cvd_handle_t {
   std::vector<cvd_iteration_record> records;
 
   bool lastFusedTail = false, lastCross = false;  // cvd_path_info: what the last PCG solve ran
+  bool tailStageRows = false;  // pcgTailScope: the fused tail's temporal-level workgroups stage their rows of the inverse in LDS
   int lastKD = 0;
   // cvd_product_launch_debug: {threads per workgroup, SPEC, KD, kind, work items, numCU} of the last launchMatvec (kind -1: none yet)
   int lastProduct[6] = {0, 0, 0, -1, 0, 0};

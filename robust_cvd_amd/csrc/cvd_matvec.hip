@@ -248,6 +248,7 @@ void launchMatvec(Ctx& c, const double* x, const double* z, const double* pOld, 
 bool pcgTailScope(Ctx& c, bool coarse, int nThreads, size_t& lds, int& ldsFinish, int& ldsScratch) {
   cvd_handle* h = c.h;
   const int F = c.L.F, B = c.L.B;
+  h->tailStageRows = false;  // (true only where this call chooses the staged launch)
   if (!h->opt.pcg_fused_tail || h->tailDisabled || h->dist() || B > 256 || h->forceGeneric) return false;
   if (coarse && !h->coarse.denseMode) return false;
   const int split = denseRowSplit(h);
@@ -264,28 +265,43 @@ bool pcgTailScope(Ctx& c, bool coarse, int nThreads, size_t& lds, int& ldsFinish
   const int denseEnd = (coarse && !poseT) ? F * kCB + nThreads + 16 : 0;    // the dense-level workgroups' (Z^T q + partial sums)
   ldsFinish = update;
   // (frame workgroups that walk rows of the dense level themselves: Z^T q + partial sums behind their two regions)
-  ldsScratch = std::max(update + finish + (coarse && split < kCB ? denseEnd : 0), denseEnd);
-  lds = static_cast<size_t>(ldsScratch + 24) * sizeof(double);
-  if (lds > kMaxLds) return false;
+  const int unstaged = std::max(update + finish + (coarse && split < kCB ? denseEnd : 0), denseEnd);
+  // (the temporal levels' workgroups stage their rows of the inverse in LDS in front of the grid barrier where that fits and keeps
+  // the launch co-resident: TailUpdate::stageRows; otherwise they read the rows from memory behind it, as the two-launch path does)
+  int stagedEnd = 0;
+  if (ts.Ainv != nullptr) stagedEnd = std::max(stagedEnd, tlStagedLds(ts.NT));
+  if (poseT) stagedEnd = std::max(stagedEnd, tlStagedLds(h->coarse.ptN));
   // occupancy of this (kernel, block size, LDS size) on this device: asked once
   static std::map<std::tuple<int, int, int, size_t>, int> perCuCache;
   static std::mutex cacheMutex;
-  int perCu = 0;
-  {
+  auto resident = [&](size_t bytes) {
+    if (bytes > kMaxLds) return false;
+    int perCu = 0;
     std::lock_guard<std::mutex> lock(cacheMutex);
-    const auto key = std::make_tuple(h->device, c.KD, nThreads, lds);
+    const auto key = std::make_tuple(h->device, c.KD, nThreads, bytes);
     auto it = perCuCache.find(key);
     if (it == perCuCache.end()) {
       CVD_DISPATCH_KD(c.KD, {
-        allowLds((k_pcg_tail<KD>), lds);
-        HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, reinterpret_cast<const void*>(&k_pcg_tail<KD>), nThreads, lds));
+        allowLds((k_pcg_tail<KD>), bytes);
+        HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, reinterpret_cast<const void*>(&k_pcg_tail<KD>), nThreads, bytes));
       });
       perCuCache[key] = perCu;
     } else {
       perCu = it->second;
     }
+    return static_cast<long long>(perCu) * h->numCU >= grid;
+  };
+  if (stagedEnd > 0 && h->dbg.tail_no_row_staging == 0) {
+    ldsScratch = std::max(unstaged, stagedEnd);
+    lds = static_cast<size_t>(ldsScratch + 24) * sizeof(double);
+    if (resident(lds)) {
+      h->tailStageRows = true;
+      return true;
+    }
   }
-  return static_cast<long long>(perCu) * h->numCU >= grid;
+  ldsScratch = unstaged;
+  lds = static_cast<size_t>(ldsScratch + 24) * sizeof(double);
+  return resident(lds);
 }
 
 void launchPcgTail(Ctx& c, const double* x, const double* pOld, double* pNew, int useBeta, const double* lam, double* q,
@@ -307,7 +323,7 @@ void launchPcgTail(Ctx& c, const double* x, const double* pOld, double* pNew, in
                      h->dCounters.p + 1, h->dTailBar.p, h->dFdot.p + 4 * static_cast<size_t>(F) + 32, ldsFinish, ldsScratch, ds,
                      ts.Ainv != nullptr ? temporalStepDev(h) : static_cast<const TlStep*>(nullptr),
                      poseT ? poseTemporalStepDev(h) : static_cast<const TlStep*>(nullptr),
-                     (c.cross && h->xDiagRows) ? 1 : 0};
+                     (c.cross && h->xDiagRows) ? 1 : 0, h->tailStageRows ? 1 : 0};
   const int grid = F + (withCoarse && !poseT && split > 0 ? (F + kDenseFramesPerGroup - 1) / kDenseFramesPerGroup : 0) +
                    (ts.Ainv != nullptr ? ts.S * ts.parts : 0) + (poseT ? kCB * tlParts(h->coarse.ptNn) : 0);
   const int slot = h->tBegin(KC_CG_UPDATE);  // (timed under the update class: the finish class stays empty on this path)
@@ -345,7 +361,7 @@ void touchModule_matvec() {
 #ifdef CVD_TAIL_PROFILE
 extern "C" int32_t cvd_debug_tail_profile(unsigned long long* out) {
   (void)hipDeviceSynchronize();
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(cvd::g_tailProf), sizeof(unsigned long long) * 1024 * 8) == hipSuccess ? 0 : 1;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(cvd::g_tailProf), sizeof(unsigned long long) * 1024 * 16) == hipSuccess ? 0 : 1;
 }
 #endif
 #ifdef CVD_MV_PROFILE

@@ -98,6 +98,15 @@ __device__ __forceinline__ bool matvecFinishBody(const Layout& L, const double* 
   const int tid = threadIdx.x;
   const double beta = useBeta ? scal[S_BETA] : 0.0;
   const size_t base = static_cast<size_t>(f) * B;
+  // (FUSED: the row range first -- it is the one address the row walk below waits for -- and whether the frame has regulariser rows:
+  // asked here, not behind the barriers; k_matvec_finish asks where it always did)
+  int e0 = 0, e1 = 0;
+  bool regRowsOn = false;
+  if constexpr (FUSED) {
+    e0 = fiOff[f];
+    e1 = fiOff[f + 1];
+    regRowsOn = Hdiag == nullptr && inRange[f];
+  }
   // One global round trip for the inputs (B <= 256: one element per thread): the loads of z / mask / p_old / x / lam
   // are issued together with the coarse correction's, the direction is formed after the barrier and stays in a
   // register for the damping term and p.q at the end.
@@ -139,7 +148,10 @@ __device__ __forceinline__ bool matvecFinishBody(const Layout& L, const double* 
       xf[i] = x[base + i];
     }
   }
-  const int e0 = fiOff[f], e1 = fiOff[f + 1];
+  if constexpr (!FUSED) {
+    e0 = fiOff[f];
+    e1 = fiOff[f + 1];
+  }
   // The frame's partial rows (contiguous; independent streaming loads, four in flight per thread) are summed BEFORE the
   // barrier: they depend on nothing but the row range, so their way from L2 overlaps the vector loads above instead of
   // following them (this kernel is a chain of dependent round trips, not a bandwidth problem).
@@ -198,7 +210,7 @@ __device__ __forceinline__ bool matvecFinishBody(const Layout& L, const double* 
     if (i >= B) continue;
     // search direction from the two-level preconditioned residual z + Z c (coarse part only on active unknowns)
     const double pv = vz[e] + (coarseAtLds(cl, L, i) + (tlOn ? tlAt(tls, tt[e]) : 0.0)) * vm[e] + (useBeta ? beta * vp[e] : 0.0);
-    pNew[base + i] = pv;
+    if constexpr (!FUSED) pNew[base + i] = pv;  // (FUSED: the caller stores carry.pv / carry.qv behind its arrival at the grid barrier)
     pvReg[e] = pv;
     pf[i] = pv * vm[e];
     // (no pair kernel ran: the partial buffer is stale; shared focal: frame 0's slot collects every row's entry below)
@@ -232,7 +244,7 @@ __device__ __forceinline__ bool matvecFinishBody(const Layout& L, const double* 
       qf[i] += (a0 + a1) + (a2 + a3);
     }
     __syncthreads();
-  } else if (Hdiag == nullptr && inRange[f]) {
+  } else if (FUSED ? regRowsOn : (Hdiag == nullptr && inRange[f])) {
     // J_reg^T (J_reg p) from the cached rows (k_reg_cache)
     // (deterministic build: the first wave alone -- the rows' LDS atomics then land in program order)
     const int regStride = CVD_DETERMINISTIC ? 64 : nT;
@@ -282,7 +294,7 @@ __device__ __forceinline__ bool matvecFinishBody(const Layout& L, const double* 
     if (i >= B) continue;
     const double pv = pvReg[e];
     const double qv = qf[i] * vm[e] + (distMode == 2 ? 0.0 : vlam[e] * pv);
-    q[base + i] = qv;
+    if constexpr (!FUSED) q[base + i] = qv;
     qf[i] = qv;
     dot += pv * qv;
     if (e == 0) { carry.pv = pv; carry.qv = qv; }
@@ -404,8 +416,10 @@ __host__ __device__ inline int cgUpdatePartDoubles(int B, int nThreads) {
 // hat's share of r^T P t, and the temporal interpolation of the new t for every frame (tl).  init: t = A_T^-1 q_T, r_T = q_T with
 // sq = the restriction of the first residual.  LDS: NT + 2 nn doubles at sm.  Returns false when nothing was written.
 #ifdef CVD_TAIL_PROFILE  // tools/tail_profile.py: wall-clock (100 MHz) stamps of k_pcg_tail's workgroups
-__device__ unsigned long long g_tailProf[1024 * 8];
-#define TAIL_STAMP(slot) do { if (threadIdx.x == 0) g_tailProf[(blockIdx.x & 1023) * 8 + (slot)] = wall_clock64(); } while (0)
+// slots: 0 start, 1 finish half done, 2 operands requested, 3 released, 4 end, 5-7 levels (node sums, rows, interpolation),
+// 8 levels: rows staged, 10 arrival done (first wave: ticket in hand; the releasing workgroup: records written)
+__device__ unsigned long long g_tailProf[1024 * 16];
+#define TAIL_STAMP(slot) do { if (threadIdx.x == 0) g_tailProf[(blockIdx.x & 1023) * 16 + (slot)] = wall_clock64(); } while (0)
 #else
 #define TAIL_STAMP(slot) do {} while (0)
 #endif
@@ -414,7 +428,11 @@ struct NoMid {  // (the kernels that are not k_pcg_tail: nothing happens between
   __device__ bool first(double&, double&) { return true; }
   __device__ bool second(double&) { return true; }
   __device__ unsigned int generation() { return 0u; }
+  __device__ bool stageRows() { return false; }
 };
+// LDS doubles of a temporal level's workgroup in k_pcg_tail that stages its rows of the inverse in front of the grid barrier
+// (tlLevelRows): the kTlSpan + 1 rows of NT doubles behind its tlRowsLds(NT) (host and device agree on the layout)
+__host__ __device__ inline int tlStagedLds(int NT) { return tlRowsLds(NT) + (kTlSpan + 1) * NT; }
 typedef unsigned int cvd_u32x4 __attribute__((ext_vector_type(4)));
 template <bool FUSED, typename Mid>
 __device__ __forceinline__ bool tlLevelRows(const TlStep* __restrict__ tsp, int wg, int F, double& alpha, int init, double sDone,
@@ -436,14 +454,46 @@ __device__ __forceinline__ bool tlLevelRows(const TlStep* __restrict__ tsp, int 
   double* tn = qT + ts.NT;         // span + 1 new coefficients of this hat
   double* red = tn + ts.span + 1;  // span + 1 products t r_T, [span + 1 .. ]: flag
   // (the coefficients the wave's first row updates depend on nothing this launch computes: requested before the grid barrier.
-  // The row itself as well -- 8 doubles per lane -- spills at the 80 registers of k_pcg_tail.)
+  // The row itself -- 8 doubles per lane -- would spill at the 80 registers of k_pcg_tail if held across the barrier: the fused
+  // kernel stages it in LDS instead, below.)
   double rOldPre = 0.0, tOldPre = 0.0;
   if (lane == 0 && !init) {
     const int e = s * ts.nn + aLo + (wv < nA ? wv : 0);
     rOldPre = ts.rT[e];
     tOldPre = tin[e];
   }
+  // FUSED, staged: the rows themselves wait in LDS.  Every wave copies the row(s) it will walk -- they depend on nothing this
+  // launch computes, and the workgroup idles in front of the barrier -- eight loads per lane in flight, stored as they are
+  // consumed: nothing is held in registers across the barrier.  The product below reads the same entries in the same order.
+  double* stage = sm + tlRowsLds(ts.NT);  // [span + 1][NT]
+  bool staged = false;
   if constexpr (FUSED) {
+    staged = mid.stageRows();
+    if (staged) {
+      constexpr int kStageBatch = 8;
+      for (int k = wv; k < nA; k += nW) {
+        const double* row = ts.Ainv + static_cast<size_t>(s * ts.nn + aLo + k) * ts.ld;
+        double* dst = stage + static_cast<size_t>(k) * ts.NT;
+        for (int c0 = 0; c0 < ts.NT; c0 += 64 * kStageBatch) {
+          double v[kStageBatch];
+#pragma unroll
+          for (int u = 0; u < kStageBatch; ++u) {
+            const int c = c0 + u * 64 + lane;
+            v[u] = row[min(c, ts.NT - 1)];
+          }
+#pragma unroll
+          for (int u = 0; u < kStageBatch; ++u) {
+            const int c = c0 + u * 64 + lane;
+            if (c < ts.NT) dst[c] = v[u];
+          }
+        }
+      }
+    }
+    TAIL_STAMP(8);
+  }
+  bool on = false;
+  if constexpr (FUSED) {
+    on = *ts.fail == 0;  // (set when the level was built: asked in front of the grid barrier, not behind the node sums)
     if (!mid.second(alpha)) return false;
   }
   const double inv = 1.0 / static_cast<double>(ts.step);
@@ -520,7 +570,7 @@ __device__ __forceinline__ bool tlLevelRows(const TlStep* __restrict__ tsp, int 
   }
   if (sDone != 0.0) return false;  // uniform; nothing written yet
   if constexpr (FUSED) TAIL_STAMP(5);
-  const bool on = *ts.fail == 0;
+  if constexpr (!FUSED) on = *ts.fail == 0;
   for (int k = wv; k < nA; k += nW) {
     const int a = aLo + k, e = s * ts.nn + a;
     const double* row = ts.Ainv + static_cast<size_t>(e) * ts.ld;
@@ -533,11 +583,20 @@ __device__ __forceinline__ bool tlLevelRows(const TlStep* __restrict__ tsp, int 
       rOld = ts.rT[e];
       tOld = tin[e];
     }
-    for (; c + 64 < ts.NT; c += 128) {
-      acc0 += row[c] * qT[c];
-      acc1 += row[c + 64] * qT[c + 64];
+    if (staged) {  // (the wave's own copy: LDS operations of a wave complete in order, and two workgroup barriers lie between)
+      const double* srow = stage + static_cast<size_t>(k) * ts.NT;
+      for (; c + 64 < ts.NT; c += 128) {
+        acc0 += srow[c] * qT[c];
+        acc1 += srow[c + 64] * qT[c + 64];
+      }
+      if (c < ts.NT) acc0 += srow[c] * qT[c];
+    } else {
+      for (; c + 64 < ts.NT; c += 128) {
+        acc0 += row[c] * qT[c];
+        acc1 += row[c + 64] * qT[c + 64];
+      }
+      if (c < ts.NT) acc0 += row[c] * qT[c];
     }
-    if (c < ts.NT) acc0 += row[c] * qT[c];
     const double d = ts.weight * waveSum(acc0 + acc1);
     if (lane == 0) {
       const double rn = init ? qT[e] : rOld - alpha * qT[e];
@@ -1026,45 +1085,52 @@ inline __global__ void k_pcg_scalars_dist(const double* __restrict__ parts, int 
 // agent-scope loads (publishPartial / readPartial, cdna_hip_programming.md G16 R1), every wave drains its stores first.
 // The spin is bounded: a launch whose workgroups are not all resident abandons (the host checks the occupancy and serialises
 // gated kernels of different handles, so this is a safety net) and the host's progress check reports the stalled PCG.
-// The barrier carries the one reduction the halves need: the LAST workgroup to arrive sums the nParts published partials
-// (p.q shares of the frames), publishes the sum and only then releases the others, which read that one double.
-// Split in two: tailArrive right after the finish half (the workgroup's payload is published; nothing it requests afterwards
-// delays its arrival), tailWait after the update half's operand requests.  Waiting costs MEMORY TRAFFIC: every poll is an
+// The barrier carries the one reduction the halves need: the FIRST WAVE of the last workgroup to arrive sums the nParts published
+// partials (p.q shares of the frames) and releases the others with records that hold the sum.
+// Split in two: tailArrive right after the finish half (only the payload that crosses the barrier is drained in front of it: the
+// direction and the product, which nobody in this launch reads from memory, are stored behind it; the first wave waits for its
+// ticket there, and the last arriver's release does not wait on its own update half's operand requests), tailWait after the update
+// half's operand requests.  Waiting costs MEMORY TRAFFIC: every poll is an
 // L2-bypassing load, and hundreds of workgroups polling one address saturate the memory channel that holds it -- the finish
 // halves still running slowed down 2x (measured with stamps, tools/tail_profile.py: 12.3 -> 7.6 us median when the poll
 // interval went from 4 to 32 sleep units).  The release word is therefore replicated over kTailBarCopies pages (different
 // channels), each workgroup polls the copy blockIdx % kTailBarCopies at a long interval.
 // bar: [0] arrivals, [1] abandon flag, generation copies at bar[kTailBarStride * (1 + k)].
-// scratch: 24 doubles of LDS ([0..15] wave partials, [16] role, [17] generation, [18] the sum).
+// scratch: 24 doubles of LDS ([16] role, [17] generation, [18] the sum; [0..15] unused since the first wave sums alone).
 constexpr int kTailBarCopies = 16;
 constexpr int kTailBarStride = 1024;  // unsigned ints: 4 KB
-// (thread 0 reads its generation copy with tailGeneration at the START of the kernel and keeps the arrival ticket in a register
-// until tailWait: neither round trip sits between the finish half and the operand requests)
+// (thread 0 reads its generation copy with tailGeneration at the START of the kernel: that round trip does not sit between the
+// finish half and the arrival)
 __device__ __forceinline__ unsigned int tailGeneration(const unsigned int* bar) {
   if (threadIdx.x != 0) return 0u;
   return *reinterpret_cast<const volatile unsigned int*>(bar + kTailBarStride * (1 + (blockIdx.x & (kTailBarCopies - 1))));
 }
-__device__ __forceinline__ unsigned int tailArrive(unsigned int* bar) {
+// tailArrive: the FIRST WAVE alone takes the ticket and waits for it; the workgroup that drew the last one releases the others
+// right there -- its first wave sums the nParts published partials (lane l: partials l, l + 64, ... in that order, then waveSum: a
+// fixed order), re-arms the count and writes the release records -- without a workgroup barrier, and without waiting on the update
+// half's operand requests: those are issued meanwhile by the other waves, which in every workgroup return from here at once (the
+// first wave of the releasing workgroup issues its own behind the release).  Role (1: wait,
+// 2: released the others), generation and the sum are left in the scratch words for tailWait.
+__device__ __forceinline__ void tailArrive(unsigned int* bar, unsigned int nGroups, unsigned int gen, const double* __restrict__ parts,
+                                           int nParts, double* __restrict__ scratch) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: its published payload has landed
   __syncthreads();
-  if (threadIdx.x != 0) return 0u;
-  return __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// The release word of a copy is a 16-byte RECORD {generation, sum (2 words), generation}, written with ONE 16-byte store and read
-// with one 16-byte load: the sum travels with the flag, so the last arriver neither publishes it separately nor drains that store
-// before releasing (2.5 us of the 7 between the last arrival and the release).  A reader accepts a record whose two generation
-// words agree (a 16-byte access of one lane is one transaction; the second word guards against a torn one anyway).
-__device__ __forceinline__ bool tailWait(unsigned int* bar, unsigned int nGroups, unsigned int gen, unsigned int ticket,
-                                         const double* __restrict__ parts, int nParts, double* __restrict__ scratch, double& sum) {
-  int* role = reinterpret_cast<int*>(scratch + 16);
-  if (threadIdx.x == 0) {
-    *role = (ticket == nGroups - 1) ? 2 : 1;
-    *reinterpret_cast<unsigned int*>(scratch + 17) = gen;
-  }
-  __syncthreads();
-  gen = *reinterpret_cast<unsigned int*>(scratch + 17);
-  if (*role == 2) {
-    const double v = blockSumPartials(parts, nParts, scratch);
+  if (threadIdx.x >= 64) return;
+  unsigned int ticket = 0u;
+  if (threadIdx.x == 0) ticket = __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  ticket = __builtin_amdgcn_readfirstlane(ticket);
+  gen = __builtin_amdgcn_readfirstlane(gen);  // (thread 0 read it at the start of the kernel)
+  const bool last = ticket == nGroups - 1;
+  if (last) {
+    double a = 0.0;
+    for (int k0 = threadIdx.x; k0 < nParts + static_cast<int>(threadIdx.x); k0 += 8 * 64) {  // (eight loads in flight per lane: 512 partials a trip)
+      double w[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) w[u] = k0 + u * 64 < nParts ? readPartial(parts + k0 + u * 64) : 0.0;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) a += w[u];
+    }
+    const double v = waveSum(a);
     if (threadIdx.x == 0) __hip_atomic_store(bar, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (threadIdx.x < kTailBarCopies) {
       cvd_u32x4 rec;
@@ -1074,7 +1140,23 @@ __device__ __forceinline__ bool tailWait(unsigned int* bar, unsigned int nGroups
       rec.w = gen + 1u;
       *reinterpret_cast<volatile cvd_u32x4*>(bar + kTailBarStride * (1 + threadIdx.x)) = rec;
     }
-    sum = v;
+    if (threadIdx.x == 0) scratch[18] = v;
+  }
+  if (threadIdx.x == 0) {
+    *reinterpret_cast<int*>(scratch + 16) = last ? 2 : 1;
+    *reinterpret_cast<unsigned int*>(scratch + 17) = gen;
+  }
+}
+// The release word of a copy is a 16-byte RECORD {generation, sum (2 words), generation}, written with ONE 16-byte store and read
+// with one 16-byte load: the sum travels with the flag, so the last arriver neither publishes it separately nor drains that store
+// before releasing (2.5 us of the 7 between the last arrival and the release).  A reader accepts a record whose two generation
+// words agree (a 16-byte access of one lane is one transaction; the second word guards against a torn one anyway).
+__device__ __forceinline__ bool tailWait(unsigned int* bar, double* __restrict__ scratch, double& sum) {
+  int* role = reinterpret_cast<int*>(scratch + 16);
+  __syncthreads();  // (tailArrive's first wave left role, generation and -- the releasing workgroup -- the sum)
+  const unsigned int gen = *reinterpret_cast<unsigned int*>(scratch + 17);
+  if (*role == 2) {
+    sum = scratch[18];
     return true;
   }
   if (threadIdx.x == 0) {
@@ -1126,6 +1208,8 @@ struct TailUpdate {
   const TlStep* ts;        // third level (device copy of its descriptor), nullptr: off
   const TlStep* tp;        // temporal pose level (coarse_level 3), nullptr: off
   int diagInProduct;       // explicit cross blocks: H_ff p_f is one of the frame's partial rows (k_cross_matvec), not the finish half's work
+  int stageRows;           // 1: the temporal levels' workgroups copy their rows of the inverse to LDS in front of the grid barrier
+                           // (tlStagedLds doubles each; 0: the launch would not fit or not be co-resident with them -- rows from memory)
 };
 
 template <int KD>
@@ -1146,7 +1230,9 @@ inline __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6))
   const CoarseStep csOff{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   TAIL_STAMP(0);
   const unsigned int barGen = tailGeneration(U.gridBar);
-  unsigned int barTicket = 0u;
+  // (r^T z of the previous iteration, for alpha: S_RZ is rewritten only by the last workgroup to take the update half's ticket, i.e.
+  // after every workgroup has passed the grid barrier -- read here, not in a round trip of its own behind the release)
+  const double rzOld = scal[S_RZ];
   auto first = [&](double& pv, double& qv) -> bool {
     if (f < L.F) {
       TailCarry carry{0.0, 0.0};
@@ -1160,16 +1246,21 @@ inline __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6))
       return false;  // (dense-level workgroup of a launch enqueued past convergence)
     }
     TAIL_STAMP(1);
-    barTicket = tailArrive(U.gridBar);
+    tailArrive(U.gridBar, gridDim.x, barGen, fdot, L.F, sm + U.ldsScratch);
+    TAIL_STAMP(10);
+    // (nobody in this launch reads the direction and the product from memory: stored behind the arrival, not drained in front of it)
+    if (f < L.F && static_cast<int>(threadIdx.x) < L.B) {
+      pNew[static_cast<size_t>(f) * L.B + threadIdx.x] = pv;
+      q[static_cast<size_t>(f) * L.B + threadIdx.x] = qv;
+    }
     return true;
   };
   auto second = [&](double& alpha) -> bool {
     double pq;
     TAIL_STAMP(2);
-    if (!tailWait(U.gridBar, gridDim.x, barGen, barTicket, fdot, L.F, sm + U.ldsScratch, pq)) return false;
+    if (!tailWait(U.gridBar, sm + U.ldsScratch, pq)) return false;
     TAIL_STAMP(3);
-    // (S_RZ is rewritten only by the last workgroup to take the update half's ticket, i.e. after every workgroup has read it)
-    alpha = scal[S_RZ] / pq;
+    alpha = rzOld / pq;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
       scal[S_PQ] = pq;
       scal[S_ALPHA] = alpha;
@@ -1184,7 +1275,9 @@ inline __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6))
     __device__ bool second(double& alpha) { return f2(alpha); }
     // (the barrier's generation at the start of this launch: tailWait left it in the scratch words for every thread)
     __device__ unsigned int generation() { return *reinterpret_cast<unsigned int*>(scratch + 17); }
-  } mid{first, second, sm + U.ldsScratch};
+    bool stage;
+    __device__ bool stageRows() { return stage; }
+  } mid{first, second, sm + U.ldsScratch, U.stageRows != 0};
   cgUpdateBody<true>(L, 0, nullptr, U.minv, nullptr, nullptr, scal, U.counter, U.dx, U.r, U.z, U.fdotRZ, U.fdotRR, U.tol2, nullptr,
                      U.modeActive, U.hostMirror, csOff, U.ds, nullptr, sm, mid, 0, L.F, nullptr, U.ts, U.tp);
   TAIL_STAMP(4);
