@@ -734,6 +734,65 @@ int32_t cvd_raft_sepconv_gru_timed(cvd_handle* h, int32_t batch, int32_t height,
                                    const float* const* weights, const float* const* biases, float* out, void* stream,
                                    double* kernel_ms);
 
+/* ---- The stock convolutions of RAFT's update block and the block itself, DESIGN.md §3.17.  Independent of cvd_set_video.  f32,
+ * forward only.  DEVICE arrays, enqueued on `stream`: kernel launches only, no copy, no host synchronisation, no atomics; every
+ * output element is written once in a fixed operation order, so results repeat bit for bit and do not depend on how an input is
+ * segmented.
+ *
+ * One convolution -- reference raft/core/update.py:11-12, 100-104, 142-144 (the nn.Conv2d of FlowHead, BasicMotionEncoder and
+ * the mask head: square filter, stride 1, padding kernel_size / 2) with the ReLU behind it (:16, :107-113, :143) and the factor
+ * of :155:
+ *   out[b][out_first_channel + o][y][x] = scale * act(bias[o] + sum_{c,i,j} weight[o][c][i][j] in[b][c][y + i - r][x + j - r]),
+ * r = kernel_size / 2, the input outside the image counting 0; ONE launch.
+ *   segments          host array of num_segments (1..3) device arrays; segments[i] is [batch][segment_channels[i]][height][width].
+ *                     The input is their concatenation along the channels, which is never formed.
+ *   segment_channels  host array; one segment: any count >= 1; several: positive multiples of 32.  Their sum must be in_channels.
+ *   weights, biases   host arrays of num_weights (1 or 2) device arrays in torch's layout, weight
+ *                     [out_channels][in_channels][kernel_size][kernel_size], bias [out_channels].  Two tensors are stacked along
+ *                     the output channels (o = 0 .. 2 out_channels - 1) and need out_channels in multiples of 64.  Any alignment:
+ *                     weights are read as float4 where their rows start on 16 bytes, as floats elsewhere.
+ *   kernel_size       1, 3 or 7;  stride, dilation, groups: must be 1
+ *   activation        0 none, 1 ReLU;  scale multiplies after the activation (a power of two gives the bits of a separate multiply)
+ *   out               [batch][out_total_channels][height][width]; only channels out_first_channel .. out_first_channel +
+ *                     num_weights out_channels - 1 are written.  The tensor must not overlap a segment.
+ * Rejected before any device work, with an error that names the value: sizes < 1, a filter size other than 1, 3, 7, a stride,
+ * dilation or groups other than 1, null arrays, more than three segments, several segments not in multiples of 32 channels,
+ * segments that do not sum to in_channels, an output window that exceeds its tensor, an output that overlaps an input. */
+int32_t cvd_raft_conv2d_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t num_segments,
+                               const float* const* segments, const int32_t* segment_channels, int32_t num_weights,
+                               const float* const* weights, const float* const* biases, int32_t in_channels, int32_t out_channels,
+                               int32_t kernel_size, int32_t stride, int32_t dilation, int32_t groups, int32_t activation, float scale,
+                               float* out, int32_t out_total_channels, int32_t out_first_channel, void* stream);
+/* The block -- reference raft/core/update.py:133-156 (BasicUpdateBlock.forward with hidden_dim = 128, input_dim = 128) and what it
+ * calls (:96-114 BasicMotionEncoder.forward, :37-75 SepConvGRU.forward, :8-16 FlowHead.forward):
+ *   cor = relu(convc1(corr)); cor = relu(convc2(cor)); flo = relu(convf1(flow)); flo = relu(convf2(flo));
+ *   motion_features = [relu(conv([cor, flo])), flow];  net_out = gru(net, [inp, motion_features]);
+ *   delta_flow = flow_head.conv2(relu(flow_head.conv1(net_out)));  mask = 0.25 * mask.2(relu(mask.0(net_out)))
+ * No cat is formed.  8 launches of the convolution above (7 with a null mask: flow_head.conv1 and mask.0 are one launch, mask.2
+ * falls away) and the 4 unchanged launches of cvd_raft_sepconv_gru_device.  Scratch (768 batch height width floats and the
+ * GRU's) belongs to the handle and keeps its high-water size, under the GRU's rule: calls on one device must be ordered on one
+ * stream; a call that has to grow the scratch allocates, every later call of that size only enqueues.
+ *   net, inp          [batch][128][height][width];  corr [batch][corr_channels][height][width];  flow [batch][2][height][width]
+ *   cor_planes        in_channels of encoder.convc1.weight (corr_levels (2 corr_radius + 1)^2 = 324 in RAFT); must equal corr_channels
+ *   weights, biases   host arrays of 15 device arrays in the order encoder.convc1, encoder.convc2, encoder.convf1, encoder.convf2,
+ *                     encoder.conv, gru.convz1, gru.convr1, gru.convq1, gru.convz2, gru.convr2, gru.convq2, flow_head.conv1,
+ *                     flow_head.conv2, mask.0, mask.2, in torch's layout and the reference's shapes; the GRU's 16-byte aligned
+ *   net_out [batch][128][height][width], delta_flow [batch][2][height][width], mask [batch][576][height][width] or NULL (not
+ *   computed); none may overlap an input or another output.
+ * Rejected before any device work: sizes < 1, corr_channels != cor_planes, null arrays, overlapping arrays, a GRU weight that is
+ * not 16-byte aligned. */
+int32_t cvd_raft_update_block_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t corr_channels,
+                                     int32_t cor_planes, const float* net, const float* inp, const float* corr, const float* flow,
+                                     const float* const* weights, const float* const* biases, float* net_out, float* delta_flow,
+                                     float* mask, void* stream);
+/* The same call for measurement (tools/raftblock_bench.py): HIP events around every launch on `stream` and host waits;
+ * kernel_ms[12] = {convc1, convc2, convf1, convf2, conv (with the flow copy), the GRU's four as in cvd_raft_sepconv_gru_timed,
+ * flow_head.conv1 | mask.0, flow_head.conv2, mask.2 (0 with a null mask)} in milliseconds. */
+int32_t cvd_raft_update_block_timed(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t corr_channels,
+                                    int32_t cor_planes, const float* net, const float* inp, const float* corr, const float* flow,
+                                    const float* const* weights, const float* const* biases, float* net_out, float* delta_flow,
+                                    float* mask, void* stream, double* kernel_ms);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

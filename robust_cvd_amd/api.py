@@ -405,6 +405,113 @@ def raft_check_gru(h_shape, x_shapes, weight_shapes, bias_shapes):
     return B, H, W
 
 
+CONV_KERNEL_SIZES = (1, 3, 7)     # the instantiations of csrc/cvd_raftconv.h; kConvSegmentMultiple / kConvMaxSegments / kConvTile
+CONV_SEGMENT_MULTIPLE = 32
+CONV_MAX_SEGMENTS = 3
+CONV_STACK_MULTIPLE = 64
+RAFT_COR_PLANES = 4 * 81          # corr_levels (2 corr_radius + 1)^2 of the RAFT the reference builds
+# The update block's 15 convolutions in the order of cvd_raft_update_block_device's weight and bias tables (the order of the
+# reference module's state dict): (name, out channels, in channels, filter size).  The six of the GRU are GRU_PARAMETERS.
+UPDATE_BLOCK_PARAMETERS = ("encoder.convc1", "encoder.convc2", "encoder.convf1", "encoder.convf2", "encoder.conv",
+                           "gru.convz1", "gru.convr1", "gru.convq1", "gru.convz2", "gru.convr2", "gru.convq2",
+                           "flow_head.conv1", "flow_head.conv2", "mask.0", "mask.2")
+
+
+def raft_block_weight_shape(name, cor_planes=RAFT_COR_PLANES):
+    """Shape of `<name>.weight` of the reference's BasicUpdateBlock(hidden_dim=128, input_dim=128)."""
+    if name.startswith("gru."):
+        return raft_gru_weight_shape(name[4:])
+    o, c, k = {"encoder.convc1": (256, int(cor_planes), 1), "encoder.convc2": (192, 256, 3), "encoder.convf1": (128, 2, 7),
+               "encoder.convf2": (64, 128, 3), "encoder.conv": (126, 256, 3), "flow_head.conv1": (256, 128, 3),
+               "flow_head.conv2": (2, 256, 3), "mask.0": (256, 128, 3), "mask.2": (576, 256, 1)}[name]
+    return (o, c, k, k)
+
+
+def raft_check_conv2d(segment_shapes, weight_shapes, bias_shapes, out_channels_total=None, out_first=0, stride=1, dilation=1,
+                      groups=1):
+    """(B, H, W, N) of one convolution of csrc/cvd_raftconv.h: the input's segments [B, C_i, H, W] (one of any C >= 1, or up to
+    three in multiples of 32), one weight [O, sum C_i, k, k] with k in (1, 3, 7) or two alike stacked along O (O a multiple of 64),
+    biases [O]; N = the output channels written, at out_first of a tensor of out_channels_total (default: exactly N).
+    ValueError (before any device work) for anything else."""
+    who = "RAFT conv2d"
+    for name, v in (("stride", stride), ("dilation", dilation), ("groups", groups)):
+        if v != 1 and tuple(v if isinstance(v, (tuple, list)) else (v,)) not in ((1,), (1, 1)):
+            raise ValueError(f"{who}: {name} must be 1 (got {v})")
+    segs = [tuple(int(v) for v in s) for s in segment_shapes]
+    if not 1 <= len(segs) <= CONV_MAX_SEGMENTS:
+        raise ValueError(f"{who}: the input must be one tensor or a tuple of up to {CONV_MAX_SEGMENTS} (got {len(segs)})")
+    if len(segs[0]) != 4:
+        raise ValueError(f"{who}: the input must be (B, C, H, W) (got {segs[0]})")
+    B, _, H, W = segs[0]
+    if B * H * W == 0:
+        raise ValueError(f"{who}: B H W = 0 (the input is {segs[0]})")
+    for s in segs:
+        if len(s) != 4 or (s[0], s[2], s[3]) != (B, H, W):
+            raise ValueError(f"{who}: a segment has shape {s}, expected ({B}, C, {H}, {W})")
+        if s[1] < 1:
+            raise ValueError(f"{who}: a segment has {s[1]} channels")
+        if len(segs) > 1 and s[1] % CONV_SEGMENT_MULTIPLE:
+            raise ValueError(f"{who}: a segment has {s[1]} channels, not a positive multiple of {CONV_SEGMENT_MULTIPLE} "
+                             "(several segments)")
+    cin = sum(s[1] for s in segs)
+    ws = [tuple(int(v) for v in s) for s in weight_shapes]
+    bs = [tuple(int(v) for v in s) for s in bias_shapes]
+    if not 1 <= len(ws) <= 2 or len(bs) != len(ws):
+        raise ValueError(f"{who}: one weight and bias, or two stacked, are expected (got {len(ws)}, {len(bs)})")
+    if len(ws[0]) != 4 or ws[0][2] != ws[0][3] or ws[0][2] not in CONV_KERNEL_SIZES:
+        raise ValueError(f"{who}: the filter must be square of size {CONV_KERNEL_SIZES} (weight {ws[0]})")
+    if ws[0][0] < 1:
+        raise ValueError(f"{who}: no output channels (weight {ws[0]})")
+    if ws[0][1] != cin:
+        raise ValueError(f"{who}: the input has {cin} channels, the weight {ws[0]} takes {ws[0][1]}")
+    for w, b in zip(ws, bs):
+        if w != ws[0]:
+            raise ValueError(f"{who}: stacked weights must have one shape (got {ws})")
+        if b != (w[0],):
+            raise ValueError(f"{who}: a bias must be ({w[0]},) (got {b})")
+    if len(ws) == 2 and ws[0][0] % CONV_STACK_MULTIPLE:
+        raise ValueError(f"{who}: stacked weights need output channels in multiples of {CONV_STACK_MULTIPLE} (got {ws[0][0]})")
+    N = ws[0][0] * len(ws)
+    total = N if out_channels_total is None else int(out_channels_total)
+    if int(out_first) < 0 or int(out_first) + N > total:
+        raise ValueError(f"{who}: the output window, channels {out_first} .. {int(out_first) + N - 1}, exceeds the tensor's {total}")
+    return B, H, W, N
+
+
+def raft_check_update_block(net_shape, inp_shape, corr_shape, flow_shape, weight_shapes, bias_shapes):
+    """(B, H, W) of BasicUpdateBlock.forward's inputs: net and inp [B, 128, H, W], corr [B, cor_planes, H, W] with cor_planes the
+    in_channels of encoder.convc1.weight, flow [B, 2, H, W]; the 15 weight and bias shapes in UPDATE_BLOCK_PARAMETERS order.
+    ValueError (before any device work) for anything else."""
+    who = "RAFT update block"
+    net_shape, inp_shape, corr_shape, flow_shape = (tuple(int(v) for v in s) for s in (net_shape, inp_shape, corr_shape, flow_shape))
+    if len(net_shape) != 4 or net_shape[1] != GRU_HIDDEN:
+        raise ValueError(f"{who}: net must be (B, {GRU_HIDDEN}, H, W) (got {net_shape})")
+    B, _, H, W = net_shape
+    if B * H * W == 0:
+        raise ValueError(f"{who}: B H W = 0 (net is {net_shape})")
+    if inp_shape != (B, 128, H, W):
+        raise ValueError(f"{who}: inp must be {(B, 128, H, W)} (got {inp_shape})")
+    if flow_shape != (B, 2, H, W):
+        raise ValueError(f"{who}: flow must be {(B, 2, H, W)} (got {flow_shape})")
+    if len(weight_shapes) != 15 or len(bias_shapes) != 15:
+        raise ValueError(f"{who}: 15 weights and 15 biases are expected, in the order {UPDATE_BLOCK_PARAMETERS}")
+    ws = [tuple(int(v) for v in s) for s in weight_shapes]
+    if len(ws[0]) != 4 or ws[0][1] < 1:
+        raise ValueError(f"{who}: encoder.convc1.weight must be (256, cor_planes, 1, 1) (got {ws[0]})")
+    cor_planes = ws[0][1]
+    if len(corr_shape) != 4 or (corr_shape[0], corr_shape[2], corr_shape[3]) != (B, H, W):
+        raise ValueError(f"{who}: corr must be ({B}, {cor_planes}, {H}, {W}) (got {corr_shape})")
+    if corr_shape[1] != cor_planes:
+        raise ValueError(f"{who}: corr has {corr_shape[1]} channels, encoder.convc1 takes {cor_planes}")
+    for name, w, b in zip(UPDATE_BLOCK_PARAMETERS, ws, bias_shapes):
+        want = raft_block_weight_shape(name, cor_planes)
+        if w != want:
+            raise ValueError(f"{who}: {name}.weight must be {want} (got {w})")
+        if tuple(int(v) for v in b) != (want[0],):
+            raise ValueError(f"{who}: {name}.bias must be ({want[0]},) (got {tuple(b)})")
+    return B, H, W
+
+
 class _DeviceArrays:
     """Raw device buffers of the numpy mirror of a `*_device` entry point (null stream, blocking copies); freed on exit."""
 
@@ -521,7 +628,7 @@ EXPORTED_SYMBOLS = [
     "cvd_get_xform_desc", "cvd_num_xform_params", "cvd_get_xform_params", "cvd_set_xform_params",
     "cvd_get_pose_params", "cvd_set_pose_params", "cvd_block_size", "cvd_normalize_depth", "cvd_pose_optimization",
     "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_scene_flow_loss", "cvd_scene_flow_loss_device", "cvd_spatial_losses", "cvd_spatial_losses_device", "cvd_param_chunk", "cvd_parameter_l1", "cvd_parameter_l1_device", "cvd_param_step", "cvd_param_step_device", "cvd_dataset_create", "cvd_dataset_clear", "cvd_dataset_set_colors", "cvd_dataset_set_flows", "cvd_dataset_set_depth_orig", "cvd_dataset_set_cameras", "cvd_dataset_set_xforms", "cvd_dataset_set_maps", "cvd_dataset_batch", "cvd_dataset_batch_device", "cvd_dataset_bad_indices",
-    "cvd_raft_corr_pyramid_device", "cvd_raft_corr_lookup_device", "cvd_raft_upsample_flow_device", "cvd_raft_sepconv_gru_device", "cvd_raft_sepconv_gru_timed", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
+    "cvd_raft_corr_pyramid_device", "cvd_raft_corr_lookup_device", "cvd_raft_upsample_flow_device", "cvd_raft_sepconv_gru_device", "cvd_raft_sepconv_gru_timed", "cvd_raft_conv2d_device", "cvd_raft_update_block_device", "cvd_raft_update_block_timed", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
     "cvd_get_kernel_times", "cvd_get_comm_times", "cvd_get_dense_times", "cvd_set_kernel_timing", "cvd_num_active_constraints", "cvd_coarse_debug", "cvd_temporal_debug", "cvd_path_info", "cvd_abi_revision",
     "cvd_block_inverse_debug", "cvd_dense_inverse_debug", "cvd_epipolar_debug", "cvd_flow_masks_debug",
     "cvd_product_launch_debug", "cvd_assembly_launch_debug",
@@ -1128,6 +1235,72 @@ class Solver(Binding):
                 raise RuntimeError("raft_sepconv_gru: the device reported an error")
             dev.download(do, out)
         return out
+
+    def raft_conv2d(self, x, weights, biases, relu=False, scale=1.0, out=None, out_first=0):
+        """One convolution of the update block (csrc/cvd_raftconv.h): x [B, C, H, W] f32 or a tuple of up to three
+        (channel counts in multiples of 32, never concatenated); weights = one array [O, C, k, k] (k = 1, 3, 7; stride 1, padding
+        k // 2) or a list of two alike, stacked along O; biases alike; scale * act(conv + bias).  With `out` [B, C_out, H, W] the
+        result goes to its channels out_first .. and the other channels keep their values; the array itself is returned (a copy)."""
+        import numpy as np
+        segs = [np.asarray(a) for a in (x if isinstance(x, (tuple, list)) else (x,))]
+        ws = [np.asarray(a) for a in (weights if isinstance(weights, (tuple, list)) else (weights,))]
+        bs = [np.asarray(a) for a in (biases if isinstance(biases, (tuple, list)) else (biases,))]
+        given = None if out is None else np.asarray(out)
+        for a in segs + ws + bs + ([] if given is None else [given]):
+            if a.dtype != np.float32:
+                raise TypeError(f"raft_conv2d: every array must be float32 (got {a.dtype})")
+        B, H, W, N = raft_check_conv2d([a.shape for a in segs], [a.shape for a in ws], [a.shape for a in bs],
+                                       None if given is None else (given.shape[1] if given.ndim == 4 else -1), out_first)
+        if given is not None and (given.shape[0], given.shape[2], given.shape[3]) != (B, H, W):
+            raise ValueError(f"raft_conv2d: out has shape {given.shape}, expected ({B}, C, {H}, {W})")
+        res = np.zeros((B, N, H, W), np.float32) if given is None else np.ascontiguousarray(given).copy()
+        with _DeviceArrays() as dev:
+            ds = [dev.upload(np.ascontiguousarray(a)) for a in segs]
+            dw = [dev.upload(np.ascontiguousarray(a)) for a in ws]
+            db = [dev.upload(np.ascontiguousarray(a)) for a in bs]
+            do = dev.upload(res)
+            self._check(self._fn("raft_conv2d_device")(
+                self._h, C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(len(ds)), (C.c_void_p * len(ds))(*[p.value for p in ds]),
+                (C.c_int32 * len(ds))(*[a.shape[1] for a in segs]), C.c_int32(len(dw)), (C.c_void_p * len(dw))(*[p.value for p in dw]),
+                (C.c_void_p * len(db))(*[p.value for p in db]), C.c_int32(ws[0].shape[1]), C.c_int32(ws[0].shape[0]),
+                C.c_int32(ws[0].shape[2]), C.c_int32(1), C.c_int32(1), C.c_int32(1), C.c_int32(1 if relu else 0), C.c_float(scale),
+                do, C.c_int32(res.shape[1]), C.c_int32(out_first), None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("raft_conv2d: the device reported an error")
+            dev.download(do, res)
+        return res
+
+    def raft_update_block(self, net, inp, corr, flow, weights, biases, compute_mask=True):
+        """BasicUpdateBlock.forward (raft/core/update.py:133-156): net, inp [B, 128, H, W], corr
+        [B, cor_planes, H, W], flow [B, 2, H, W] f32, weights / biases = the 15 of UPDATE_BLOCK_PARAMETERS in torch's shapes ->
+        (net [B, 128, H, W], mask [B, 576, H, W] or None without compute_mask, delta_flow [B, 2, H, W])."""
+        import numpy as np
+        net, inp, corr, flow = (np.asarray(a) for a in (net, inp, corr, flow))
+        weights, biases = [np.asarray(a) for a in weights], [np.asarray(a) for a in biases]
+        for a in [net, inp, corr, flow] + weights + biases:
+            if a.dtype != np.float32:
+                raise TypeError(f"raft_update_block: every array must be float32 (got {a.dtype})")
+        B, H, W = raft_check_update_block(net.shape, inp.shape, corr.shape, flow.shape, [a.shape for a in weights],
+                                          [a.shape for a in biases])
+        net_out = np.zeros((B, GRU_HIDDEN, H, W), np.float32)
+        delta = np.zeros((B, 2, H, W), np.float32)
+        mask = np.zeros((B, 576, H, W), np.float32) if compute_mask else None
+        with _DeviceArrays() as dev:
+            dn, di, dc, df = (dev.upload(np.ascontiguousarray(a)) for a in (net, inp, corr, flow))
+            dw = [dev.upload(np.ascontiguousarray(a)) for a in weights]
+            db = [dev.upload(np.ascontiguousarray(a)) for a in biases]
+            do, dd = dev.alloc(net_out.nbytes), dev.alloc(delta.nbytes)
+            dm = dev.alloc(mask.nbytes) if compute_mask else None
+            self._check(self._fn("raft_update_block_device")(
+                self._h, C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(corr.shape[1]), C.c_int32(weights[0].shape[1]),
+                dn, di, dc, df, (C.c_void_p * 15)(*[p.value for p in dw]), (C.c_void_p * 15)(*[p.value for p in db]), do, dd, dm, None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("raft_update_block: the device reported an error")
+            dev.download(do, net_out)
+            dev.download(dd, delta)
+            if compute_mask:
+                dev.download(dm, mask)
+        return net_out, mask, delta
 
     def num_active_constraints(self):
         return int(self._lib.cvd_num_active_constraints(self._h))

@@ -854,6 +854,33 @@ int32_t cvd_raft_sepconv_gru_timed(cvd_handle* h, int32_t batch, int32_t height,
   CVD_TRY(h, raftSepConvGruDevice(h, batch, height, width, hidden, num_segments, segments, segment_channels, weights, biases, out,
                                   static_cast<hipStream_t>(stream), kernel_ms));
 }
+// reference raft/core/update.py:8-16, 96-114, 141-145 (the nn.Conv2d of FlowHead, BasicMotionEncoder and the mask head, their ReLU)
+int32_t cvd_raft_conv2d_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t num_segments,
+                               const float* const* segments, const int32_t* segment_channels, int32_t num_weights,
+                               const float* const* weights, const float* const* biases, int32_t in_channels, int32_t out_channels,
+                               int32_t kernel_size, int32_t stride, int32_t dilation, int32_t groups, int32_t activation, float scale,
+                               float* out, int32_t out_total_channels, int32_t out_first_channel, void* stream) {
+  CVD_TRY(h, raftConv2dDevice(h, batch, height, width, num_segments, segments, segment_channels, num_weights, weights, biases,
+                              in_channels, out_channels, kernel_size, stride, dilation, groups, activation, scale, out,
+                              out_total_channels, out_first_channel, static_cast<hipStream_t>(stream)));
+}
+// reference raft/core/update.py:133-156 (BasicUpdateBlock.forward)
+int32_t cvd_raft_update_block_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t corr_channels,
+                                     int32_t cor_planes, const float* net, const float* inp, const float* corr, const float* flow,
+                                     const float* const* weights, const float* const* biases, float* net_out, float* delta_flow,
+                                     float* mask, void* stream) {
+  CVD_TRY(h, raftUpdateBlockDevice(h, batch, height, width, corr_channels, cor_planes, net, inp, corr, flow, weights, biases, net_out,
+                                   delta_flow, mask, static_cast<hipStream_t>(stream), nullptr));
+}
+int32_t cvd_raft_update_block_timed(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t corr_channels,
+                                    int32_t cor_planes, const float* net, const float* inp, const float* corr, const float* flow,
+                                    const float* const* weights, const float* const* biases, float* net_out, float* delta_flow,
+                                    float* mask, void* stream, double* kernel_ms) {
+  if (!kernel_ms) return cvd_raft_update_block_device(h, batch, height, width, corr_channels, cor_planes, net, inp, corr, flow, weights,
+                                                      biases, net_out, delta_flow, mask, stream);
+  CVD_TRY(h, raftUpdateBlockDevice(h, batch, height, width, corr_channels, cor_planes, net, inp, corr, flow, weights, biases, net_out,
+                                   delta_flow, mask, static_cast<hipStream_t>(stream), kernel_ms));
+}
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {

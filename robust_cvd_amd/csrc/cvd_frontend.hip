@@ -2,7 +2,7 @@
 // consumers, flow-guided and bilateral filters, feature tracks, flow consistency masks, the fine-tuning consistency,
 // scene-flow and spatial losses, the parameter regulariser and the optimizer step, the fine-tuning batches, RAFT's correlation pyramid / lookup and convex
 // upsampling (cvd_raftops.h: k_corr_pyramid, k_corr_lookup, k_convex_upsample), the SepConvGRU of RAFT's update block
-// (cvd_raftgru.h: k_gru_gemm).  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
+// (cvd_raftgru.h: k_gru_gemm) and its other convolutions (cvd_raftconv.h: k_raft_conv).  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
 // through a pointer to the incomplete type).
 #include "cvd_host.h"
 #include "cvd_dense.h"
@@ -21,6 +21,7 @@
 #include "cvd_batch.h"
 #include "cvd_raftops.h"
 #include "cvd_raftgru.h"
+#include "cvd_raftconv.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -132,6 +133,9 @@ struct Frontend {
   // cvd_raftgru.h: sigmoid(z), r h and the state between the halves, 128 B H W floats each.  The device entry point uses them on
   // the caller's stream (the loss operators' rule: calls on one device are ordered on one stream).
   DevBuf<float> dGru;
+  // cvd_raftconv.h: the update block's intermediates (cor1, cor_flo, flo1, motion_features; the stacked heads' hidden tensor lies
+  // over the first two, which are dead by then), 768 B H W floats, under the same rule.
+  DevBuf<float> dBlock;
 };
 
 std::shared_ptr<Frontend> makeFrontend() { return std::make_shared<Frontend>(); }
@@ -2284,6 +2288,244 @@ void raftSepConvGruDevice(cvd_handle* h, int B, int H, int W, const float* hidde
   if (kernelMs) {
     timer.wait();
     timer.collect();
+  }
+}
+
+// ---- The stock convolutions of RAFT's update block and the block itself (reference raft/core/update.py:8-16, 96-114, 133-156;
+// cvd_raftconv.h).  Device arrays on the caller's stream: enqueued launches only. ------------------------------------
+namespace {
+template <int KS>
+void launchRaftConvK(const ConvArgs& A, bool vec, dim3 grid, hipStream_t s) {
+  if constexpr (KS != 7) {
+    if (vec) {
+      hipLaunchKernelGGL((k_raft_conv<KS, true>), grid, dim3(kConvThreads), 0, s, A);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((k_raft_conv<KS, false>), grid, dim3(kConvThreads), 0, s, A);
+}
+
+// One launch.  The arguments have been checked by the callers (checkRaftConvShape and their own pointer checks).
+void launchRaftConv(const ConvArgs& A, int ks, hipStream_t s) {
+  const long long tiles = (A.M + kConvTile - 1) / kConvTile;
+  const dim3 grid(static_cast<unsigned>(tiles), static_cast<unsigned>((A.N + kConvTile - 1) / kConvTile));
+  // float4 weight loads only where every row of every tensor starts on 16 bytes
+  bool vec = (static_cast<long long>(A.Cin) * ks * ks) % 4 == 0;
+  for (int i = 0; i < (A.N > A.nPer ? 2 : 1); ++i) vec = vec && (reinterpret_cast<uintptr_t>(A.w[i]) & 15) == 0;
+  switch (ks) {
+    case 1: launchRaftConvK<1>(A, vec, grid, s); break;
+    case 3: launchRaftConvK<3>(A, vec, grid, s); break;
+    default: launchRaftConvK<7>(A, vec, grid, s); break;
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// (M, HW) of a convolution over B x H x W pixels with the filter and the workgroup count in range
+long long checkRaftConvShape(const char* who, int B, int H, int W, int ks) {
+  if (B < 1 || H < 1 || W < 1) throw std::runtime_error(fmt("%s: batch, height and width must be >= 1 (got %d, %d, %d)", who, B, H, W));
+  if (ks != 1 && ks != 3 && ks != 7) throw std::runtime_error(fmt("%s: kernel_size must be 1, 3 or 7 (got %d)", who, ks));
+  const long long HW = static_cast<long long>(H) * W;
+  if (HW > 0x7fffffffll) throw std::runtime_error(fmt("%s: %d x %d pixels per image exceed 2^31", who, H, W));
+  const long long M = HW * B;
+  if ((M + kConvTile - 1) / kConvTile > 0x7fffffffll) throw std::runtime_error(fmt("%s: %lld pixels exceed the grid", who, M));
+  return M;
+}
+
+bool rangesOverlap(const void* a, long long aFloats, const void* b, long long bFloats) {
+  const uintptr_t alo = reinterpret_cast<uintptr_t>(a), ahi = alo + static_cast<uintptr_t>(aFloats) * sizeof(float);
+  const uintptr_t blo = reinterpret_cast<uintptr_t>(b), bhi = blo + static_cast<uintptr_t>(bFloats) * sizeof(float);
+  return alo < bhi && blo < ahi;
+}
+
+ConvArgs raftConvArgs(int B, int H, int W) {
+  ConvArgs A{};
+  A.H = H; A.W = W; A.HW = H * W;
+  A.M = static_cast<long long>(A.HW) * B;
+  A.scale = 1.f;
+  return A;
+}
+void raftConvInput(ConvArgs& A, const float* p, int c0, int C, int n) {
+  A.seg[A.numSeg++] = ConvSegment{p, c0, C, n};
+  A.Cin += n;
+}
+void raftConvWeights(ConvArgs& A, const float* w0, const float* b0, const float* w1, const float* b1, int nPer) {
+  A.w[0] = w0; A.bias[0] = b0; A.w[1] = w1; A.bias[1] = b1;
+  A.nPer = nPer;
+  A.N = w1 ? 2 * nPer : nPer;
+}
+void raftConvOutput(ConvArgs& A, float* out, int outC, int outC0, int relu) {
+  A.out = out; A.outC = outC; A.outC0 = outC0; A.relu = relu;
+}
+}  // namespace
+
+void raftConv2dDevice(cvd_handle*, int B, int H, int W, int numSegments, const float* const* segments,
+                      const int32_t* segmentChannels, int numWeights, const float* const* weights, const float* const* biases,
+                      int inChannels, int outChannels, int kernelSize, int stride, int dilation, int groups, int relu, float scale,
+                      float* out, int outTotalChannels, int outFirstChannel, hipStream_t s) {
+  const char* who = "raft conv2d";
+  const long long M = checkRaftConvShape(who, B, H, W, kernelSize);
+  if (stride != 1) throw std::runtime_error(fmt("%s: stride must be 1 (got %d)", who, stride));
+  if (dilation != 1) throw std::runtime_error(fmt("%s: dilation must be 1 (got %d)", who, dilation));
+  if (groups != 1) throw std::runtime_error(fmt("%s: groups must be 1 (got %d)", who, groups));
+  if (relu != 0 && relu != 1) throw std::runtime_error(fmt("%s: activation must be 0 (none) or 1 (ReLU) (got %d)", who, relu));
+  if (numSegments < 1 || numSegments > kConvMaxSegments)
+    throw std::runtime_error(fmt("%s: num_segments must be 1..%d (got %d)", who, kConvMaxSegments, numSegments));
+  if (numWeights < 1 || numWeights > 2) throw std::runtime_error(fmt("%s: num_weights must be 1 or 2 (got %d)", who, numWeights));
+  if (!segments || !segmentChannels || !weights || !biases || !out) throw std::runtime_error(fmt("%s: null array", who));
+  long long sum = 0;
+  for (int i = 0; i < numSegments; ++i) {
+    const int c = segmentChannels[i];
+    if (c < 1) throw std::runtime_error(fmt("%s: segment %d has %d channels", who, i, c));
+    if (numSegments > 1 && c % kConvSegmentMultiple)
+      throw std::runtime_error(fmt("%s: segment %d has %d channels, not a positive multiple of %d (several segments)", who, i, c,
+                                   kConvSegmentMultiple));
+    if (!segments[i]) throw std::runtime_error(fmt("%s: null segment %d", who, i));
+    sum += c;
+  }
+  if (sum != inChannels)
+    throw std::runtime_error(fmt("%s: the segments hold %lld channels, the weights' in_channels is %d", who, sum, inChannels));
+  if (static_cast<long long>(inChannels) * kernelSize * kernelSize > 0x7fffffffll)
+    throw std::runtime_error(fmt("%s: in_channels %d exceeds the kernel's range", who, inChannels));
+  if (outChannels < 1) throw std::runtime_error(fmt("%s: out_channels must be >= 1 (got %d)", who, outChannels));
+  if (numWeights == 2 && outChannels % kConvTile)
+    throw std::runtime_error(fmt("%s: two stacked weight tensors need out_channels in multiples of %d (got %d)", who, kConvTile, outChannels));
+  for (int i = 0; i < numWeights; ++i)
+    if (!weights[i] || !biases[i]) throw std::runtime_error(fmt("%s: null weight or bias %d", who, i));
+  const long long N = static_cast<long long>(outChannels) * numWeights;
+  if (outFirstChannel < 0 || outTotalChannels < 1 || outFirstChannel + N > outTotalChannels)
+    throw std::runtime_error(fmt("%s: the output window, channels %d .. %lld, exceeds the tensor's %d channels", who, outFirstChannel,
+                                 outFirstChannel + N - 1, outTotalChannels));
+  for (int i = 0; i < numSegments; ++i)
+    if (rangesOverlap(out, outTotalChannels * M, segments[i], segmentChannels[i] * M))
+      throw std::runtime_error(fmt("%s: out overlaps segment %d of the input", who, i));
+
+  ConvArgs A = raftConvArgs(B, H, W);
+  for (int i = 0; i < numSegments; ++i) raftConvInput(A, segments[i], 0, segmentChannels[i], segmentChannels[i]);
+  raftConvWeights(A, weights[0], biases[0], numWeights == 2 ? weights[1] : nullptr, numWeights == 2 ? biases[1] : nullptr, outChannels);
+  raftConvOutput(A, out, outTotalChannels, outFirstChannel, relu);
+  A.scale = scale;
+  launchRaftConv(A, kernelSize, s);
+}
+
+// BasicUpdateBlock.forward.  weights / biases: the 15 tensors in the order include/cvd_hip.h documents.
+// kernelMs (measurement only, may be null): 12 entries, the launches in their order; with it the call waits on the host.
+void raftUpdateBlockDevice(cvd_handle* h, int B, int H, int W, int corrChannels, int corPlanes, const float* net, const float* inp,
+                           const float* corr, const float* flow, const float* const* weights, const float* const* biases,
+                           float* netOut, float* deltaFlow, float* mask, hipStream_t s, double* kernelMs) {
+  const char* who = "raft update block";
+  const long long M = checkRaftConvShape(who, B, H, W, 3);
+  if (corrChannels < 1) throw std::runtime_error(fmt("%s: corr_channels must be >= 1 (got %d)", who, corrChannels));
+  if (corrChannels != corPlanes)
+    throw std::runtime_error(fmt("%s: corr has %d channels, encoder.convc1 takes %d", who, corrChannels, corPlanes));
+  if (!net || !inp || !corr || !flow || !weights || !biases || !netOut || !deltaFlow) throw std::runtime_error(fmt("%s: null array", who));
+  for (int i = 0; i < 15; ++i)
+    if (!weights[i] || !biases[i]) throw std::runtime_error(fmt("%s: null weight or bias %d", who, i));
+  struct Span { const float* p; long long channels; const char* name; };
+  const Span ins[] = {{net, 128, "net"}, {inp, 128, "inp"}, {corr, corrChannels, "corr"}, {flow, 2, "flow"}};
+  const Span outs[] = {{netOut, 128, "net_out"}, {deltaFlow, 2, "delta_flow"}, {mask, 576, "mask"}};
+  for (const Span& o : outs) {
+    if (!o.p) continue;
+    for (const Span& i : ins)
+      if (rangesOverlap(o.p, o.channels * M, i.p, i.channels * M)) throw std::runtime_error(fmt("%s: %s overlaps %s", who, o.name, i.name));
+    for (const Span& o2 : outs)
+      if (o2.p && o2.p != o.p && rangesOverlap(o.p, o.channels * M, o2.p, o2.channels * M))
+        throw std::runtime_error(fmt("%s: %s overlaps %s", who, o.name, o2.name));
+  }
+  for (int i = 5; i < 11; ++i) checkAligned16(who, "gru weight", weights[i]);   // (before any launch: the GRU's own check comes later)
+
+  Frontend& fe = *h->frontend;
+  const size_t m = static_cast<size_t>(M);
+  fe.dBlock.ensure(768 * m);
+  float* cor1 = fe.dBlock.p;               // 256 channels
+  float* corFlo = cor1 + 256 * m;          // 256: convc2 -> 0..191, convf2 -> 192..255
+  float* flo1 = corFlo + 256 * m;          // 128
+  float* motion = flo1 + 128 * m;          // 128: conv -> 0..125, flow -> 126..127
+  float* hidden = cor1;                    // 512 (256 without the mask): flow_head.conv1 | mask.0, once cor1 and cor_flo are dead
+  fe.dGru.ensure(3 * 128 * m);             // (the GRU's scratch, so that its call below does not allocate between launches)
+
+  KernelTimer enc(s, kernelMs, 5);
+  enc.mark();
+  {  // encoder.convc1: 1 x 1, corr -> 256, ReLU
+    ConvArgs A = raftConvArgs(B, H, W);
+    raftConvInput(A, corr, 0, corrChannels, corrChannels);
+    raftConvWeights(A, weights[0], biases[0], nullptr, nullptr, 256);
+    raftConvOutput(A, cor1, 256, 0, 1);
+    launchRaftConv(A, 1, s);
+    enc.mark();
+  }
+  {  // encoder.convc2: 3 x 3, 256 -> 192, ReLU, into cor_flo 0..191
+    ConvArgs A = raftConvArgs(B, H, W);
+    raftConvInput(A, cor1, 0, 256, 256);
+    raftConvWeights(A, weights[1], biases[1], nullptr, nullptr, 192);
+    raftConvOutput(A, corFlo, 256, 0, 1);
+    launchRaftConv(A, 3, s);
+    enc.mark();
+  }
+  {  // encoder.convf1: 7 x 7, 2 -> 128, ReLU
+    ConvArgs A = raftConvArgs(B, H, W);
+    raftConvInput(A, flow, 0, 2, 2);
+    raftConvWeights(A, weights[2], biases[2], nullptr, nullptr, 128);
+    raftConvOutput(A, flo1, 128, 0, 1);
+    launchRaftConv(A, 7, s);
+    enc.mark();
+  }
+  {  // encoder.convf2: 3 x 3, 128 -> 64, ReLU, into cor_flo 192..255
+    ConvArgs A = raftConvArgs(B, H, W);
+    raftConvInput(A, flo1, 0, 128, 128);
+    raftConvWeights(A, weights[3], biases[3], nullptr, nullptr, 64);
+    raftConvOutput(A, corFlo, 256, 192, 1);
+    launchRaftConv(A, 3, s);
+    enc.mark();
+  }
+  {  // encoder.conv: 3 x 3, 256 -> 126, ReLU, into motion_features 0..125; the same launch copies flow to 126..127
+    ConvArgs A = raftConvArgs(B, H, W);
+    raftConvInput(A, corFlo, 0, 256, 256);
+    raftConvWeights(A, weights[4], biases[4], nullptr, nullptr, 126);
+    raftConvOutput(A, motion, 128, 0, 1);
+    A.copySrc = flow; A.copyC = 2; A.copyC0 = 126;
+    launchRaftConv(A, 3, s);
+    enc.mark();
+  }
+  if (kernelMs) {
+    enc.wait();
+    enc.collect();
+  }
+  {  // gru: the existing four launches, x = (inp, motion_features)
+    const float* segs[2] = {inp, motion};
+    const int32_t chans[2] = {128, 128};
+    raftSepConvGruDevice(h, B, H, W, net, 2, segs, chans, weights + 5, biases + 5, netOut, s, kernelMs ? kernelMs + 5 : nullptr);
+  }
+  KernelTimer heads(s, kernelMs ? kernelMs + 9 : nullptr, 3);
+  heads.mark();
+  const int hiddenC = mask ? 512 : 256;
+  {  // flow_head.conv1 and mask.0 stacked: 3 x 3, 128 -> 256 (+ 256), ReLU
+    ConvArgs A = raftConvArgs(B, H, W);
+    raftConvInput(A, netOut, 0, 128, 128);
+    raftConvWeights(A, weights[11], biases[11], mask ? weights[13] : nullptr, mask ? biases[13] : nullptr, 256);
+    raftConvOutput(A, hidden, hiddenC, 0, 1);
+    launchRaftConv(A, 3, s);
+    heads.mark();
+  }
+  {  // flow_head.conv2: 3 x 3, 256 -> 2
+    ConvArgs A = raftConvArgs(B, H, W);
+    raftConvInput(A, hidden, 0, hiddenC, 256);
+    raftConvWeights(A, weights[12], biases[12], nullptr, nullptr, 2);
+    raftConvOutput(A, deltaFlow, 2, 0, 0);
+    launchRaftConv(A, 3, s);
+    heads.mark();
+  }
+  if (mask) {  // mask.2: 1 x 1, 256 -> 576, x 0.25
+    ConvArgs A = raftConvArgs(B, H, W);
+    raftConvInput(A, hidden, 256, 512, 256);
+    raftConvWeights(A, weights[14], biases[14], nullptr, nullptr, 576);
+    raftConvOutput(A, mask, 576, 0, 0);
+    A.scale = 0.25f;
+    launchRaftConv(A, 1, s);
+    heads.mark();
+  }
+  if (kernelMs) {
+    heads.wait();
+    heads.collect();
   }
 }
 

@@ -777,5 +777,12 @@ void raftUpsampleFlowDevice(cvd_handle* h, int N, int H, int W, const float* flo
 void raftSepConvGruDevice(cvd_handle* h, int B, int H, int W, const float* hidden, int numSegments, const float* const* segments,
                           const int32_t* segmentChannels, const float* const* weights, const float* const* biases, float* out,
                           hipStream_t s, double* kernelMs);
+void raftConv2dDevice(cvd_handle* h, int B, int H, int W, int numSegments, const float* const* segments,
+                      const int32_t* segmentChannels, int numWeights, const float* const* weights, const float* const* biases,
+                      int inChannels, int outChannels, int kernelSize, int stride, int dilation, int groups, int relu, float scale,
+                      float* out, int outTotalChannels, int outFirstChannel, hipStream_t s);
+void raftUpdateBlockDevice(cvd_handle* h, int B, int H, int W, int corrChannels, int corPlanes, const float* net, const float* inp,
+                           const float* corr, const float* flow, const float* const* weights, const float* const* biases,
+                           float* netOut, float* deltaFlow, float* mask, hipStream_t s, double* kernelMs);
 
 }  // namespace cvd

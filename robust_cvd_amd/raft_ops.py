@@ -19,6 +19,11 @@ csrc/cvd_raftgru.h: `from robust_cvd_amd.raft_ops import SepC
 ValueError / TypeError and before any device work, other sizes than (128, 256), segments of x that are not multiples of 32
 channels, CPU tensors, other dtypes, and an input or parameter that requires grad while grad mode is on.
 
+BasicMotionEncoder, FlowHead and BasicUpdateBlock are the rest of the update block (raft/core/update.py:8-16, 96-114, 133-156)
+with the reference's parameter names, on csrc/cvd_raftconv.h: `from robust_cvd_amd.raft_ops import
+BasicUpdateBlock` in raft/core/update.py (or raft/core/raft.py).  A block call is 8 launches beside the GRU's 4, no cat, on the
+current stream; the same domain rules and error types as SepConvGRU.
+
 Import this module (torch) before anything loads libcvd_hip.so.
 """
 import ctypes as C
@@ -133,6 +138,138 @@ class SepConvGRU(torch.nn.Module):
         _call(h.device, "raft_sepconv_gru_device", C.c_int32(B), C.c_int32(H), C.c_int32(W), tc.ptr(h), C.c_int32(len(segs)),
               seg_table, seg_channels, w_table, b_table, tc.ptr(out))
         return out
+
+
+def _check_forward(who, named):
+    """SepConvGRU's rules for a dict of named tensors: GPU, float32, no grad wanted, one device."""
+    for name, t in named.items():
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise ValueError(f"{who} runs on GPU tensors: {name} is not on a GPU (there is no CPU path)")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{who}: {name} must be float32 (got {t.dtype})")
+        if torch.is_grad_enabled() and t.requires_grad:
+            raise ValueError(f"{who} is forward only: {name} requires grad (call it under torch.no_grad())")
+    if len({t.device for t in named.values()}) != 1:
+        raise ValueError(f"{who}: the tensors are on different devices")
+
+
+def _conv2d(who, segs, convs, relu, scale=1.0, out=None, out_first=0):
+    """One launch of csrc/cvd_raftconv.h: the tensors `segs` (never concatenated) through one Conv2d module or two stacked along
+    the output channels, into a new tensor or the channels out_first .. of `out`."""
+    named = {f"x[{i}]": t for i, t in enumerate(segs)}
+    for i, m in enumerate(convs):
+        named[f"weight[{i}]"], named[f"bias[{i}]"] = m.weight, m.bias
+    if out is not None:
+        named["out"] = out
+    _check_forward(who, named)
+    for m in convs:
+        api.raft_check_conv2d([t.shape for t in segs], [m.weight.shape], [m.bias.shape], stride=m.stride, dilation=m.dilation,
+                              groups=m.groups)
+    B, H, W, N = api.raft_check_conv2d([t.shape for t in segs], [m.weight.shape for m in convs], [m.bias.shape for m in convs],
+                                       None if out is None else out.shape[1], out_first)
+    segs = [t.detach().contiguous() for t in segs]
+    weights = [m.weight.detach().contiguous() for m in convs]
+    biases = [m.bias.detach().contiguous() for m in convs]
+    if out is None:
+        out = torch.empty((B, N, H, W), dtype=torch.float32, device=segs[0].device)
+    elif not out.is_contiguous() or (out.shape[0], out.shape[2], out.shape[3]) != (B, H, W):
+        raise ValueError(f"{who}: out must be a contiguous ({B}, C, {H}, {W}) tensor (got {tuple(out.shape)})")
+    _call(out.device, "raft_conv2d_device", C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(len(segs)),
+          (C.c_void_p * len(segs))(*[t.data_ptr() for t in segs]), (C.c_int32 * len(segs))(*[t.shape[1] for t in segs]),
+          C.c_int32(len(weights)), (C.c_void_p * len(weights))(*[t.data_ptr() for t in weights]),
+          (C.c_void_p * len(biases))(*[t.data_ptr() for t in biases]), C.c_int32(weights[0].shape[1]), C.c_int32(weights[0].shape[0]),
+          C.c_int32(weights[0].shape[2]), C.c_int32(1), C.c_int32(1), C.c_int32(1), C.c_int32(1 if relu else 0), C.c_float(scale),
+          tc.ptr(out), C.c_int32(out.shape[1]), C.c_int32(out_first))
+    return out
+
+
+def _segments(x):
+    return tuple(x) if isinstance(x, (tuple, list)) else (x,)
+
+
+class FlowHead(torch.nn.Module):
+    """The reference's FlowHead (raft/core/update.py:8-16): conv2(relu(conv1(x))), two launches of csrc/cvd_raftconv.h."""
+
+    def __init__(self, input_dim=128, hidden_dim=256):
+        super().__init__()
+        self.conv1 = torch.nn.Conv2d(input_dim, hidden_dim, 3, padding=1)
+        self.conv2 = torch.nn.Conv2d(hidden_dim, 2, 3, padding=1)
+
+    def forward(self, x):
+        return _conv2d("FlowHead", (_conv2d("FlowHead", _segments(x), (self.conv1,), True),), (self.conv2,), False)
+
+
+class BasicMotionEncoder(torch.nn.Module):
+    """The reference's BasicMotionEncoder (raft/core/update.py:96-114): five launches of csrc/cvd_raftconv.h, the two cat replaced
+    by channel windows of the outputs (the last launch also copies flow into channels 126..127 when it runs inside the block; on
+    its own this module copies it with torch).  args: corr_levels and corr_radius are read (default 4, 4)."""
+
+    def __init__(self, args=None):
+        super().__init__()
+        cor_planes = getattr(args, "corr_levels", 4) * (2 * getattr(args, "corr_radius", 4) + 1) ** 2
+        self.convc1 = torch.nn.Conv2d(cor_planes, 256, 1, padding=0)
+        self.convc2 = torch.nn.Conv2d(256, 192, 3, padding=1)
+        self.convf1 = torch.nn.Conv2d(2, 128, 7, padding=3)
+        self.convf2 = torch.nn.Conv2d(128, 64, 3, padding=1)
+        self.conv = torch.nn.Conv2d(64 + 192, 128 - 2, 3, padding=1)
+
+    def forward(self, flow, corr):
+        who = "BasicMotionEncoder"
+        _check_forward(who, {"flow": flow, "corr": corr})
+        if flow.dim() != 4 or corr.dim() != 4 or flow.shape[1] != 2:
+            raise ValueError(f"{who}: flow must be (B, 2, H, W) and corr (B, C, H, W) (got {tuple(flow.shape)}, {tuple(corr.shape)})")
+        B, _, H, W = flow.shape
+        cor_flo = torch.empty((B, 256, H, W), dtype=torch.float32, device=flow.device)
+        out = torch.empty((B, 128, H, W), dtype=torch.float32, device=flow.device)
+        _conv2d(who, (_conv2d(who, (corr,), (self.convc1,), True),), (self.convc2,), True, out=cor_flo, out_first=0)
+        _conv2d(who, (_conv2d(who, (flow,), (self.convf1,), True),), (self.convf2,), True, out=cor_flo, out_first=192)
+        _conv2d(who, (cor_flo,), (self.conv,), True, out=out, out_first=0)
+        out[:, 126:] = flow.detach()
+        return out
+
+
+class BasicUpdateBlock(torch.nn.Module):
+    """The reference's BasicUpdateBlock(args, hidden_dim=128, input_dim=128) (raft/core/update.py:133-156) with its parameter names
+    and shapes (encoder.convc1 .. gru.convq2, flow_head.conv1 / conv2, mask.0 / mask.2), so the update_block.* part of a RAFT
+    state dict loads unchanged.  forward(net, inp, corr, flow) -> (net, mask, delta_flow) is ONE call of the library: 8 launches
+    of csrc/cvd_raftconv.h beside the 4 of the GRU, no cat, enqueued on the current stream without a host wait.
+    compute_mask=False returns None for the mask and skips mask.0 and mask.2 (7 launches).  Forward only, float32, GPU tensors; the
+    results are new tensors.  The scratch is the device handle's: calls on one device are ordered on one stream."""
+
+    def __init__(self, args=None, hidden_dim=128, input_dim=128):
+        super().__init__()
+        if (hidden_dim, input_dim) != (api.GRU_HIDDEN, 128):
+            raise ValueError(f"BasicUpdateBlock: hidden_dim = {api.GRU_HIDDEN} and input_dim = 128 are the only sizes of the kernels "
+                             f"(RAFT's); got {hidden_dim}, {input_dim}")
+        self.args = args
+        self.encoder = BasicMotionEncoder(args)
+        self.gru = SepConvGRU(hidden_dim=hidden_dim, input_dim=128 + hidden_dim)
+        self.flow_head = FlowHead(hidden_dim, hidden_dim=256)
+        self.mask = torch.nn.Sequential(torch.nn.Conv2d(128, 256, 3, padding=1), torch.nn.ReLU(inplace=True),
+                                        torch.nn.Conv2d(256, 64 * 9, 1, padding=0))
+
+    def forward(self, net, inp, corr, flow, upsample=True, compute_mask=True):
+        who = "BasicUpdateBlock"
+        modules = [self.get_submodule(n) for n in api.UPDATE_BLOCK_PARAMETERS]
+        weights, biases = [m.weight for m in modules], [m.bias for m in modules]
+        named = {"net": net, "inp": inp, "corr": corr, "flow": flow,
+                 **{f"{n}.weight": w for n, w in zip(api.UPDATE_BLOCK_PARAMETERS, weights)},
+                 **{f"{n}.bias": b for n, b in zip(api.UPDATE_BLOCK_PARAMETERS, biases)}}
+        _check_forward(who, named)
+        B, H, W = api.raft_check_update_block(net.shape, inp.shape, corr.shape, flow.shape, [w.shape for w in weights],
+                                              [b.shape for b in biases])
+        net, inp, corr, flow = (t.detach().contiguous() for t in (net, inp, corr, flow))
+        weights = [w.detach().contiguous() for w in weights]
+        biases = [b.detach().contiguous() for b in biases]
+        dev = net.device
+        net_out = torch.empty((B, api.GRU_HIDDEN, H, W), dtype=torch.float32, device=dev)
+        delta_flow = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev)
+        mask = torch.empty((B, 576, H, W), dtype=torch.float32, device=dev) if compute_mask else None
+        _call(dev, "raft_update_block_device", C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(corr.shape[1]),
+              C.c_int32(weights[0].shape[1]), tc.ptr(net), tc.ptr(inp), tc.ptr(corr), tc.ptr(flow),
+              (C.c_void_p * 15)(*[t.data_ptr() for t in weights]), (C.c_void_p * 15)(*[t.data_ptr() for t in biases]),
+              tc.ptr(net_out), tc.ptr(delta_flow), tc.ptr(mask) if compute_mask else None)
+        return net_out, mask, delta_flow
 
 
 def upsample_flow(flow, mask):
