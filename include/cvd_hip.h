@@ -793,6 +793,59 @@ int32_t cvd_raft_update_block_timed(cvd_handle* h, int32_t batch, int32_t height
                                     const float* const* weights, const float* const* biases, float* net_out, float* delta_flow,
                                     float* mask, void* stream, double* kernel_ms);
 
+/* ---- RAFT's feature and context encoders, DESIGN.md §3.18 -- reference raft/core/extractor.py:8-60 (ResidualBlock) and :124-197
+ * (BasicEncoder); SmallEncoder and BottleneckBlock are out of scope.  Independent of cvd_set_video.  f32, forward only, eval mode.
+ * DEVICE arrays, enqueued on `stream`: kernel launches only, no copy, no host synchronisation, no atomics; every output element is
+ * written once in a fixed operation order, so results repeat bit for bit and an image's result does not depend on its batch.
+ *
+ * One convolution -- square filter of kernel_size 1, 3 or 7, stride 1 or 2, padding kernel_size / 2, ONE launch:
+ *   x [batch][in_channels][height][width] -> out [batch][out_channels][ho][wo], ho = (height - 1) / stride + 1, wo alike
+ *   y = bias[o] + sum_{c,i,j} weight[o][c][i][j] x[b][c][stride y + i - r][stride x + j - r], the input outside the image counting 0;
+ *   norm != NULL: a host array of four device vectors [out_channels] in the state dict's order {weight, bias, running_mean,
+ *                 running_var} of an nn.BatchNorm2d in eval mode: y = (y - running_mean) / sqrt(running_var + eps) * weight + bias
+ *   relu != 0:    y = max(y, 0)
+ *   residual != NULL ([batch][out_channels][ho][wo]): y = max(residual + y, 0)
+ * weight is torch's [out_channels][in_channels][k][k], any alignment (float4 loads where its rows start on 16 bytes).  out must
+ * not overlap x, the weights or the residual.
+ * Rejected before any device work, with an error that names the value: null arrays, sizes < 1, a filter other than 1, 3, 7, a stride
+ * other than 1, 2, relu other than 0, 1, eps <= 0 with a norm, height width above 2^31, an output that overlaps x or the residual. */
+int32_t cvd_raft_encoder_conv_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels,
+                                     int32_t out_channels, int32_t kernel_size, int32_t stride, const float* x, const float* weight,
+                                     const float* bias, const float* const* norm, float eps, int32_t relu, const float* residual,
+                                     float* out, void* stream);
+/* nn.InstanceNorm2d(affine=False, track_running_stats=False) per (image, channel) plane of x [batch][channels][height][width]:
+ *   y = (x - mean) / sqrt(var + eps), var the biased variance; relu and residual as above.  Two launches: the statistics (mean first,
+ *   then squared deviations from it, f64 sums in a fixed order; two doubles per plane in scratch of the handle, under the rule of
+ *   cvd_raft_sepconv_gru_device) and the elementwise pass.  out may BE x (in place); any other overlap of out with x or the residual,
+ *   planes of one element (the reference: "Expected more than 1 spatial element"), eps <= 0, null arrays, sizes < 1 and
+ *   height width above 2^31 are rejected before any device work. */
+int32_t cvd_raft_instance_norm_device(cvd_handle* h, int32_t batch, int32_t channels, int32_t height, int32_t width, const float* x,
+                                      float eps, int32_t relu, const float* residual, float* out, void* stream);
+/* BasicEncoder.forward in eval mode (no dropout):
+ *   images     [batch][3][height][width], already scaled to [-1, 1]
+ *   norm_mode  0 none, 1 instance, 2 batch (eval: running statistics); eps is the norms' (1e-5 in torch)
+ *   weights, biases   host arrays of 16 device arrays in the state dict's order: conv1, layer1.0.conv1, layer1.0.conv2,
+ *              layer1.1.conv1, layer1.1.conv2, layer2.0.conv1, layer2.0.conv2, layer2.0.downsample.0, layer2.1.conv1, layer2.1.conv2,
+ *              layer3.0.conv1, layer3.0.conv2, layer3.0.downsample.0, layer3.1.conv1, layer3.1.conv2, conv2 ([output_dim][128][1][1])
+ *   norms      batch only (else ignored, may be NULL): host array of 15 x 4 device vectors, norm i belonging to convolution i (norm1,
+ *              layer1.0.norm1, layer1.0.norm2, .., layer2.0.norm3 (= downsample.1), ..), each as {weight, bias, running_mean,
+ *              running_var}
+ *   out        [batch][output_dim][ceil(height / 8)][ceil(width / 8)]
+ * 16 launches of the convolution above (none, batch); instance: 15 more of each of the two norm kernels.  Intermediates are scratch
+ * of the handle (high-water size, grown before the first launch) under the GRU's rule: calls on one device are ordered on one stream.
+ * The result equals, bit for bit, the stages chained through the two entry points above.
+ * Rejected before any device work: null arrays, sizes < 1, an unknown norm_mode, eps <= 0 with a norm, height width above 2^31,
+ * feature planes of one element under instance norm, an output that overlaps the images. */
+int32_t cvd_raft_encoder_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t output_dim, int32_t norm_mode,
+                                float eps, const float* images, const float* const* weights, const float* const* biases,
+                                const float* const* norms, float* out, void* stream);
+/* The same call for measurement (tools/raftenc_bench.py): HIP events around every launch on `stream` and a host wait;
+ * kernel_ms[48]: entry 3 i is convolution i, 3 i + 1 and 3 i + 2 the statistics and the elementwise pass of the instance norm behind
+ * it (0 where there is none), in milliseconds. */
+int32_t cvd_raft_encoder_timed(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t output_dim, int32_t norm_mode,
+                               float eps, const float* images, const float* const* weights, const float* const* biases,
+                               const float* const* norms, float* out, void* stream, double* kernel_ms);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

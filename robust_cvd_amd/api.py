@@ -307,16 +307,12 @@ def _hip_runtime():
     of a `*_device` entry point needs (Solver.dataset_batch(device_entry=True)); torch callers use torch's tensors instead."""
     global _hip
     if _hip is None:
-        load_library()
-        path = None
-        with open("/proc/self/maps") as f:
-            for line in f:
-                if "libamdhip64" in line:
-                    path = line.split()[-1]
-                    break
-        if path is None:
+        # The runtime libcvd_hip.so itself is bound to: symbols looked up through the library's own handle resolve in its
+        # dependencies.  (A process may hold a second copy -- torch imported after the library brings its own -- and device memory
+        # of one runtime means nothing to the other.)
+        lib = C.CDLL(load_library()._name)
+        if not hasattr(lib, "hipMalloc"):
             raise RuntimeError("the HIP runtime is not loaded in this process")
-        lib = C.CDLL(path)
         lib.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
         lib.hipFree.argtypes = [C.c_void_p]
         lib.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -512,6 +508,146 @@ def raft_check_update_block(net_shape, inp_shape, corr_shape, flow_shape, weight
     return B, H, W
 
 
+ENCODER_KERNEL_SIZES = (1, 3, 7)       # the instantiations of csrc/cvd_raftenc.h
+ENCODER_STRIDES = (1, 2)
+ENCODER_NORM_MODES = {"none": 0, "instance": 1, "batch": 2}      # norm_mode of cvd_raft_encoder_device
+# The sixteen convolutions of the reference's BasicEncoder in the order of cvd_raft_encoder_device's weight and bias tables (the
+# order of the module's state dict): name -> (out channels, in channels, filter, stride); conv2's out channels are output_dim.
+ENCODER_LAYERS = (("conv1", 64, 3, 7, 2),
+                  ("layer1.0.conv1", 64, 64, 3, 1), ("layer1.0.conv2", 64, 64, 3, 1),
+                  ("layer1.1.conv1", 64, 64, 3, 1), ("layer1.1.conv2", 64, 64, 3, 1),
+                  ("layer2.0.conv1", 96, 64, 3, 2), ("layer2.0.conv2", 96, 96, 3, 1), ("layer2.0.downsample.0", 96, 64, 1, 2),
+                  ("layer2.1.conv1", 96, 96, 3, 1), ("layer2.1.conv2", 96, 96, 3, 1),
+                  ("layer3.0.conv1", 128, 96, 3, 2), ("layer3.0.conv2", 128, 128, 3, 1), ("layer3.0.downsample.0", 128, 96, 1, 2),
+                  ("layer3.1.conv1", 128, 128, 3, 1), ("layer3.1.conv2", 128, 128, 3, 1),
+                  ("conv2", None, 128, 1, 1))
+ENCODER_PARAMETERS = tuple(l[0] for l in ENCODER_LAYERS)
+# The fifteen norm modules, norm i behind convolution i (layerX.0.norm3 is also registered as layerX.0.downsample.1), and the order of
+# a norm's four vectors in the entry point's table (the state dict's).
+ENCODER_NORMS = tuple("norm1" if n == "conv1" else n.replace("downsample.0", "norm3").replace("conv", "norm")
+                      for n in ENCODER_PARAMETERS[:15])
+ENCODER_NORM_VECTORS = ("weight", "bias", "running_mean", "running_var")
+
+
+def raft_encoder_weight_shape(name, output_dim=256):
+    """Shape of `<name>.weight` of the reference's BasicEncoder(output_dim)."""
+    o, c, k, _s = dict((l[0], l[1:]) for l in ENCODER_LAYERS)[name]
+    return (int(output_dim) if o is None else o, c, k, k)
+
+
+def raft_encoder_out_size(size, stride=8):
+    """An axis of `size` pixels after stride-2 layers of padding k // 2 that multiply to `stride`: ceil(size / stride)."""
+    size = int(size)
+    while stride > 1:
+        size = (size - 1) // 2 + 1
+        stride //= 2
+    return size
+
+
+def raft_check_encoder_conv(x_shape, weight_shape, bias_shape, stride=1, norm_shapes=None, eps=1e-5, residual_shape=None):
+    """(B, H, W, Cin, N, k, Ho, Wo) of one convolution of csrc/cvd_raftenc.h: x [B, Cin, H, W], weight [N, Cin, k, k] with k in
+    (1, 3, 7), stride 1 or 2, padding k // 2, bias [N], optionally the four [N] vectors of an eval batch norm and a residual of the
+    output's shape.  ValueError (before any device work) for anything else."""
+    who = "RAFT encoder conv"
+    x_shape, ws, bs = (tuple(int(v) for v in s) for s in (x_shape, weight_shape, bias_shape))
+    if len(x_shape) != 4:
+        raise ValueError(f"{who}: x must be (B, C, H, W) (got {x_shape})")
+    B, C, H, W = x_shape
+    if B * C * H * W == 0:
+        raise ValueError(f"{who}: B C H W = 0 (x is {x_shape})")
+    if H * W > 2 ** 31 - 1:
+        raise ValueError(f"{who}: {H} x {W} pixels per image exceed 2^31")
+    if isinstance(stride, (tuple, list)):
+        if len(set(stride)) != 1:
+            raise ValueError(f"{who}: stride must be the same on both axes (got {stride})")
+        stride = stride[0]
+    if stride not in ENCODER_STRIDES:
+        raise ValueError(f"{who}: stride must be 1 or 2 (got {stride})")
+    if len(ws) != 4 or ws[2] != ws[3] or ws[2] not in ENCODER_KERNEL_SIZES:
+        raise ValueError(f"{who}: the filter must be square of size {ENCODER_KERNEL_SIZES} (weight {ws})")
+    if ws[0] < 1:
+        raise ValueError(f"{who}: no output channels (weight {ws})")
+    if ws[1] != C:
+        raise ValueError(f"{who}: x has {C} channels, the weight {ws} takes {ws[1]}")
+    N, k = ws[0], ws[2]
+    if bs != (N,):
+        raise ValueError(f"{who}: bias must be ({N},) (got {bs})")
+    if norm_shapes is not None:
+        shapes = [tuple(int(v) for v in s) for s in norm_shapes]
+        if len(shapes) != 4 or any(s != (N,) for s in shapes):
+            raise ValueError(f"{who}: the norm must be four vectors ({N},) in the order {ENCODER_NORM_VECTORS} (got {shapes})")
+        if not float(eps) > 0.0:
+            raise ValueError(f"{who}: eps must be > 0 (got {eps})")
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if residual_shape is not None and tuple(int(v) for v in residual_shape) != (B, N, Ho, Wo):
+        raise ValueError(f"{who}: residual must be {(B, N, Ho, Wo)} (got {tuple(residual_shape)})")
+    return B, H, W, C, N, k, Ho, Wo
+
+
+def raft_check_instance_norm(x_shape, eps=1e-5, residual_shape=None):
+    """(B, C, H, W) of the instance norm of csrc/cvd_raftenc.h; ValueError for an empty tensor, planes of one element (the
+    reference's own refusal), eps <= 0 or a residual of another shape."""
+    who = "RAFT instance norm"
+    x_shape = tuple(int(v) for v in x_shape)
+    if len(x_shape) != 4:
+        raise ValueError(f"{who}: x must be (B, C, H, W) (got {x_shape})")
+    B, C, H, W = x_shape
+    if B * C * H * W == 0:
+        raise ValueError(f"{who}: B C H W = 0 (x is {x_shape})")
+    if H * W < 2:
+        raise ValueError(f"{who}: Expected more than 1 spatial element (x is {x_shape})")
+    if H * W > 2 ** 31 - 1:
+        raise ValueError(f"{who}: {H} x {W} pixels per image exceed 2^31")
+    if not float(eps) > 0.0:
+        raise ValueError(f"{who}: eps must be > 0 (got {eps})")
+    if residual_shape is not None and tuple(int(v) for v in residual_shape) != x_shape:
+        raise ValueError(f"{who}: residual must be {x_shape} (got {tuple(residual_shape)})")
+    return B, C, H, W
+
+
+def raft_check_encoder(image_shape, weight_shapes, bias_shapes, norm="none", norm_shapes=None, eps=1e-5):
+    """(B, H, W, output_dim, norm_mode, (h, w)) of BasicEncoder.forward: images [B, 3, H, W], the 16 weight and bias shapes in
+    ENCODER_PARAMETERS order, norm in ("none", "instance", "batch"), for "batch" the 15 x 4 vectors' shapes in ENCODER_NORMS order;
+    (h, w) = the features' size ceil(H / 8) x ceil(W / 8).  ValueError (before any device work) for anything else."""
+    who = "RAFT encoder"
+    if norm not in ENCODER_NORM_MODES:
+        raise ValueError(f"{who}: norm must be one of {tuple(ENCODER_NORM_MODES)} (got {norm!r}; group norm is not built)")
+    image_shape = tuple(int(v) for v in image_shape)
+    if len(image_shape) != 4 or image_shape[1] != 3:
+        raise ValueError(f"{who}: the images must be (B, 3, H, W) (got {image_shape})")
+    B, _, H, W = image_shape
+    if B * H * W == 0:
+        raise ValueError(f"{who}: B H W = 0 (the images are {image_shape})")
+    if H * W > 2 ** 31 - 1:
+        raise ValueError(f"{who}: {H} x {W} pixels per image exceed 2^31")
+    if len(weight_shapes) != 16 or len(bias_shapes) != 16:
+        raise ValueError(f"{who}: 16 weights and 16 biases are expected, in the order {ENCODER_PARAMETERS}")
+    ws = [tuple(int(v) for v in s) for s in weight_shapes]
+    if len(ws[15]) != 4 or ws[15][0] < 1:
+        raise ValueError(f"{who}: conv2.weight must be (output_dim, 128, 1, 1) (got {ws[15]})")
+    output_dim = ws[15][0]
+    for name, w, b in zip(ENCODER_PARAMETERS, ws, bias_shapes):
+        want = raft_encoder_weight_shape(name, output_dim)
+        if w != want:
+            raise ValueError(f"{who}: {name}.weight must be {want} (got {w})")
+        if tuple(int(v) for v in b) != (want[0],):
+            raise ValueError(f"{who}: {name}.bias must be ({want[0]},) (got {tuple(b)})")
+    if norm != "none" and not float(eps) > 0.0:
+        raise ValueError(f"{who}: eps must be > 0 (got {eps})")
+    if norm == "batch":
+        if norm_shapes is None or len(norm_shapes) != 15:
+            raise ValueError(f"{who}: batch norm needs 15 norms of four vectors, in the order {ENCODER_NORMS}")
+        for name, layer, vectors in zip(ENCODER_NORMS, ENCODER_PARAMETERS, norm_shapes):
+            n = raft_encoder_weight_shape(layer)[0]
+            shapes = [tuple(int(v) for v in s) for s in vectors]
+            if len(shapes) != 4 or any(s != (n,) for s in shapes):
+                raise ValueError(f"{who}: {name} must be four vectors ({n},) in the order {ENCODER_NORM_VECTORS} (got {shapes})")
+    h, w = raft_encoder_out_size(H), raft_encoder_out_size(W)
+    if norm == "instance" and h * w < 2:
+        raise ValueError(f"{who}: Expected more than 1 spatial element: {H} x {W} images give {h} x {w} features under instance norm")
+    return B, H, W, output_dim, ENCODER_NORM_MODES[norm], (h, w)
+
+
 class _DeviceArrays:
     """Raw device buffers of the numpy mirror of a `*_device` entry point (null stream, blocking copies); freed on exit."""
 
@@ -628,7 +764,8 @@ EXPORTED_SYMBOLS = [
     "cvd_get_xform_desc", "cvd_num_xform_params", "cvd_get_xform_params", "cvd_set_xform_params",
     "cvd_get_pose_params", "cvd_set_pose_params", "cvd_block_size", "cvd_normalize_depth", "cvd_pose_optimization",
     "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_scene_flow_loss", "cvd_scene_flow_loss_device", "cvd_spatial_losses", "cvd_spatial_losses_device", "cvd_param_chunk", "cvd_parameter_l1", "cvd_parameter_l1_device", "cvd_param_step", "cvd_param_step_device", "cvd_dataset_create", "cvd_dataset_clear", "cvd_dataset_set_colors", "cvd_dataset_set_flows", "cvd_dataset_set_depth_orig", "cvd_dataset_set_cameras", "cvd_dataset_set_xforms", "cvd_dataset_set_maps", "cvd_dataset_batch", "cvd_dataset_batch_device", "cvd_dataset_bad_indices",
-    "cvd_raft_corr_pyramid_device", "cvd_raft_corr_lookup_device", "cvd_raft_upsample_flow_device", "cvd_raft_sepconv_gru_device", "cvd_raft_sepconv_gru_timed", "cvd_raft_conv2d_device", "cvd_raft_update_block_device", "cvd_raft_update_block_timed", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
+    "cvd_raft_corr_pyramid_device", "cvd_raft_corr_lookup_device", "cvd_raft_upsample_flow_device", "cvd_raft_sepconv_gru_device", "cvd_raft_sepconv_gru_timed", "cvd_raft_conv2d_device", "cvd_raft_update_block_device", "cvd_raft_update_block_timed",
+    "cvd_raft_encoder_conv_device", "cvd_raft_instance_norm_device", "cvd_raft_encoder_device", "cvd_raft_encoder_timed", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
     "cvd_get_kernel_times", "cvd_get_comm_times", "cvd_get_dense_times", "cvd_set_kernel_timing", "cvd_num_active_constraints", "cvd_coarse_debug", "cvd_temporal_debug", "cvd_path_info", "cvd_abi_revision",
     "cvd_block_inverse_debug", "cvd_dense_inverse_debug", "cvd_epipolar_debug", "cvd_flow_masks_debug",
     "cvd_product_launch_debug", "cvd_assembly_launch_debug",
@@ -1301,6 +1438,96 @@ class Solver(Binding):
             if compute_mask:
                 dev.download(dm, mask)
         return net_out, mask, delta
+
+    def raft_encoder_conv(self, x, weight, bias, stride=1, norm=None, eps=1e-5, relu=False, residual=None):
+        """One convolution of RAFT's encoders (csrc/cvd_raftenc.h): x [B, C, H, W] f32, weight [N, C, k, k] (k = 1,
+        3, 7), stride 1 or 2, padding k // 2; then + bias, the eval batch norm of `norm` = (weight, bias, running_mean, running_var),
+        ReLU, relu(residual + y), each optional -> [B, N, ceil(H / stride), ceil(W / stride)]."""
+        import numpy as np
+        x, weight, bias = (np.asarray(a) for a in (x, weight, bias))
+        norm = None if norm is None else [np.asarray(a) for a in norm]
+        residual = None if residual is None else np.asarray(residual)
+        for a in [x, weight, bias] + (norm or []) + ([] if residual is None else [residual]):
+            if a.dtype != np.float32:
+                raise TypeError(f"raft_encoder_conv: every array must be float32 (got {a.dtype})")
+        B, H, W, Cin, N, k, Ho, Wo = raft_check_encoder_conv(x.shape, weight.shape, bias.shape, stride,
+                                                             None if norm is None else [a.shape for a in norm], eps,
+                                                             None if residual is None else residual.shape)
+        stride = stride[0] if isinstance(stride, (tuple, list)) else stride
+        out = np.zeros((B, N, Ho, Wo), np.float32)
+        with _DeviceArrays() as dev:
+            dx, dw, db = (dev.upload(np.ascontiguousarray(a)) for a in (x, weight, bias))
+            dn = None if norm is None else (C.c_void_p * 4)(*[dev.upload(np.ascontiguousarray(a)).value for a in norm])
+            dr = None if residual is None else dev.upload(np.ascontiguousarray(residual))
+            do = dev.alloc(out.nbytes)
+            self._check(self._fn("raft_encoder_conv_device")(
+                self._h, C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(Cin), C.c_int32(N), C.c_int32(k), C.c_int32(stride), dx, dw,
+                db, dn, C.c_float(eps), C.c_int32(1 if relu else 0), dr, do, None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("raft_encoder_conv: the device reported an error")
+            dev.download(do, out)
+        return out
+
+    def raft_instance_norm(self, x, eps=1e-5, relu=False, residual=None, inplace=False):
+        """nn.InstanceNorm2d without affine and running statistics (csrc/cvd_raftenc.h) per (image, channel) plane
+        of x [B, C, H, W] f32, then ReLU and relu(residual + y), each optional.  inplace: the device output is the device input
+        (the returned array is new either way)."""
+        import numpy as np
+        x = np.asarray(x)
+        residual = None if residual is None else np.asarray(residual)
+        for a in [x] + ([] if residual is None else [residual]):
+            if a.dtype != np.float32:
+                raise TypeError(f"raft_instance_norm: every array must be float32 (got {a.dtype})")
+        B, Cn, H, W = raft_check_instance_norm(x.shape, eps, None if residual is None else residual.shape)
+        out = np.zeros(x.shape, np.float32)
+        with _DeviceArrays() as dev:
+            dx = dev.upload(np.ascontiguousarray(x))
+            dr = None if residual is None else dev.upload(np.ascontiguousarray(residual))
+            do = dx if inplace else dev.alloc(out.nbytes)
+            self._check(self._fn("raft_instance_norm_device")(
+                self._h, C.c_int32(B), C.c_int32(Cn), C.c_int32(H), C.c_int32(W), dx, C.c_float(eps), C.c_int32(1 if relu else 0), dr,
+                do, None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("raft_instance_norm: the device reported an error")
+            dev.download(do, out)
+        return out
+
+    def raft_encoder(self, images, weights, biases, norm="none", norms=None, eps=1e-5, kernel_ms=None):
+        """BasicEncoder.forward in eval mode (raft/core/extractor.py:173-197): images [B, 3, H, W] f32 scaled to
+        [-1, 1], weights / biases = the 16 of ENCODER_PARAMETERS in torch's shapes, norm in ("none", "instance", "batch"), for
+        "batch" norms = 15 x (weight, bias, running_mean, running_var) in ENCODER_NORMS order -> [B, output_dim, ceil(H / 8),
+        ceil(W / 8)].  kernel_ms (measurement): a list that receives the 48 per-launch milliseconds of cvd_raft_encoder_timed."""
+        import numpy as np
+        images = np.asarray(images)
+        weights, biases = [np.asarray(a) for a in weights], [np.asarray(a) for a in biases]
+        norms = None if norms is None else [[np.asarray(a) for a in four] for four in norms]
+        for a in [images] + weights + biases + [a for four in (norms or []) for a in four]:
+            if a.dtype != np.float32:
+                raise TypeError(f"raft_encoder: every array must be float32 (got {a.dtype})")
+        B, H, W, output_dim, mode, (h, w) = raft_check_encoder(images.shape, [a.shape for a in weights], [a.shape for a in biases], norm,
+                                                               None if norms is None else [[a.shape for a in four] for four in norms],
+                                                               eps)
+        out = np.zeros((B, output_dim, h, w), np.float32)
+        with _DeviceArrays() as dev:
+            di = dev.upload(np.ascontiguousarray(images))
+            dw = (C.c_void_p * 16)(*[dev.upload(np.ascontiguousarray(a)).value for a in weights])
+            db = (C.c_void_p * 16)(*[dev.upload(np.ascontiguousarray(a)).value for a in biases])
+            dn = None
+            if norm == "batch":
+                dn = (C.c_void_p * 60)(*[dev.upload(np.ascontiguousarray(a)).value for four in norms for a in four])
+            do = dev.alloc(out.nbytes)
+            args = (self._h, C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(output_dim), C.c_int32(mode), C.c_float(eps), di, dw, db,
+                    dn, do, None)
+            if kernel_ms is None:
+                self._check(self._fn("raft_encoder_device")(*args))
+            else:
+                ms = (C.c_double * 48)()
+                self._check(self._fn("raft_encoder_timed")(*args, ms))
+                kernel_ms[:] = list(ms)
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("raft_encoder: the device reported an error")
+            dev.download(do, out)
+        return out
 
     def num_active_constraints(self):
         return int(self._lib.cvd_num_active_constraints(self._h))

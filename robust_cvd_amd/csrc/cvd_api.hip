@@ -881,6 +881,32 @@ int32_t cvd_raft_update_block_timed(cvd_handle* h, int32_t batch, int32_t height
   CVD_TRY(h, raftUpdateBlockDevice(h, batch, height, width, corr_channels, cor_planes, net, inp, corr, flow, weights, biases, net_out,
                                    delta_flow, mask, static_cast<hipStream_t>(stream), kernel_ms));
 }
+// reference raft/core/extractor.py:8-60, 124-197 (the nn.Conv2d of BasicEncoder and ResidualBlock with the norm, ReLU and residual behind them)
+int32_t cvd_raft_encoder_conv_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels,
+                                     int32_t out_channels, int32_t kernel_size, int32_t stride, const float* x, const float* weight,
+                                     const float* bias, const float* const* norm, float eps, int32_t relu, const float* residual,
+                                     float* out, void* stream) {
+  CVD_TRY(h, raftEncoderConvDevice(h, batch, height, width, in_channels, out_channels, kernel_size, stride, x, weight, bias, norm, eps,
+                                   relu, residual, out, static_cast<hipStream_t>(stream)));
+}
+// nn.InstanceNorm2d without affine and running statistics, as fnet uses it (raft/core/extractor.py:32-36, 135-136)
+int32_t cvd_raft_instance_norm_device(cvd_handle* h, int32_t batch, int32_t channels, int32_t height, int32_t width, const float* x,
+                                      float eps, int32_t relu, const float* residual, float* out, void* stream) {
+  CVD_TRY(h, raftInstanceNormDevice(h, batch, channels, height, width, x, eps, relu, residual, out, static_cast<hipStream_t>(stream)));
+}
+// reference raft/core/extractor.py:173-197 (BasicEncoder.forward in eval mode)
+int32_t cvd_raft_encoder_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t output_dim, int32_t norm_mode,
+                                float eps, const float* images, const float* const* weights, const float* const* biases,
+                                const float* const* norms, float* out, void* stream) {
+  CVD_TRY(h, raftEncoderDevice(h, batch, height, width, output_dim, norm_mode, eps, images, weights, biases, norms, out,
+                               static_cast<hipStream_t>(stream), nullptr));
+}
+int32_t cvd_raft_encoder_timed(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t output_dim, int32_t norm_mode,
+                               float eps, const float* images, const float* const* weights, const float* const* biases,
+                               const float* const* norms, float* out, void* stream, double* kernel_ms) {
+  CVD_TRY(h, raftEncoderDevice(h, batch, height, width, output_dim, norm_mode, eps, images, weights, biases, norms, out,
+                               static_cast<hipStream_t>(stream), kernel_ms));
+}
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {

@@ -2,7 +2,8 @@
 // consumers, flow-guided and bilateral filters, feature tracks, flow consistency masks, the fine-tuning consistency,
 // scene-flow and spatial losses, the parameter regulariser and the optimizer step, the fine-tuning batches, RAFT's correlation pyramid / lookup and convex
 // upsampling (cvd_raftops.h: k_corr_pyramid, k_corr_lookup, k_convex_upsample), the SepConvGRU of RAFT's update block
-// (cvd_raftgru.h: k_gru_gemm) and its other convolutions (cvd_raftconv.h: k_raft_conv).  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
+// (cvd_raftgru.h: k_gru_gemm), its other convolutions (cvd_raftconv.h: k_raft_conv) and RAFT's encoders (cvd_raftenc.h: k_enc_conv,
+// k_instnorm_stats, k_instnorm_apply).  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
 // through a pointer to the incomplete type).
 #include "cvd_host.h"
 #include "cvd_dense.h"
@@ -22,6 +23,7 @@
 #include "cvd_raftops.h"
 #include "cvd_raftgru.h"
 #include "cvd_raftconv.h"
+#include "cvd_raftenc.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -136,6 +138,10 @@ struct Frontend {
   // cvd_raftconv.h: the update block's intermediates (cor1, cor_flo, flo1, motion_features; the stacked heads' hidden tensor lies
   // over the first two, which are dead by then), 768 B H W floats, under the same rule.
   DevBuf<float> dBlock;
+  // cvd_raftenc.h: the encoder's intermediates (three rotating tensors and the downsample branch's) and the instance norm's
+  // (mean, rstd) per plane, under the same rule.
+  DevBuf<float> dEnc;
+  DevBuf<double> dEncStats;
 };
 
 std::shared_ptr<Frontend> makeFrontend() { return std::make_shared<Frontend>(); }
@@ -2526,6 +2532,221 @@ void raftUpdateBlockDevice(cvd_handle* h, int B, int H, int W, int corrChannels,
   if (kernelMs) {
     heads.wait();
     heads.collect();
+  }
+}
+
+// ---- RAFT's feature and context encoders (reference raft/core/extractor.py:8-60, 124-197; cvd_raftenc.h).  Device
+// arrays on the caller's stream: enqueued launches only. ----------------------------------------------------------------------------
+namespace {
+template <int KS, int STRIDE>
+void launchEncConvK(const EncConvArgs& A, bool vec, dim3 grid, hipStream_t s) {
+  if constexpr (KS != 7) {
+    if (vec) {
+      hipLaunchKernelGGL((k_enc_conv<KS, STRIDE, true>), grid, dim3(kEncThreads), 0, s, A);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((k_enc_conv<KS, STRIDE, false>), grid, dim3(kEncThreads), 0, s, A);
+}
+
+struct EncDims {
+  int Ho, Wo;
+  long long HW, HWo, M;
+};
+
+// the sizes of a convolution over B x H x W input pixels with the filter, the stride and the workgroup count in range
+EncDims checkEncConvShape(const char* who, int B, int H, int W, int ks, int stride) {
+  if (B < 1 || H < 1 || W < 1) throw std::runtime_error(fmt("%s: batch, height and width must be >= 1 (got %d, %d, %d)", who, B, H, W));
+  if (ks != 1 && ks != 3 && ks != 7) throw std::runtime_error(fmt("%s: kernel_size must be 1, 3 or 7 (got %d)", who, ks));
+  if (stride != 1 && stride != 2) throw std::runtime_error(fmt("%s: stride must be 1 or 2 (got %d)", who, stride));
+  EncDims d{};
+  d.HW = static_cast<long long>(H) * W;
+  if (d.HW > 0x7fffffffll) throw std::runtime_error(fmt("%s: %d x %d pixels per image exceed 2^31", who, H, W));
+  d.Ho = (H - 1) / stride + 1;
+  d.Wo = (W - 1) / stride + 1;
+  d.HWo = static_cast<long long>(d.Ho) * d.Wo;
+  d.M = d.HWo * B;
+  if ((d.M + kEncTile - 1) / kEncTile > 0x7fffffffll) throw std::runtime_error(fmt("%s: %lld pixels exceed the grid", who, d.M));
+  return d;
+}
+
+// One launch.  The arguments have been checked by the callers.  norm: {weight, bias, running_mean, running_var} or null.
+void launchEncConv(int B, int H, int W, int Cin, int N, int ks, int stride, const float* x, const float* w, const float* bias,
+                   const float* const* norm, float eps, int relu, const float* residual, float* out, hipStream_t s) {
+  EncConvArgs A{};
+  A.x = x; A.w = w; A.bias = bias;
+  if (norm) {
+    A.gamma = norm[0]; A.beta = norm[1]; A.mean = norm[2]; A.var = norm[3];
+  }
+  A.residual = residual; A.out = out; A.eps = eps; A.relu = relu;
+  A.Cin = Cin; A.N = N;
+  A.H = H; A.W = W; A.HW = H * W;
+  A.Ho = (H - 1) / stride + 1; A.Wo = (W - 1) / stride + 1; A.HWo = A.Ho * A.Wo;
+  A.M = static_cast<long long>(A.HWo) * B;
+  const dim3 grid(static_cast<unsigned>((A.M + kEncTile - 1) / kEncTile), static_cast<unsigned>((N + kEncTile - 1) / kEncTile));
+  // float4 weight loads only where every row starts on 16 bytes
+  const bool vec = (static_cast<long long>(Cin) * ks * ks) % 4 == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0;
+  switch (ks * 10 + stride) {
+    case 11: launchEncConvK<1, 1>(A, vec, grid, s); break;
+    case 12: launchEncConvK<1, 2>(A, vec, grid, s); break;
+    case 31: launchEncConvK<3, 1>(A, vec, grid, s); break;
+    case 32: launchEncConvK<3, 2>(A, vec, grid, s); break;
+    case 71: launchEncConvK<7, 1>(A, vec, grid, s); break;
+    default: launchEncConvK<7, 2>(A, vec, grid, s); break;
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// The two launches of the instance norm over `planes` planes of HW elements; stats: 2 planes doubles.  Checked by the callers.
+// mark (may be empty) is called after each launch.
+template <class Mark>
+void launchInstanceNorm(long long planes, int HW, const float* x, double eps, int relu, const float* residual, float* out, double* stats,
+                        hipStream_t s, Mark&& mark) {
+  InstNormArgs A{};
+  A.x = x; A.residual = residual; A.out = out; A.stats = stats; A.eps = eps; A.relu = relu; A.HW = HW;
+  A.total = planes * HW;
+  hipLaunchKernelGGL(k_instnorm_stats, dim3(static_cast<unsigned>(planes)), dim3(kNormThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+  mark();
+  hipLaunchKernelGGL(k_instnorm_apply, dim3(static_cast<unsigned>((A.total + kNormThreads - 1) / kNormThreads)), dim3(kNormThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+  mark();
+}
+
+void checkNormSize(const char* who, long long planes, long long HW) {
+  if (HW < 2) throw std::runtime_error(fmt("%s: planes of %lld element: instance norm expects more than 1 spatial element", who, HW));
+  if (planes > 0x7fffffffll || (planes * HW + kNormThreads - 1) / kNormThreads > 0x7fffffffll)
+    throw std::runtime_error(fmt("%s: %lld planes of %lld elements exceed the grid", who, planes, HW));
+}
+}  // namespace
+
+void raftEncoderConvDevice(cvd_handle*, int B, int H, int W, int inChannels, int outChannels, int kernelSize, int stride,
+                           const float* x, const float* weight, const float* bias, const float* const* norm, float eps, int relu,
+                           const float* residual, float* out, hipStream_t s) {
+  const char* who = "raft encoder conv";
+  const EncDims d = checkEncConvShape(who, B, H, W, kernelSize, stride);
+  if (inChannels < 1) throw std::runtime_error(fmt("%s: in_channels must be >= 1 (got %d)", who, inChannels));
+  if (outChannels < 1) throw std::runtime_error(fmt("%s: out_channels must be >= 1 (got %d)", who, outChannels));
+  if (static_cast<long long>(inChannels) * kernelSize * kernelSize > 0x7fffffffll)
+    throw std::runtime_error(fmt("%s: in_channels %d exceeds the kernel's range", who, inChannels));
+  if (relu != 0 && relu != 1) throw std::runtime_error(fmt("%s: relu must be 0 or 1 (got %d)", who, relu));
+  if (!x || !weight || !bias || !out) throw std::runtime_error(fmt("%s: null array", who));
+  if (norm) {
+    for (int i = 0; i < 4; ++i)
+      if (!norm[i]) throw std::runtime_error(fmt("%s: null norm vector %d", who, i));
+    if (!(eps > 0.f)) throw std::runtime_error(fmt("%s: eps must be > 0 (got %g)", who, static_cast<double>(eps)));
+  }
+  const long long outFloats = d.M * outChannels;
+  if (rangesOverlap(out, outFloats, x, d.HW * B * inChannels)) throw std::runtime_error(fmt("%s: out overlaps x", who));
+  if (residual && rangesOverlap(out, outFloats, residual, outFloats)) throw std::runtime_error(fmt("%s: out overlaps the residual", who));
+  launchEncConv(B, H, W, inChannels, outChannels, kernelSize, stride, x, weight, bias, norm, eps, relu, residual, out, s);
+}
+
+void raftInstanceNormDevice(cvd_handle* h, int B, int channels, int H, int W, const float* x, float eps, int relu,
+                            const float* residual, float* out, hipStream_t s) {
+  const char* who = "raft instance norm";
+  if (B < 1 || channels < 1 || H < 1 || W < 1)
+    throw std::runtime_error(fmt("%s: batch, channels, height and width must be >= 1 (got %d, %d, %d, %d)", who, B, channels, H, W));
+  const long long HW = static_cast<long long>(H) * W;
+  if (HW > 0x7fffffffll) throw std::runtime_error(fmt("%s: %d x %d pixels per image exceed 2^31", who, H, W));
+  const long long planes = static_cast<long long>(B) * channels;
+  checkNormSize(who, planes, HW);
+  if (relu != 0 && relu != 1) throw std::runtime_error(fmt("%s: relu must be 0 or 1 (got %d)", who, relu));
+  if (!(eps > 0.f)) throw std::runtime_error(fmt("%s: eps must be > 0 (got %g)", who, static_cast<double>(eps)));
+  if (!x || !out) throw std::runtime_error(fmt("%s: null array", who));
+  const long long n = planes * HW;
+  if (out != x && rangesOverlap(out, n, x, n)) throw std::runtime_error(fmt("%s: out overlaps x (only out == x, in place, is allowed)", who));
+  if (residual && rangesOverlap(out, n, residual, n)) throw std::runtime_error(fmt("%s: out overlaps the residual", who));
+  Frontend& fe = *h->frontend;
+  fe.dEncStats.ensure(2 * static_cast<size_t>(planes));
+  launchInstanceNorm(planes, static_cast<int>(HW), x, static_cast<double>(eps), relu, residual, out, fe.dEncStats.p, s, [] {});
+}
+
+// BasicEncoder.forward.  weights / biases / norms: the tables include/cvd_hip.h documents.
+// kernelMs (measurement only, may be null): 48 entries; with it the call waits on the host.
+void raftEncoderDevice(cvd_handle* h, int B, int H, int W, int outputDim, int normMode, float eps, const float* images,
+                       const float* const* weights, const float* const* biases, const float* const* norms, float* out,
+                       hipStream_t s, double* kernelMs) {
+  const char* who = "raft encoder";
+  checkEncConvShape(who, B, H, W, 7, 2);
+  if (outputDim < 1) throw std::runtime_error(fmt("%s: output_dim must be >= 1 (got %d)", who, outputDim));
+  if (normMode < 0 || normMode > 2) throw std::runtime_error(fmt("%s: norm_mode must be 0 (none), 1 (instance) or 2 (batch) (got %d)", who, normMode));
+  if (normMode != 0 && !(eps > 0.f)) throw std::runtime_error(fmt("%s: eps must be > 0 (got %g)", who, static_cast<double>(eps)));
+  if (!images || !weights || !biases || !out || (normMode == 2 && !norms)) throw std::runtime_error(fmt("%s: null array", who));
+  for (int i = 0; i < 16; ++i)
+    if (!weights[i] || !biases[i]) throw std::runtime_error(fmt("%s: null weight or bias %d", who, i));
+  if (normMode == 2)
+    for (int i = 0; i < 60; ++i)
+      if (!norms[i]) throw std::runtime_error(fmt("%s: null norm vector %d", who, i));
+  const int H1 = (H - 1) / 2 + 1, W1 = (W - 1) / 2 + 1, H2 = (H1 - 1) / 2 + 1, W2 = (W1 - 1) / 2 + 1, H3 = (H2 - 1) / 2 + 1,
+            W3 = (W2 - 1) / 2 + 1;
+  const size_t b = static_cast<size_t>(B);
+  const size_t m1 = b * H1 * W1, m2 = b * H2 * W2, m3 = b * H3 * W3;
+  if (normMode == 1) checkNormSize(who, static_cast<long long>(B) * 128, static_cast<long long>(H3) * W3);
+  if (rangesOverlap(out, static_cast<long long>(m3) * outputDim, images, static_cast<long long>(b) * 3 * H * W))
+    throw std::runtime_error(fmt("%s: out overlaps the images", who));
+
+  // three rotating tensors (a block's input, its middle, its output) and the downsample branch's
+  Frontend& fe = *h->frontend;
+  const size_t big = std::max(64 * m1, std::max(96 * m2, 128 * m3)), small = std::max(96 * m2, 128 * m3);
+  fe.dEnc.ensure(3 * big + small);
+  fe.dEncStats.ensure(2 * b * 128);
+  float* bufA = fe.dEnc.p;
+  float* bufB = bufA + big;
+  float* bufC = bufB + big;
+  float* bufD = bufC + big;
+
+  constexpr int kLaunchesMost = 46;
+  double phaseMs[kLaunchesMost];
+  int slot[kLaunchesMost];
+  int launches = 0;
+  KernelTimer timer(s, kernelMs ? phaseMs : nullptr, kLaunchesMost);
+  timer.mark();
+  // convolution `idx` with its norm, ReLU and residual; under instance norm the norm is the two launches behind it, in place
+  const auto conv = [&](int idx, const float* x, int Cin, int Hin, int Win, int N, int ks, int stride, int relu, const float* residual,
+                        float* y) {
+    const bool normed = idx < 15;
+    const int Ho = (Hin - 1) / stride + 1, Wo = (Win - 1) / stride + 1;
+    if (normMode == 1 && normed) {
+      launchEncConv(B, Hin, Win, Cin, N, ks, stride, x, weights[idx], biases[idx], nullptr, eps, 0, nullptr, y, s);
+      slot[launches++] = 3 * idx;
+      timer.mark();
+      int part = 1;
+      launchInstanceNorm(static_cast<long long>(B) * N, Ho * Wo, y, static_cast<double>(eps), relu, residual, y, fe.dEncStats.p, s, [&] {
+        slot[launches++] = 3 * idx + part++;
+        timer.mark();
+      });
+    } else {
+      launchEncConv(B, Hin, Win, Cin, N, ks, stride, x, weights[idx], biases[idx], normMode == 2 && normed ? norms + 4 * idx : nullptr,
+                    eps, relu, residual, y, s);
+      slot[launches++] = 3 * idx;
+      timer.mark();
+    }
+  };
+  // a ResidualBlock: conv1 = idx, conv2 = idx + 1, downsample.0 = idx + 2 (stride 2 only)
+  const auto block = [&](int idx, const float* x, int Cin, int Hin, int Win, int N, int stride, float* mid, float* y) {
+    const int Ho = (Hin - 1) / stride + 1, Wo = (Win - 1) / stride + 1;
+    conv(idx, x, Cin, Hin, Win, N, 3, stride, 1, nullptr, mid);
+    const float* residual = x;
+    if (stride != 1) {
+      conv(idx + 2, x, Cin, Hin, Win, N, 1, stride, 0, nullptr, bufD);
+      residual = bufD;
+    }
+    conv(idx + 1, mid, N, Ho, Wo, N, 3, 1, 1, residual, y);
+  };
+  conv(0, images, 3, H, W, 64, 7, 2, 1, nullptr, bufA);
+  block(1, bufA, 64, H1, W1, 64, 1, bufB, bufC);
+  block(3, bufC, 64, H1, W1, 64, 1, bufB, bufA);
+  block(5, bufA, 64, H1, W1, 96, 2, bufB, bufC);
+  block(8, bufC, 96, H2, W2, 96, 1, bufB, bufA);
+  block(10, bufA, 96, H2, W2, 128, 2, bufB, bufC);
+  block(13, bufC, 128, H3, W3, 128, 1, bufB, bufA);
+  conv(15, bufA, 128, H3, W3, outputDim, 1, 1, 0, nullptr, out);
+  if (kernelMs) {
+    timer.wait();
+    timer.collect();
+    std::fill(kernelMs, kernelMs + 48, 0.0);
+    for (int i = 0; i < launches; ++i) kernelMs[slot[i]] = phaseMs[i];
   }
 }
 

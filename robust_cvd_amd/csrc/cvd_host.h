@@ -784,5 +784,13 @@ void raftConv2dDevice(cvd_handle* h, int B, int H, int W, int numSegments, const
 void raftUpdateBlockDevice(cvd_handle* h, int B, int H, int W, int corrChannels, int corPlanes, const float* net, const float* inp,
                            const float* corr, const float* flow, const float* const* weights, const float* const* biases,
                            float* netOut, float* deltaFlow, float* mask, hipStream_t s, double* kernelMs);
+void raftEncoderConvDevice(cvd_handle* h, int B, int H, int W, int inChannels, int outChannels, int kernelSize, int stride,
+                           const float* x, const float* weight, const float* bias, const float* const* norm, float eps, int relu,
+                           const float* residual, float* out, hipStream_t s);
+void raftInstanceNormDevice(cvd_handle* h, int B, int channels, int H, int W, const float* x, float eps, int relu,
+                            const float* residual, float* out, hipStream_t s);
+void raftEncoderDevice(cvd_handle* h, int B, int H, int W, int outputDim, int normMode, float eps, const float* images,
+                       const float* const* weights, const float* const* biases, const float* const* norms, float* out,
+                       hipStream_t s, double* kernelMs);
 
 }  // namespace cvd

@@ -24,6 +24,12 @@ with the reference's parameter names, on csrc/cvd_raftconv.h:
 BasicUpdateBlock` in raft/core/update.py (or raft/core/raft.py).  A block call is 8 launches beside the GRU's 4, no cat, on the
 current stream; the same domain rules and error types as SepConvGRU.
 
+ResidualBlock, BasicEncoder and RAFT are the encoders and the whole network (raft/core/extractor.py:8-60, 124-197,
+raft/core/raft.py) with the reference's module, parameter and buffer names, on csrc/cvd_raftenc.h:
+`from robust_cvd_amd.raft_ops import RAFT` where optical_flow_homography.py imports the class is the whole integration; the
+reference's checkpoint loads with strict=True.  An encoder call is one library call of 16 convolution launches (plus two per instance
+norm); eval mode only.  SmallEncoder, BottleneckBlock and SmallUpdateBlock (args.small) are out of scope and refused.
+
 Import this module (torch) before anything loads libcvd_hip.so.
 """
 import ctypes as C
@@ -270,6 +276,263 @@ class BasicUpdateBlock(torch.nn.Module):
               (C.c_void_p * 15)(*[t.data_ptr() for t in weights]), (C.c_void_p * 15)(*[t.data_ptr() for t in biases]),
               tc.ptr(net_out), tc.ptr(delta_flow), tc.ptr(mask) if compute_mask else None)
         return net_out, mask, delta_flow
+
+
+def _make_norm(who, norm_fn, planes):
+    """The reference's norm module of a layer, for its parameter and buffer names; its forward is never called."""
+    if norm_fn == "batch":
+        return torch.nn.BatchNorm2d(planes)
+    if norm_fn == "instance":
+        return torch.nn.InstanceNorm2d(planes)
+    if norm_fn == "none":
+        return torch.nn.Sequential()
+    raise ValueError(f"{who}: norm_fn must be 'instance', 'batch' or 'none' (got {norm_fn!r}; group norm has no kernel)")
+
+
+def _norm_vectors(who, norm):
+    """(the four vectors of an eval BatchNorm2d in api.ENCODER_NORM_VECTORS order, eps); ValueError in training mode."""
+    if norm.training:
+        raise ValueError(f"{who}: batch norm in training mode has no kernel: call .eval() (or RAFT.freeze_bn())")
+    if not norm.affine or not norm.track_running_stats:
+        raise ValueError(f"{who}: the batch norm must have affine parameters and running statistics")
+    return [norm.weight, norm.bias, norm.running_mean, norm.running_var], float(norm.eps)
+
+
+def _encoder_conv(who, x, conv, norm, relu, residual=None):
+    """One convolution of csrc/cvd_raftenc.h with what follows it in the reference: conv, `norm` (a BatchNorm2d in eval mode: fused;
+    an InstanceNorm2d: the two launches behind, in place; an empty Sequential: nothing), ReLU, relu(residual + y)."""
+    named = {"x": x, "weight": conv.weight, "bias": conv.bias}
+    if residual is not None:
+        named["residual"] = residual
+    vectors, eps = None, 1e-5
+    if isinstance(norm, torch.nn.BatchNorm2d):
+        vectors, eps = _norm_vectors(who, norm)
+        named.update({f"norm.{n}": v for n, v in zip(api.ENCODER_NORM_VECTORS, vectors)})
+    instance = isinstance(norm, torch.nn.InstanceNorm2d)
+    if instance:
+        eps = float(norm.eps)
+    _check_forward(who, named)
+    for name, v in (("dilation", conv.dilation), ("groups", conv.groups)):
+        if v not in (1, (1, 1)):
+            raise ValueError(f"{who}: {name} must be 1 (got {v})")
+    if tuple(conv.padding) != (conv.kernel_size[0] // 2,) * 2:
+        raise ValueError(f"{who}: padding must be kernel_size // 2 (got {conv.padding})")
+    B, H, W, Cin, N, k, Ho, Wo = api.raft_check_encoder_conv(x.shape, conv.weight.shape, conv.bias.shape, tuple(conv.stride),
+                                                             None if vectors is None else [v.shape for v in vectors], eps,
+                                                             None if residual is None else residual.shape)
+    if instance:
+        api.raft_check_instance_norm((B, N, Ho, Wo), eps)
+    x = x.detach().contiguous()
+    residual = None if residual is None else residual.detach().contiguous()
+    weight, bias = conv.weight.detach().contiguous(), conv.bias.detach().contiguous()
+    vectors = None if vectors is None else [v.detach().contiguous() for v in vectors]
+    out = torch.empty((B, N, Ho, Wo), dtype=torch.float32, device=x.device)
+    fused = not instance
+    _call(x.device, "raft_encoder_conv_device", C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(Cin), C.c_int32(N), C.c_int32(k),
+          C.c_int32(conv.stride[0]), tc.ptr(x), tc.ptr(weight), tc.ptr(bias),
+          None if vectors is None else (C.c_void_p * 4)(*[v.data_ptr() for v in vectors]), C.c_float(eps),
+          C.c_int32(1 if relu and fused else 0), tc.ptr(residual) if fused else None, tc.ptr(out))
+    if instance:
+        _call(x.device, "raft_instance_norm_device", C.c_int32(B), C.c_int32(N), C.c_int32(Ho), C.c_int32(Wo), tc.ptr(out), C.c_float(eps),
+              C.c_int32(1 if relu else 0), tc.ptr(residual), tc.ptr(out))
+    return out
+
+
+class ResidualBlock(torch.nn.Module):
+    """The reference's ResidualBlock (raft/core/extractor.py:8-60) with its module, parameter and buffer names (norm3 is also
+    downsample.1, as there), on csrc/cvd_raftenc.h: relu(x' + relu(norm2(conv2(relu(norm1(conv1(x))))))), x' = x
+    or norm3(downsample.0(x)) under stride 2.  Two or three convolution launches with the batch norm, ReLU and residual fused; the
+    instance norm is two more launches behind each.  norm_fn: 'instance', 'batch' (eval mode only) or 'none'; 'group' is refused.
+    BottleneckBlock is out of scope."""
+
+    def __init__(self, in_planes, planes, norm_fn="group", stride=1):
+        super().__init__()
+        who = "ResidualBlock"
+        if stride not in api.ENCODER_STRIDES:
+            raise ValueError(f"{who}: stride must be 1 or 2 (got {stride})")
+        self.conv1 = torch.nn.Conv2d(in_planes, planes, kernel_size=3, padding=1, stride=stride)
+        self.conv2 = torch.nn.Conv2d(planes, planes, kernel_size=3, padding=1)
+        self.relu = torch.nn.ReLU(inplace=True)
+        self.norm1 = _make_norm(who, norm_fn, planes)
+        self.norm2 = _make_norm(who, norm_fn, planes)
+        self.downsample = None
+        if stride != 1:
+            self.norm3 = _make_norm(who, norm_fn, planes)
+            self.downsample = torch.nn.Sequential(torch.nn.Conv2d(in_planes, planes, kernel_size=1, stride=stride), self.norm3)
+
+    def forward(self, x):
+        who = "ResidualBlock"
+        y = _encoder_conv(who, x, self.conv1, self.norm1, True)
+        if self.downsample is not None:
+            x = _encoder_conv(who, x, self.downsample[0], self.norm3, False)
+        return _encoder_conv(who, y, self.conv2, self.norm2, True, residual=x)
+
+
+class BasicEncoder(torch.nn.Module):
+    """The reference's BasicEncoder (raft/core/extractor.py:124-197) with its module, parameter and buffer names, so the fnet.* and
+    cnet.* parts of a RAFT state dict load unchanged.  forward(x), x a [B, 3, H, W] tensor scaled to [-1, 1] or a list of two (the
+    list is returned as two tensors, like the reference's), is ONE call of the library (cvd_raft_encoder_device):
+    16 convolution launches with bias, eval batch norm, ReLU and residual fused, and under instance norm two more launches behind
+    each of the first fifteen.  A list is concatenated along the batch with one torch.cat of the two images (the reference does the
+    same); the two results are views of the one output.  Forward only, float32, GPU tensors, eval mode: norm_fn='group', batch norm
+    in training mode and dropout > 0 in training mode are refused (ValueError) before any device work.  The scratch is the device
+    handle's: calls on one device are ordered on one stream.  SmallEncoder and BottleneckBlock are out of scope."""
+
+    def __init__(self, output_dim=128, norm_fn="batch", dropout=0.0):
+        super().__init__()
+        who = "BasicEncoder"
+        self.norm_fn = norm_fn
+        self.norm1 = _make_norm(who, norm_fn, 64)
+        self.conv1 = torch.nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3)
+        self.relu1 = torch.nn.ReLU(inplace=True)
+        self.layer1 = torch.nn.Sequential(ResidualBlock(64, 64, norm_fn, 1), ResidualBlock(64, 64, norm_fn, 1))
+        self.layer2 = torch.nn.Sequential(ResidualBlock(64, 96, norm_fn, 2), ResidualBlock(96, 96, norm_fn, 1))
+        self.layer3 = torch.nn.Sequential(ResidualBlock(96, 128, norm_fn, 2), ResidualBlock(128, 128, norm_fn, 1))
+        self.conv2 = torch.nn.Conv2d(128, output_dim, kernel_size=1)
+        self.dropout = torch.nn.Dropout2d(p=dropout) if dropout > 0 else None
+        # the reference's initialisation (the norms' weight 1 and bias 0 are torch's defaults)
+        for m in self.modules():
+            if isinstance(m, torch.nn.Conv2d):
+                torch.nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+
+    def check_mode(self):
+        """ValueError where the module's mode has no kernel: dropout or a batch norm in training mode."""
+        who = "BasicEncoder"
+        if self.training and self.dropout is not None:
+            raise ValueError(f"{who}: dropout in training mode has no kernel: call .eval()")
+        for m in self.modules():
+            if isinstance(m, torch.nn.BatchNorm2d) and m.training:
+                raise ValueError(f"{who}: batch norm in training mode has no kernel: call .eval() (or RAFT.freeze_bn())")
+
+    def forward(self, x):
+        who = "BasicEncoder"
+        is_list = isinstance(x, (tuple, list))
+        images = list(x) if is_list else [x]
+        if is_list and len(images) != 2:
+            raise ValueError(f"{who}: a list input must hold two tensors (got {len(images)})")
+        self.check_mode()
+        convs = [self.get_submodule(n) for n in api.ENCODER_PARAMETERS]
+        weights, biases = [m.weight for m in convs], [m.bias for m in convs]
+        named = {**{f"x[{i}]": t for i, t in enumerate(images)},
+                 **{f"{n}.weight": w for n, w in zip(api.ENCODER_PARAMETERS, weights)},
+                 **{f"{n}.bias": b for n, b in zip(api.ENCODER_PARAMETERS, biases)}}
+        norms, eps = None, 1e-5
+        if self.norm_fn == "batch":
+            norms = []
+            for n in api.ENCODER_NORMS:
+                vectors, eps = _norm_vectors(f"{who}: {n}", self.get_submodule(n))
+                norms.append(vectors)
+                named.update({f"{n}.{v}": t for v, t in zip(api.ENCODER_NORM_VECTORS, vectors)})
+        elif self.norm_fn == "instance":
+            eps = float(self.norm1.eps)
+        _check_forward(who, named)
+        if any(t.dim() != 4 or t.shape != images[0].shape for t in images):
+            raise ValueError(f"{who}: the images must be (B, 3, H, W) alike (got {[tuple(t.shape) for t in images]})")
+        batch = images[0].shape[0]
+        shape = (batch * len(images),) + tuple(images[0].shape[1:])
+        B, H, W, output_dim, mode, (h, w) = api.raft_check_encoder(
+            shape, [t.shape for t in weights], [t.shape for t in biases], self.norm_fn,
+            None if norms is None else [[t.shape for t in four] for four in norms], eps)
+        x = torch.cat([t.detach() for t in images], 0) if is_list else images[0].detach()
+        x = x.contiguous()
+        weights = [t.detach().contiguous() for t in weights]
+        biases = [t.detach().contiguous() for t in biases]
+        table = None
+        if norms is not None:
+            flat = [t.detach().contiguous() for four in norms for t in four]
+            table = (C.c_void_p * 60)(*[t.data_ptr() for t in flat])
+        out = torch.empty((B, output_dim, h, w), dtype=torch.float32, device=x.device)
+        _call(x.device, "raft_encoder_device", C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(output_dim), C.c_int32(mode),
+              C.c_float(eps), tc.ptr(x), (C.c_void_p * 16)(*[t.data_ptr() for t in weights]),
+              (C.c_void_p * 16)(*[t.data_ptr() for t in biases]), table, tc.ptr(out))
+        return torch.split(out, [batch, batch], dim=0) if is_list else out
+
+
+class RAFT(torch.nn.Module):
+    """The reference's RAFT (raft/core/raft.py) without `small`, with its module, parameter and buffer names: the state dict has the
+    reference's 179 keys in its order, so a checkpoint loads with strict=True, also through torch.nn.DataParallel(RAFT(args)).module
+    as the reference loads it.  `from robust_cvd_amd.raft_ops import RAFT` is the whole integration.
+
+    forward(image1, image2, iters=12, flow_init=None, upsample=True, test_mode=False), images [B, 3, H, W] in 0..255, returns what
+    the reference returns: (flow at 1/8, upsampled flow) under test_mode, else the list of the upsampled flow of every iteration.
+    Everything runs on the library: fnet on both images in one encoder call, CorrBlock, cnet, and per
+    iteration the lookup, BasicUpdateBlock and upsample_flow; the image scaling, tanh / relu of the context split and the coordinate
+    adds stay torch ops.  Under test_mode only the last iteration computes the mask and the upsampling (the same bits: the earlier
+    masks are never read).  Forward only, float32, GPU tensors, batch norm in eval mode (.eval() or freeze_bn()); H and W multiples
+    of 8 and at least 128 (the four-level pyramid needs 16 x 16 features).  args.small is refused: SmallEncoder, BottleneckBlock and
+    SmallUpdateBlock are out of scope."""
+
+    def __init__(self, args):
+        super().__init__()
+        if getattr(args, "small", False):
+            raise ValueError("RAFT: args.small has no kernels (SmallEncoder and SmallUpdateBlock are out of scope)")
+        self.args = args
+        self.hidden_dim = hdim = 128
+        self.context_dim = cdim = 128
+        args.corr_levels = 4
+        args.corr_radius = 4
+        dropout = getattr(args, "dropout", 0)
+        args.dropout = dropout
+        self.fnet = BasicEncoder(output_dim=256, norm_fn="instance", dropout=dropout)
+        self.cnet = BasicEncoder(output_dim=hdim + cdim, norm_fn="batch", dropout=dropout)
+        self.update_block = BasicUpdateBlock(args, hidden_dim=hdim)
+
+    def freeze_bn(self):
+        for m in self.modules():
+            if isinstance(m, torch.nn.BatchNorm2d):
+                m.eval()
+
+    def forward(self, image1, image2, iters=12, flow_init=None, upsample=True, test_mode=False):
+        who = "RAFT"
+        named = {"image1": image1, "image2": image2}
+        if flow_init is not None:
+            named["flow_init"] = flow_init
+        _check_forward(who, named)
+        if image1.dim() != 4 or image1.shape[1] != 3 or image1.shape != image2.shape:
+            raise ValueError(f"{who}: image1 and image2 must be (B, 3, H, W) alike (got {tuple(image1.shape)}, {tuple(image2.shape)})")
+        B, _, H, W = image1.shape
+        if H % 8 or W % 8:
+            raise ValueError(f"{who}: height and width must be multiples of 8 (got {H} x {W}; pad the images as the reference's InputPadder does)")
+        h, w = H // 8, W // 8
+        if min(h, w) < 16:
+            raise ValueError(f"{who}: {H} x {W} images give {h} x {w} features; the four-level correlation pyramid needs 16 x 16")
+        if flow_init is not None and tuple(flow_init.shape) != (B, 2, h, w):
+            raise ValueError(f"{who}: flow_init must be {(B, 2, h, w)} (got {tuple(flow_init.shape)})")
+        if int(iters) < 1:
+            raise ValueError(f"{who}: iters must be >= 1 (got {iters})")
+        if any(p.device != image1.device for p in self.parameters()):
+            raise ValueError(f"{who}: the parameters and the images are on different devices")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise ValueError(f"{who} is forward only: its parameters require grad (call it under torch.no_grad())")
+        self.fnet.check_mode()
+        self.cnet.check_mode()
+        image1 = (2 * (image1 / 255.0) - 1.0).contiguous()
+        image2 = (2 * (image2 / 255.0) - 1.0).contiguous()
+        fmap1, fmap2 = self.fnet([image1, image2])
+        corr_fn = CorrBlock(fmap1, fmap2, radius=self.args.corr_radius)
+        cnet = self.cnet(image1)
+        net, inp = torch.split(cnet, [self.hidden_dim, self.context_dim], dim=1)
+        net = torch.tanh(net).contiguous()
+        inp = torch.relu(inp).contiguous()
+        ys, xs = torch.meshgrid(torch.arange(h, device=image1.device), torch.arange(w, device=image1.device), indexing="ij")
+        coords0 = torch.stack([xs, ys], dim=0).float()[None].repeat(B, 1, 1, 1)
+        coords1 = coords0.clone()
+        if flow_init is not None:
+            coords1 = coords1 + flow_init
+        flow_predictions = []
+        flow_up = None
+        for it in range(int(iters)):
+            corr = corr_fn(coords1)
+            flow = coords1 - coords0
+            wanted = not test_mode or it == int(iters) - 1
+            net, up_mask, delta_flow = self.update_block(net, inp, corr, flow, compute_mask=wanted)
+            coords1 = coords1 + delta_flow
+            if wanted:
+                flow_up = upsample_flow(coords1 - coords0, up_mask)
+                flow_predictions.append(flow_up)
+        if test_mode:
+            return coords1 - coords0, flow_up
+        return flow_predictions
 
 
 def upsample_flow(flow, mask):
