@@ -846,6 +846,66 @@ int32_t cvd_raft_encoder_timed(cvd_handle* h, int32_t batch, int32_t height, int
                                float eps, const float* images, const float* const* weights, const float* const* biases,
                                const float* const* norms, float* out, void* stream, double* kernel_ms);
 
+/* ---- The decoder of MiDaS v2.1, DESIGN.md §3.19 -- reference monodepth/midas_v2/midas_net.py:57-74 behind the backbone and
+ * blocks.py:41-159 (Interpolate, ResidualConvUnit, FeatureFusionBlock).  The ResNeXt backbone, backward and DepthModel's file I/O are
+ * out of scope.  Independent of cvd_set_video.  f32, forward only.  DEVICE arrays, enqueued on `stream`: kernel launches only, no
+ * copy, no host synchronisation, no atomics; every output element is written once in a fixed operation order, so results repeat bit
+ * for bit and an image's result does not depend on its batch.
+ *
+ * One convolution -- square filter of kernel_size 1 or 3, stride 1, padding kernel_size / 2:
+ *   x [batch][in_channels][height][width] -> out [batch][out_channels][height][width]
+ *   sum  = sum_{c,i,j} weight[o][c][i][j] x'[b][c][y + i - r][x + j - r], x' = max(x, 0) with relu_in, else x (x itself is not
+ *          modified), the input outside the image counting 0
+ *   t    = sum + bias[o] (bias may be NULL: t = sum);  relu != 0: t = max(t, 0)
+ *   a != NULL ([batch][out_channels][height][width]): t = t + (relu_a ? max(a, 0) : a)
+ *   b != NULL (like a): out = b + t, else out = t
+ * (a ResidualConvUnit rectifies its input in place, so its `out + x` adds max(x, 0): a with relu_a; b is the other path of
+ * FeatureFusionBlock's `output += resConfUnit1(xs[1])`.)
+ * split: 0 = the rule, S = a function of in_channels kernel_size^2 and height width alone (cvd_midas.h: midasSplit); 1 .. the chunks
+ * of K = forced (tests, measurement).  With S > 1 the S slices of K write partial sums to scratch of the handle [S][batch]
+ * [out_channels][height][width] and a second launch sums them in f64 in the order s = 0 .. S - 1, rounds once and applies the
+ * epilogue.  The scratch follows the rule of cvd_raft_sepconv_gru_device (high-water size, grown before the first launch; calls on
+ * one device are ordered on one stream).  out must not overlap x, a or b.
+ * Rejected before any device work, with an error that names the value: null arrays (bias, a, b may be NULL), sizes < 1, a filter
+ * other than 1, 3, flags other than 0, 1, a split outside its range, height width above 2^31, an output that overlaps an input. */
+int32_t cvd_midas_conv_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels, int32_t out_channels,
+                              int32_t kernel_size, const float* x, const float* weight, const float* bias, int32_t relu_in, int32_t relu,
+                              const float* a, int32_t relu_a, const float* b, int32_t split, float* out, void* stream);
+/* Bilinear x 2 as torch.nn.functional.interpolate(scale_factor=2, mode="bilinear") with align_corners != 0 (FeatureFusionBlock) or
+ * 0 (Interpolate): x [batch][channels][height][width] -> out [batch][channels][2 height][2 width], ONE launch, one thread per output
+ * element; a 1 x 1 input gives four copies.  out must not overlap x. */
+int32_t cvd_midas_upsample2x_device(cvd_handle* h, int32_t batch, int32_t channels, int32_t height, int32_t width, int32_t align_corners,
+                                    const float* x, float* out, void* stream);
+/* The output head behind Interpolate in ONE launch: output_conv.2 (in_channels -> mid_channels = 32, 3 x 3), ReLU, output_conv.4
+ * (32 -> 1, 1 x 1), and ReLU where non_negative != 0:
+ *   x [batch][in_channels][height][width], weight2 [32][in_channels][3][3], bias2 [32], weight4 [1][32][1][1], bias4 [1]
+ *   -> out [batch][height][width].  The 32-channel tensor is never written.  mid_channels other than 32 is refused. */
+int32_t cvd_midas_head_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels, int32_t mid_channels,
+                              const float* x, const float* weight2, const float* bias2, const float* weight4, const float* bias4,
+                              int32_t non_negative, float* out, void* stream);
+/* MidasNet.forward behind the backbone:
+ *   channels4, heights4, widths4   host arrays: the four feature maps' sizes, layer1 first; heights4[k] = 2 heights4[k + 1] exactly,
+ *              widths alike (images whose sides are multiples of 32)
+ *   maps       host array of the 4 device arrays [batch][channels4[k]][heights4[k]][widths4[k]]; they are read only
+ *   weights    host array of 21 device arrays in the state dict's order without refinenet4.resConfUnit1 (which never runs):
+ *              layer1_rn .. layer4_rn, refinenet4.resConfUnit2.{conv1, conv2}, refinenet3.resConfUnit1.{conv1, conv2},
+ *              refinenet3.resConfUnit2.{conv1, conv2}, refinenet2 and refinenet1 alike, output_conv.0, output_conv.2, output_conv.4
+ *   biases     host array of 17 device arrays: those of weights 4 .. 20 (the layerK_rn convolutions have none)
+ *   out        [batch][4 heights4[0]][4 widths4[0]]
+ * 19 launches of the convolution above (and the folds of those that split), 5 upsamplings and the head.  Intermediates are scratch of
+ * the handle under the same rule.  The result equals, bit for bit, the stages chained through the three entry points above.
+ * Rejected before any device work: null arrays, sizes < 1, feature maps that are not exact halvings, height width above 2^31, an
+ * output that overlaps a feature map. */
+int32_t cvd_midas_decoder_device(cvd_handle* h, int32_t batch, int32_t features, const int32_t* channels4, const int32_t* heights4,
+                                 const int32_t* widths4, const float* const* maps, const float* const* weights,
+                                 const float* const* biases, int32_t non_negative, float* out, void* stream);
+/* The same call for measurement (tools/midas_bench.py): HIP events around every launch on `stream` and a host wait; kernel_ms[44]:
+ * entry 2 i is convolution i of the weight table (i = 0 .. 18), 2 i + 1 its fold (0 without a split), 38 .. 42 the upsamplings in the
+ * order they run, 43 the head, in milliseconds. */
+int32_t cvd_midas_decoder_timed(cvd_handle* h, int32_t batch, int32_t features, const int32_t* channels4, const int32_t* heights4,
+                                const int32_t* widths4, const float* const* maps, const float* const* weights,
+                                const float* const* biases, int32_t non_negative, float* out, void* stream, double* kernel_ms);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

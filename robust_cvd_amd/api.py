@@ -648,6 +648,151 @@ def raft_check_encoder(image_shape, weight_shapes, bias_shapes, norm="none", nor
     return B, H, W, output_dim, ENCODER_NORM_MODES[norm], (h, w)
 
 
+# ---- the decoder of MiDaS v2.1 (csrc/cvd_midas.h) ----------------------------------------------------------------
+MIDAS_KERNEL_SIZES = (1, 3)            # the instantiations of csrc/cvd_midas.h
+MIDAS_BACKBONE_CHANNELS = (256, 512, 1024, 2048)     # layer1 .. layer4 of the ResNeXt-101 backbone
+MIDAS_HEAD_MID = 32                    # output_conv.2's channels, the head kernel's only width
+MIDAS_MAX_SPLIT = 32
+MIDAS_TIMED_SLOTS = 44                 # kernel_ms of cvd_midas_decoder_timed
+_MIDAS_UNITS = tuple(f"refinenet{r}.resConfUnit{u}.conv{c}" for r in (4, 3, 2, 1) for u in (1, 2) for c in (1, 2))
+# The 23 convolutions of the reference's MidasNet.scratch in the state dict's order; the 42 keys: a weight each, a bias for all but
+# the four layerK_rn.
+MIDAS_STATE_DICT_LAYERS = tuple(f"layer{k}_rn" for k in (1, 2, 3, 4)) + _MIDAS_UNITS + ("output_conv.0", "output_conv.2", "output_conv.4")
+MIDAS_STATE_DICT_KEYS = tuple("scratch." + n + "." + v for n in MIDAS_STATE_DICT_LAYERS
+                              for v in (("weight",) if n.endswith("_rn") else ("weight", "bias")))
+# The 21 of them that run, in the order of cvd_midas_decoder_device's weight table (refinenet4.resConfUnit1 never runs: the first
+# fusion block is called with one input); the bias table holds those of entries 4 .. 20.
+MIDAS_PARAMETERS = tuple(n for n in MIDAS_STATE_DICT_LAYERS if not n.startswith("refinenet4.resConfUnit1."))
+
+
+def midas_weight_shape(name, features=256, channels=MIDAS_BACKBONE_CHANNELS):
+    """Shape of `scratch.<name>.weight` of the reference's MidasNet(features) over a backbone with `channels`."""
+    features = int(features)
+    if name.endswith("_rn"):
+        return (features, int(channels[int(name[5]) - 1]), 3, 3)
+    return {"output_conv.0": (128, features, 3, 3), "output_conv.2": (MIDAS_HEAD_MID, 128, 3, 3),
+            "output_conv.4": (1, MIDAS_HEAD_MID, 1, 1)}.get(name, (features, features, 3, 3))
+
+
+def midas_split(K, HW, kernel_size=3):
+    """The split count S of a convolution of csrc/cvd_midas.h (midasSplit there) with K = in_channels kernel_size^2 over images of HW
+    pixels: as many slices of K as bring the 64-pixel tiles of ONE image to 64 workgroups per channel tile, each slice whole chains
+    (4 chunks of 72 k for 3 x 3, 8 chunks of 32 for 1 x 1), at most 32.  A function of K and HW alone: not of the batch, the output
+    channels or the device."""
+    chunk_k, fold = (32, 8) if int(kernel_size) == 1 else (72, 4)
+    chunks = (int(K) + chunk_k - 1) // chunk_k
+    chains = (chunks + fold - 1) // fold
+    tiles = (int(HW) + 63) // 64
+    want = max(1, min(64 // tiles, MIDAS_MAX_SPLIT, chains))
+    per = (chains + want - 1) // want
+    return (chains + per - 1) // per
+
+
+def midas_slice_channels(in_channels, kernel_size, split):
+    """The channel ranges [(c0, c1), ..] of the slices a convolution runs with under `split` (a forced split may shrink: slices are
+    whole chains)."""
+    cc, fold = (32, 8) if int(kernel_size) == 1 else (8, 4)
+    chunks = (int(in_channels) + cc - 1) // cc
+    chains = (chunks + fold - 1) // fold
+    per = (chains + int(split) - 1) // int(split)
+    step = per * fold * cc
+    return [(c0, min(c0 + step, int(in_channels))) for c0 in range(0, int(in_channels), step)]
+
+
+def _midas_shape4(who, name, shape):
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 4:
+        raise ValueError(f"{who}: {name} must be (B, C, H, W) (got {shape})")
+    B, Cn, H, W = shape
+    if B * Cn * H * W == 0:
+        raise ValueError(f"{who}: B C H W = 0 ({name} is {shape})")
+    if H * W > 2 ** 31 - 1:
+        raise ValueError(f"{who}: {H} x {W} pixels per image exceed 2^31")
+    return shape
+
+
+def midas_check_conv(x_shape, weight_shape, bias_shape=None, a_shape=None, b_shape=None, split=0):
+    """(B, H, W, Cin, N, k) of one convolution of csrc/cvd_midas.h: x [B, Cin, H, W], weight [N, Cin, k, k] with k in (1, 3), stride
+    1, padding k // 2, bias [N] or None, addends a and b of the output's shape or None, split 0 (the rule) or 1 .. the chunks of K.
+    ValueError (before any device work) for anything else."""
+    who = "MiDaS conv"
+    B, Cn, H, W = _midas_shape4(who, "x", x_shape)
+    ws = tuple(int(v) for v in weight_shape)
+    if len(ws) != 4 or ws[2] != ws[3] or ws[2] not in MIDAS_KERNEL_SIZES:
+        raise ValueError(f"{who}: the filter must be square of size {MIDAS_KERNEL_SIZES} (weight {ws})")
+    if ws[0] < 1:
+        raise ValueError(f"{who}: no output channels (weight {ws})")
+    if ws[1] != Cn:
+        raise ValueError(f"{who}: x has {Cn} channels, the weight {ws} takes {ws[1]}")
+    N, k = ws[0], ws[2]
+    if bias_shape is not None and tuple(int(v) for v in bias_shape) != (N,):
+        raise ValueError(f"{who}: bias must be ({N},) (got {tuple(bias_shape)})")
+    for name, s in (("a", a_shape), ("b", b_shape)):
+        if s is not None and tuple(int(v) for v in s) != (B, N, H, W):
+            raise ValueError(f"{who}: the addend {name} must be {(B, N, H, W)} (got {tuple(s)})")
+    chunks = (Cn + (32 if k == 1 else 8) - 1) // (32 if k == 1 else 8)
+    if int(split) != split or not 0 <= split <= chunks:
+        raise ValueError(f"{who}: split must be 0 (the rule) or 1 .. {chunks}, the chunks of K (got {split})")
+    return B, H, W, Cn, N, k
+
+
+def midas_check_upsample2x(x_shape):
+    """(B, C, H, W) of the bilinear x 2 upsampling; ValueError for anything but a non-empty (B, C, H, W) whose output plane stays
+    below 2^31 pixels."""
+    who = "MiDaS upsample2x"
+    B, Cn, H, W = _midas_shape4(who, "x", x_shape)
+    if 4 * H * W > 2 ** 31 - 1:
+        raise ValueError(f"{who}: {2 * H} x {2 * W} output pixels per plane exceed 2^31")
+    return B, Cn, H, W
+
+
+def midas_check_head(x_shape, weight2_shape, bias2_shape, weight4_shape, bias4_shape):
+    """(B, H, W, Cin) of the output head: x [B, Cin, H, W], output_conv.2 [32, Cin, 3, 3] and [32], output_conv.4 [1, 32, 1, 1] and
+    [1]."""
+    who = "MiDaS head"
+    B, Cn, H, W = _midas_shape4(who, "x", x_shape)
+    got = [tuple(int(v) for v in s) for s in (weight2_shape, bias2_shape, weight4_shape, bias4_shape)]
+    if len(got[0]) == 4 and got[0][0] != MIDAS_HEAD_MID:
+        raise ValueError(f"{who}: the middle width must be {MIDAS_HEAD_MID} (output_conv.2.weight is {got[0]})")
+    want = [(MIDAS_HEAD_MID, Cn, 3, 3), (MIDAS_HEAD_MID,), (1, MIDAS_HEAD_MID, 1, 1), (1,)]
+    for name, g, w in zip(("output_conv.2.weight", "output_conv.2.bias", "output_conv.4.weight", "output_conv.4.bias"), got, want):
+        if g != w:
+            raise ValueError(f"{who}: {name} must be {w} (got {g})")
+    return B, H, W, Cn
+
+
+def midas_check_decoder(map_shapes, weight_shapes, bias_shapes):
+    """(B, features, channels[4], heights[4], widths[4]) of the decoder: four feature maps [B, C_k, H_k, W_k] with H_k = 2 H_{k+1}
+    and W_k = 2 W_{k+1} exactly, the 21 weight and 17 bias shapes in MIDAS_PARAMETERS order.  ValueError for anything else."""
+    who = "MiDaS decoder"
+    if len(map_shapes) != 4:
+        raise ValueError(f"{who}: four feature maps are expected (got {len(map_shapes)})")
+    maps = [_midas_shape4(who, f"feature map {k + 1}", s) for k, s in enumerate(map_shapes)]
+    B = maps[0][0]
+    for k in range(4):
+        if maps[k][0] != B:
+            raise ValueError(f"{who}: feature map {k + 1} has batch {maps[k][0]}, feature map 1 has {B}")
+        if k and (maps[k - 1][2], maps[k - 1][3]) != (2 * maps[k][2], 2 * maps[k][3]):
+            raise ValueError(f"{who}: feature map {k} is {maps[k - 1][2]} x {maps[k - 1][3]}, not twice feature map {k + 1}'s "
+                             f"{maps[k][2]} x {maps[k][3]} (image sides must be multiples of 32)")
+    if 16 * maps[0][2] * maps[0][3] > 2 ** 31 - 1:
+        raise ValueError(f"{who}: {4 * maps[0][2]} x {4 * maps[0][3]} output pixels per image exceed 2^31")
+    if len(weight_shapes) != 21 or len(bias_shapes) != 17:
+        raise ValueError(f"{who}: 21 weights and 17 biases are expected, in the order {MIDAS_PARAMETERS} (biases from entry 4 on)")
+    ws = [tuple(int(v) for v in s) for s in weight_shapes]
+    if len(ws[0]) != 4 or ws[0][0] < 1:
+        raise ValueError(f"{who}: layer1_rn.weight must be (features, {maps[0][1]}, 3, 3) (got {ws[0]})")
+    features = ws[0][0]
+    channels = [m[1] for m in maps]
+    for i, (name, w) in enumerate(zip(MIDAS_PARAMETERS, ws)):
+        want = midas_weight_shape(name, features, channels)
+        if w != want:
+            raise ValueError(f"{who}: {name}.weight must be {want} (got {w})")
+        if i >= 4 and tuple(int(v) for v in bias_shapes[i - 4]) != (want[0],):
+            raise ValueError(f"{who}: {name}.bias must be ({want[0]},) (got {tuple(bias_shapes[i - 4])})")
+    return B, features, channels, [m[2] for m in maps], [m[3] for m in maps]
+
+
 class _DeviceArrays:
     """Raw device buffers of the numpy mirror of a `*_device` entry point (null stream, blocking copies); freed on exit."""
 
@@ -765,7 +910,9 @@ EXPORTED_SYMBOLS = [
     "cvd_get_pose_params", "cvd_set_pose_params", "cvd_block_size", "cvd_normalize_depth", "cvd_pose_optimization",
     "cvd_pose_optimization_step", "cvd_evaluate", "cvd_sample_pair_constraints", "cvd_get_sampled_constraints", "cvd_sample_triplet_constraints", "cvd_get_sampled_triplet_constraints", "cvd_set_dynamic_masks", "cvd_corner_min_eigenval", "cvd_dynamic_distance", "cvd_apply_depth_xforms", "cvd_depth_param_maps", "cvd_spatial_warp_maps", "cvd_flow_guided_filter", "cvd_bilateral_filter", "cvd_epipolar_static_flags", "cvd_compute_tracks", "cvd_get_tracks", "cvd_flow_consistency_masks", "cvd_consistency_loss", "cvd_consistency_loss_device", "cvd_scene_flow_loss", "cvd_scene_flow_loss_device", "cvd_spatial_losses", "cvd_spatial_losses_device", "cvd_param_chunk", "cvd_parameter_l1", "cvd_parameter_l1_device", "cvd_param_step", "cvd_param_step_device", "cvd_dataset_create", "cvd_dataset_clear", "cvd_dataset_set_colors", "cvd_dataset_set_flows", "cvd_dataset_set_depth_orig", "cvd_dataset_set_cameras", "cvd_dataset_set_xforms", "cvd_dataset_set_maps", "cvd_dataset_batch", "cvd_dataset_batch_device", "cvd_dataset_bad_indices",
     "cvd_raft_corr_pyramid_device", "cvd_raft_corr_lookup_device", "cvd_raft_upsample_flow_device", "cvd_raft_sepconv_gru_device", "cvd_raft_sepconv_gru_timed", "cvd_raft_conv2d_device", "cvd_raft_update_block_device", "cvd_raft_update_block_timed",
-    "cvd_raft_encoder_conv_device", "cvd_raft_instance_norm_device", "cvd_raft_encoder_device", "cvd_raft_encoder_timed", "cvd_get_summary", "cvd_num_records", "cvd_get_records",
+    "cvd_raft_encoder_conv_device", "cvd_raft_instance_norm_device", "cvd_raft_encoder_device", "cvd_raft_encoder_timed",
+    "cvd_midas_conv_device", "cvd_midas_upsample2x_device", "cvd_midas_head_device", "cvd_midas_decoder_device", "cvd_midas_decoder_timed",
+    "cvd_get_summary", "cvd_num_records", "cvd_get_records",
     "cvd_get_kernel_times", "cvd_get_comm_times", "cvd_get_dense_times", "cvd_set_kernel_timing", "cvd_num_active_constraints", "cvd_coarse_debug", "cvd_temporal_debug", "cvd_path_info", "cvd_abi_revision",
     "cvd_block_inverse_debug", "cvd_dense_inverse_debug", "cvd_epipolar_debug", "cvd_flow_masks_debug",
     "cvd_product_launch_debug", "cvd_assembly_launch_debug",
@@ -1526,6 +1673,105 @@ class Solver(Binding):
                 kernel_ms[:] = list(ms)
             if _hip_runtime().hipDeviceSynchronize() != 0:
                 raise RuntimeError("raft_encoder: the device reported an error")
+            dev.download(do, out)
+        return out
+
+    @staticmethod
+    def _midas_f32(who, arrays):
+        import numpy as np
+        for a in arrays:
+            if a is not None and a.dtype != np.float32:
+                raise TypeError(f"{who}: every array must be float32 (got {a.dtype})")
+
+    def midas_conv(self, x, weight, bias=None, relu_in=False, relu=False, a=None, relu_a=False, b=None, split=0):
+        """One convolution of the MiDaS decoder (csrc/cvd_midas.h): x [B, C, H, W] f32, weight [N, C, k, k] (k = 1,
+        3), stride 1, padding k // 2 -> [B, N, H, W]: t = conv(max(x, 0) under relu_in, else x) + bias (or none); max(t, 0) under
+        relu; t + (max(a, 0) under relu_a, else a) with an addend a; b + t with a second addend b.  split: 0 = the rule
+        (midas_split), else the forced number of slices of K."""
+        import numpy as np
+        x, weight = np.asarray(x), np.asarray(weight)
+        bias, a, b = (None if v is None else np.asarray(v) for v in (bias, a, b))
+        self._midas_f32("midas_conv", [x, weight, bias, a, b])
+        B, H, W, Cin, N, k = midas_check_conv(x.shape, weight.shape, None if bias is None else bias.shape,
+                                              None if a is None else a.shape, None if b is None else b.shape, split)
+        out = np.zeros((B, N, H, W), np.float32)
+        with _DeviceArrays() as dev:
+            dx, dw = dev.upload(np.ascontiguousarray(x)), dev.upload(np.ascontiguousarray(weight))
+            db, da, d2 = (None if v is None else dev.upload(np.ascontiguousarray(v)) for v in (bias, a, b))
+            do = dev.alloc(out.nbytes)
+            self._check(self._fn("midas_conv_device")(
+                self._h, C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(Cin), C.c_int32(N), C.c_int32(k), dx, dw, db,
+                C.c_int32(1 if relu_in else 0), C.c_int32(1 if relu else 0), da, C.c_int32(1 if relu_a else 0), d2, C.c_int32(split),
+                do, None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("midas_conv: the device reported an error")
+            dev.download(do, out)
+        return out
+
+    def midas_upsample2x(self, x, align_corners=True):
+        """Bilinear x 2 of x [B, C, H, W] f32 as torch.nn.functional.interpolate(scale_factor=2, mode="bilinear", align_corners=...)
+        (csrc/cvd_midas.h) -> [B, C, 2 H, 2 W]."""
+        import numpy as np
+        x = np.asarray(x)
+        self._midas_f32("midas_upsample2x", [x])
+        B, Cn, H, W = midas_check_upsample2x(x.shape)
+        out = np.zeros((B, Cn, 2 * H, 2 * W), np.float32)
+        with _DeviceArrays() as dev:
+            dx = dev.upload(np.ascontiguousarray(x))
+            do = dev.alloc(out.nbytes)
+            self._check(self._fn("midas_upsample2x_device")(
+                self._h, C.c_int32(B), C.c_int32(Cn), C.c_int32(H), C.c_int32(W), C.c_int32(1 if align_corners else 0), dx, do, None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("midas_upsample2x: the device reported an error")
+            dev.download(do, out)
+        return out
+
+    def midas_head(self, x, weight2, bias2, weight4, bias4, non_negative=True):
+        """The output head behind Interpolate in one launch (csrc/cvd_midas.h): x [B, C, H, W] f32, output_conv.2 [32, C, 3, 3] and
+        [32], ReLU, output_conv.4 [1, 32, 1, 1] and [1], ReLU under non_negative -> [B, H, W]."""
+        import numpy as np
+        arrays = [np.asarray(v) for v in (x, weight2, bias2, weight4, bias4)]
+        self._midas_f32("midas_head", arrays)
+        B, H, W, Cin = midas_check_head(*[v.shape for v in arrays])
+        out = np.zeros((B, H, W), np.float32)
+        with _DeviceArrays() as dev:
+            dx, dw2, db2, dw4, db4 = (dev.upload(np.ascontiguousarray(v)) for v in arrays)
+            do = dev.alloc(out.nbytes)
+            self._check(self._fn("midas_head_device")(
+                self._h, C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(Cin), C.c_int32(MIDAS_HEAD_MID), dx, dw2, db2, dw4, db4,
+                C.c_int32(1 if non_negative else 0), do, None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("midas_head: the device reported an error")
+            dev.download(do, out)
+        return out
+
+    def midas_decoder(self, maps, weights, biases, non_negative=True, kernel_ms=None):
+        """MidasNet.forward behind the backbone (monodepth/midas_v2/midas_net.py:62-74): maps = the four feature
+        maps [B, C_k, H_k, W_k] f32 (layer1 first, each half the one before), weights / biases = the 21 / 17 of MIDAS_PARAMETERS in
+        torch's shapes -> [B, 4 H_1, 4 W_1].  kernel_ms (measurement): a list that receives the 44 per-launch milliseconds of
+        cvd_midas_decoder_timed."""
+        import numpy as np
+        maps = [np.asarray(v) for v in maps]
+        weights, biases = [np.asarray(v) for v in weights], [np.asarray(v) for v in biases]
+        self._midas_f32("midas_decoder", maps + weights + biases)
+        B, features, channels, heights, widths = midas_check_decoder([v.shape for v in maps], [v.shape for v in weights],
+                                                                     [v.shape for v in biases])
+        out = np.zeros((B, 4 * heights[0], 4 * widths[0]), np.float32)
+        with _DeviceArrays() as dev:
+            dm = (C.c_void_p * 4)(*[dev.upload(np.ascontiguousarray(v)).value for v in maps])
+            dw = (C.c_void_p * 21)(*[dev.upload(np.ascontiguousarray(v)).value for v in weights])
+            db = (C.c_void_p * 17)(*[dev.upload(np.ascontiguousarray(v)).value for v in biases])
+            do = dev.alloc(out.nbytes)
+            args = (self._h, C.c_int32(B), C.c_int32(features), (C.c_int32 * 4)(*channels), (C.c_int32 * 4)(*heights),
+                    (C.c_int32 * 4)(*widths), dm, dw, db, C.c_int32(1 if non_negative else 0), do, None)
+            if kernel_ms is None:
+                self._check(self._fn("midas_decoder_device")(*args))
+            else:
+                ms = (C.c_double * MIDAS_TIMED_SLOTS)()
+                self._check(self._fn("midas_decoder_timed")(*args, ms))
+                kernel_ms[:] = list(ms)
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("midas_decoder: the device reported an error")
             dev.download(do, out)
         return out
 

@@ -907,6 +907,35 @@ int32_t cvd_raft_encoder_timed(cvd_handle* h, int32_t batch, int32_t height, int
   CVD_TRY(h, raftEncoderDevice(h, batch, height, width, output_dim, norm_mode, eps, images, weights, biases, norms, out,
                                static_cast<hipStream_t>(stream), kernel_ms));
 }
+// reference monodepth/midas_v2/blocks.py:41-159, midas_net.py:31-74 (the decoder's convolutions, upsamplings and output head)
+int32_t cvd_midas_conv_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels, int32_t out_channels,
+                              int32_t kernel_size, const float* x, const float* weight, const float* bias, int32_t relu_in, int32_t relu,
+                              const float* a, int32_t relu_a, const float* b, int32_t split, float* out, void* stream) {
+  CVD_TRY(h, midasConvDevice(h, batch, height, width, in_channels, out_channels, kernel_size, x, weight, bias, relu_in, relu, a, relu_a, b,
+                             split, out, static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_midas_upsample2x_device(cvd_handle* h, int32_t batch, int32_t channels, int32_t height, int32_t width, int32_t align_corners,
+                                    const float* x, float* out, void* stream) {
+  CVD_TRY(h, midasUpsample2xDevice(h, batch, channels, height, width, align_corners, x, out, static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_midas_head_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels, int32_t mid_channels,
+                              const float* x, const float* weight2, const float* bias2, const float* weight4, const float* bias4,
+                              int32_t non_negative, float* out, void* stream) {
+  CVD_TRY(h, midasHeadDevice(h, batch, height, width, in_channels, mid_channels, x, weight2, bias2, weight4, bias4, non_negative, out,
+                             static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_midas_decoder_device(cvd_handle* h, int32_t batch, int32_t features, const int32_t* channels4, const int32_t* heights4,
+                                 const int32_t* widths4, const float* const* maps, const float* const* weights,
+                                 const float* const* biases, int32_t non_negative, float* out, void* stream) {
+  CVD_TRY(h, midasDecoderDevice(h, batch, features, channels4, heights4, widths4, maps, weights, biases, non_negative, out,
+                                static_cast<hipStream_t>(stream), nullptr));
+}
+int32_t cvd_midas_decoder_timed(cvd_handle* h, int32_t batch, int32_t features, const int32_t* channels4, const int32_t* heights4,
+                                const int32_t* widths4, const float* const* maps, const float* const* weights,
+                                const float* const* biases, int32_t non_negative, float* out, void* stream, double* kernel_ms) {
+  CVD_TRY(h, midasDecoderDevice(h, batch, features, channels4, heights4, widths4, maps, weights, biases, non_negative, out,
+                                static_cast<hipStream_t>(stream), kernel_ms));
+}
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {

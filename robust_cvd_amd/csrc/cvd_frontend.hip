@@ -2,8 +2,8 @@
 // consumers, flow-guided and bilateral filters, feature tracks, flow consistency masks, the fine-tuning consistency,
 // scene-flow and spatial losses, the parameter regulariser and the optimizer step, the fine-tuning batches, RAFT's correlation pyramid / lookup and convex
 // upsampling (cvd_raftops.h: k_corr_pyramid, k_corr_lookup, k_convex_upsample), the SepConvGRU of RAFT's update block
-// (cvd_raftgru.h: k_gru_gemm), its other convolutions (cvd_raftconv.h: k_raft_conv) and RAFT's encoders (cvd_raftenc.h: k_enc_conv,
-// k_instnorm_stats, k_instnorm_apply).  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
+// (cvd_raftgru.h: k_gru_gemm), its other convolutions (cvd_raftconv.h: k_raft_conv), RAFT's encoders (cvd_raftenc.h: k_enc_conv,
+// k_instnorm_stats, k_instnorm_apply) and the decoder of MiDaS v2.1 (cvd_midas.h: k_midas_conv, k_midas_fold, k_midas_upsample2x).  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
 // through a pointer to the incomplete type).
 #include "cvd_host.h"
 #include "cvd_dense.h"
@@ -24,6 +24,7 @@
 #include "cvd_raftgru.h"
 #include "cvd_raftconv.h"
 #include "cvd_raftenc.h"
+#include "cvd_midas.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -142,6 +143,8 @@ struct Frontend {
   // (mean, rstd) per plane, under the same rule.
   DevBuf<float> dEnc;
   DevBuf<double> dEncStats;
+  // cvd_midas.h: the decoder's intermediates and the partial sums of a split convolution, under the same rule.
+  DevBuf<float> dMidas, dMidasSplit;
 };
 
 std::shared_ptr<Frontend> makeFrontend() { return std::make_shared<Frontend>(); }
@@ -2746,6 +2749,289 @@ void raftEncoderDevice(cvd_handle* h, int B, int H, int W, int outputDim, int no
     timer.wait();
     timer.collect();
     std::fill(kernelMs, kernelMs + 48, 0.0);
+    for (int i = 0; i < launches; ++i) kernelMs[slot[i]] = phaseMs[i];
+  }
+}
+
+// ---- The decoder of MiDaS v2.1 (reference monodepth/midas_v2/midas_net.py:57-74, blocks.py:41-159; cvd_midas.h).
+// Device arrays on the caller's stream: enqueued launches only. ---------------------------------------------------------------------
+namespace {
+struct MidasDims {
+  long long HW, M;
+};
+
+MidasDims checkMidasShape(const char* who, int B, int H, int W) {
+  if (B < 1 || H < 1 || W < 1) throw std::runtime_error(fmt("%s: batch, height and width must be >= 1 (got %d, %d, %d)", who, B, H, W));
+  MidasDims d{};
+  d.HW = static_cast<long long>(H) * W;
+  if (d.HW > 0x7fffffffll) throw std::runtime_error(fmt("%s: %d x %d pixels per image exceed 2^31", who, H, W));
+  d.M = d.HW * B;
+  if ((d.M + kMidasTile - 1) / kMidasTile > 0x7fffffffll) throw std::runtime_error(fmt("%s: %lld pixels exceed the grid", who, d.M));
+  return d;
+}
+
+void checkMidasChannels(const char* who, int Cin, int N, int ks, long long M) {
+  if (ks != 1 && ks != 3) throw std::runtime_error(fmt("%s: kernel_size must be 1 or 3 (got %d)", who, ks));
+  if (Cin < 1) throw std::runtime_error(fmt("%s: in_channels must be >= 1 (got %d)", who, Cin));
+  if (N < 1) throw std::runtime_error(fmt("%s: out_channels must be >= 1 (got %d)", who, N));
+  if (static_cast<long long>(Cin) * ks * ks > 0x7fffffffll) throw std::runtime_error(fmt("%s: in_channels %d exceeds the kernel's range", who, Cin));
+  if ((N + kMidasTile - 1) / kMidasTile > 65535) throw std::runtime_error(fmt("%s: out_channels %d exceeds the grid", who, N));
+  if ((M * N + kMidasThreads - 1) / kMidasThreads > 0x7fffffffll)
+    throw std::runtime_error(fmt("%s: %lld pixels of %d channels exceed the grid", who, M, N));
+}
+
+int midasChunks(int Cin, int ks) {
+  const int cc = ks == 1 ? MidasShape<1>::kChunkChannels : MidasShape<3>::kChunkChannels;
+  return (Cin + cc - 1) / cc;
+}
+
+// the split the convolution runs with: `forced` >= 1 as given (checked by the caller), 0 = the rule
+int midasSplitFor(int Cin, int ks, long long HW, int forced) {
+  return forced > 0 ? forced : midasSplit(static_cast<long long>(Cin) * ks * ks, HW, ks);
+}
+
+// floats of split scratch a convolution needs (0 without a split)
+size_t midasSplitFloats(int S, long long M, int N) { return S > 1 ? static_cast<size_t>(S) * static_cast<size_t>(M) * N : 0; }
+
+// One convolution: one launch, with S > 1 the fold behind it.  Checked by the callers; `partial` holds midasSplitFloats floats.
+// mark (may be empty) is called after each launch; returns the launches (1 or 2).
+template <class Mark>
+int launchMidasConv(int B, int H, int W, int Cin, int N, int ks, const float* x, const float* w, const float* bias, int reluIn, int relu,
+                    const float* a, int reluA, const float* b, int S, float* partial, float* out, hipStream_t s, Mark&& mark) {
+  MidasConvArgs A{};
+  A.x = x; A.w = w; A.bias = bias; A.a = a; A.b = b; A.out = out; A.partial = partial;
+  A.reluIn = reluIn; A.relu = relu; A.reluA = reluA;
+  A.Cin = Cin; A.N = N; A.H = H; A.W = W; A.HW = H * W;
+  A.M = static_cast<long long>(A.HW) * B;
+  const int fold = ks == 1 ? MidasShape<1>::kFold : MidasShape<3>::kFold;
+  const int chunks = midasChunks(Cin, ks), chains = (chunks + fold - 1) / fold;
+  const int per = (chains + S - 1) / S;                   // chains per slice
+  A.S = (chains + per - 1) / per;                         // (the rule's S already has this form; a forced one may shrink)
+  A.chunksPerSlice = per * fold;
+  const dim3 grid(static_cast<unsigned>((A.M + kMidasTile - 1) / kMidasTile), static_cast<unsigned>((N + kMidasTile - 1) / kMidasTile),
+                  static_cast<unsigned>(A.S));
+  // float4 weight loads only where every row starts on 16 bytes
+  const bool vec = (static_cast<long long>(Cin) * ks * ks) % 4 == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0;
+  if (ks == 1) {
+    if (vec) hipLaunchKernelGGL((k_midas_conv<1, true, false>), grid, dim3(kMidasThreads), 0, s, A);
+    else hipLaunchKernelGGL((k_midas_conv<1, false, false>), grid, dim3(kMidasThreads), 0, s, A);
+  } else {
+    if (vec) hipLaunchKernelGGL((k_midas_conv<3, true, false>), grid, dim3(kMidasThreads), 0, s, A);
+    else hipLaunchKernelGGL((k_midas_conv<3, false, false>), grid, dim3(kMidasThreads), 0, s, A);
+  }
+  HIP_CHECK(hipGetLastError());
+  mark();
+  if (A.S == 1) return 1;
+  hipLaunchKernelGGL(k_midas_fold, dim3(static_cast<unsigned>((A.M * N + kMidasThreads - 1) / kMidasThreads)), dim3(kMidasThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+  mark();
+  return 2;
+}
+
+void launchMidasUpsample(long long planes, int H, int W, int align, const float* x, float* out, hipStream_t s) {
+  MidasUpsampleArgs A{};
+  A.x = x; A.out = out; A.H = H; A.W = W;
+  A.total = planes * 4 * H * W;
+  const dim3 grid(static_cast<unsigned>((A.total + kMidasThreads - 1) / kMidasThreads));
+  if (align) hipLaunchKernelGGL((k_midas_upsample2x<true>), grid, dim3(kMidasThreads), 0, s, A);
+  else hipLaunchKernelGGL((k_midas_upsample2x<false>), grid, dim3(kMidasThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+}
+
+void checkMidasUpsampleSize(const char* who, long long planes, int H, int W) {
+  const long long HW = static_cast<long long>(H) * W;
+  if (HW > 0x7fffffffll / 4) throw std::runtime_error(fmt("%s: %d x %d output pixels per plane exceed 2^31", who, 2 * H, 2 * W));
+  if (planes > 0x7fffffffll || (planes * 4 * HW + kMidasThreads - 1) / kMidasThreads > 0x7fffffffll)
+    throw std::runtime_error(fmt("%s: %lld planes of %lld elements exceed the grid", who, planes, 4 * HW));
+}
+
+void launchMidasHead(int B, int H, int W, int Cin, const float* x, const float* w2, const float* b2, const float* w4, const float* b4,
+                     int nonNegative, float* out, hipStream_t s) {
+  MidasConvArgs A{};
+  A.x = x; A.w = w2; A.bias = b2; A.w4 = w4; A.b4 = b4; A.out = out;
+  A.nonNegative = nonNegative;
+  A.Cin = Cin; A.N = kMidasHeadMid; A.H = H; A.W = W; A.HW = H * W;
+  A.M = static_cast<long long>(A.HW) * B;
+  A.S = 1;
+  A.chunksPerSlice = midasChunks(Cin, 3);
+  const dim3 grid(static_cast<unsigned>((A.M + kMidasHeadPixels - 1) / kMidasHeadPixels));
+  const bool vec = (static_cast<long long>(Cin) * 9) % 4 == 0 && (reinterpret_cast<uintptr_t>(w2) & 15) == 0;
+  if (vec) hipLaunchKernelGGL((k_midas_conv<3, true, true>), grid, dim3(kMidasThreads), 0, s, A);
+  else hipLaunchKernelGGL((k_midas_conv<3, false, true>), grid, dim3(kMidasThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+}
+
+void checkFlag(const char* who, const char* name, int v) {
+  if (v != 0 && v != 1) throw std::runtime_error(fmt("%s: %s must be 0 or 1 (got %d)", who, name, v));
+}
+}  // namespace
+
+void midasConvDevice(cvd_handle* h, int B, int H, int W, int inChannels, int outChannels, int kernelSize, const float* x,
+                     const float* weight, const float* bias, int reluIn, int relu, const float* a, int reluA, const float* b, int split,
+                     float* out, hipStream_t s) {
+  const char* who = "midas conv";
+  const MidasDims d = checkMidasShape(who, B, H, W);
+  checkMidasChannels(who, inChannels, outChannels, kernelSize, d.M);
+  checkFlag(who, "relu_in", reluIn);
+  checkFlag(who, "relu", relu);
+  checkFlag(who, "relu_a", reluA);
+  const int chunks = midasChunks(inChannels, kernelSize);
+  if (split < 0 || split > chunks)
+    throw std::runtime_error(fmt("%s: split must be 0 (the rule) or 1 .. %d, the chunks of K (got %d)", who, chunks, split));
+  if (!x || !weight || !out) throw std::runtime_error(fmt("%s: null array", who));
+  const long long outFloats = d.M * outChannels;
+  if (rangesOverlap(out, outFloats, x, d.M * inChannels)) throw std::runtime_error(fmt("%s: out overlaps x", who));
+  if (a && rangesOverlap(out, outFloats, a, outFloats)) throw std::runtime_error(fmt("%s: out overlaps the addend a", who));
+  if (b && rangesOverlap(out, outFloats, b, outFloats)) throw std::runtime_error(fmt("%s: out overlaps the addend b", who));
+  const int S = midasSplitFor(inChannels, kernelSize, d.HW, split);
+  Frontend& fe = *h->frontend;
+  fe.dMidasSplit.ensure(midasSplitFloats(S, d.M, outChannels));
+  launchMidasConv(B, H, W, inChannels, outChannels, kernelSize, x, weight, bias, reluIn, relu, a, reluA, b, S, fe.dMidasSplit.p, out, s,
+                  [] {});
+}
+
+void midasUpsample2xDevice(cvd_handle*, int B, int channels, int H, int W, int alignCorners, const float* x, float* out, hipStream_t s) {
+  const char* who = "midas upsample2x";
+  if (B < 1 || channels < 1 || H < 1 || W < 1)
+    throw std::runtime_error(fmt("%s: batch, channels, height and width must be >= 1 (got %d, %d, %d, %d)", who, B, channels, H, W));
+  checkFlag(who, "align_corners", alignCorners);
+  const long long planes = static_cast<long long>(B) * channels;
+  checkMidasUpsampleSize(who, planes, H, W);
+  if (!x || !out) throw std::runtime_error(fmt("%s: null array", who));
+  const long long n = planes * H * W;
+  if (rangesOverlap(out, 4 * n, x, n)) throw std::runtime_error(fmt("%s: out overlaps x", who));
+  launchMidasUpsample(planes, H, W, alignCorners, x, out, s);
+}
+
+void midasHeadDevice(cvd_handle*, int B, int H, int W, int inChannels, int midChannels, const float* x, const float* weight2,
+                     const float* bias2, const float* weight4, const float* bias4, int nonNegative, float* out, hipStream_t s) {
+  const char* who = "midas head";
+  const MidasDims d = checkMidasShape(who, B, H, W);
+  if ((d.M + kMidasHeadPixels - 1) / kMidasHeadPixels > 0x7fffffffll) throw std::runtime_error(fmt("%s: %lld pixels exceed the grid", who, d.M));
+  if (inChannels < 1) throw std::runtime_error(fmt("%s: in_channels must be >= 1 (got %d)", who, inChannels));
+  if (static_cast<long long>(inChannels) * 9 > 0x7fffffffll) throw std::runtime_error(fmt("%s: in_channels %d exceeds the kernel's range", who, inChannels));
+  if (midChannels != kMidasHeadMid) throw std::runtime_error(fmt("%s: mid_channels must be %d (got %d)", who, kMidasHeadMid, midChannels));
+  checkFlag(who, "non_negative", nonNegative);
+  if (!x || !weight2 || !bias2 || !weight4 || !bias4 || !out) throw std::runtime_error(fmt("%s: null array", who));
+  if (rangesOverlap(out, d.M, x, d.M * inChannels)) throw std::runtime_error(fmt("%s: out overlaps x", who));
+  launchMidasHead(B, H, W, inChannels, x, weight2, bias2, weight4, bias4, nonNegative, out, s);
+}
+
+// MidasNet.forward behind the backbone.  channels / heights / widths: of the four feature maps, layer 1 first.
+// weights (21) / biases (17): the tables include/cvd_hip.h documents.  kernelMs (measurement only, may be null): 44 entries; with it the
+// call waits on the host.
+void midasDecoderDevice(cvd_handle* h, int B, int features, const int* channels, const int* heights, const int* widths,
+                        const float* const* maps, const float* const* weights, const float* const* biases, int nonNegative, float* out,
+                        hipStream_t s, double* kernelMs) {
+  const char* who = "midas decoder";
+  if (!channels || !heights || !widths || !maps || !weights || !biases || !out) throw std::runtime_error(fmt("%s: null array", who));
+  if (features < 1) throw std::runtime_error(fmt("%s: features must be >= 1 (got %d)", who, features));
+  checkFlag(who, "non_negative", nonNegative);
+  long long M[4];
+  for (int k = 0; k < 4; ++k) {
+    const MidasDims d = checkMidasShape(who, B, heights[k], widths[k]);
+    M[k] = d.M;
+    if (channels[k] < 1) throw std::runtime_error(fmt("%s: channels of feature map %d must be >= 1 (got %d)", who, k + 1, channels[k]));
+    checkMidasChannels(who, channels[k], features, 3, d.M);
+    if (k > 0 && (heights[k - 1] != 2 * heights[k] || widths[k - 1] != 2 * widths[k]))
+      throw std::runtime_error(fmt("%s: feature map %d is %d x %d, not twice map %d's %d x %d", who, k, heights[k - 1], widths[k - 1], k + 1,
+                                   heights[k], widths[k]));
+    if (!maps[k]) throw std::runtime_error(fmt("%s: null feature map %d", who, k + 1));
+  }
+  const int H1 = heights[0], W1 = widths[0];
+  if (static_cast<long long>(H1) * W1 > 0x7fffffffll / 16)
+    throw std::runtime_error(fmt("%s: %d x %d output pixels per image exceed 2^31", who, 4 * H1, 4 * W1));
+  const long long Mout = 16 * M[0];
+  checkMidasShape(who, B, 4 * H1, 4 * W1);
+  checkMidasChannels(who, features, std::max(features, 128), 3, 4 * M[0]);
+  checkMidasUpsampleSize(who, static_cast<long long>(B) * std::max(features, 128), 2 * H1, 2 * W1);
+  for (int i = 0; i < 21; ++i)
+    if (!weights[i]) throw std::runtime_error(fmt("%s: null weight %d", who, i));
+  for (int i = 0; i < 17; ++i)
+    if (!biases[i]) throw std::runtime_error(fmt("%s: null bias %d", who, i));
+  for (int k = 0; k < 4; ++k)
+    if (rangesOverlap(out, Mout, maps[k], M[k] * channels[k])) throw std::runtime_error(fmt("%s: out overlaps feature map %d", who, k + 1));
+
+  // scratch: the four layerK_rn outputs, three rotating tensors of the largest level, the path (up to features channels at twice
+  // level 1), output_conv.0's result and its upsampling; and the split convolutions' partial sums
+  const size_t F = static_cast<size_t>(features);
+  size_t n[4], off[4], total = 0, split = 0;
+  for (int k = 0; k < 4; ++k) {
+    n[k] = F * static_cast<size_t>(M[k]);
+    off[k] = total;
+    total += n[k];
+    const long long HW = static_cast<long long>(heights[k]) * widths[k];
+    split = std::max(split, midasSplitFloats(midasSplitFor(channels[k], 3, HW, 0), M[k], features));
+    split = std::max(split, midasSplitFloats(midasSplitFor(features, 3, HW, 0), M[k], features));
+  }
+  split = std::max(split, midasSplitFloats(midasSplitFor(features, 3, 4ll * H1 * W1, 0), 4 * M[0], 128));
+  const size_t oT = total, oP = oT + 3 * n[0], oH0 = oP + 4 * n[0], oH1 = oH0 + 128 * 4 * static_cast<size_t>(M[0]);
+  total = oH1 + 128 * static_cast<size_t>(Mout);
+  Frontend& fe = *h->frontend;
+  fe.dMidas.ensure(total);
+  fe.dMidasSplit.ensure(split);
+  float* base = fe.dMidas.p;
+  float* L[4] = {base + off[0], base + off[1], base + off[2], base + off[3]};
+  float* T0 = base + oT;
+  float* T1 = T0 + n[0];
+  float* T2 = T1 + n[0];
+  float* P = base + oP;
+  float* H0 = base + oH0;
+  float* Hup = base + oH1;
+
+  constexpr int kSlots = 44;
+  double phaseMs[kSlots];
+  int slot[kSlots];
+  int launches = 0;
+  KernelTimer timer(s, kernelMs ? phaseMs : nullptr, kSlots);
+  timer.mark();
+  // convolution `idx` of the weight table (bias idx - 4, none for the first four): slot 2 idx, its fold 2 idx + 1
+  const auto conv = [&](int idx, int k, const float* x, int Cin, int N, int reluIn, const float* a, const float* b, float* y) {
+    int part = 0;
+    const long long HW = static_cast<long long>(heights[k]) * widths[k];
+    launchMidasConv(B, heights[k], widths[k], Cin, N, 3, x, weights[idx], idx < 4 ? nullptr : biases[idx - 4], reluIn, 0, a, 1, b,
+                    midasSplitFor(Cin, 3, HW, 0), fe.dMidasSplit.p, y, s, [&] {
+                      slot[launches++] = 2 * idx + part++;
+                      timer.mark();
+                    });
+  };
+  const auto upsample = [&](int which, long long planes, int H, int W, int align, const float* x, float* y) {
+    launchMidasUpsample(planes, H, W, align, x, y, s);
+    slot[launches++] = 38 + which;
+    timer.mark();
+  };
+  for (int k = 0; k < 4; ++k) conv(k, k, maps[k], channels[k], features, 0, nullptr, nullptr, L[k]);
+  // refinenet4 .. refinenet1: FeatureFusionBlock.forward with the in-place ReLU of its units (blocks.py:66-75, 94-111)
+  for (int k = 3; k >= 0; --k) {
+    const int w0 = k == 3 ? 4 : 6 + 4 * (2 - k);         // the block's first weight: rn4 has resConfUnit2 only
+    const float* o = L[k];
+    if (k < 3) {
+      conv(w0, k, L[k], features, features, 1, nullptr, nullptr, T0);           // resConfUnit1.conv1(relu(x1))
+      conv(w0 + 1, k, T0, features, features, 1, L[k], P, T1);                  // path + (conv2(relu(.)) + relu(x1))
+      o = T1;
+    }
+    const int u2 = k == 3 ? w0 : w0 + 2;
+    conv(u2, k, o, features, features, 1, nullptr, nullptr, T0);                // resConfUnit2.conv1(relu(o))
+    conv(u2 + 1, k, T0, features, features, 1, o, nullptr, T2);                 // conv2(relu(.)) + relu(o)
+    upsample(3 - k, static_cast<long long>(B) * features, heights[k], widths[k], 1, T2, P);
+  }
+  // output_conv: 0 (features -> 128 at twice level 1), Interpolate, then 2, ReLU, 4 and the last ReLU in the head's launch
+  {
+    int part = 0;
+    launchMidasConv(B, 2 * H1, 2 * W1, features, 128, 3, P, weights[18], biases[14], 0, 0, nullptr, 0, nullptr,
+                    midasSplitFor(features, 3, 4ll * H1 * W1, 0), fe.dMidasSplit.p, H0, s, [&] {
+                      slot[launches++] = 36 + part++;
+                      timer.mark();
+                    });
+  }
+  upsample(4, static_cast<long long>(B) * 128, 2 * H1, 2 * W1, 0, H0, Hup);
+  launchMidasHead(B, 4 * H1, 4 * W1, 128, Hup, weights[19], biases[15], weights[20], biases[16], nonNegative, out, s);
+  slot[launches++] = 43;
+  timer.mark();
+  if (kernelMs) {
+    timer.wait();
+    timer.collect();
+    std::fill(kernelMs, kernelMs + kSlots, 0.0);
     for (int i = 0; i < launches; ++i) kernelMs[slot[i]] = phaseMs[i];
   }
 }

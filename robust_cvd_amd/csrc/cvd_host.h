@@ -792,5 +792,15 @@ void raftInstanceNormDevice(cvd_handle* h, int B, int channels, int H, int W, co
 void raftEncoderDevice(cvd_handle* h, int B, int H, int W, int outputDim, int normMode, float eps, const float* images,
                        const float* const* weights, const float* const* biases, const float* const* norms, float* out,
                        hipStream_t s, double* kernelMs);
+// the decoder of MiDaS v2.1 (cvd_midas.h)
+void midasConvDevice(cvd_handle* h, int B, int H, int W, int inChannels, int outChannels, int kernelSize, const float* x,
+                     const float* weight, const float* bias, int reluIn, int relu, const float* a, int reluA, const float* b, int split,
+                     float* out, hipStream_t s);
+void midasUpsample2xDevice(cvd_handle* h, int B, int channels, int H, int W, int alignCorners, const float* x, float* out, hipStream_t s);
+void midasHeadDevice(cvd_handle* h, int B, int H, int W, int inChannels, int midChannels, const float* x, const float* weight2,
+                     const float* bias2, const float* weight4, const float* bias4, int nonNegative, float* out, hipStream_t s);
+void midasDecoderDevice(cvd_handle* h, int B, int features, const int* channels, const int* heights, const int* widths,
+                        const float* const* maps, const float* const* weights, const float* const* biases, int nonNegative, float* out,
+                        hipStream_t s, double* kernelMs);
 
 }  // namespace cvd
