@@ -26,6 +26,9 @@ typedef struct cvd_debug_options {
   int32_t tail_no_row_staging;   /* 1: the temporal levels' workgroups of k_pcg_tail read their rows of the inverse from memory behind
                                     the grid barrier (the path a launch takes when the staged rows would not fit the LDS or the device)
                                     instead of staging them in LDS in front of it; cvd_path_info reports which ran */
+  int32_t tail_closes_scalars;   /* 1: k_pcg_tail always sums the r^T z shares and finishes the PCG scalars itself (its last workgroup),
+                                    also where the next product would sum them in its prologue (the shares mode); cvd_path_info
+                                    reports which ran */
 } cvd_debug_options;
 void cvd_debug_options_default(cvd_debug_options* o);
 int32_t cvd_set_debug_options(cvd_handle* h, const cvd_debug_options* o);

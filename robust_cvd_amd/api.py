@@ -56,6 +56,7 @@ class DebugOptions(C.Structure):
         ("pcg_lockstep", C.c_int32),
         ("stall_fused_tail_once", C.c_int32),
         ("tail_no_row_staging", C.c_int32),
+        ("tail_closes_scalars", C.c_int32),
     ]
 
 
@@ -934,7 +935,7 @@ class Solver(Binding):
     def set_options(self, pcg_relative_tolerance=None, pcg_max_iterations=None, verbose=None,
                     coarse_level=None, robust_loss=None, **variants):
         """Options persist per handle: only the fields given change (robust_loss: 0 Cauchy = reference, 1 Huber).  Names of
-        cvd_debug_options (force_iterations, force_sharded_path, pcg_lockstep, stall_fused_tail_once, tail_no_row_staging: test / measurement hooks,
+        cvd_debug_options (force_iterations, force_sharded_path, pcg_lockstep, stall_fused_tail_once, tail_no_row_staging, tail_closes_scalars: test / measurement hooks,
         include/cvd_hip_debug.h) are routed to cvd_set_debug_options."""
         debug = {k: variants.pop(k) for k in list(variants) if k in dict(DebugOptions._fields_) and k != "struct_size"}
         if debug:
@@ -1828,6 +1829,8 @@ class Solver(Binding):
         self._check(self._fn("path_info")(self._h, out))
         form = {-1: "none", 0: "exact sparse factor", 1: "exact dense inverse", 2: "temporal pose level"}[out[1]]
         return {"pose_graph_level": form, "depth_grid_level": bool(out[2]), "fused_tail": bool(out[3] & 1), "tail_rows_staged": bool(out[3] & 2),
+                # (the next product sums the tail's r^T z shares; how many there were)
+                "product_sums_shares": bool(out[3] & 4), "rz_shares": out[3] >> 8,
                 "tail_disabled": bool(out[4]),
                 "taps": out[5], "work_items": out[6], "cross_blocks": bool(out[7])}
 

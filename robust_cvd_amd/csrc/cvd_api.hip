@@ -299,6 +299,7 @@ void cvd_debug_options_default(cvd_debug_options* o) {
   o->pcg_lockstep = 0;
   o->stall_fused_tail_once = 0;
   o->tail_no_row_staging = 0;
+  o->tail_closes_scalars = 0;
 }
 int32_t cvd_set_debug_options(cvd_handle* h, const cvd_debug_options* o) {
   CVD_TRY(h, {
@@ -1080,6 +1081,8 @@ int32_t cvd_path_info(cvd_handle* h, int32_t* out8) {
     out8[1] = !h->coarseOn ? -1 : (h->coarse.temporalPose ? 2 : (h->coarse.denseMode ? 1 : 0));
     out8[2] = h->temporal.on ? 1 : 0;
     out8[3] = h->lastFusedTail ? (h->tailStageRows ? 3 : 1) : 0;  // (bit 1: its temporal-level workgroups staged their rows in LDS)
+    // (bit 2: the tail left its r^T z shares to the next product -- their count from bit 8 up)
+    if (h->lastFusedTail && h->lastShares) out8[3] |= 4 | (h->lastShareCount << 8);
     out8[4] = h->tailDisabled ? 1 : 0;
     out8[5] = h->lastKD;
     out8[6] = static_cast<int32_t>(h->itemFa.size());

@@ -389,6 +389,9 @@ struct cvd_handle_t {
   std::vector<cvd_iteration_record> records;
 
   bool lastFusedTail = false, lastCross = false;  // cvd_path_info: what the last PCG solve ran
+  bool lastShares = false;                        // ... its products summed the fused tail's r^T z shares (lastShareCount of them)
+  int lastShareCount = 0;
+  int sharesF = -1, sharesN = -1;                 // frames / shares of the layout the words behind the PCG scalars (SH_RZ, SH_RR) hold
   bool tailStageRows = false;  // pcgTailScope: the fused tail's temporal-level workgroups stage their rows of the inverse in LDS
   int lastKD = 0;
   // cvd_product_launch_debug: {threads per workgroup, SPEC, KD, kind, work items, numCU} of the last launchMatvec (kind -1: none yet)
@@ -669,11 +672,22 @@ void launchDenseSpdInversePair(cvd_handle* h, const DinvRequest& a, const DinvRe
 CoarseView coarseView(cvd_handle* h, bool on, bool walk);
 void prepareMatvec(Ctx& c, const double* x);
 // tailFused: only the partial products are launched; the caller follows with launchPcgTail (finish + update in one launch)
+// sharesIteration k >= 1 (after pcgSharesScope said yes): the product of iteration k sums the r^T z shares the tail of iteration
+// k - 1 left behind and closes that iteration's scalars (k_matvec_pairs_fast<..., SHARES>)
 void launchMatvec(Ctx& c, const double* x, const double* z, const double* pOld, double* pNew, int useBeta, const double* lam,
-                  double* q, bool withCoarse = false, bool tailFused = false);
+                  double* q, bool withCoarse = false, bool tailFused = false, int sharesIteration = 0);
 bool pcgTailScope(Ctx& c, bool coarse, int nThreads, size_t& lds, int& ldsFinish, int& ldsScratch);
+// Where the fused tail may leave its shares of r^T z to the next product (layout: TailUpdate::shares); false: the tail closes.
+struct PcgShares {
+  int count = 0;        // shares of r^T z: frames, dense-level parts, temporal levels' parts
+  int levelShare0 = 0;  // first share of the temporal levels' workgroups
+  int levelWg0 = 0;     // their first workgroup of the tail's launch
+};
+bool pcgSharesScope(Ctx& c, bool coarse, PcgShares& sh);
 void launchPcgTail(Ctx& c, const double* x, const double* pOld, double* pNew, int useBeta, const double* lam, double* q,
-                   bool withCoarse, int nThreads, size_t lds, int ldsFinish, int ldsScratch, double tol2);
+                   bool withCoarse, int nThreads, size_t lds, int ldsFinish, int ldsScratch, double tol2,
+                   const PcgShares* shares = nullptr);
+void launchPcgClose(Ctx& c, int enqueued);
 void launchBlockInverseRaw(cvd_handle* h, const Layout& L, const double* dH, const double* dLam, float* dMinv, int* dFail, int variant,
                            hipStream_t onStream = nullptr);
 void launchBlockInverse(Ctx& c, hipStream_t onStream = nullptr);   // (onStream: one GPU, B <= 256 only)

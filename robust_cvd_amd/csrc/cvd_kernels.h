@@ -287,6 +287,17 @@ enum : int { S_RZ = 0, S_RZOLD = 1, S_BETA = 2, S_PQ = 3, S_ALPHA = 4, S_RR = 5,
              S_RZPART = 18,  // block-Jacobi part of r^T z while the coarse level (cvd_coarse.h) is pending
              S_NACTIVE = 19, // number of active unknowns (k_step_stats)
              S_COUNT = 20 };
+// Shares mode of the fused PCG tail (cvd_pcg.h: k_pcg_tail ends without closing r^T z; the next product sums the shares): its words
+// live BEHIND the scalars in the same allocation, so the product reaches them through the `scal` argument it has anyway.
+//   SH_MIRROR   the host's progress mirror (a pointer, written once when the buffers are made)
+//   SH_ABANDON  != 0: a tail of this solve abandoned its grid barrier -- nobody closes an iteration any more
+//   SH_RING     r^T z after the iterations of even / odd count: the workgroups of a product read the slot the launch does not write
+//   SH_RZ, SH_RR  kPcgSharesCap shares of r^T z (frames, dense-level parts, temporal levels' parts) and of r^T r (frames); the
+//               words beyond a solve's share count are zero, so that every sum runs over the whole array in one fixed order
+constexpr int kPcgSharesCap = 512;   // eight loads per lane of one wave
+constexpr int kPcgMirrorAddressSlot = 15;   // of the host's 16-double pinned mirror buffer ([0 .. 8] are the mirror): the buffer's own
+                                            // address, staged there once for the copy into SH_MIRROR
+enum : int { SH_MIRROR = 24, SH_ABANDON = 32, SH_RING = 34, SH_RZ = 64, SH_RR = SH_RZ + kPcgSharesCap, SH_END = SH_RR + kPcgSharesCap };
 
 // Sum of a short global array (F per-frame partials, L2-resident) by every workgroup that needs the scalar:
 // cheaper than a separate 1-block reduction kernel + its launch boundary. `red` = 4 doubles of LDS.
@@ -846,6 +857,43 @@ __device__ __forceinline__ void fastRows(const Layout& L, double iz, double u, d
   m12 = wiz * vv;
 }
 
+// One wave's sum of the kPcgSharesCap shares in a FIXED order (lane l holds words l, l + 64, ..., l + 448): the lane's eight in a
+// tree, then waveSum.  Every workgroup of the product and k_pcg_close get the same bits.
+__device__ __forceinline__ double pcgSharesSum(const double (&w)[8]) {
+  return waveSum(((w[0] + w[1]) + (w[2] + w[3])) + ((w[4] + w[5]) + (w[6] + w[7])));
+}
+// The bookkeeping of pcgFinishScalars for an iteration whose r^T z was summed from the shares (one thread: workgroup 0 of the next
+// product, or k_pcg_close behind the last tail): `applied` iterations are through, rzs is the new r^T z, old the one before.
+__device__ __forceinline__ void pcgCloseFromShares(double* scal, int applied, double rzs, double old, double beta, double done,
+                                                   double* hostMirror) {
+  scal[S_RZOLD] = old;
+  scal[S_BETA] = beta;
+  scal[S_ITERS] = static_cast<double>(applied);
+  scal[S_DONE] = done;
+  scal[S_RZ] = rzs;
+  scal[SH_RING + (applied & 1)] = rzs;
+  if (hostMirror != nullptr)
+    __hip_atomic_store(hostMirror + 1 + (applied & 7), 4.0 * (static_cast<double>(applied) + 1.0) + done, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// The product's first wave behind the sum: beta and the stop flag (1: converged, NaN or an abandoned barrier -- the launch writes
+// nothing) of iteration `applied`; ctl = lane 0 .. 4: r^T z before the sum, S_TARGET, SH_ABANDON, SH_MIRROR, S_DONE.  Thread 0 of
+// workgroup 0 does the bookkeeping -- unless the PCG was done before the launch (later iterations are no-ops) or a grid barrier
+// was abandoned (the mirror stalls, the host falls back: nobody advances S_ITERS).
+__device__ __forceinline__ void pcgSharesClose(const double* scal, int applied, double rzs, double ctl, double& beta, double& stop) {
+  const double old = readLane(ctl, 0), target = readLane(ctl, 1), abandon = readLane(ctl, 2), mirror = readLane(ctl, 3);
+  const double sDone = readLane(ctl, 4);
+  double done = sDone;
+  if (done == 0.0) done = !(rzs == rzs) ? 2.0 : (rzs <= target ? 1.0 : 0.0);
+  beta = (old != 0.0) ? rzs / old : 0.0;
+  stop = (done != 0.0 || abandon != 0.0) ? 1.0 : 0.0;
+  if (__builtin_expect(blockIdx.x == 0 && threadIdx.x == 0 && sDone == 0.0 && abandon == 0.0, 0))
+    // (`scal` is const in the kernel's signature, which all forms share; the array is the handle's own and writable, the pointer is
+    // derived from the restrict-qualified argument itself, and every read of the launch's first wave lies in front of these stores)
+    pcgCloseFromShares(const_cast<double*>(scal), applied, rzs, old, beta, done,
+                       reinterpret_cast<double*>(static_cast<unsigned long long>(__double_as_longlong(mirror))));
+}
+
 #ifdef CVD_MV_PROFILE  // tools/mv_profile.py: wall-clock (100 MHz) stamps of the hot product's workgroups
 __device__ unsigned long long g_mvProf[4096 * 8];
 #define MV_STAMP(slot) do { if ((threadIdx.x & 63) == 0) g_mvProf[(blockIdx.x & 4095) * 8 + (slot)] = wall_clock64(); } while (0)
@@ -866,7 +914,13 @@ constexpr int kRedStride = 4 * 33 + 1;     // 128 columns (lane pairs pre-summed
 #ifndef CVD_MV_EARLY
 #define CVD_MV_EARLY 1   // 1: direction 0's first table record is requested at the top of the kernel
 #endif
-template <int KD, int NT, int SPEC = 0, bool DENSE = false>
+// SHARES (list mode; chosen per launch by launchMatvec): the tail of the previous iteration left its shares of r^T z unsummed
+// (SH_RZ above) and `useBeta` carries the iteration's index k >= 1.  The first wave of every workgroup requests the shares in the
+// prologue's load phase and sums them in a fixed order, so all workgroups form bit-identical beta = r^T z / (the sum before: SH_RING,
+// S_RZ0 for k = 1) and the same convergence flag; workgroup 0 writes the scalars and the host mirror as pcgFinishScalars would have.
+// S_DONE may be read stale or fresh by the others: a flag that was set before this launch returns everybody (the writer then writes
+// nothing), and a fresh one is the value the reader computes itself.
+template <int KD, int NT, int SPEC = 0, bool DENSE = false, bool SHARES = false>
 inline __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SPEC ? ((KD <= 4 && !DENSE) ? CVD_MV_WAVES : 3) : 2))) void k_matvec_pairs_fast(Layout L, Table T, Items it, const double* __restrict__ x,
                                                            const FrameConst* __restrict__ fc,
                                                            const double* __restrict__ mask,
@@ -875,7 +929,8 @@ inline __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SPEC 
                                                            double* __restrict__ qPart, CoarseView V) {
   // (PCG already converged: iterations enqueued ahead return -- tested after the prologue's loads have been issued, so
   // that the flag does not cost a dependent global round trip of its own in every working launch)
-  const double sDone = scal[S_DONE];
+  double sDone = 0.0;
+  if constexpr (!SHARES) sDone = scal[S_DONE];   // (SHARES: one of the first wave's words below)
   extern __shared__ __attribute__((aligned(16))) double sm[];
   constexpr int NV = KD == 1 ? kRedVals : 11;  // the depth-block sums exist only with one tap per side
   const int B = L.B;
@@ -904,17 +959,45 @@ inline __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SPEC 
   const int fa = recp->fa, fb = recp->fb;
   const int slotA = recp->slotA, slotB = recp->slotB;
   const long long cbD[2] = {recp->b0, recp->b1}, ceD[2] = {recp->e0, recp->e1};
-  const double beta = useBeta ? scal[S_BETA] : 0.0;
+  double beta = 0.0;
+  if constexpr (!SHARES) beta = useBeta ? scal[S_BETA] : 0.0;   // (SHARES: formed behind the first barrier)
   // The frame constants (R, t, fy, J_l of both frames) are wave-uniform READ-ONLY global data at an address that depends on
   // blockIdx only: the compiler fetches them with scalar loads straight into SGPRs (round 5; rounds 2-4 staged the two structs in
   // LDS and moved 26 doubles per direction into SGPRs through v_readfirstlane: ~200 instructions per wave and direction).
   // (Staged in LDS instead, same box, 4140-pair set: 41.4 / 41.9 us against 39.6; without the early request below 40.8.)
   const FrameConst* __restrict__ fcF[2] = {fc + fa, fc + fb};
   // The first table record of direction 0 is requested before anything else: it is back when the prologue's barriers are.
-  // (not the bicubic variant: six more live registers through the prologue spill at its budget)
-  constexpr bool kEarlyPrime = KD <= 4 && CVD_MV_EARLY;
+  // (not the bicubic variant: six more live registers through the prologue spill at its budget; nor the one-wave workgroups of the
+  // shares mode, for the same reason)
+  constexpr bool kEarlyPrime = KD <= 4 && CVD_MV_EARLY && !(SHARES && NT == 64);
   RecordStream<DENSE> rs;   // (list mode: the next trip's table record is in flight during this trip's arithmetic)
   if constexpr (kEarlyPrime) rs.primeClamped(T, cbD[0], tid, static_cast<int>(ceD[0] - cbD[0]));
+  // SHARES: the first wave's eight shares per lane (the whole array: the words beyond the solve's share count are zero), requested
+  // in FRONT of the phase's other loads -- the waits those need cover them, the sum behind the phase needs none of its own -- and,
+  // one word per lane 0 .. 4 (the lanes beyond repeat the last), what the closing needs beside them: r^T z before the sum (the ring slot this launch does not write;
+  // the first iteration's is the first residual's), S_TARGET, the abandon word, the mirror's address and S_DONE.  All of it stays in the
+  // first wave's vector registers: the loop's scalar registers are what this kernel is short of.  One-wave workgroups (the
+  // deterministic build) close at once, a round trip of their own in front of everything else: sixteen registers held across
+  // the phase do not fit beside their four elements of eight vectors per thread.
+  double vsh[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double vctl = 0.0, shBeta = 0.0, shStop = 0.0;
+  if constexpr (SHARES) {
+    if (tid < 64) {
+      const double* __restrict__ sh = scal + SH_RZ + tid;
+#pragma unroll
+      for (int u = 0; u < 8; ++u) vsh[u] = sh[u * 64];
+      const int prevAt = useBeta == 1 ? static_cast<int>(S_RZ0) : SH_RING + ((useBeta - 1) & 1);
+      vctl = scal[tid == 0 ? prevAt : (tid == 1 ? static_cast<int>(S_TARGET) : (tid == 2 ? static_cast<int>(SH_ABANDON) : (tid == 3 ? static_cast<int>(SH_MIRROR) : static_cast<int>(S_DONE))))];
+      if constexpr (NT == 64) {
+        pcgSharesClose(scal, useBeta, pcgSharesSum(vsh), vctl, shBeta, shStop);
+        if (tid == 0) {
+          red[0] = shBeta;
+          red[1] = shStop;
+        }
+        __builtin_amdgcn_sched_barrier(0);   // (the phase's loads stay behind: the seventeen registers are free again)
+      }
+    }
+  }
   // Prologue in ONE global round trip (the workgroup lives ~5 us, a dependent load costs ~1 us of it): every thread
   // issues its loads of x / z / p_old / mask for both frames, the coarse correction c_f (see CoarseView), the third level's
   // coefficients and taps and the epilogue's frame constants in the same phase, and the search direction is formed after the
@@ -1007,8 +1090,24 @@ inline __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(SPEC 
   }
   if constexpr (kUsePriv)
     for (int i = tid; i < kPriv * 2 * B; i += NT) qpriv[i] = 0.0;
+  if constexpr (SHARES) {
+    if (tid < 64) {  // beta and the stop flag for the workgroup through LDS (red is the reduction's: free until the loop is through)
+      if constexpr (NT > 64) {
+        pcgSharesClose(scal, useBeta, pcgSharesSum(vsh), vctl, shBeta, shStop);
+        if (tid == 0) {
+          red[0] = shBeta;
+          red[1] = shStop;
+        }
+      }
+    }
+  }
   __syncthreads();
-  if (sDone != 0.0) return;  // uniform; nothing has been written to global memory yet
+  if constexpr (SHARES) {
+    beta = red[0];
+    if (uniformValue(red[1]) != 0.0) return;  // uniform; only workgroup 0 has written (the scalars)
+  } else {
+    if (sDone != 0.0) return;  // uniform; nothing has been written to global memory yet
+  }
 #pragma unroll
   for (int e = 0; e < EPT; ++e) {
     const int i = tid + e * NT;

@@ -67,9 +67,27 @@ void prepareMatvec(Ctx& c, const double* x) {
   HIP_CHECK(hipGetLastError());
 }
 
+// The product the PCG loop launches for this problem: the list-mode fast kernel in its Cauchy compile-time variant (SPEC 1),
+// four depth taps per side (the bilinear grids), no triplet kernel behind it -- the only product that sums the fused tail's r^T z
+// shares (k_matvec_triplets, k_cross_matvec, the dense-mode and the generic kernels read beta from the scalars; the Global level's
+// KD = 1 instantiation pays for the shares prologue with scalar-register restores in its loop's set-up and the bicubic one has no
+// registers to spare, so neither is built).  Mirrors launchMatvec.
+static bool productSumsShares(const Ctx& c) {
+  const cvd_handle* h = c.h;
+  if (c.cross || !c.L.includeStatic || c.nItems <= 0 || h->dense) return false;
+  if (h->forceGeneric || c.KS != 0 || !fastLoss(c.L)) return false;
+  if (!(c.L.N == 1 && c.L.lossType == CVD_STATIC_REPRO_DISPARITY)) return false;   // (SPEC 0: runtime loss branches)
+  // (SPEC 2, the Huber variant: its shares forms miss the budget -- <4,256,2> spills a vector register (8 B of scratch), <4,128,2>
+  // restores more scalar registers in its loop segment than its twin -- and are not built)
+  if (c.L.robustKind != 0) return false;
+  if (c.KD != 4) return false;
+  return !(c.trip && c.TT.nGroups > 0);
+}
+
 void launchMatvec(Ctx& c, const double* x, const double* z, const double* pOld, double* pNew, int useBeta,
-                         const double* lam, double* q, bool withCoarse, bool tailFused) {
+                         const double* lam, double* q, bool withCoarse, bool tailFused, int sharesIteration) {
   cvd_handle* h = c.h;
+  if (sharesIteration > 0 && !productSumsShares(c)) throw std::runtime_error("launchMatvec: this product cannot sum the tail's shares");
   hipStream_t s = h->stream;
   const CoarseView cF = coarseView(h, withCoarse, coarseFusedConsumers());  // z + Z c: the coarse part of the preconditioned residual
   const size_t B = c.L.B;
@@ -126,6 +144,19 @@ void launchMatvec(Ctx& c, const double* x, const double* z, const double* pOld, 
 #define CVD_LAUNCH_PAIRS_FAST_S(NTV, SPECV)                                                                              \
       CVD_DISPATCH_KD(c.KD, {                                                                                            \
         recordLaunch(NTV, SPECV, KD, 1, c.nItems);                                                                       \
+        if constexpr (SPECV == 1 && KD == 4) {                                                                           \
+          if (sharesIteration > 0) { /* (the shares instantiation: `useBeta` carries the iteration's index) */          \
+            allowLds((k_matvec_pairs_fast<KD, NTV, SPECV, false, true>), ldsFast);                                       \
+            if (evStart)                                                                                                 \
+              hipExtLaunchKernelGGL((k_matvec_pairs_fast<KD, NTV, SPECV, false, true>), dim3(c.nItems), dim3(NTV), ldsFast, s, \
+                                    evStart, evStop, 0, c.L, c.T, c.it, x, fcp, maskp, z, pOld, scalp, sharesIteration,  \
+                                    h->dQPart.p, cF);                                                                    \
+            else                                                                                                         \
+              hipLaunchKernelGGL((k_matvec_pairs_fast<KD, NTV, SPECV, false, true>), dim3(c.nItems), dim3(NTV), ldsFast, s, c.L, \
+                                 c.T, c.it, x, fcp, maskp, z, pOld, scalp, sharesIteration, h->dQPart.p, cF);             \
+            break;                                                                                                       \
+          }                                                                                                              \
+        }                                                                                                                \
         allowLds((k_matvec_pairs_fast<KD, NTV, SPECV>), ldsFast);                                                        \
         if (evStart)                                                                                                     \
           hipExtLaunchKernelGGL((k_matvec_pairs_fast<KD, NTV, SPECV>), dim3(c.nItems), dim3(NTV), ldsFast, s, evStart, evStop, 0, \
@@ -304,8 +335,35 @@ bool pcgTailScope(Ctx& c, bool coarse, int nThreads, size_t& lds, int& ldsFinish
   return resident(lds);
 }
 
+// Shares mode of the fused tail (cvd_pcg.h): the tail ends when its slowest workgroup has stored its share of r^T z, and the next
+// product sums the shares in its prologue.  In scope when the solve runs the fused tail (the caller has asked pcgTailScope), the
+// product is the one that can sum (productSumsShares), the host checks the mirror only for iterations a later product closes (not in
+// lockstep, not with the per-iteration trace), the test option does not force the closing tail, and the shares fit the cap.
+// Share layout: the frames' r^T z, the dense level's parts (its workgroups' rows, then the frame workgroups' rows), the depth-grid
+// level's parts, the temporal pose level's parts.
+bool pcgSharesScope(Ctx& c, bool coarse, PcgShares& sh) {
+  cvd_handle* h = c.h;
+  if (h->dbg.tail_closes_scalars != 0 || h->dbg.pcg_lockstep != 0 || h->opt.verbose >= 2 || !productSumsShares(c)) return false;
+  const int F = c.L.F;
+  const int split = denseRowSplit(h);
+  const TlStep ts = temporalStep(h);
+  const bool poseT = coarse && h->coarse.temporalPose;
+  const bool dense = coarse && !poseT;
+  const int nDenseWg = (dense && split > 0) ? (F + kDenseFramesPerGroup - 1) / kDenseFramesPerGroup : 0;
+  sh.levelShare0 = F + ((dense && split > 0) ? F : 0) + ((dense && split < kCB) ? F : 0);
+  sh.levelWg0 = F + nDenseWg;
+  sh.count = sh.levelShare0 + (ts.Ainv != nullptr ? ts.S * ts.parts : 0) + (poseT ? kCB * tlParts(h->coarse.ptNn) : 0);
+  return sh.count <= kPcgSharesCap;
+}
+
+void launchPcgClose(Ctx& c, int enqueued) {
+  cvd_handle* h = c.h;
+  hipLaunchKernelGGL(k_pcg_close, dim3(1), dim3(64), 0, h->stream, h->dScal.p, enqueued, h->hPcg);
+  HIP_CHECK(hipGetLastError());
+}
+
 void launchPcgTail(Ctx& c, const double* x, const double* pOld, double* pNew, int useBeta, const double* lam, double* q,
-                   bool withCoarse, int nThreads, size_t lds, int ldsFinish, int ldsScratch, double tol2) {
+                   bool withCoarse, int nThreads, size_t lds, int ldsFinish, int ldsScratch, double tol2, const PcgShares* shares) {
   cvd_handle* h = c.h;
   hipStream_t s = h->stream;
   const int F = c.L.F;
@@ -314,16 +372,23 @@ void launchPcgTail(Ctx& c, const double* x, const double* pOld, double* pNew, in
   const int finishDoubles = 3 * static_cast<int>(c.L.B) + 8 + kCB + (nThreads / 256 - 1) * 256 + kTlMaxS;  // (pcgTailScope)
   const TlStep ts = temporalStep(h);
   const bool poseT = withCoarse && h->coarse.temporalPose;
-  const DenseStep ds = (withCoarse && !poseT) ? DenseStep{h->coarse.denseInv.p, h->coarse.qc.p, h->coarse.rc.p, h->coarse.c.p, h->coarse.dotPart.p,
+  // (shares mode: every share of r^T z goes into the one array behind the PCG scalars, in pcgSharesScope's layout)
+  double* sharesRz = shares != nullptr ? h->dScal.p + SH_RZ : nullptr;
+  double* densePart = shares != nullptr ? sharesRz + F : h->coarse.dotPart.p;
+  double* densePart2 = shares != nullptr ? sharesRz + F + (split > 0 ? F : 0) : h->coarse.dotPart.p + F;
+  const DenseStep ds = (withCoarse && !poseT) ? DenseStep{h->coarse.denseInv.p, h->coarse.qc.p, h->coarse.rc.p, h->coarse.c.p, densePart,
                                                h->coarse.modeActive.p, h->coarse.fail.p, split, ldsFinish + finishDoubles,
-                                               h->coarse.dotPart.p + F}
+                                               densePart2}
                                   : DenseStep{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, kCB, 0, nullptr};
   double* fd = h->dFdot.p;
-  const TailUpdate U{h->dMinv.p, h->dDx.p, h->dR.p, h->dZ.p, fd + F, fd + 2 * F, tol2, h->coarse.modeActive.p, h->hPcg,
-                     h->dCounters.p + 1, h->dTailBar.p, h->dFdot.p + 4 * static_cast<size_t>(F) + 32, ldsFinish, ldsScratch, ds,
+  const TailUpdate U{h->dMinv.p, h->dDx.p, h->dR.p, h->dZ.p, shares != nullptr ? sharesRz : fd + F,
+                     shares != nullptr ? h->dScal.p + SH_RR : fd + 2 * F, tol2, h->coarse.modeActive.p, h->hPcg,
+                     shares != nullptr ? static_cast<unsigned int*>(nullptr) : h->dCounters.p + 1, h->dTailBar.p,
+                     h->dFdot.p + 4 * static_cast<size_t>(F) + 32, ldsFinish, ldsScratch, ds,
                      ts.Ainv != nullptr ? temporalStepDev(h) : static_cast<const TlStep*>(nullptr),
                      poseT ? poseTemporalStepDev(h) : static_cast<const TlStep*>(nullptr),
-                     (c.cross && h->xDiagRows) ? 1 : 0, h->tailStageRows ? 1 : 0};
+                     (c.cross && h->xDiagRows) ? 1 : 0, h->tailStageRows ? 1 : 0, sharesRz,
+                     shares != nullptr ? shares->levelShare0 : 0, shares != nullptr ? shares->levelWg0 : 0};
   const int grid = F + (withCoarse && !poseT && split > 0 ? (F + kDenseFramesPerGroup - 1) / kDenseFramesPerGroup : 0) +
                    (ts.Ainv != nullptr ? ts.S * ts.parts : 0) + (poseT ? kCB * tlParts(h->coarse.ptNn) : 0);
   const int slot = h->tBegin(KC_CG_UPDATE);  // (timed under the update class: the finish class stays empty on this path)

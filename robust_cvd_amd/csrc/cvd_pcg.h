@@ -429,6 +429,10 @@ struct NoMid {  // (the kernels that are not k_pcg_tail: nothing happens between
   __device__ bool second(double&) { return true; }
   __device__ unsigned int generation() { return 0u; }
   __device__ bool stageRows() { return false; }
+  // (k_pcg_tail's shares mode, below: the launch closes r^T z itself / a level's share goes where its descriptor says / no flag)
+  __device__ bool closes() { return true; }
+  __device__ double* levelShare(double* fromDescriptor) { return fromDescriptor; }
+  __device__ void gaveUp() {}
 };
 // LDS doubles of a temporal level's workgroup in k_pcg_tail that stages its rows of the inverse in front of the grid barrier
 // (tlLevelRows): the kTlSpan + 1 rows of NT doubles behind its tlRowsLds(NT) (host and device agree on the layout)
@@ -541,7 +545,10 @@ __device__ __forceinline__ bool tlLevelRows(const TlStep* __restrict__ tsp, int 
         qT[e] = __hiloint2double(static_cast<int>(r4.z), static_cast<int>(r4.y));
       }
       __syncthreads();
-      if (*bad) return false;
+      if (*bad) {
+        mid.gaveUp();
+        return false;
+      }
     }
   }
   if (direct) {
@@ -620,7 +627,7 @@ __device__ __forceinline__ bool tlLevelRows(const TlStep* __restrict__ tsp, int 
   if (tid == 0) {
     double d = 0.0;
     for (int k = 0; k < nA; ++k) d += red[k];
-    publishPartial(ts.dotPart + wg, d);
+    storeMaybePublished(mid.levelShare(ts.dotPart + wg), d, mid.closes());
   }
   if constexpr (FUSED) TAIL_STAMP(7);
   return true;
@@ -662,6 +669,11 @@ __device__ __forceinline__ void cgUpdateBody(const Layout& L, int init, const do
   const bool fusedY = !init && cs.Wb != nullptr;
   const bool fusedDense = !init && ds.Ainv != nullptr;  // (the grid then has F extra workgroups)
   const int nWaves = nThreads >> 6;
+  // closes: the last workgroup to leave sums the shares of r^T z and finishes the PCG scalars (below).  false (k_pcg_tail's shares
+  // mode, chosen per launch): the shares are stored plainly -- nobody in the launch reads them -- into ONE array the caller laid out
+  // (fdotRZ / fdotRR, ds.dotPart, ds.dotPart2 and mid.levelShare point into it), no ticket is drawn, and the next product's prologue
+  // (k_matvec_pairs_fast<..., SHARES>) or k_pcg_close sums them: the launch ends when its slowest workgroup has stored its share.
+  const bool closes = mid.closes();
   // Logical workgroup index: [0, nF) the frames, then the levels' workgroups.  A launch of its own (not the fused tail, whose
   // workgroups are all resident) dispatches the LEVELS' workgroups first: theirs is the longest dependent chain of the launch, and
   // behind a thousand frame workgroups -- four rounds of the device at configs[4] -- it started when everything else was done.
@@ -749,7 +761,7 @@ __device__ __forceinline__ void cgUpdateBody(const Layout& L, int init, const do
       t += __shfl_xor(t, 1, 64);
       t += __shfl_xor(t, 2, 64);
       t += __shfl_xor(t, 4, 64);
-      if (tid == 0) publishPartial(dotSlot, t);
+      if (tid == 0) storeMaybePublished(dotSlot, t, closes);
     }
     __syncthreads();  // (psum is reused)
   };
@@ -957,8 +969,8 @@ __device__ __forceinline__ void cgUpdateBody(const Layout& L, int init, const do
   if (tid == 0) {
     double a = 0.0, b = 0.0;
     for (int w = 0; w < nWaves; ++w) { a += red[w]; b += red[16 + w]; }
-    publishPartial(fdotRZ + f, a);
-    publishPartial(fdotRR + f, b);
+    storeMaybePublished(fdotRZ + f, a, closes);
+    storeMaybePublished(fdotRR + f, b, closes);
   }
   if (fusedY) {
     // y_f <- y_f - alpha (W Z^T q)_f (ypart is complete: two barriers since it was written); |y_f|^2 is this
@@ -993,6 +1005,7 @@ __device__ __forceinline__ void cgUpdateBody(const Layout& L, int init, const do
     denseRows(f, ds.rowSplit, kCB - ds.rowSplit, qcs, psum, on0, w, false, ds.dotPart2 + f);
   }
   }  // frame workgroups
+  if (!closes) return;
   // last workgroup: rz_new = sum, beta = rz_new / rz_old (device-side scalars, no host round trip)
   if (lastBlockArrivesLite(counter, gridDim.x, reinterpret_cast<int*>(red + 40))) {
     double a = 0.0, b = 0.0, cY = 0.0;
@@ -1210,6 +1223,11 @@ struct TailUpdate {
   int diagInProduct;       // explicit cross blocks: H_ff p_f is one of the frame's partial rows (k_cross_matvec), not the finish half's work
   int stageRows;           // 1: the temporal levels' workgroups copy their rows of the inverse to LDS in front of the grid barrier
                            // (tlStagedLds doubles each; 0: the launch would not fit or not be co-resident with them -- rows from memory)
+  // shares mode (cgUpdateBody: closes = false): the share array (SH_RZ behind the PCG scalars; fdotRZ / fdotRR / ds.dotPart /
+  // ds.dotPart2 point into it, `counter` is not used), nullptr: the launch closes r^T z itself.  The temporal levels' workgroups --
+  // blockIdx levelWg0 onwards, the depth-grid level's parts, then the temporal pose level's -- store at levelShare0 onwards.
+  double* shares;
+  int levelShare0, levelWg0;
 };
 
 template <int KD>
@@ -1258,7 +1276,12 @@ inline __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6))
   auto second = [&](double& alpha) -> bool {
     double pq;
     TAIL_STAMP(2);
-    if (!tailWait(U.gridBar, sm + U.ldsScratch, pq)) return false;
+    if (!tailWait(U.gridBar, sm + U.ldsScratch, pq)) {
+      // (shares mode: the product that would close this iteration must not -- the mirror stalls and the host falls back, as it
+      // does when the parent's closing never gets its last ticket)
+      if (U.shares != nullptr && threadIdx.x == 0) publishPartial(scal + SH_ABANDON, 1.0);
+      return false;
+    }
     TAIL_STAMP(3);
     alpha = rzOld / pq;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -1277,10 +1300,45 @@ inline __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6))
     __device__ unsigned int generation() { return *reinterpret_cast<unsigned int*>(scratch + 17); }
     bool stage;
     __device__ bool stageRows() { return stage; }
-  } mid{first, second, sm + U.ldsScratch, U.stageRows != 0};
+    double* shares;
+    double* abandonWord;
+    int levelShare0, levelWg0;
+    __device__ bool closes() { return shares == nullptr; }
+    __device__ double* levelShare(double* fromDescriptor) {
+      return shares != nullptr ? shares + levelShare0 + (static_cast<int>(blockIdx.x) - levelWg0) : fromDescriptor;
+    }
+    __device__ void gaveUp() {  // (a level's node sums timed out: as an abandoned grid barrier)
+      if (shares != nullptr && threadIdx.x == 0) publishPartial(abandonWord, 1.0);
+    }
+  } mid{first, second, sm + U.ldsScratch, U.stageRows != 0, U.shares, scal + SH_ABANDON, U.levelShare0, U.levelWg0};
   cgUpdateBody<true>(L, 0, nullptr, U.minv, nullptr, nullptr, scal, U.counter, U.dx, U.r, U.z, U.fdotRZ, U.fdotRR, U.tol2, nullptr,
                      U.modeActive, U.hostMirror, csOff, U.ds, nullptr, sm, mid, 0, L.F, nullptr, U.ts, U.tp);
   TAIL_STAMP(4);
+}
+
+// Behind the last enqueued tail of a shares-mode solve (one wave): nothing follows that would sum its shares.  Sums them in the
+// product's order (pcgSharesSum), r^T r too, and finishes the scalars as the product of iteration `enqueued` would have -- unless
+// the PCG is done (the product that found out has written everything; iterations behind it were no-ops), a grid barrier was
+// abandoned (nobody closes: the host falls back) or the iteration is closed already (S_ITERS): idempotent in all three.
+inline __global__ __launch_bounds__(64) void k_pcg_close(double* __restrict__ scal, int enqueued, double* __restrict__ hostMirror) {
+  const int lane = threadIdx.x;
+  double wz[8], wr[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    wz[u] = scal[SH_RZ + lane + u * 64];
+    wr[u] = scal[SH_RR + lane + u * 64];
+  }
+  const double done0 = scal[S_DONE], abandon = scal[SH_ABANDON], old = scal[S_RZ], target = scal[S_TARGET];
+  const int applied = static_cast<int>(scal[S_ITERS]);
+  const double rz = pcgSharesSum(wz), rr = pcgSharesSum(wr);
+  if (lane != 0 || abandon != 0.0) return;
+  if (done0 == 0.0 && applied == enqueued - 1) {
+    const double done = !(rz == rz) ? 2.0 : (rz <= target ? 1.0 : 0.0);
+    pcgCloseFromShares(scal, enqueued, rz, old, (old != 0.0) ? rz / old : 0.0, done, hostMirror);
+    scal[S_RR] = rr;
+  } else if (applied >= 1) {
+    scal[S_RR] = rr;  // (r^T r of the last iteration that was applied: the products do not sum it)
+  }
 }
 
 // xcand = x + dx with the lower bound 0 on theta_k[0] when requested (ParameterBlock::Plus projection).

@@ -1268,7 +1268,8 @@ void ensureBuffers(Ctx& c) {
   h->dCostItem.ensure(std::max(1, c.nItems));
   h->dCostFrame.ensure(c.L.F);
   h->dFocal.ensure(static_cast<size_t>(c.L.F) * 2);
-  h->dScal.ensure(S_COUNT);
+  const bool newScal = h->dScal.p == nullptr;
+  h->dScal.ensure(SH_END);  // (the PCG scalars and, behind them, the words of the fused tail's shares mode)
   h->dFc.ensure(c.L.F);
   h->dFail.ensure(1);
   if (!h->dCounters.p) {
@@ -1279,6 +1280,14 @@ void ensureBuffers(Ctx& c) {
   if (!h->hPcg) {
     HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h->hPcg), 16 * sizeof(double)));
     for (auto& e : h->pcgEvent) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  if (newScal) {
+    // shares mode: zero shares, no abandoned barrier, and the mirror's address where the closing product finds it (SH_MIRROR; it
+    // travels through the pinned buffer itself: kPcgMirrorAddressSlot is not one of the mirror's)
+    HIP_CHECK(hipMemsetAsync(h->dScal.p, 0, SH_END * sizeof(double), h->stream));
+    std::memcpy(h->hPcg + kPcgMirrorAddressSlot, &h->hPcg, sizeof(double*));
+    HIP_CHECK(hipMemcpyAsync(h->dScal.p + SH_MIRROR, h->hPcg + kPcgMirrorAddressSlot, sizeof(double), hipMemcpyHostToDevice, h->stream));
+    h->sharesF = h->sharesN = -1;
   }
 }
 // Median of every frame's source depth (reference lib/PoseOptimizer.cpp:1363-1375: std::nth_element at size / 2), the

@@ -38,6 +38,9 @@ int runPcg(Ctx& c, const double* x, const std::function<void()>& tail) {
     cvd_handle* h = c.h;
     HIP_CHECK(hipStreamSynchronize(h->stream));
     HIP_CHECK(hipMemsetAsync(h->dCounters.p, 0, 8 * sizeof(unsigned int), h->stream));
+    // (the shares mode's words behind the scalars: the abandon flag, the ring, the shares -- the mirror's address in front stays)
+    HIP_CHECK(hipMemsetAsync(h->dScal.p + SH_ABANDON, 0, (SH_END - SH_ABANDON) * sizeof(double), h->stream));
+    h->sharesF = h->sharesN = -1;
     if (h->temporal.counter.p) HIP_CHECK(hipMemsetAsync(h->temporal.counter.p, 0, 4 * sizeof(unsigned int), h->stream));
     if (h->dTailBar.p)
       HIP_CHECK(hipMemsetAsync(h->dTailBar.p, 0, static_cast<size_t>(kTailBarStride) * (1 + kTailBarCopies) * sizeof(unsigned int), h->stream));
@@ -147,6 +150,18 @@ static int runPcgAttempt(Ctx& c, const double* x, const std::function<void()>& t
     // (the temporal level's node-sum records carry the barrier's generation, which restarts with its words)
     if (tsOn.rec != nullptr) HIP_CHECK(hipMemsetAsync(tsOn.rec, 0, 2 * static_cast<size_t>(tsOn.NT) * sizeof(double), s));
   }
+  // ... and whether that tail leaves the sum of its r^T z shares to the next product (pcgSharesScope)
+  PcgShares sharesLayout;
+  const bool shares = fusedTail && pcgSharesScope(c, coarse, sharesLayout);
+  h->lastShares = shares;
+  h->lastShareCount = shares ? sharesLayout.count : 0;
+  if (shares && (h->sharesF != F || h->sharesN != sharesLayout.count)) {
+    // the sums run over the whole arrays: the words beyond this solve's shares must be zero (a solve with the same layout
+    // overwrites every word the last one wrote)
+    HIP_CHECK(hipMemsetAsync(h->dScal.p + SH_RZ, 0, 2 * static_cast<size_t>(kPcgSharesCap) * sizeof(double), s));
+    h->sharesF = F;
+    h->sharesN = sharesLayout.count;
+  }
   const bool ownerMode = ownerShardedUpdate(h, coarse);
   const int maxIt = std::max(1, c.h->opt.pcg_max_iterations);
   // Convergence is decided on the device (S_DONE, set by the last workgroup of k_cg_update); how far the host runs ahead of it
@@ -159,8 +174,10 @@ static int runPcgAttempt(Ctx& c, const double* x, const std::function<void()>& t
   auto enqueueIteration = [&](int it, int useBeta) {
     h->curPcgIter = it;
     if (fusedTail) {
-      launchMatvec(c, x, h->dZ.p, pOld, pNew, useBeta, h->dLam.p, h->dQ.p, coarse, true);
-      launchPcgTail(c, x, pOld, pNew, useBeta, h->dLam.p, h->dQ.p, coarse, nThreads, ldsTail, ldsFinish, ldsScratch, tol2);
+      // (shares mode: the product of iteration `it` >= 1 closes iteration it - 1; the first one has nothing to close)
+      launchMatvec(c, x, h->dZ.p, pOld, pNew, useBeta, h->dLam.p, h->dQ.p, coarse, true, shares ? it : 0);
+      launchPcgTail(c, x, pOld, pNew, useBeta, h->dLam.p, h->dQ.p, coarse, nThreads, ldsTail, ldsFinish, ldsScratch, tol2,
+                    shares ? &sharesLayout : nullptr);
       std::swap(pOld, pNew);
       return;
     }
@@ -245,6 +262,9 @@ static int runPcgAttempt(Ctx& c, const double* x, const std::function<void()>& t
     }
   }
   h->curPcgIter = -1;
+  // shares mode: no product follows the last enqueued tail -- one workgroup sums its shares and finishes the scalars (a no-op when
+  // the PCG is done, a barrier was abandoned or the iteration is closed)
+  if (shares && enq > 0) launchPcgClose(c, enq);
   if (ownerMode) {
     // the step and the residual of the frames live on their owners: everybody needs both (step statistics, candidate point)
     const int ct = h->tBegin(KC_COMM_PRODUCT);

@@ -2,9 +2,11 @@
 """Development aid (GPU): where the workgroups of k_pcg_tail (finish + update of a PCG iteration in one launch) spend their life.
 Library variant with wall-clock stamps (100 MHz):
     python -c "from robust_cvd_amd import build; build.build_variant('tailprof', ['CVD_TAIL_PROFILE'], ['cvd_matvec'])"
-then  python tools/tail_profile.py [pairs_level [variant [nostage]]]
+then  python tools/tail_profile.py [pairs_level [variant [nostage | closing]]]
 (variant: another stamped library lib/libcvd_hip_<variant>.so, e.g. of a tree with one step taken out; nostage: the levels' rows
-from memory behind the barrier, cvd_debug_options::tail_no_row_staging)"""
+from memory behind the barrier, cvd_debug_options::tail_no_row_staging; closing: the tail sums its r^T z shares and finishes the
+scalars itself, cvd_debug_options::tail_closes_scalars -- the default leaves them to the next product and the launch ends with its
+slowest workgroup's share)"""
 import ctypes as C
 import os
 import sys
@@ -22,9 +24,13 @@ v = synth.make_video(300, 384, 224, seed=bench.SEED, extra_offsets=level)
 s = api.Solver(0)
 p = OptParams.defaults()
 bench.prepare(s, v, p)
-s.set_options(pcg_lockstep=1)
+# every launch that leaves stamps must be a working one.  Lockstep would do (no launch is enqueued past convergence) but keeps
+# the closing tail; an iteration cap below the count a solve of this level needs does the same for both modes.
+s.set_options(pcg_max_iterations=12)
 if len(sys.argv) > 3 and sys.argv[3] == "nostage":
     s.set_options(tail_no_row_staging=1)
+if len(sys.argv) > 3 and sys.argv[3] == "closing":
+    s.set_options(tail_closes_scalars=1)
 p.max_iterations = 2
 s.pose_optimization_step(p, p.depth_deform_reg_final, convert_poses=False)   # the stamps of the LAST tail launch stay
 lib = api.load_library()
@@ -68,5 +74,6 @@ for name, rows in groups:
         print(f"  {'  post-barrier chain':22s} min {x.min():6.2f}  median {np.median(x):6.2f}  mean {x.mean():6.2f}  max {x.max():6.2f}")
     if "level's" in name and rows[:, 5].min() > 0:   # (tlLevelRows' own stamps)
         for label, x in (("  node sums (q_T)", us(rows[:, 5] - rows[:, 3])), ("  rows + update", us(rows[:, 6] - rows[:, 5])),
-                         ("  interpolation + share", us(rows[:, 7] - rows[:, 6])), ("  ticket", us(rows[:, 4] - rows[:, 7]))):
+                         ("  interpolation + share", us(rows[:, 7] - rows[:, 6])),
+                         ("  ticket (closing tail)", us(rows[:, 4] - rows[:, 7]))):
             print(f"  {label:22s} min {x.min():6.2f}  median {np.median(x):6.2f}  mean {x.mean():6.2f}  max {x.max():6.2f}")
