@@ -29,6 +29,12 @@ typedef struct cvd_debug_options {
   int32_t tail_closes_scalars;   /* 1: k_pcg_tail always sums the r^T z shares and finishes the PCG scalars itself (its last workgroup),
                                     also where the next product would sum them in its prologue (the shares mode); cvd_path_info
                                     reports which ran */
+  int32_t asm_force_stage_depth; /* the segment walk of the assembly (fast list kernel, SPEC 1 / 2): 0 = as many staging rows per wave
+                                    for the other frame's parameters as the LDS holds (2, 1 or 0); 1 + k = exactly k rows (k = 0, 1, 2;
+                                    an evaluation fails if they do not fit); cvd_assembly_launch_debug reports which ran */
+  int32_t asm_force_part_units;  /* work list of the fast list assembly: 0 = the product rule for the units (128 constraints each) a part
+                                    (one workgroup) gets at most; k > 0 = at most k, so that a test problem of a few frames has parts
+                                    whose waves walk several units and segments as a 300-frame problem's do */
 } cvd_debug_options;
 void cvd_debug_options_default(cvd_debug_options* o);
 int32_t cvd_set_debug_options(cvd_handle* h, const cvd_debug_options* o);
@@ -85,12 +91,13 @@ int32_t cvd_temporal_debug(cvd_handle* h, int32_t* dims6, double* a_t, double* a
  * kind (0: generic list kernel, 1: fast list kernel, 2: fast dense-mode kernel, 3: explicit cross blocks; -1: no product yet),
  * work items (= workgroups of the launch), compute units the workgroup-size rule counted}. */
 int32_t cvd_product_launch_debug(cvd_handle* h, int32_t* out6);
-/* Test hook: what the handle's last assembly launch (gradient and frame blocks of cvd_evaluate or of an LM iteration) was.  out6 =
+/* Test hook: what the handle's last assembly launch (gradient and frame blocks of cvd_evaluate or of an LM iteration) was.  out8 =
  * {threads per workgroup, SPEC (as above), KD, kind (0: generic kernel, 1: fast list kernel, 2: fast dense-mode kernel, 3: fold of the
  * dense walk's records; -1: no assembly yet), workgroups of the launch (list mode: parts of the work list), parts that belong to
- * frames split into several parts (0: no frame is split)}.  cost_frame (optional, one double per frame): the per-frame costs that
+ * frames split into several parts (0: no frame is split), staging rows per wave of the segment walk (0, 1, 2; -1: the launch walked
+ * units, not segments), segments of that walk's work list (0 with -1)}.  cost_frame (optional, one double per frame): the per-frame costs that
  * launch left behind -- a frame's regularisers and the constraints of the pairs it is the source of; their sum is the cost. */
-int32_t cvd_assembly_launch_debug(cvd_handle* h, int32_t* out6, double* cost_frame);
+int32_t cvd_assembly_launch_debug(cvd_handle* h, int32_t* out8, double* cost_frame);
 
 #ifdef __cplusplus
 }

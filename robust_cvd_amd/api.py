@@ -57,6 +57,8 @@ class DebugOptions(C.Structure):
         ("stall_fused_tail_once", C.c_int32),
         ("tail_no_row_staging", C.c_int32),
         ("tail_closes_scalars", C.c_int32),
+        ("asm_force_stage_depth", C.c_int32),
+        ("asm_force_part_units", C.c_int32),
     ]
 
 
@@ -935,7 +937,7 @@ class Solver(Binding):
     def set_options(self, pcg_relative_tolerance=None, pcg_max_iterations=None, verbose=None,
                     coarse_level=None, robust_loss=None, **variants):
         """Options persist per handle: only the fields given change (robust_loss: 0 Cauchy = reference, 1 Huber).  Names of
-        cvd_debug_options (force_iterations, force_sharded_path, pcg_lockstep, stall_fused_tail_once, tail_no_row_staging, tail_closes_scalars: test / measurement hooks,
+        cvd_debug_options (force_iterations, force_sharded_path, pcg_lockstep, stall_fused_tail_once, tail_no_row_staging, tail_closes_scalars, asm_force_stage_depth, asm_force_part_units: test / measurement hooks,
         include/cvd_hip_debug.h) are routed to cvd_set_debug_options."""
         debug = {k: variants.pop(k) for k in list(variants) if k in dict(DebugOptions._fields_) and k != "struct_size"}
         if debug:
@@ -1844,14 +1846,15 @@ class Solver(Binding):
 
     def assembly_launch_debug(self):
         """The handle's last assembly launch (cvd_assembly_launch_debug): workgroup size, kernel variant, workgroups, parts of split
-        frames, and the per-frame costs it wrote (their sum is the cost of the evaluation)."""
+        frames, staging rows per wave and segments of the segment walk (stage_depth -1: a unit loop ran), and the per-frame costs it wrote
+        (their sum is the cost of the evaluation)."""
         import numpy as np
-        out = (C.c_int32 * 6)()
+        out = (C.c_int32 * 8)()
         cost = np.zeros(self.num_frames, dtype=np.float64)
         self._check(self._fn("assembly_launch_debug")(self._h, out, cost.ctypes.data_as(C.POINTER(C.c_double))))
         kind = {-1: "none", 0: "generic", 1: "fast list", 2: "fast dense", 3: "dense fold"}[out[3]]
         return {"threads": out[0], "spec": out[1], "kd": out[2], "kind": out[3], "kind_name": kind, "workgroups": out[4],
-                "split_parts": out[5], "cost_frame": cost}
+                "split_parts": out[5], "stage_depth": out[6], "segments": out[7], "cost_frame": cost}
 
     def coarse_debug(self):
         """(A_c, A_c^-1 as applied, pivot failures) of the coarse preconditioner level after the last solve."""

@@ -300,11 +300,16 @@ void cvd_debug_options_default(cvd_debug_options* o) {
   o->stall_fused_tail_once = 0;
   o->tail_no_row_staging = 0;
   o->tail_closes_scalars = 0;
+  o->asm_force_stage_depth = 0;
+  o->asm_force_part_units = 0;
 }
 int32_t cvd_set_debug_options(cvd_handle* h, const cvd_debug_options* o) {
   CVD_TRY(h, {
     if (o->struct_size != CVD_STRUCT_STAMP(cvd_debug_options))
       throw std::runtime_error("cvd_debug_options: struct_size does not match this library's cvd_hip_debug.h (start from cvd_debug_options_default)");
+    if (o->asm_force_stage_depth < 0 || o->asm_force_stage_depth > 3) throw std::runtime_error("asm_force_stage_depth in {0, 1, 2, 3}");
+    if (o->asm_force_part_units < 0) throw std::runtime_error("asm_force_part_units >= 0");
+    if (o->asm_force_part_units != h->dbg.asm_force_part_units) h->tableValid = false;  // (the work list is cut when the table is compiled)
     h->dbg = *o;
     h->distForced = h->world == 1 && (h->comm != nullptr || h->localGroup || h->phantom) && o->force_sharded_path != 0;
   });
@@ -1094,9 +1099,9 @@ int32_t cvd_product_launch_debug(cvd_handle* h, int32_t* out6) {
     for (int i = 0; i < 6; ++i) out6[i] = h->lastProduct[i];
   });
 }
-int32_t cvd_assembly_launch_debug(cvd_handle* h, int32_t* out6, double* cost_frame) {
+int32_t cvd_assembly_launch_debug(cvd_handle* h, int32_t* out8, double* cost_frame) {
   CVD_TRY(h, {
-    for (int i = 0; i < 6; ++i) out6[i] = h->lastAssembly[i];
+    for (int i = 0; i < 8; ++i) out8[i] = h->lastAssembly[i];
     const size_t F = static_cast<size_t>(h->F);
     if (cost_frame && h->lastAssembly[3] >= 0 && h->dCostFrame.n >= F) {  // (kind -1: nothing to read, cost_frame is left as it is)
       h->dCostFrame.download(cost_frame, F, h->stream);

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "cvd_kernels.h"
+#include "cvd_asm_segments.h"
 
 namespace cvd {
 
@@ -295,11 +296,49 @@ inline __global__ void k_extract_diag(Layout L, const double* __restrict__ hBloc
 #ifdef CVD_ASM_PROFILE
 __device__ unsigned long long g_asmProf[2048 * 16];
 #define ASM_STAMP(slot) do { if (lane == 0) g_asmProf[(blockIdx.x & 2047) * 16 + (slot)] = wall_clock64(); } while (0)
+// Per-wave sums over the wave's units of the specialised walk (the 16 slots above are all taken): [0] the wait for the unit descriptor,
+// [1] for the pair's frames and offsets, [2] for the other frame's constants, the staged parameters and the first record, [3] the walk
+// itself, [4] the number of units.  Every stamp waits for all outstanding loads first, so the phases do not overlap: the build measures
+// how the loop's time divides, it is not the product's schedule.
+__device__ unsigned long long g_asmWait[2048 * 8 * 8];
+#define ASM_WAIT_DECL unsigned long long asmT[5] = {0, 0, 0, 0, 0}; unsigned long long asmT0 = 0
+#define ASM_WAIT_BEGIN() do { asmT0 = wall_clock64(); } while (0)
+#define ASM_WAIT_LAP(k) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long t_ = wall_clock64(); \
+                             asmT[k] += t_ - asmT0; asmT0 = t_; } while (0)
+#define ASM_WAIT_MARK(k) do { const unsigned long long t_ = wall_clock64(); asmT[k] += t_ - asmT0; asmT0 = t_; } while (0)
+#define ASM_WAIT_FLUSH() do { if (lane == 0) for (int k_ = 0; k_ < 5; ++k_) g_asmWait[((blockIdx.x & 2047) * 8 + (wv & 7)) * 8 + k_] = asmT[k_]; } while (0)
+#define ASM_WAIT_PARAMS , unsigned long long (&asmT)[5], unsigned long long& asmT0
+#define ASM_WAIT_ARGS , asmT, asmT0
 #else
 #define ASM_STAMP(slot) do {} while (0)
+#define ASM_WAIT_DECL
+#define ASM_WAIT_BEGIN() do {} while (0)
+#define ASM_WAIT_LAP(k) do {} while (0)
+#define ASM_WAIT_MARK(k) do {} while (0)
+#define ASM_WAIT_FLUSH() do {} while (0)
+#define ASM_WAIT_PARAMS
+#define ASM_WAIT_ARGS
 #endif
 // Every instantiation runs kAsmThreads per workgroup.  The packed triangle leaves room for ONE workgroup per CU, so the waves per
 // SIMD are the workgroup's waves / 4: 8 waves need <= 256 VGPRs, 12 would need <= 168 (the specialised walk then spills 102), 16 <= 128.
+
+// The frame scalars of a (pair, side) entry: they hold for every constraint of the entry, whichever unit or segment it is walked in.
+struct AsmEntryScalars {
+  double RaU[9], RbU[9], dTU[3];
+  double fxa, fya, ifxb, ifyb;
+  __device__ __forceinline__ void form(const Layout& L, const FrameConst& Fa, const FrameConst& Fb) {
+    const double A = L.aspect;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { RaU[i] = uniformValue(Fa.R[i]); RbU[i] = uniformValue(Fb.R[i]); }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) dTU[i] = uniformValue(Fa.t[i] - Fb.t[i]);
+    fya = uniformValue(Fa.fy);
+    fxa = fya * A;
+    const double fyb = uniformValue(Fb.fy);
+    ifyb = uniformValue(1.0 / fyb);
+    ifxb = uniformValue(1.0 / (fyb * A));
+  }
+};
 
 // The walk of one unit with the variant fixed at compile time (k_assemble_fast's SPEC = 1 / 2: one value parameter per vertex,
 // ReproDisparity, Cauchy / Huber -- the rule of k_matvec_pairs_fast).  `side` is the own frame's role in the pair (0: the source,
@@ -316,135 +355,269 @@ __device__ unsigned long long g_asmProf[2048 * 16];
 //    (asmLocalToAxisAngle).
 //  * Hardware reciprocals with two Newton steps (rcpFast / rsqrtFast) instead of IEEE divisions; rho and rho' written out.
 //  * The next trip's table record is in flight during this trip's arithmetic (RecordStream, primed by the caller before it stages).
+// asmConstraintSpec is one valid constraint (table record nd, d) of that walk: residual, the own side's Jacobian, its share of the sums.
+template <int KD, int SPEC>
+__device__ __forceinline__ void asmConstraintSpec(const Layout& L, const AsmEntryScalars& S, const float4 nd, const float2 d,
+                                                  const bool side, const double* __restrict__ xa, const double* __restrict__ xb,
+                                                  double* Hs, double* gs, double (&PP)[28], double (&gp)[7], double (&GD)[19],
+                                                  double& cost) {
+  const double A = L.aspect;
+  const double (&RaU)[9] = S.RaU;
+  const double (&RbU)[9] = S.RbU;
+  const double (&dTU)[3] = S.dTU;
+  const double fxa = S.fxa, fya = S.fya, ifxb = S.ifxb, ifyb = S.ifyb;
+  const double da = static_cast<double>(d.x), db = static_cast<double>(d.y);
+  // The own side's taps are kept for the accumulation; the other side's only interpolate its depth and are formed first, so the two
+  // sets and a selected copy are never held together (bicubic: 8 weights a side).  own = xf's side: `side` picks which of a / b.
+  FastTaps<KD> tm;
+  double Dm = 0.0, Do = 0.0;
+  {
+    FastTaps<KD> to;
+    fastGather<KD>(L, side ? nd.x : nd.z, side ? nd.y : nd.w, to);
+    const double* __restrict__ xo_ = side ? xa : xb;
+#pragma unroll
+    for (int k = 0; k < KD; ++k)
+      if (to.ok(k)) Do += xo_[7 + to.I(k)] * to.Wt(k);
+  }
+  fastGather<KD>(L, side ? nd.z : nd.x, side ? nd.w : nd.y, tm);
+  {
+    const double* __restrict__ xm_ = side ? xb : xa;
+#pragma unroll
+    for (int k = 0; k < KD; ++k)
+      if (tm.ok(k)) Dm += xm_[7 + tm.I(k)] * tm.Wt(k);
+  }
+  const double Da = (side ? Do : Dm) * da;
+  const double Db = (side ? Dm : Do) * db;
+  const double pax = static_cast<double>(nd.x), pay = static_cast<double>(nd.y);
+  const double pbx = static_cast<double>(nd.z), pby = static_cast<double>(nd.w);
+  double ca[3], Rca[3];
+  fastRay(RaU, pax, pay, fxa, fya, ca, Rca);
+  const double v[3] = {dTU[0] + Rca[0] * Da, dTU[1] + Rca[1] * Da, dTU[2] + Rca[2] * Da};
+  double zz, iz, u, vv, r[3], dr2dA, dr2dDb;
+  fastProject<true>(L, RbU, v, ifxb, ifyb, pbx, pby, zz, iz, u, vv, r[0], r[1]);
+  fastDepthResidual<true>(L, kLossDisparity, zz, iz, Db, r[2], dr2dA, dr2dDb);
+  const double sq = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+  const double w = fastRobustRho1<SPEC>(L, sq);     // rho'
+  if (!side) cost += fastRobustRho0<SPEC>(L, sq);  // rho: on the source visit (every constraint is counted once)
+
+  // d r / d q (rows, fastRows);  G = M R_b^T
+  double m00, m11, m02, m12;
+  fastRows(L, iz, u, vv, ifxb, ifyb, m00, m11, m02, m12);
+  const double m22 = -dr2dA;
+  double G[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    G[0][i] = m00 * RbU[i * 3 + 0] + m02 * RbU[i * 3 + 2];
+    G[1][i] = m11 * RbU[i * 3 + 1] + m12 * RbU[i * 3 + 2];
+    G[2][i] = m22 * RbU[i * 3 + 2];
+  }
+  double Jp[3][7];  // columns 3..5: local basis (see above)
+  double JD[3];
+  if (!side) {
+    const double X[3] = {Da * Rca[0], Da * Rca[1], Da * Rca[2]};
+    const double cf0 = pax * A, cf1 = pay;
+    const double dXdf[3] = {Da * (RaU[0] * cf0 + RaU[1] * cf1), Da * (RaU[3] * cf0 + RaU[4] * cf1),
+                            Da * (RaU[6] * cf0 + RaU[7] * cf1)};
+#pragma unroll
+    for (int rr = 0; rr < 3; ++rr) {
+      Jp[rr][0] = G[rr][0]; Jp[rr][1] = G[rr][1]; Jp[rr][2] = G[rr][2];
+      Jp[rr][3] = X[1] * G[rr][2] - X[2] * G[rr][1];
+      Jp[rr][4] = X[2] * G[rr][0] - X[0] * G[rr][2];
+      Jp[rr][5] = X[0] * G[rr][1] - X[1] * G[rr][0];
+      Jp[rr][6] = dot3(G[rr], dXdf);
+      JD[rr] = dot3(G[rr], Rca);
+    }
+  } else {
+#pragma unroll
+    for (int rr = 0; rr < 3; ++rr) {
+      Jp[rr][0] = -G[rr][0]; Jp[rr][1] = -G[rr][1]; Jp[rr][2] = -G[rr][2];
+      Jp[rr][3] = G[rr][1] * v[2] - G[rr][2] * v[1];
+      Jp[rr][4] = G[rr][2] * v[0] - G[rr][0] * v[2];
+      Jp[rr][5] = G[rr][0] * v[1] - G[rr][1] * v[0];
+    }
+    Jp[0][6] = -L.ws * u * ifyb;
+    Jp[1][6] = -L.ws * vv * ifyb;
+    Jp[2][6] = 0.0;
+    JD[0] = 0.0; JD[1] = 0.0; JD[2] = dr2dDb;
+  }
+  // ---- accumulate
+  int qi = 0;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    gp[i] += w * (Jp[0][i] * r[0] + Jp[1][i] * r[1] + Jp[2][i] * r[2]);
+#pragma unroll
+    for (int j = 0; j <= i; ++j) {
+      PP[qi] += w * (Jp[0][i] * Jp[0][j] + Jp[1][i] * Jp[1][j] + Jp[2][i] * Jp[2][j]);
+      ++qi;
+    }
+  }
+  double v7[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) v7[i] = w * (Jp[0][i] * JD[0] + Jp[1][i] * JD[1] + Jp[2][i] * JD[2]);
+  const double sDD = w * (JD[0] * JD[0] + JD[1] * JD[1] + JD[2] * JD[2]);
+  const double sDr = w * (JD[0] * r[0] + JD[1] * r[1] + JD[2] * r[2]);
+  const double dm = side ? db : da;  // d D / d theta_k = w_k d
+  if constexpr (KD == 1) {
+    // (Global / Identity: the single depth block is hit by every sample -> the kernel's register accumulators)
+    const double fac = tm.Wt(0) * dm;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) GD[i] += v7[i] * fac;
+    GD[17] += sDr * fac;
+    GD[14] += sDD * fac * fac;
+  } else {
+#pragma unroll
+    for (int ka = 0; ka < KD; ++ka) {
+      if (!tm.ok(ka)) continue;
+      const double fa = tm.Wt(ka) * dm;
+      const int ct = 7 + tm.I(ka);
+      const int rowBase = ct * (ct + 1) / 2;
+      atomicAdd(&gs[ct], sDr * fa);
+#pragma unroll
+      for (int i = 0; i < 7; ++i) atomicAdd(&Hs[rowBase + i], v7[i] * fa);
+      const double sfa = sDD * fa;
+#pragma unroll
+      for (int kb = 0; kb <= ka; ++kb) {
+        if (!tm.ok(kb)) continue;
+        const int c2 = 7 + tm.I(kb);
+        // (bilinear taps at gx = 1 are not in index order: order the pair; the bicubic taps are)
+        const int hi = (KD == 16 || ct > c2) ? ct : c2, lo = (KD == 16 || ct > c2) ? c2 : ct;
+        atomicAdd(&Hs[packedIdx(hi, lo)], sfa * (tm.Wt(kb) * dm));
+      }
+    }
+  }
+}
+
 template <int KD, int SPEC>
 __device__ __forceinline__ void asmWalkSpec(const Layout& L, const Table& T, RecordStream<false>& rs, long long cBegin, int n,
                                             int lane, const bool side, const FrameConst& Fa, const FrameConst& Fb,
                                             const double* __restrict__ xa, const double* __restrict__ xb, double* Hs,
-                                            double* gs, double (&PP)[28], double (&gp)[7], double (&GD)[19], double& cost) {
-  const double A = L.aspect;
-  double RaU[9], RbU[9], dTU[3];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) { RaU[i] = uniformValue(Fa.R[i]); RbU[i] = uniformValue(Fb.R[i]); }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) dTU[i] = uniformValue(Fa.t[i] - Fb.t[i]);
-  const double fya = uniformValue(Fa.fy), fxa = fya * A;
-  const double fyb = uniformValue(Fb.fy);
-  const double ifyb = uniformValue(1.0 / fyb), ifxb = uniformValue(1.0 / (fyb * A));
+                                            double* gs, double (&PP)[28], double (&gp)[7], double (&GD)[19], double& cost ASM_WAIT_PARAMS) {
+  AsmEntryScalars S;
+  S.form(L, Fa, Fb);
+  ASM_WAIT_LAP(2);
   for (int ci = lane; ci < n; ci += 64) {
     float4 nd;
     float2 d;
     if (!rs.take(T, cBegin, ci, 64, n, 0, 0, 0, nd, d)) continue;
-    const double da = static_cast<double>(d.x), db = static_cast<double>(d.y);
-    FastTaps<KD> ta, tb;
-    fastGather<KD>(L, nd.x, nd.y, ta);
-    fastGather<KD>(L, nd.z, nd.w, tb);
-    double Da = 0.0, Db = 0.0;
-#pragma unroll
-    for (int k = 0; k < KD; ++k) {
-      if (ta.ok(k)) Da += xa[7 + ta.I(k)] * ta.Wt(k);
-      if (tb.ok(k)) Db += xb[7 + tb.I(k)] * tb.Wt(k);
-    }
-    Da *= da;
-    Db *= db;
-    const double pax = static_cast<double>(nd.x), pay = static_cast<double>(nd.y);
-    const double pbx = static_cast<double>(nd.z), pby = static_cast<double>(nd.w);
-    double ca[3], Rca[3];
-    fastRay(RaU, pax, pay, fxa, fya, ca, Rca);
-    const double v[3] = {dTU[0] + Rca[0] * Da, dTU[1] + Rca[1] * Da, dTU[2] + Rca[2] * Da};
-    double zz, iz, u, vv, r[3], dr2dA, dr2dDb;
-    fastProject<true>(L, RbU, v, ifxb, ifyb, pbx, pby, zz, iz, u, vv, r[0], r[1]);
-    fastDepthResidual<true>(L, kLossDisparity, zz, iz, Db, r[2], dr2dA, dr2dDb);
-    const double sq = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-    const double w = fastRobustRho1<SPEC>(L, sq);     // rho'
-    if (!side) cost += fastRobustRho0<SPEC>(L, sq);  // rho: on the source visit (every constraint is counted once)
+    asmConstraintSpec<KD, SPEC>(L, S, nd, d, side, xa, xb, Hs, gs, PP, gp, GD, cost);
+  }
+}
 
-    // d r / d q (rows, fastRows);  G = M R_b^T
-    double m00, m11, m02, m12;
-    fastRows(L, iz, u, vv, ifxb, ifyb, m00, m11, m02, m12);
-    const double m22 = -dr2dA;
-    double G[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      G[0][i] = m00 * RbU[i * 3 + 0] + m02 * RbU[i * 3 + 2];
-      G[1][i] = m11 * RbU[i * 3 + 1] + m12 * RbU[i * 3 + 2];
-      G[2][i] = m22 * RbU[i * 3 + 2];
-    }
-    double Jp[3][7];  // columns 3..5: local basis (see above)
-    double JD[3];
-    if (!side) {
-      const double X[3] = {Da * Rca[0], Da * Rca[1], Da * Rca[2]};
-      const double cf0 = pax * A, cf1 = pay;
-      const double dXdf[3] = {Da * (RaU[0] * cf0 + RaU[1] * cf1), Da * (RaU[3] * cf0 + RaU[4] * cf1),
-                              Da * (RaU[6] * cf0 + RaU[7] * cf1)};
-#pragma unroll
-      for (int rr = 0; rr < 3; ++rr) {
-        Jp[rr][0] = G[rr][0]; Jp[rr][1] = G[rr][1]; Jp[rr][2] = G[rr][2];
-        Jp[rr][3] = X[1] * G[rr][2] - X[2] * G[rr][1];
-        Jp[rr][4] = X[2] * G[rr][0] - X[0] * G[rr][2];
-        Jp[rr][5] = X[0] * G[rr][1] - X[1] * G[rr][0];
-        Jp[rr][6] = dot3(G[rr], dXdf);
-        JD[rr] = dot3(G[rr], Rca);
-      }
-    } else {
-#pragma unroll
-      for (int rr = 0; rr < 3; ++rr) {
-        Jp[rr][0] = -G[rr][0]; Jp[rr][1] = -G[rr][1]; Jp[rr][2] = -G[rr][2];
-        Jp[rr][3] = G[rr][1] * v[2] - G[rr][2] * v[1];
-        Jp[rr][4] = G[rr][2] * v[0] - G[rr][0] * v[2];
-        Jp[rr][5] = G[rr][0] * v[1] - G[rr][1] * v[0];
-      }
-      Jp[0][6] = -L.ws * u * ifyb;
-      Jp[1][6] = -L.ws * vv * ifyb;
-      Jp[2][6] = 0.0;
-      JD[0] = 0.0; JD[1] = 0.0; JD[2] = dr2dDb;
-    }
-    // ---- accumulate
-    int qi = 0;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      gp[i] += w * (Jp[0][i] * r[0] + Jp[1][i] * r[1] + Jp[2][i] * r[2]);
-#pragma unroll
-      for (int j = 0; j <= i; ++j) {
-        PP[qi] += w * (Jp[0][i] * Jp[0][j] + Jp[1][i] * Jp[1][j] + Jp[2][i] * Jp[2][j]);
-        ++qi;
-      }
-    }
-    double v7[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) v7[i] = w * (Jp[0][i] * JD[0] + Jp[1][i] * JD[1] + Jp[2][i] * JD[2]);
-    const double sDD = w * (JD[0] * JD[0] + JD[1] * JD[1] + JD[2] * JD[2]);
-    const double sDr = w * (JD[0] * r[0] + JD[1] * r[1] + JD[2] * r[2]);
-    const FastTaps<KD>& tm = side ? tb : ta;
-    const double dm = side ? db : da;  // d D / d theta_k = w_k d
-    if constexpr (KD == 1) {
-      // (Global / Identity: the single depth block is hit by every sample -> the kernel's register accumulators)
-      const double fac = tm.Wt(0) * dm;
-#pragma unroll
-      for (int i = 0; i < 7; ++i) GD[i] += v7[i] * fac;
-      GD[17] += sDr * fac;
-      GD[14] += sDD * fac * fac;
-    } else {
-#pragma unroll
-      for (int ka = 0; ka < KD; ++ka) {
-        if (!tm.ok(ka)) continue;
-        const double fa = tm.Wt(ka) * dm;
-        const int ct = 7 + tm.I(ka);
-        const int rowBase = ct * (ct + 1) / 2;
-        atomicAdd(&gs[ct], sDr * fa);
-#pragma unroll
-        for (int i = 0; i < 7; ++i) atomicAdd(&Hs[rowBase + i], v7[i] * fa);
-        const double sfa = sDD * fa;
-#pragma unroll
-        for (int kb = 0; kb <= ka; ++kb) {
-          if (!tm.ok(kb)) continue;
-          const int c2 = 7 + tm.I(kb);
-          // (bilinear taps at gx = 1 are not in index order: order the pair; the bicubic taps are)
-          const int hi = (KD == 16 || ct > c2) ? ct : c2, lo = (KD == 16 || ct > c2) ? c2 : ct;
-          atomicAdd(&Hs[packedIdx(hi, lo)], sfa * (tm.Wt(kb) * dm));
-        }
-      }
+// B doubles from global memory straight into an LDS row, no register in between (LDS-DMA, one dword per lane and instruction: the rows
+// are 8-byte aligned, B may be odd).  The destination of an instruction is the wave-uniform address in M0 plus 4 bytes per lane; M0
+// is the compiler's, so it is saved and restored within the statement.  The compiler does not count these loads: the caller waits for
+// them with an `s_waitcnt vmcnt(0)` of its own before it reads the row (asmWalkSegments, at the switch of segments).
+__device__ __forceinline__ void asmStageAhead(const double* __restrict__ src, double* dstRow, int B, int lane) {
+  const unsigned int* g = reinterpret_cast<const unsigned int*>(src);
+  const unsigned int lds = static_cast<unsigned int>(reinterpret_cast<uintptr_t>(
+      (__attribute__((address_space(3))) void*)dstRow));  // (the row's byte address within the workgroup's LDS)
+  const int nDw = 2 * B;
+  for (int k0 = 0; k0 < nDw; k0 += 64) {
+    if (k0 + lane < nDw) {
+      unsigned int keep;
+      const unsigned int dst = __builtin_amdgcn_readfirstlane(lds + 4u * static_cast<unsigned int>(k0));
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep) : "v"(g + k0 + lane), "s"(dst) : "memory");
     }
   }
+}
+
+// How a launch's segment list reaches the kernel.  k_assemble_fast's parameter list is fixed (tests/test_codegen_assembly.py
+// instantiates it by its argument types), and cvd_kernels.h, where AsmWork lives, is tied to the committed counter files by its hash.
+// A list-mode launch has no dense records, so the list travels in that argument: records = the segments, recOff = the (part, wave)
+// offsets, fpOff = the staging depth as an integer in a pointer's bits.  Only these two functions know.
+inline DenseRecords asmSegsAsArgument(const AsmSegs& s) {
+  return DenseRecords{reinterpret_cast<const double*>(s.seg), s.waveOff,
+                      reinterpret_cast<const int*>(static_cast<uintptr_t>(s.depth)), nullptr};
+}
+__host__ __device__ __forceinline__ AsmSegs asmSegsFromArgument(const DenseRecords& d) {
+  return AsmSegs{reinterpret_cast<const AsmSegment*>(d.records), d.recOff,
+                 static_cast<int32_t>(reinterpret_cast<uintptr_t>(d.fpOff))};
+}
+
+// The walk of a wave's SEGMENTS (cvd_asm_segments.h; the multi-wave build's SPEC = 1 / 2): what asmWalkSpec does per unit is done
+// once per segment, and what a segment needs is requested while the one before it is walked.
+//  * The segment record is one scalar load; the next one is read while this one is walked.
+//  * The frame scalars are formed and the other frame's parameters staged once per segment.
+//  * The record stream runs through: every trip requests the next trip's record, the last trip of a segment the first record of the
+//    next segment.
+//  * segs.depth = 2: two staging rows per wave.  The last trip of a segment also requests the next segment's other-frame parameters
+//    into the row that is not in use (asmStageAhead), so the switch only waits for what has been in flight for a trip.  depth = 1:
+//    one row, copied through registers at the switch.  STAGE = false (depth 0): the other frame's parameters are read from memory.
+// One copy of the trip loop for both roles and all segments (the accumulators must not be kept twice: asmWalkSpec's note).
+template <int KD, int SPEC, bool STAGE>
+__device__ __forceinline__ void asmWalkSegments(const Layout& L, const Table& T, const double* __restrict__ x,
+                                                const FrameConst* __restrict__ fc, const int f, const AsmSegs& segs, const int wv,
+                                                const int lane, const double* xf, double* xstage, double* Hs, double* gs,
+                                                double (&PP)[28], double (&gp)[7], double (&GD)[19], double& cost) {
+  const int B = L.B;
+  const int slot = static_cast<int>(blockIdx.x) * (kAsmThreads / 64) + wv;
+  int si = __builtin_amdgcn_readfirstlane(segs.waveOff[slot]);
+  const int sEnd = __builtin_amdgcn_readfirstlane(segs.waveOff[slot + 1]);
+  if (si >= sEnd) return;  // (a part with fewer units than waves)
+  ASM_WAIT_DECL;
+  ASM_WAIT_BEGIN();
+  const bool ahead = STAGE && segs.depth == 2;
+  double* rows = xstage + static_cast<size_t>(wv) * (ahead ? 2 : 1) * B;
+  int row = 0;
+  AsmSegment cur = segs.seg[si];
+  bool fresh = true;  // nothing of `cur` has been requested yet (the wave's first segment)
+  float4 ndNext = make_float4(0.f, 0.f, 0.f, 0.f);
+  float2 dNext = make_float2(0.f, 0.f);
+  for (;;) {
+    // What `cur` still needs before it can be walked.  Its first record and, with two rows, its staged parameters were requested
+    // in the last trip of the segment before it; the wave's first segment requests everything here, and with one row the copy is
+    // made here, through registers (a wave's LDS operations execute in order: its reads of the row in the last trip are done before
+    // these writes land).  One wait for all of it.
+    if (fresh && lane < cur.count) { dNext = (T.dsrc + cur.first)[lane]; ndNext = (T.ndc + cur.first)[lane]; }
+    if constexpr (STAGE) {
+      if (fresh || !ahead) {
+        const double* __restrict__ xo = x + static_cast<size_t>(cur.other) * B;
+        double* xw = rows + static_cast<size_t>(row) * B;
+        for (int i = lane; i < B; i += 64) xw[i] = xo[i];
+      }
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    fresh = false;
+    const bool more = cur.last == 0;
+    AsmSegment nxt = cur;
+    if (more) nxt = segs.seg[si + 1];  // (one scalar load, in flight while this segment is walked; needed in its last trip)
+    const bool side = cur.side != 0;
+    AsmEntryScalars S;
+    S.form(L, side ? fc[cur.other] : fc[f], side ? fc[f] : fc[cur.other]);
+    const double* xov = STAGE ? rows + static_cast<size_t>(row) * B : x + static_cast<size_t>(cur.other) * B;
+    const double* xa = side ? xov : xf;
+    const double* xb = side ? xf : xov;
+    const int n = cur.count;
+    ASM_WAIT_LAP(2);
+    for (int base = 0; base < n; base += 64) {  // (every lane runs every trip: the last one requests for the next segment)
+      const int ci = base + lane;
+      const float4 nd = ndNext;
+      const float2 d = dNext;
+      // the next record of the wave's stream: this segment's next trip, or the next segment's first (one load site, scalar selects;
+      // 32-bit offsets from the scalar base)
+      const bool within = base + 64 < n;
+      const long long rb = within ? cur.first : nxt.first;
+      const int ri = within ? ci + 64 : lane;
+      const int rn = within ? n : (more ? nxt.count : 0);
+      if (ri < rn) {
+        dNext = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(T.dsrc + rb) + static_cast<unsigned int>(ri) * 8u);
+        ndNext = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(T.ndc + rb) + static_cast<unsigned int>(ri) * 16u);
+      }
+      if (!within && more && ahead)
+        asmStageAhead(x + static_cast<size_t>(nxt.other) * B, rows + static_cast<size_t>(row ^ 1) * B, B, lane);
+      if (ci < n && d.x > 0.f) asmConstraintSpec<KD, SPEC>(L, S, nd, d, side, xa, xb, Hs, gs, PP, gp, GD, cost);
+    }
+    ASM_WAIT_MARK(3);  // (no wait here: what the next segment waits for at its top counts as its wait)
+#ifdef CVD_ASM_PROFILE
+    ++asmT[4];
+#endif
+    if (!more) break;
+    if (ahead) row ^= 1;
+    ++si;
+    cur = nxt;
+  }
+  ASM_WAIT_FLUSH();
 }
 
 // Rotation rows / columns of a frame's sums from the local basis of asmWalkSpec to the axis-angle parameters: with J = Jl (row i =
@@ -567,7 +740,8 @@ __device__ __forceinline__ double asmRegularisersSpec(const Layout& L, int f, in
 // the regularisers and the write-out as ever.  One workgroup per frame (blockIdx.x = frame; the work list is not used).
 // SPEC (as on k_matvec_pairs_fast, chosen by the same rule): 1 = one value parameter per vertex, ReproDisparity, Cauchy; 2 = the same
 // with Huber; 0 = the runtime-variant walk below (everything else, shared intrinsics -- their extra focal column sits in the loop --
-// and the DENSE / FOLD instantiations).  SPEC != 0 walks its units through asmWalkSpec.
+// and the DENSE / FOLD instantiations).  SPEC != 0 walks segments through asmWalkSegments (the list arrives in `dr`:
+// asmSegsAsArgument; the one-wave deterministic build walks its units through asmWalkSpec).
 template <int KD, bool DENSE = false, bool STAGE = false, bool FOLD = false, int SPEC = 0>
 inline __global__ __launch_bounds__(kAsmThreads) void k_assemble_fast(Layout L, Table T, const double* __restrict__ x,
                                                        const FrameConst* __restrict__ fc,
@@ -674,9 +848,17 @@ inline __global__ __launch_bounds__(kAsmThreads) void k_assemble_fast(Layout L, 
   if (L.includeStatic) {
     // one unit (slice of a (pair, side) entry) per WAVE at a time: the waves run through their units independently
     // (no barrier until the end), 64 lanes over the slice's constraints
+    if constexpr (SPEC != 0 && NT > 64) {
+      // segments, one contiguous run of the part's units per wave (the one-wave deterministic build keeps the unit loop below)
+      const AsmSegs segs = asmSegsFromArgument(dr);
+      asmWalkSegments<KD, SPEC, STAGE>(L, T, x, fc, f, segs, wv, lane, xf, xstage, Hs, gs, PP, gp, GD, cost);
+    } else {
+    ASM_WAIT_DECL;
     for (int u = me.u0 + wv; u < me.u1; u += NT / 64) {
+      if constexpr (SPEC != 0) ASM_WAIT_BEGIN();
       const int2 unit = work.units[u];
       const int code = __builtin_amdgcn_readfirstlane(unit.x);
+      if constexpr (SPEC != 0) ASM_WAIT_LAP(0);
       const int p = code >> 1;
       const int side = code & 1;  // 0: f is the source of pair p, 1: f is the target
       const int o = side ? T.pairA[p] : T.pairB[p];
@@ -689,6 +871,10 @@ inline __global__ __launch_bounds__(kAsmThreads) void k_assemble_fast(Layout L, 
         const long long cb = pOff + __builtin_amdgcn_readfirstlane(unit.y);
         const long long pEnd = T.pairOff[p + 1];
         const int n = static_cast<int>((cb + kAsmUnit < pEnd ? cb + kAsmUnit : pEnd) - cb);
+#ifdef CVD_ASM_PROFILE
+        asm volatile("" :: "s"(o), "s"(n));  // (the header's values are formed in front of the stamp)
+#endif
+        ASM_WAIT_LAP(1);
         RecordStream<false> rs;
         rs.prime(T, cb, lane, n);
         // (the unit's first record is requested before the staging copy: one round trip for both; LDS ordering as below)
@@ -698,7 +884,11 @@ inline __global__ __launch_bounds__(kAsmThreads) void k_assemble_fast(Layout L, 
         }
         const double* xov = STAGE ? xw : xo;
         asmWalkSpec<KD, SPEC>(L, T, rs, cb, n, lane, side != 0, Fa, Fb, side ? xov : xf,
-                              side ? xf : xov, Hs, gs, PP, gp, GD, cost);
+                              side ? xf : xov, Hs, gs, PP, gp, GD, cost ASM_WAIT_ARGS);
+        ASM_WAIT_LAP(3);
+#ifdef CVD_ASM_PROFILE
+        ++asmT[4];
+#endif
         continue;
       }
       if constexpr (STAGE) {
@@ -967,6 +1157,8 @@ inline __global__ __launch_bounds__(kAsmThreads) void k_assemble_fast(Layout L, 
           }
         }
       }
+    }
+    if constexpr (SPEC != 0) ASM_WAIT_FLUSH();
     }
   }
   ASM_STAMP(4 + wv);  // each wave's end of the constraint loop

@@ -167,28 +167,44 @@ double evalFull(Ctx& c, const double* x, bool withStats, bool noReadBack) {
   const size_t ldsRest = 3 * B * 8 + 2 * sizeof(FrameConst) + 4 * 36 * 8;
   int panelCap = 0;
   const bool fastFits = ldsFast <= kMaxLds;
-  auto recordAsm = [h](int threads, int spec, int kd, int kind, int groups, int splitParts) {  // (cvd_assembly_launch_debug)
-    const int v[6] = {threads, spec, kd, kind, groups, splitParts};
-    for (int i = 0; i < 6; ++i) h->lastAssembly[i] = v[i];
+  auto recordAsm = [h](int threads, int spec, int kd, int kind, int groups, int splitParts, int stageDepth = -1, int segments = 0) {  // (cvd_assembly_launch_debug)
+    const int v[8] = {threads, spec, kd, kind, groups, splitParts, stageDepth, segments};
+    for (int i = 0; i < 8; ++i) h->lastAssembly[i] = v[i];
   };
   if (fast && fastFits) {
     h->dAsmScratch.ensure(static_cast<size_t>(h->nAsmSlots) * (B * (B + 1) / 2 + B + 4));
     const AsmWork work{h->dAsmParts.p, h->dAsmUnits.p, h->dAsmScratch.p, h->dAsmCount.p};
-    // STAGE: the other frame's parameters in a per-wave LDS buffer whenever the LDS holds 8 B doubles more (cvd_assembly.h)
+    // STAGE: the other frame's parameters in per-wave LDS rows (8 B doubles each) as far as the LDS holds them (cvd_assembly.h)
     // SPEC: the default pipeline's variant fixed at compile time, by the rule of the pair product (cvd_matvec.hip); shared
     // intrinsics (an extra focal column inside the loop) and the dense mode stay on the runtime-variant walk.
     const int spec = (!h->dense && c.L.N == 1 && c.L.lossType == CVD_STATIC_REPRO_DISPARITY && c.L.intrOpt != CVD_INTR_SHARED)
                          ? (c.L.robustKind == 0 ? 1 : 2) : 0;
-    const size_t ldsStage = ldsFast + static_cast<size_t>(kAsmThreads / 64) * B * 8;
-    const bool stage = ldsStage <= kMaxLds;
+    const size_t ldsRow = static_cast<size_t>(kAsmThreads / 64) * B * 8;  // one staging row per wave
+    // Staging rows per wave.  The unit loops (runtime variant, dense mode, one-wave deterministic build) use one when it fits.  The
+    // segment walk (SPEC != 0, several waves) uses two when they fit -- the second receives the next segment's parameters while
+    // this one is walked -- else one, else none; cvd_debug_options::asm_force_stage_depth picks one of the three for a test.
+    const bool segWalk = spec != 0 && kAsmThreads > 64;
+    int depth = ldsFast + ldsRow <= kMaxLds ? 1 : 0;
+    if (segWalk && ldsFast + 2 * ldsRow <= kMaxLds) depth = 2;
+    if (segWalk && h->dbg.asm_force_stage_depth != 0) {
+      const int forced = h->dbg.asm_force_stage_depth - 1;
+      if (forced < 0 || forced > 2 || ldsFast + forced * ldsRow > kMaxLds)
+        throw std::runtime_error(fmt("asm_force_stage_depth: %d staging rows per wave do not fit the LDS at B = %d", forced, static_cast<int>(B)));
+      depth = forced;
+    }
+    const size_t ldsStage = ldsFast + static_cast<size_t>(depth) * ldsRow;
+    const bool stage = depth > 0;
+    const AsmSegs segs{h->dAsmSegs.p, h->dAsmWaveOff.p, depth};
+    if (segWalk && !h->dAsmWaveOff.p) throw std::logic_error("assembly: the segment list of the work list is missing");
 #define CVD_LAUNCH_ASM_S(DENSEV, STAGEV, SPECV)                                                                            \
     CVD_DISPATCH_KD(c.KD, {                                                                                              \
-      recordAsm(kAsmThreads, SPECV, KD, DENSEV ? 2 : 1, h->nAsmParts, h->nAsmSlots);                                       \
+      if (SPECV != 0 && kAsmThreads > 64) recordAsm(kAsmThreads, SPECV, KD, 1, h->nAsmParts, h->nAsmSlots, depth, h->nAsmSegs); \
+      else recordAsm(kAsmThreads, SPECV, KD, DENSEV ? 2 : 1, h->nAsmParts, h->nAsmSlots);                                  \
       allowLds((k_assemble_fast<KD, DENSEV, STAGEV, false, SPECV>), STAGEV ? ldsStage : ldsFast);                          \
       hipLaunchKernelGGL((k_assemble_fast<KD, DENSEV, STAGEV, false, SPECV>), dim3(h->nAsmParts),                          \
                          dim3(kAsmThreads), STAGEV ? ldsStage : ldsFast, s,                                                \
                          c.L, c.T, x, h->dFc.p, h->dMask.p, h->dMedian.p, h->dRegOwner.p, h->dInRange.p, work, h->dG.p, h->dH.p,  \
-                         h->dCostFrame.p, h->dFocal.p, h->dFocal.p + c.L.F);                                             \
+                         h->dCostFrame.p, h->dFocal.p, h->dFocal.p + c.L.F, asmSegsAsArgument(segs));                    \
     })
 #define CVD_LAUNCH_ASM(DENSEV, STAGEV) CVD_LAUNCH_ASM_S(DENSEV, STAGEV, 0)
 #ifndef CVD_ASM_STAGE
@@ -302,5 +318,9 @@ void touchModule_eval() {
 extern "C" int32_t cvd_debug_asm_profile(unsigned long long* out) {  // (same translation unit as the launches: the symbol is per unit)
   (void)hipDeviceSynchronize();
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(cvd::g_asmProf), sizeof(unsigned long long) * 2048 * 16) == hipSuccess ? 0 : 1;
+}
+extern "C" int32_t cvd_debug_asm_waits(unsigned long long* out) {  // g_asmWait: [part & 2047][wave][8]
+  (void)hipDeviceSynchronize();
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(cvd::g_asmWait), sizeof(unsigned long long) * 2048 * 8 * 8) == hipSuccess ? 0 : 1;
 }
 #endif

@@ -37,6 +37,7 @@
 
 #include "../../include/cvd_hip_debug.h"
 #include "cvd_kernels.h"
+#include "cvd_asm_segments.h"
 
 
 namespace cvd {
@@ -244,6 +245,9 @@ struct cvd_handle_t {
   DevBuf<double> dAsmScratch;
   DevBuf<unsigned int> dAsmCount;
   int nAsmParts = 0, nAsmSlots = 0;
+  DevBuf<AsmSegment> dAsmSegs;     // segments of the specialised list-mode walk and their (part, wave) offsets (cvd_asm_segments.h)
+  DevBuf<int32_t> dAsmWaveOff;
+  int nAsmSegs = 0;
   int numCU = 256;
   hipStream_t stream2 = nullptr;                       // side stream of the asynchronous rebuild of the SPARSE coarse level
   rocblas_handle rbMain = nullptr;                     // main-stream handle (batched block inverses beyond B = 256)
@@ -396,8 +400,9 @@ struct cvd_handle_t {
   int lastKD = 0;
   // cvd_product_launch_debug: {threads per workgroup, SPEC, KD, kind, work items, numCU} of the last launchMatvec (kind -1: none yet)
   int lastProduct[6] = {0, 0, 0, -1, 0, 0};
-  // cvd_assembly_launch_debug: {threads per workgroup, SPEC, KD, kind, workgroups, parts of split frames} of the last evalFull (kind -1: none yet)
-  int lastAssembly[6] = {0, 0, 0, -1, 0, 0};
+  // cvd_assembly_launch_debug: {threads per workgroup, SPEC, KD, kind, workgroups, parts of split frames, staging rows per wave of the
+  // segment walk (-1: a unit loop ran), its segments} of the last evalFull (kind -1: none yet)
+  int lastAssembly[8] = {0, 0, 0, -1, 0, 0, -1, 0};
   bool tailDisabled = false;  // k_pcg_tail abandoned its grid barrier once on this handle: two-launch tail from then on (runPcg)
   bool forceGeneric = false;  // test hook: route the products through the generic (all-variants) kernel
 

@@ -1111,7 +1111,9 @@ void compileTable(cvd_handle* h, const std::vector<int>& range, bool withTriplet
     for (int f = 0; f < h->F; ++f) activeFrames += inRange[f] ? 1 : 0;
     constexpr double partsPerCU = 1.0;  // (1.5 / 2 / 3 / 4 parts per CU measured on the 4140-pair set: 0.44 / 0.42 / 0.46 / 0.51 ms against 0.38)
     const long long denom = std::max<long long>(1, std::max<long long>(activeFrames, static_cast<long long>(partsPerCU * h->numCU)));
-    const int capU = static_cast<int>(std::max<long long>(kAsmThreads / 64, (static_cast<long long>(units.size()) + denom - 1) / denom));
+    const int capRule = static_cast<int>(std::max<long long>(kAsmThreads / 64, (static_cast<long long>(units.size()) + denom - 1) / denom));
+    // (cvd_debug_options::asm_force_part_units: a small test problem gets the long runs per wave that the rule gives a large one)
+    const int capU = h->dbg.asm_force_part_units > 0 ? h->dbg.asm_force_part_units : capRule;
     std::vector<AsmPart> parts;
     int slots = 0;
     for (int f = 0; f < h->F; ++f) {
@@ -1137,6 +1139,21 @@ void compileTable(cvd_handle* h, const std::vector<int>& range, bool withTriplet
     h->nAsmSlots = slots;
     h->dAsmParts.upload(parts.data(), parts.size(), s);
     h->dAsmUnits.upload(units.data(), units.size(), s);
+    // the specialised list-mode walk reads segments instead of units (cvd_asm_segments.h), indexed by launch order and wave
+    h->nAsmSegs = 0;
+    if (!h->dense) {
+      std::vector<AsmUnitRange> ranges(parts.size());
+      for (size_t q = 0; q < parts.size(); ++q) ranges[q] = AsmUnitRange{parts[q].u0, parts[q].u1};
+      std::vector<AsmUnitDesc> descs(units.size());
+      for (size_t u = 0; u < units.size(); ++u) descs[u] = AsmUnitDesc{units[u].x, units[u].y};
+      std::vector<AsmSegment> segs;
+      std::vector<int32_t> waveOff;
+      cutAsmSegments(ranges, descs, h->pairA.data(), h->pairB.data(), h->pairOff.data(), kAsmThreads / 64, kAsmUnit, segs, waveOff);
+      h->nAsmSegs = static_cast<int>(segs.size());
+      if (segs.empty()) segs.push_back(AsmSegment{});  // (the kernel's argument is never a null pointer)
+      h->dAsmSegs.upload(segs.data(), segs.size(), s);
+      h->dAsmWaveOff.upload(waveOff.data(), waveOff.size(), s);
+    }
     if (h->dAsmCount.n < static_cast<size_t>(h->F)) {
       h->dAsmCount.ensure(h->F);
       HIP_CHECK(hipMemsetAsync(h->dAsmCount.p, 0, sizeof(unsigned int) * h->F, s));
