@@ -906,6 +906,62 @@ int32_t cvd_midas_decoder_timed(cvd_handle* h, int32_t batch, int32_t features, 
                                 const int32_t* widths4, const float* const* maps, const float* const* weights,
                                 const float* const* biases, int32_t non_negative, float* out, void* stream, double* kernel_ms);
 
+/* ---- the backbone of MiDaS v2.1 (csrc/cvd_resnext.h): torchvision's ResNet(Bottleneck, blocks, groups,
+ * width_per_group) in eval mode -- the ResNeXt-101 32x8d that the reference's monodepth/midas_v2/blocks.py:6-31 builds -- on device
+ * arrays, f32, forward only, launches on `stream` with no host synchronisation.  No atomics: a call repeats bit for bit.  An axis of
+ * `height` gives (height - 1) / stride + 1 outputs.  norm: host array of the 4 device vectors {weight, bias, running_mean,
+ * running_var} of the nn.BatchNorm2d behind the convolution, applied as y = (y - mean) / sqrt(var + eps) * weight + bias, or null
+ * for none. ---- */
+/* nn.Conv2d(groups channels_per_group, groups channels_per_group, 3, stride, padding=1, groups=groups, bias=False), the norm, and
+ * ReLU where relu != 0, in ONE launch:
+ *   x [batch][groups channels_per_group][height][width], weight [groups channels_per_group][channels_per_group][3][3] (torch's
+ *   layout) -> out [batch][groups channels_per_group][ho][wo].
+ * channels_per_group is 8, 16, 32 or 64 (the four stages of 32x8d); any groups >= 1; stride 1 or 2.  Rejected before any device
+ * work, with an error that names the value: null arrays, sizes < 1, another channels_per_group or stride, eps <= 0 with a norm,
+ * height width above 2^31, an output that overlaps the input. */
+int32_t cvd_resnext_grouped_conv_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t groups,
+                                        int32_t channels_per_group, int32_t stride, const float* x, const float* weight,
+                                        const float* const* norm, float eps, int32_t relu, float* out, void* stream);
+/* The dense convolutions, WITHOUT bias: kernel_size 7 at stride 2 (the stem, padding 3) or kernel_size 1 at stride 1 or 2, then the
+ * norm, ReLU where relu != 0, and with a residual [batch][out_channels][ho][wo] y = max(residual + y, 0):
+ *   x [batch][in_channels][height][width], weight [out_channels][in_channels][kernel_size][kernel_size] -> out [batch][out_channels][ho][wo].
+ * split: 0 = the rule -- K = in_channels kernel_size^2 is cut into as many slices as bring the 64-pixel tiles of ONE image's output
+ * to 64 workgroups, whole chains each (8 chunks of 32 channels; 3 chunks of 2 channels x 49 taps), at most 32; a function of K and
+ * ho wo alone -- otherwise the forced slice count (1 .. the chunks of K).  A split convolution is two launches: partial sums to
+ * scratch of the handle (the GRU's rule: calls on one device are ordered on one stream), then a fold in f64 in slice order, rounded
+ * once, with the epilogue.  Rejected before any device work: as above, a kernel_size / stride pair that is not built, a split
+ * outside its range, an output that overlaps x or the residual. */
+int32_t cvd_resnext_conv_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels, int32_t out_channels,
+                                int32_t kernel_size, int32_t stride, const float* x, const float* weight, const float* const* norm,
+                                float eps, int32_t relu, const float* residual, int32_t split, float* out, void* stream);
+/* nn.MaxPool2d(3, 2, 1): x [batch][channels][height][width] -> out [batch][channels][ho][wo] at stride 2, ONE launch, one thread per
+ * output element; padding counts as minus infinity.  out must not overlap x. */
+int32_t cvd_resnext_maxpool_device(cvd_handle* h, int32_t batch, int32_t channels, int32_t height, int32_t width, const float* x,
+                                   float* out, void* stream);
+/* ResNet.forward up to layer4, as MidasNet.forward reads it:
+ *   blocks4    host array: the block counts of layer1 .. layer4 ((3, 4, 23, 3) with groups 32, width_per_group 8 is ResNeXt-101
+ *              32x8d: 104 convolutions and one pool)
+ *   images     [batch][3][height][width], height and width multiples of 32
+ *   weights    host array of one device array per convolution in the state dict's order: conv1 (the stem), then per block conv1,
+ *              conv2, conv3 and, in every stage's first block, downsample.0.  Stage k has planes = 64 2^k, width = planes
+ *              width_per_group / 64 * groups: conv1 1 x 1 in -> width, conv2 grouped 3 x 3 with the block's stride, conv3 1 x 1
+ *              width -> 4 planes, downsample.0 1 x 1 with the stride (torchvision's v1.5 form)
+ *   norms      host array of 4 device vectors per convolution, {weight, bias, running_mean, running_var}, in the same order
+ *   outs4      host array of the four caller-owned output maps [batch][256 2^k][height / 2^(k+2)][width / 2^(k+2)]
+ * One launch per convolution (and the folds of those that split) and the pool.  Intermediates are scratch of the handle under the
+ * same rule.  The result equals, bit for bit, the stages chained through the three entry points above.
+ * Rejected before any device work: null arrays, sizes < 1, channels per group that are not built, eps <= 0, image sides that are not
+ * multiples of 32, height width above 2^31, output maps that overlap the images or each other. */
+int32_t cvd_midas_backbone_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, const int32_t* blocks4, int32_t groups,
+                                  int32_t width_per_group, float eps, const float* images, const float* const* weights,
+                                  const float* const* norms, float* const* outs4, void* stream);
+/* The same call for measurement (tools/midasnet_bench.py): HIP events around every launch on `stream` and a host wait; kernel_ms
+ * [2 n + 1] for n convolutions: entry 2 i is convolution i of the weight table, 2 i + 1 its fold (0 without a split), 2 n the pool,
+ * in milliseconds. */
+int32_t cvd_midas_backbone_timed(cvd_handle* h, int32_t batch, int32_t height, int32_t width, const int32_t* blocks4, int32_t groups,
+                                 int32_t width_per_group, float eps, const float* images, const float* const* weights,
+                                 const float* const* norms, float* const* outs4, void* stream, double* kernel_ms);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

@@ -5,6 +5,7 @@
 normalize_depth, pose_optimization (= optimizePoses), grid_xform_split.  There is NO fallback: if the HIP
 library is missing, or no GPU is usable, construction raises.
 """
+import collections
 import ctypes as C
 import os
 import sys
@@ -796,6 +797,170 @@ def midas_check_decoder(map_shapes, weight_shapes, bias_shapes):
     return B, features, channels, [m[2] for m in maps], [m[3] for m in maps]
 
 
+# ---- the ResNeXt backbone of MiDaS v2.1 (csrc/cvd_resnext.h) -----------------------------------------------------
+RESNEXT_GROUP_WIDTHS = (8, 16, 32, 64)         # channels per group the grouped kernel is built for
+RESNEXT_DENSE_KERNELS = ((1, 1), (1, 2), (7, 2))       # (kernel_size, stride) of the dense kernel's instantiations
+RESNEXT_MAX_SPLIT = 32
+RESNEXT101_32X8D = ((3, 4, 23, 3), 32, 8)      # blocks, groups, width_per_group of the reference's backbone
+RESNEXT_NORM_VECTORS = ("weight", "bias", "running_mean", "running_var")       # the order of a convolution's norm table
+RESNEXT_EPS = 1e-5
+
+RxConv = collections.namedtuple("RxConv", "name norm key norm_key weight_shape in_channels out_channels kernel_size stride groups")
+
+
+def resnext_conv_table(blocks=RESNEXT101_32X8D[0], groups=RESNEXT101_32X8D[1], width_per_group=RESNEXT101_32X8D[2]):
+    """The convolutions of torchvision's ResNet(Bottleneck, blocks, groups=groups, width_per_group=width_per_group) in the state dict's
+    order -- the stem, then per block conv1, conv2, conv3 and, in a stage's first block, downsample.0 --, the order of
+    cvd_midas_backbone_device's weight and norm tables.  Per convolution: torchvision's module names of the convolution and its
+    batch norm (`name`, `norm`), the same two under the reference's MidasNet.pretrained (`key`, `norm_key`: blocks.py:22-31 puts the
+    stem into layer1 as a Sequential), the weight's shape, channels, filter, stride and groups."""
+    blocks = tuple(int(b) for b in blocks)
+    groups, width_per_group = int(groups), int(width_per_group)
+    if len(blocks) != 4 or min(blocks) < 1:
+        raise ValueError(f"ResNeXt: blocks must be four counts >= 1 (got {blocks})")
+    if groups < 1 or width_per_group < 1:
+        raise ValueError(f"ResNeXt: groups and width_per_group must be >= 1 (got {groups}, {width_per_group})")
+    table = [RxConv("conv1", "bn1", "layer1.0", "layer1.1", (64, 3, 7, 7), 3, 64, 7, 2, 1)]
+    cin = 64
+    for k, count in enumerate(blocks):
+        planes = 64 << k
+        per = planes * width_per_group // 64
+        width, out = per * groups, 4 * planes
+        for i in range(count):
+            stride = 2 if (i == 0 and k > 0) else 1
+            tv = f"layer{k + 1}.{i}."
+            md = f"layer1.4.{i}." if k == 0 else tv
+            table.append(RxConv(tv + "conv1", tv + "bn1", md + "conv1", md + "bn1", (width, cin, 1, 1), cin, width, 1, 1, 1))
+            table.append(RxConv(tv + "conv2", tv + "bn2", md + "conv2", md + "bn2", (width, per, 3, 3), width, width, 3, stride, groups))
+            table.append(RxConv(tv + "conv3", tv + "bn3", md + "conv3", md + "bn3", (out, width, 1, 1), width, out, 1, 1, 1))
+            if i == 0:
+                table.append(RxConv(tv + "downsample.0", tv + "downsample.1", md + "downsample.0", md + "downsample.1", (out, cin, 1, 1),
+                                    cin, out, 1, stride, 1))
+            cin = out
+    return table
+
+
+def resnext_state_dict_keys(blocks=RESNEXT101_32X8D[0], groups=RESNEXT101_32X8D[1], width_per_group=RESNEXT101_32X8D[2],
+                            prefix="pretrained."):
+    """The backbone's state-dict keys under the reference's MidasNet in its order: per convolution its weight, then its batch norm's
+    weight, bias, running_mean, running_var and num_batches_tracked (624 keys for ResNeXt-101 32x8d)."""
+    keys = []
+    for c in resnext_conv_table(blocks, groups, width_per_group):
+        keys.append(prefix + c.key + ".weight")
+        keys.extend(prefix + c.norm_key + "." + v for v in RESNEXT_NORM_VECTORS + ("num_batches_tracked",))
+    return keys
+
+
+def resnext_split(K, HWo, kernel_size=1):
+    """The split count S of a dense convolution of csrc/cvd_resnext.h (rxSplit there) with K = in_channels kernel_size^2 whose OUTPUT
+    has HWo pixels per image: as many slices of K as bring the 64-pixel tiles of one image to 64 workgroups per channel tile, each
+    slice whole chains (8 chunks of 32 k for 1 x 1, 3 chunks of 98 for 7 x 7), at most 32.  A function of K and HWo alone."""
+    chunk_k, fold = (32, 8) if int(kernel_size) == 1 else (98, 3)
+    chunks = (int(K) + chunk_k - 1) // chunk_k
+    chains = (chunks + fold - 1) // fold
+    tiles = (int(HWo) + 63) // 64
+    want = max(1, min(64 // tiles, RESNEXT_MAX_SPLIT, chains))
+    per = (chains + want - 1) // want
+    return (chains + per - 1) // per
+
+
+def _resnext_norm(who, norm_shapes, eps, N):
+    if norm_shapes is None:
+        return
+    got = [tuple(int(v) for v in s) for s in norm_shapes]
+    if len(got) != 4 or any(g != (N,) for g in got):
+        raise ValueError(f"{who}: the norm must be the four vectors {RESNEXT_NORM_VECTORS} of shape ({N},) (got {got})")
+    if not eps > 0:
+        raise ValueError(f"{who}: eps must be > 0 (got {eps})")
+
+
+def _resnext_stride(who, stride):
+    stride = stride[0] if isinstance(stride, (tuple, list)) and len(set(stride)) == 1 else stride
+    if stride not in (1, 2):
+        raise ValueError(f"{who}: stride must be 1 or 2 (got {stride})")
+    return int(stride)
+
+
+def resnext_check_grouped_conv(x_shape, weight_shape, stride=1, norm_shapes=None, eps=RESNEXT_EPS):
+    """(B, H, W, groups, Cg, Ho, Wo) of the grouped 3 x 3 convolution: x [B, G Cg, H, W], weight [G Cg, Cg, 3, 3] with Cg in
+    RESNEXT_GROUP_WIDTHS, stride 1 or 2, padding 1, the norm's four [G Cg] vectors or None.  ValueError (before any device work) for
+    anything else."""
+    who = "ResNeXt grouped conv"
+    B, Cn, H, W = _midas_shape4(who, "x", x_shape)
+    ws = tuple(int(v) for v in weight_shape)
+    if len(ws) != 4 or ws[2:] != (3, 3):
+        raise ValueError(f"{who}: the filter must be 3 x 3 (weight {ws})")
+    if ws[0] != Cn:
+        raise ValueError(f"{who}: x has {Cn} channels, the weight {ws} writes {ws[0]} (in and out channels are equal)")
+    cg = ws[1]
+    if cg < 1 or Cn % cg:
+        raise ValueError(f"{who}: {Cn} channels are no whole groups of the weight's {cg} (weight {ws})")
+    if cg not in RESNEXT_GROUP_WIDTHS:
+        raise ValueError(f"{who}: channels per group must be one of {RESNEXT_GROUP_WIDTHS} (got {cg})")
+    stride = _resnext_stride(who, stride)
+    _resnext_norm(who, norm_shapes, eps, Cn)
+    return B, H, W, Cn // cg, cg, (H - 1) // stride + 1, (W - 1) // stride + 1
+
+
+def resnext_check_conv(x_shape, weight_shape, stride=1, norm_shapes=None, eps=RESNEXT_EPS, residual_shape=None, split=0):
+    """(B, H, W, Cin, N, k, Ho, Wo) of one dense convolution of csrc/cvd_resnext.h: x [B, Cin, H, W], weight [N, Cin, k, k] with
+    (k, stride) in RESNEXT_DENSE_KERNELS, padding k // 2, no bias, the norm's four [N] vectors or None, a residual of the output's
+    shape or None, split 0 (the rule) or 1 .. the chunks of K.  ValueError (before any device work) for anything else."""
+    who = "ResNeXt conv"
+    B, Cn, H, W = _midas_shape4(who, "x", x_shape)
+    ws = tuple(int(v) for v in weight_shape)
+    stride = _resnext_stride(who, stride)
+    if len(ws) != 4 or ws[2] != ws[3] or (ws[2], stride) not in RESNEXT_DENSE_KERNELS:
+        raise ValueError(f"{who}: (kernel_size, stride) must be one of {RESNEXT_DENSE_KERNELS} (weight {ws}, stride {stride})")
+    if ws[0] < 1:
+        raise ValueError(f"{who}: no output channels (weight {ws})")
+    if ws[1] != Cn:
+        raise ValueError(f"{who}: x has {Cn} channels, the weight {ws} takes {ws[1]}")
+    N, k = ws[0], ws[2]
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    _resnext_norm(who, norm_shapes, eps, N)
+    if residual_shape is not None and tuple(int(v) for v in residual_shape) != (B, N, Ho, Wo):
+        raise ValueError(f"{who}: the residual must be {(B, N, Ho, Wo)} (got {tuple(residual_shape)})")
+    cc = 32 if k == 1 else 2
+    chunks = (Cn + cc - 1) // cc
+    if int(split) != split or not 0 <= split <= chunks:
+        raise ValueError(f"{who}: split must be 0 (the rule) or 1 .. {chunks}, the chunks of K (got {split})")
+    return B, H, W, Cn, N, k, Ho, Wo
+
+
+def resnext_check_maxpool(x_shape):
+    """(B, C, H, W, Ho, Wo) of nn.MaxPool2d(3, 2, 1); ValueError for anything but a non-empty (B, C, H, W)."""
+    B, Cn, H, W = _midas_shape4("ResNeXt maxpool", "x", x_shape)
+    return B, Cn, H, W, (H - 1) // 2 + 1, (W - 1) // 2 + 1
+
+
+def resnext_check_backbone(image_shape, blocks, groups, width_per_group, weight_shapes, norm_shapes, eps=RESNEXT_EPS):
+    """(B, H, W, table, out_shapes) of the whole backbone: images [B, 3, H, W] with H and W multiples of 32, one weight and four norm
+    vectors per convolution of resnext_conv_table(blocks, groups, width_per_group); out_shapes = the four stages' outputs.
+    ValueError for anything else."""
+    who = "MiDaS backbone"
+    table = resnext_conv_table(blocks, groups, width_per_group)
+    B, Cn, H, W = _midas_shape4(who, "images", image_shape)
+    if Cn != 3:
+        raise ValueError(f"{who}: images must have 3 channels (got {Cn})")
+    if H % 32 or W % 32:
+        raise ValueError(f"{who}: height and width must be multiples of 32 (got {H} x {W})")
+    for k in range(4):
+        per = (64 << k) * int(width_per_group) // 64
+        if per not in RESNEXT_GROUP_WIDTHS:
+            raise ValueError(f"{who}: layer{k + 1} has {per} channels per group; {RESNEXT_GROUP_WIDTHS} are built "
+                             f"(width_per_group {width_per_group})")
+    if not eps > 0:
+        raise ValueError(f"{who}: eps must be > 0 (got {eps})")
+    if len(weight_shapes) != len(table) or len(norm_shapes) != len(table):
+        raise ValueError(f"{who}: {len(table)} weights and norms are expected (got {len(weight_shapes)}, {len(norm_shapes)})")
+    for c, w, four in zip(table, weight_shapes, norm_shapes):
+        if tuple(int(v) for v in w) != c.weight_shape:
+            raise ValueError(f"{who}: {c.name}.weight must be {c.weight_shape} (got {tuple(w)})")
+        _resnext_norm(f"{who}: {c.norm}", four, eps, c.out_channels)
+    return B, H, W, table, [(B, 256 << k, H >> (k + 2), W >> (k + 2)) for k in range(4)]
+
+
 class _DeviceArrays:
     """Raw device buffers of the numpy mirror of a `*_device` entry point (null stream, blocking copies); freed on exit."""
 
@@ -915,6 +1080,7 @@ EXPORTED_SYMBOLS = [
     "cvd_raft_corr_pyramid_device", "cvd_raft_corr_lookup_device", "cvd_raft_upsample_flow_device", "cvd_raft_sepconv_gru_device", "cvd_raft_sepconv_gru_timed", "cvd_raft_conv2d_device", "cvd_raft_update_block_device", "cvd_raft_update_block_timed",
     "cvd_raft_encoder_conv_device", "cvd_raft_instance_norm_device", "cvd_raft_encoder_device", "cvd_raft_encoder_timed",
     "cvd_midas_conv_device", "cvd_midas_upsample2x_device", "cvd_midas_head_device", "cvd_midas_decoder_device", "cvd_midas_decoder_timed",
+    "cvd_resnext_grouped_conv_device", "cvd_resnext_conv_device", "cvd_resnext_maxpool_device", "cvd_midas_backbone_device", "cvd_midas_backbone_timed",
     "cvd_get_summary", "cvd_num_records", "cvd_get_records",
     "cvd_get_kernel_times", "cvd_get_comm_times", "cvd_get_dense_times", "cvd_set_kernel_timing", "cvd_num_active_constraints", "cvd_coarse_debug", "cvd_temporal_debug", "cvd_path_info", "cvd_abi_revision",
     "cvd_block_inverse_debug", "cvd_dense_inverse_debug", "cvd_epipolar_debug", "cvd_flow_masks_debug",
@@ -1777,6 +1943,112 @@ class Solver(Binding):
                 raise RuntimeError("midas_decoder: the device reported an error")
             dev.download(do, out)
         return out
+
+    @staticmethod
+    def _resnext_norm(dev, norm):
+        import numpy as np
+        return None if norm is None else (C.c_void_p * 4)(*[dev.upload(np.ascontiguousarray(a)).value for a in norm])
+
+    def resnext_grouped_conv(self, x, weight, stride=1, norm=None, eps=RESNEXT_EPS, relu=False):
+        """nn.Conv2d(G Cg, G Cg, 3, stride, padding=1, groups=G, bias=False) (csrc/cvd_resnext.h): x [B, G Cg, H, W]
+        f32, weight [G Cg, Cg, 3, 3], Cg in RESNEXT_GROUP_WIDTHS -> [B, G Cg, Ho, Wo]; norm = (weight, bias, running_mean,
+        running_var) of the eval batch norm behind it or None; then ReLU under relu."""
+        import numpy as np
+        x, weight = np.asarray(x), np.asarray(weight)
+        norm = None if norm is None else [np.asarray(a) for a in norm]
+        self._midas_f32("resnext_grouped_conv", [x, weight] + (norm or []))
+        B, H, W, G, cg, Ho, Wo = resnext_check_grouped_conv(x.shape, weight.shape, stride, None if norm is None else [a.shape for a in norm],
+                                                            eps)
+        stride = _resnext_stride("resnext_grouped_conv", stride)
+        out = np.zeros((B, G * cg, Ho, Wo), np.float32)
+        with _DeviceArrays() as dev:
+            dx, dw = dev.upload(np.ascontiguousarray(x)), dev.upload(np.ascontiguousarray(weight))
+            dn = self._resnext_norm(dev, norm)
+            do = dev.alloc(out.nbytes)
+            self._check(self._fn("resnext_grouped_conv_device")(
+                self._h, C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(G), C.c_int32(cg), C.c_int32(stride), dx, dw, dn,
+                C.c_float(eps), C.c_int32(1 if relu else 0), do, None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("resnext_grouped_conv: the device reported an error")
+            dev.download(do, out)
+        return out
+
+    def resnext_conv(self, x, weight, stride=1, norm=None, eps=RESNEXT_EPS, relu=False, residual=None, split=0):
+        """One dense convolution of the backbone, without bias (csrc/cvd_resnext.h): x [B, C, H, W] f32, weight [N, C, k, k] with
+        (k, stride) in RESNEXT_DENSE_KERNELS, padding k // 2 -> [B, N, Ho, Wo]; the eval batch norm `norm` or None; ReLU under relu;
+        with a residual max(residual + y, 0).  split: 0 = the rule (resnext_split), else the forced number of slices of K."""
+        import numpy as np
+        x, weight = np.asarray(x), np.asarray(weight)
+        norm = None if norm is None else [np.asarray(a) for a in norm]
+        residual = None if residual is None else np.asarray(residual)
+        self._midas_f32("resnext_conv", [x, weight, residual] + (norm or []))
+        B, H, W, Cin, N, k, Ho, Wo = resnext_check_conv(x.shape, weight.shape, stride, None if norm is None else [a.shape for a in norm],
+                                                        eps, None if residual is None else residual.shape, split)
+        stride = _resnext_stride("resnext_conv", stride)
+        out = np.zeros((B, N, Ho, Wo), np.float32)
+        with _DeviceArrays() as dev:
+            dx, dw = dev.upload(np.ascontiguousarray(x)), dev.upload(np.ascontiguousarray(weight))
+            dn = self._resnext_norm(dev, norm)
+            dr = None if residual is None else dev.upload(np.ascontiguousarray(residual))
+            do = dev.alloc(out.nbytes)
+            self._check(self._fn("resnext_conv_device")(
+                self._h, C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(Cin), C.c_int32(N), C.c_int32(k), C.c_int32(stride), dx, dw,
+                dn, C.c_float(eps), C.c_int32(1 if relu else 0), dr, C.c_int32(split), do, None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("resnext_conv: the device reported an error")
+            dev.download(do, out)
+        return out
+
+    def resnext_maxpool(self, x):
+        """nn.MaxPool2d(3, 2, 1) of x [B, C, H, W] f32 (csrc/cvd_resnext.h) -> [B, C, Ho, Wo]; padding counts as minus infinity."""
+        import numpy as np
+        x = np.asarray(x)
+        self._midas_f32("resnext_maxpool", [x])
+        B, Cn, H, W, Ho, Wo = resnext_check_maxpool(x.shape)
+        out = np.zeros((B, Cn, Ho, Wo), np.float32)
+        with _DeviceArrays() as dev:
+            dx = dev.upload(np.ascontiguousarray(x))
+            do = dev.alloc(out.nbytes)
+            self._check(self._fn("resnext_maxpool_device")(self._h, C.c_int32(B), C.c_int32(Cn), C.c_int32(H), C.c_int32(W), dx, do, None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("resnext_maxpool: the device reported an error")
+            dev.download(do, out)
+        return out
+
+    def midas_backbone(self, images, weights, norms, blocks=RESNEXT101_32X8D[0], groups=RESNEXT101_32X8D[1],
+                       width_per_group=RESNEXT101_32X8D[2], eps=RESNEXT_EPS, kernel_ms=None):
+        """ResNet(Bottleneck, blocks, groups, width_per_group).forward up to layer4 in eval mode: images [B, 3, H, W]
+        f32 with sides that are multiples of 32, weights / norms = one weight and (weight, bias, running_mean, running_var) per
+        convolution of resnext_conv_table -> the four stages' outputs.  kernel_ms (measurement): a list that receives the per-launch
+        milliseconds of cvd_midas_backbone_timed (2 per convolution, then the pool)."""
+        import numpy as np
+        images = np.asarray(images)
+        weights = [np.asarray(a) for a in weights]
+        norms = [[np.asarray(a) for a in four] for four in norms]
+        self._midas_f32("midas_backbone", [images] + weights + [a for four in norms for a in four])
+        B, H, W, table, out_shapes = resnext_check_backbone(images.shape, blocks, groups, width_per_group, [a.shape for a in weights],
+                                                            [[a.shape for a in four] for four in norms], eps)
+        outs = [np.zeros(s, np.float32) for s in out_shapes]
+        n = len(table)
+        with _DeviceArrays() as dev:
+            di = dev.upload(np.ascontiguousarray(images))
+            dw = (C.c_void_p * n)(*[dev.upload(np.ascontiguousarray(a)).value for a in weights])
+            dn = (C.c_void_p * (4 * n))(*[dev.upload(np.ascontiguousarray(a)).value for four in norms for a in four])
+            douts = [dev.alloc(o.nbytes) for o in outs]
+            do = (C.c_void_p * 4)(*[d.value for d in douts])
+            args = (self._h, C.c_int32(B), C.c_int32(H), C.c_int32(W), (C.c_int32 * 4)(*[int(b) for b in blocks]), C.c_int32(groups),
+                    C.c_int32(width_per_group), C.c_float(eps), di, dw, dn, do, None)
+            if kernel_ms is None:
+                self._check(self._fn("midas_backbone_device")(*args))
+            else:
+                ms = (C.c_double * (2 * n + 1))()
+                self._check(self._fn("midas_backbone_timed")(*args, ms))
+                kernel_ms[:] = list(ms)
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("midas_backbone: the device reported an error")
+            for d, o in zip(douts, outs):
+                dev.download(d, o)
+        return outs
 
     def num_active_constraints(self):
         return int(self._lib.cvd_num_active_constraints(self._h))

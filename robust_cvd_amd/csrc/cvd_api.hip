@@ -942,6 +942,35 @@ int32_t cvd_midas_decoder_timed(cvd_handle* h, int32_t batch, int32_t features, 
   CVD_TRY(h, midasDecoderDevice(h, batch, features, channels4, heights4, widths4, maps, weights, biases, non_negative, out,
                                 static_cast<hipStream_t>(stream), kernel_ms));
 }
+// torchvision's ResNet(Bottleneck, ...) in eval mode, the backbone the reference's monodepth/midas_v2/blocks.py:6-31 builds
+int32_t cvd_resnext_grouped_conv_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t groups,
+                                        int32_t channels_per_group, int32_t stride, const float* x, const float* weight,
+                                        const float* const* norm, float eps, int32_t relu, float* out, void* stream) {
+  CVD_TRY(h, resnextGroupedConvDevice(h, batch, height, width, groups, channels_per_group, stride, x, weight, norm, eps, relu, out,
+                                      static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_resnext_conv_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels, int32_t out_channels,
+                                int32_t kernel_size, int32_t stride, const float* x, const float* weight, const float* const* norm,
+                                float eps, int32_t relu, const float* residual, int32_t split, float* out, void* stream) {
+  CVD_TRY(h, resnextConvDevice(h, batch, height, width, in_channels, out_channels, kernel_size, stride, x, weight, norm, eps, relu,
+                               residual, split, out, static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_resnext_maxpool_device(cvd_handle* h, int32_t batch, int32_t channels, int32_t height, int32_t width, const float* x,
+                                   float* out, void* stream) {
+  CVD_TRY(h, resnextMaxPoolDevice(h, batch, channels, height, width, x, out, static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_midas_backbone_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, const int32_t* blocks4, int32_t groups,
+                                  int32_t width_per_group, float eps, const float* images, const float* const* weights,
+                                  const float* const* norms, float* const* outs4, void* stream) {
+  CVD_TRY(h, midasBackboneDevice(h, batch, height, width, blocks4, groups, width_per_group, eps, images, weights, norms, outs4,
+                                 static_cast<hipStream_t>(stream), nullptr));
+}
+int32_t cvd_midas_backbone_timed(cvd_handle* h, int32_t batch, int32_t height, int32_t width, const int32_t* blocks4, int32_t groups,
+                                 int32_t width_per_group, float eps, const float* images, const float* const* weights,
+                                 const float* const* norms, float* const* outs4, void* stream, double* kernel_ms) {
+  CVD_TRY(h, midasBackboneDevice(h, batch, height, width, blocks4, groups, width_per_group, eps, images, weights, norms, outs4,
+                                 static_cast<hipStream_t>(stream), kernel_ms));
+}
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {

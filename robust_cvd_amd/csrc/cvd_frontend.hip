@@ -3,7 +3,8 @@
 // scene-flow and spatial losses, the parameter regulariser and the optimizer step, the fine-tuning batches, RAFT's correlation pyramid / lookup and convex
 // upsampling (cvd_raftops.h: k_corr_pyramid, k_corr_lookup, k_convex_upsample), the SepConvGRU of RAFT's update block
 // (cvd_raftgru.h: k_gru_gemm), its other convolutions (cvd_raftconv.h: k_raft_conv), RAFT's encoders (cvd_raftenc.h: k_enc_conv,
-// k_instnorm_stats, k_instnorm_apply) and the decoder of MiDaS v2.1 (cvd_midas.h: k_midas_conv, k_midas_fold, k_midas_upsample2x).  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
+// k_instnorm_stats, k_instnorm_apply) and the decoder of MiDaS v2.1 (cvd_midas.h: k_midas_conv, k_midas_fold, k_midas_upsample2x) and its
+// ResNeXt backbone (cvd_resnext.h: k_rx_gconv, k_rx_conv, k_rx_fold, k_rx_maxpool).  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
 // through a pointer to the incomplete type).
 #include "cvd_host.h"
 #include "cvd_dense.h"
@@ -25,6 +26,7 @@
 #include "cvd_raftconv.h"
 #include "cvd_raftenc.h"
 #include "cvd_midas.h"
+#include "cvd_resnext.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -145,6 +147,8 @@ struct Frontend {
   DevBuf<double> dEncStats;
   // cvd_midas.h: the decoder's intermediates and the partial sums of a split convolution, under the same rule.
   DevBuf<float> dMidas, dMidasSplit;
+  // cvd_resnext.h: the backbone's intermediates and the partial sums of a split convolution, under the same rule.
+  DevBuf<float> dRx, dRxSplit;
 };
 
 std::shared_ptr<Frontend> makeFrontend() { return std::make_shared<Frontend>(); }
@@ -3033,6 +3037,334 @@ void midasDecoderDevice(cvd_handle* h, int B, int features, const int* channels,
     timer.collect();
     std::fill(kernelMs, kernelMs + kSlots, 0.0);
     for (int i = 0; i < launches; ++i) kernelMs[slot[i]] = phaseMs[i];
+  }
+}
+
+// ---- The ResNeXt backbone of MiDaS v2.1 (torchvision's ResNet(Bottleneck, blocks, groups, width_per_group) in eval mode, which the
+// reference's monodepth/midas_v2/blocks.py:6-31 builds; cvd_resnext.h).  Device arrays on the caller's stream:
+// enqueued launches only. ---------------------------------------------------------------------------------------------------------------
+namespace {
+struct RxDims {
+  long long HW, HWo, M;
+  int Ho, Wo;
+};
+
+RxDims checkRxShape(const char* who, int B, int H, int W, int stride) {
+  if (B < 1 || H < 1 || W < 1) throw std::runtime_error(fmt("%s: batch, height and width must be >= 1 (got %d, %d, %d)", who, B, H, W));
+  if (stride != 1 && stride != 2) throw std::runtime_error(fmt("%s: stride must be 1 or 2 (got %d)", who, stride));
+  RxDims d{};
+  d.HW = static_cast<long long>(H) * W;
+  if (d.HW > 0x7fffffffll) throw std::runtime_error(fmt("%s: %d x %d pixels per image exceed 2^31", who, H, W));
+  d.Ho = (H - 1) / stride + 1;
+  d.Wo = (W - 1) / stride + 1;
+  d.HWo = static_cast<long long>(d.Ho) * d.Wo;
+  d.M = d.HWo * B;
+  if ((d.M + kRxTile - 1) / kRxTile > 0x7fffffffll) throw std::runtime_error(fmt("%s: %lld pixels exceed the grid", who, d.M));
+  return d;
+}
+
+void checkRxNorm(const char* who, const float* const* norm, float eps) {
+  if (!norm) return;
+  for (int i = 0; i < 4; ++i)
+    if (!norm[i]) throw std::runtime_error(fmt("%s: null norm vector %d", who, i));
+  if (!(eps > 0.f)) throw std::runtime_error(fmt("%s: eps must be > 0 (got %g)", who, static_cast<double>(eps)));
+}
+
+bool rxGroupWidthBuilt(int cg) { return cg == 8 || cg == 16 || cg == 32 || cg == 64; }
+
+// the dense convolution's channel counts and filter against the instantiations and the grid
+void checkRxChannels(const char* who, int Cin, int N, int ks, int stride, long long M) {
+  if (ks != 1 && ks != 7) throw std::runtime_error(fmt("%s: kernel_size must be 1 or 7 (got %d)", who, ks));
+  if (ks == 7 && stride != 2) throw std::runtime_error(fmt("%s: kernel_size 7 is built for stride 2 only (got stride %d)", who, stride));
+  if (Cin < 1) throw std::runtime_error(fmt("%s: in_channels must be >= 1 (got %d)", who, Cin));
+  if (N < 1) throw std::runtime_error(fmt("%s: out_channels must be >= 1 (got %d)", who, N));
+  if (static_cast<long long>(Cin) * ks * ks > 0x7fffffffll) throw std::runtime_error(fmt("%s: in_channels %d exceeds the kernel's range", who, Cin));
+  if ((N + kRxTile - 1) / kRxTile > 65535) throw std::runtime_error(fmt("%s: out_channels %d exceeds the grid", who, N));
+  if ((M * N + kRxThreads - 1) / kRxThreads > 0x7fffffffll)
+    throw std::runtime_error(fmt("%s: %lld pixels of %d channels exceed the grid", who, M, N));
+}
+
+void checkRxGroups(const char* who, int G, int cg, long long M) {
+  if (G < 1) throw std::runtime_error(fmt("%s: groups must be >= 1 (got %d)", who, G));
+  if (!rxGroupWidthBuilt(cg)) throw std::runtime_error(fmt("%s: channels per group must be 8, 16, 32 or 64 (got %d)", who, cg));
+  const long long N = static_cast<long long>(G) * cg;
+  if ((N + kRxGroupTileN - 1) / kRxGroupTileN > 65535) throw std::runtime_error(fmt("%s: %d groups of %d channels exceed the grid", who, G, cg));
+  if (M * N / kRxThreads > 0x7fffffffll) throw std::runtime_error(fmt("%s: %lld pixels of %lld channels exceed the kernel's range", who, M, N));
+}
+
+int rxChunks(int Cin, int ks) {
+  const int cc = ks == 1 ? RxShape<1>::kChunkChannels : RxShape<7>::kChunkChannels;
+  return (Cin + cc - 1) / cc;
+}
+
+// the split the convolution runs with: `forced` >= 1 as given (checked by the caller), 0 = the rule
+int rxSplitFor(int Cin, int ks, long long HWo, int forced) {
+  return forced > 0 ? forced : rxSplit(static_cast<long long>(Cin) * ks * ks, HWo, ks);
+}
+
+size_t rxSplitFloats(int S, long long M, int N) { return S > 1 ? static_cast<size_t>(S) * static_cast<size_t>(M) * N : 0; }
+
+void rxNormArgs(RxConvArgs& A, const float* const* norm, float eps) {
+  if (norm) {
+    A.gamma = norm[0]; A.beta = norm[1]; A.mean = norm[2]; A.var = norm[3];
+  }
+  A.eps = eps;
+}
+
+template <int KS, int STRIDE>
+void launchRxConvK(const RxConvArgs& A, bool vec, dim3 grid, hipStream_t s) {
+  if (vec) hipLaunchKernelGGL((k_rx_conv<KS, STRIDE, true>), grid, dim3(kRxThreads), 0, s, A);
+  else hipLaunchKernelGGL((k_rx_conv<KS, STRIDE, false>), grid, dim3(kRxThreads), 0, s, A);
+}
+
+// One dense convolution: one launch, with S > 1 the fold behind it.  Checked by the callers; `partial` holds rxSplitFloats floats.
+// norm: {weight, bias, running_mean, running_var} or null.  mark (may be empty) is called after each launch.
+template <class Mark>
+void launchRxConv(int B, int H, int W, int Cin, int N, int ks, int stride, const float* x, const float* w, const float* const* norm,
+                  float eps, int relu, const float* residual, int S, float* partial, float* out, hipStream_t s, Mark&& mark) {
+  RxConvArgs A{};
+  A.x = x; A.w = w; A.residual = residual; A.out = out; A.partial = partial; A.relu = relu;
+  rxNormArgs(A, norm, eps);
+  A.Cin = Cin; A.N = N;
+  A.H = H; A.W = W; A.HW = H * W;
+  A.Ho = (H - 1) / stride + 1; A.Wo = (W - 1) / stride + 1; A.HWo = A.Ho * A.Wo;
+  A.M = static_cast<long long>(A.HWo) * B;
+  const int fold = ks == 1 ? RxShape<1>::kFold : RxShape<7>::kFold;
+  const int chunks = rxChunks(Cin, ks), chains = (chunks + fold - 1) / fold;
+  const int per = (chains + S - 1) / S;                   // chains per slice
+  A.S = (chains + per - 1) / per;                         // (the rule's S already has this form; a forced one may shrink)
+  A.chunksPerSlice = per * fold;
+  const dim3 grid(static_cast<unsigned>((A.M + kRxTile - 1) / kRxTile), static_cast<unsigned>((N + kRxTile - 1) / kRxTile),
+                  static_cast<unsigned>(A.S));
+  // float4 weight loads only where every row starts on 16 bytes
+  const bool vec = (static_cast<long long>(Cin) * ks * ks) % 4 == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0;
+  if (ks == 7) hipLaunchKernelGGL((k_rx_conv<7, 2, false>), grid, dim3(kRxThreads), 0, s, A);
+  else if (stride == 1) launchRxConvK<1, 1>(A, vec, grid, s);
+  else launchRxConvK<1, 2>(A, vec, grid, s);
+  HIP_CHECK(hipGetLastError());
+  mark();
+  if (A.S == 1) return;
+  hipLaunchKernelGGL(k_rx_fold, dim3(static_cast<unsigned>((A.M * N + kRxThreads - 1) / kRxThreads)), dim3(kRxThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+  mark();
+}
+
+template <int CG>
+void launchRxGroupConvK(const RxConvArgs& A, int stride, dim3 grid, hipStream_t s) {
+  if (stride == 1) hipLaunchKernelGGL((k_rx_gconv<CG, 1>), grid, dim3(kRxThreads), 0, s, A);
+  else hipLaunchKernelGGL((k_rx_gconv<CG, 2>), grid, dim3(kRxThreads), 0, s, A);
+}
+
+// One grouped 3 x 3 convolution over G groups of cg channels: one launch.  Checked by the callers.
+void launchRxGroupConv(int B, int H, int W, int G, int cg, int stride, const float* x, const float* w, const float* const* norm,
+                       float eps, int relu, float* out, hipStream_t s) {
+  RxConvArgs A{};
+  A.x = x; A.w = w; A.out = out; A.relu = relu;
+  rxNormArgs(A, norm, eps);
+  A.Cin = A.N = G * cg;
+  A.H = H; A.W = W; A.HW = H * W;
+  A.Ho = (H - 1) / stride + 1; A.Wo = (W - 1) / stride + 1; A.HWo = A.Ho * A.Wo;
+  A.M = static_cast<long long>(A.HWo) * B;
+  A.S = 1;
+  const dim3 grid(static_cast<unsigned>((A.M + kRxTile - 1) / kRxTile), static_cast<unsigned>((A.N + kRxGroupTileN - 1) / kRxGroupTileN));
+  switch (cg) {
+    case 8: launchRxGroupConvK<8>(A, stride, grid, s); break;
+    case 16: launchRxGroupConvK<16>(A, stride, grid, s); break;
+    case 32: launchRxGroupConvK<32>(A, stride, grid, s); break;
+    default: launchRxGroupConvK<64>(A, stride, grid, s); break;
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+void checkRxPoolSize(const char* who, long long planes, long long HWo) {
+  if (planes > 0x7fffffffll || (planes * HWo + kRxThreads - 1) / kRxThreads > 0x7fffffffll)
+    throw std::runtime_error(fmt("%s: %lld planes of %lld elements exceed the grid", who, planes, HWo));
+}
+
+void launchRxMaxPool(long long planes, int H, int W, const float* x, float* out, hipStream_t s) {
+  RxPoolArgs A{};
+  A.x = x; A.out = out; A.H = H; A.W = W;
+  A.Ho = (H - 1) / 2 + 1; A.Wo = (W - 1) / 2 + 1;
+  A.total = planes * A.Ho * A.Wo;
+  hipLaunchKernelGGL(k_rx_maxpool, dim3(static_cast<unsigned>((A.total + kRxThreads - 1) / kRxThreads)), dim3(kRxThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+}
+}  // namespace
+
+void resnextGroupedConvDevice(cvd_handle*, int B, int H, int W, int groups, int channelsPerGroup, int stride, const float* x,
+                              const float* weight, const float* const* norm, float eps, int relu, float* out, hipStream_t s) {
+  const char* who = "resnext grouped conv";
+  const RxDims d = checkRxShape(who, B, H, W, stride);
+  checkRxGroups(who, groups, channelsPerGroup, d.M);
+  checkFlag(who, "relu", relu);
+  if (!x || !weight || !out) throw std::runtime_error(fmt("%s: null array", who));
+  checkRxNorm(who, norm, eps);
+  const long long N = static_cast<long long>(groups) * channelsPerGroup;
+  if (rangesOverlap(out, d.M * N, x, d.HW * B * N)) throw std::runtime_error(fmt("%s: out overlaps x", who));
+  launchRxGroupConv(B, H, W, groups, channelsPerGroup, stride, x, weight, norm, eps, relu, out, s);
+}
+
+void resnextConvDevice(cvd_handle* h, int B, int H, int W, int inChannels, int outChannels, int kernelSize, int stride, const float* x,
+                       const float* weight, const float* const* norm, float eps, int relu, const float* residual, int split, float* out,
+                       hipStream_t s) {
+  const char* who = "resnext conv";
+  const RxDims d = checkRxShape(who, B, H, W, stride);
+  checkRxChannels(who, inChannels, outChannels, kernelSize, stride, d.M);
+  checkFlag(who, "relu", relu);
+  const int chunks = rxChunks(inChannels, kernelSize);
+  if (split < 0 || split > chunks)
+    throw std::runtime_error(fmt("%s: split must be 0 (the rule) or 1 .. %d, the chunks of K (got %d)", who, chunks, split));
+  if (!x || !weight || !out) throw std::runtime_error(fmt("%s: null array", who));
+  checkRxNorm(who, norm, eps);
+  const long long outFloats = d.M * outChannels;
+  if (rangesOverlap(out, outFloats, x, d.HW * B * inChannels)) throw std::runtime_error(fmt("%s: out overlaps x", who));
+  if (residual && rangesOverlap(out, outFloats, residual, outFloats)) throw std::runtime_error(fmt("%s: out overlaps the residual", who));
+  const int S = rxSplitFor(inChannels, kernelSize, d.HWo, split);
+  Frontend& fe = *h->frontend;
+  fe.dRxSplit.ensure(rxSplitFloats(S, d.M, outChannels));
+  launchRxConv(B, H, W, inChannels, outChannels, kernelSize, stride, x, weight, norm, eps, relu, residual, S, fe.dRxSplit.p, out, s, [] {});
+}
+
+void resnextMaxPoolDevice(cvd_handle*, int B, int channels, int H, int W, const float* x, float* out, hipStream_t s) {
+  const char* who = "resnext maxpool";
+  if (channels < 1) throw std::runtime_error(fmt("%s: channels must be >= 1 (got %d)", who, channels));
+  const RxDims d = checkRxShape(who, B, H, W, 2);
+  const long long planes = static_cast<long long>(B) * channels;
+  checkRxPoolSize(who, planes, d.HWo);
+  if (!x || !out) throw std::runtime_error(fmt("%s: null array", who));
+  if (rangesOverlap(out, planes * d.HWo, x, planes * d.HW)) throw std::runtime_error(fmt("%s: out overlaps x", who));
+  launchRxMaxPool(planes, H, W, x, out, s);
+}
+
+// ResNet.forward up to layer4 as MidasNet.forward reads it (the four stages' outputs).  blocks: the four stages' block counts.
+// weights: one per convolution in the state dict's order (the stem, then per block conv1, conv2, conv3 and, in a stage's first
+// block, downsample.0); norms: 4 vectors per convolution in the same order.  outs: the four stages' outputs.
+// kernelMs (measurement only, may be null): 2 convolutions + 1 entries; with it the call waits on the host.
+void midasBackboneDevice(cvd_handle* h, int B, int H, int W, const int* blocks, int groups, int widthPerGroup, float eps,
+                         const float* images, const float* const* weights, const float* const* norms, float* const* outs,
+                         hipStream_t s, double* kernelMs) {
+  const char* who = "midas backbone";
+  if (!blocks || !images || !weights || !norms || !outs) throw std::runtime_error(fmt("%s: null array", who));
+  if (B < 1 || H < 1 || W < 1) throw std::runtime_error(fmt("%s: batch, height and width must be >= 1 (got %d, %d, %d)", who, B, H, W));
+  if (H % 32 != 0 || W % 32 != 0) throw std::runtime_error(fmt("%s: height and width must be multiples of 32 (got %d x %d)", who, H, W));
+  if (groups < 1) throw std::runtime_error(fmt("%s: groups must be >= 1 (got %d)", who, groups));
+  if (widthPerGroup < 1) throw std::runtime_error(fmt("%s: width_per_group must be >= 1 (got %d)", who, widthPerGroup));
+  if (!(eps > 0.f)) throw std::runtime_error(fmt("%s: eps must be > 0 (got %g)", who, static_cast<double>(eps)));
+  checkRxShape(who, B, H, W, 2);
+  int cg[4], width[4], outC[4], hs[4], ws[4], numConvs = 1;
+  long long outFloats[4];
+  const size_t b = static_cast<size_t>(B);
+  for (int k = 0; k < 4; ++k) {
+    if (blocks[k] < 1) throw std::runtime_error(fmt("%s: blocks of layer%d must be >= 1 (got %d)", who, k + 1, blocks[k]));
+    if (blocks[k] > 1000000) throw std::runtime_error(fmt("%s: blocks of layer%d exceed the call's range (got %d)", who, k + 1, blocks[k]));
+    const long long planes = 64ll << k, per = planes * widthPerGroup / 64;
+    if (per > 64 || !rxGroupWidthBuilt(static_cast<int>(per)))
+      throw std::runtime_error(fmt("%s: layer%d has %lld channels per group; 8, 16, 32 and 64 are built (width_per_group %d)", who, k + 1,
+                                   per, widthPerGroup));
+    cg[k] = static_cast<int>(per);
+    outC[k] = static_cast<int>(4 * planes);
+    hs[k] = H >> (k + 2);
+    ws[k] = W >> (k + 2);
+    const long long M = static_cast<long long>(B) * hs[k] * ws[k];
+    checkRxGroups(who, groups, cg[k], 4 * M);
+    width[k] = groups * cg[k];
+    checkRxChannels(who, width[k], outC[k], 1, 1, M);
+    checkRxChannels(who, outC[k], width[k], 1, 1, 4 * M);
+    outFloats[k] = M * outC[k];
+    numConvs += 3 * blocks[k] + 1;
+  }
+  checkRxChannels(who, 3, 64, 7, 2, static_cast<long long>(B) * (H / 2) * (W / 2));
+  checkRxPoolSize(who, static_cast<long long>(B) * 64, static_cast<long long>(H / 4) * (W / 4));
+  for (int i = 0; i < numConvs; ++i) {
+    if (!weights[i]) throw std::runtime_error(fmt("%s: null weight %d", who, i));
+    for (int j = 0; j < 4; ++j)
+      if (!norms[4 * i + j]) throw std::runtime_error(fmt("%s: null norm vector %d of convolution %d", who, j, i));
+  }
+  for (int k = 0; k < 4; ++k) {
+    if (!outs[k]) throw std::runtime_error(fmt("%s: null output map %d", who, k + 1));
+    if (rangesOverlap(outs[k], outFloats[k], images, static_cast<long long>(b) * 3 * H * W))
+      throw std::runtime_error(fmt("%s: output map %d overlaps the images", who, k + 1));
+    for (int j = 0; j < k; ++j)
+      if (rangesOverlap(outs[k], outFloats[k], outs[j], outFloats[j]))
+        throw std::runtime_error(fmt("%s: output map %d overlaps output map %d", who, k + 1, j + 1));
+  }
+
+  // scratch: the stem's output, the pooled map, a block's two middle tensors and its downsample branch at their largest, two
+  // rotating block outputs; and the split convolutions' partial sums
+  const size_t m2 = b * (H / 2) * (W / 2), m4 = b * (H / 4) * (W / 4);
+  size_t t1 = 0, t2 = 0, big = 0, split = 0;
+  {
+    int Cin = 64, hin = H / 4, win = W / 4;
+    for (int k = 0; k < 4; ++k) {
+      const size_t mIn = b * hin * win, mOut = b * hs[k] * ws[k];
+      const long long hwIn = static_cast<long long>(hin) * win, hwOut = static_cast<long long>(hs[k]) * ws[k];
+      t1 = std::max(t1, std::max(mIn, mOut) * width[k]);
+      t2 = std::max(t2, mOut * width[k]);
+      big = std::max(big, mOut * outC[k]);
+      split = std::max(split, rxSplitFloats(rxSplitFor(Cin, 1, hwIn, 0), static_cast<long long>(mIn), width[k]));        // first conv1
+      split = std::max(split, rxSplitFloats(rxSplitFor(Cin, 1, hwOut, 0), static_cast<long long>(mOut), outC[k]));       // downsample.0
+      split = std::max(split, rxSplitFloats(rxSplitFor(outC[k], 1, hwOut, 0), static_cast<long long>(mOut), width[k]));  // later conv1
+      split = std::max(split, rxSplitFloats(rxSplitFor(width[k], 1, hwOut, 0), static_cast<long long>(mOut), outC[k]));  // conv3
+      Cin = outC[k]; hin = hs[k]; win = ws[k];
+    }
+  }
+  Frontend& fe = *h->frontend;
+  fe.dRx.ensure(64 * m2 + 64 * m4 + t1 + t2 + 3 * big);
+  fe.dRxSplit.ensure(split);
+  float* stem = fe.dRx.p;
+  float* pooled = stem + 64 * m2;
+  float* T1 = pooled + 64 * m4;
+  float* T2 = T1 + t1;
+  float* DS = T2 + t2;
+  float* R[2] = {DS + big, DS + 2 * big};
+
+  const int slots = 2 * numConvs + 1;
+  std::vector<double> phaseMs(kernelMs ? slots : 0);
+  std::vector<int> slot;
+  slot.reserve(slots);
+  KernelTimer timer(s, kernelMs ? phaseMs.data() : nullptr, slots);
+  timer.mark();
+  const auto conv = [&](int idx, const float* x, int Cin, int hin, int win, int N, int ks, int stride, int relu, const float* residual,
+                        float* y) {
+    int part = 0;
+    const long long hwo = static_cast<long long>((hin - 1) / stride + 1) * ((win - 1) / stride + 1);
+    launchRxConv(B, hin, win, Cin, N, ks, stride, x, weights[idx], norms + 4 * idx, eps, relu, residual, rxSplitFor(Cin, ks, hwo, 0),
+                 fe.dRxSplit.p, y, s, [&] {
+                   slot.push_back(2 * idx + part++);
+                   timer.mark();
+                 });
+  };
+  conv(0, images, 3, H, W, 64, 7, 2, 1, nullptr, stem);
+  launchRxMaxPool(static_cast<long long>(B) * 64, H / 2, W / 2, stem, pooled, s);
+  slot.push_back(2 * numConvs);
+  timer.mark();
+  const float* cur = pooled;
+  int Cin = 64, hin = H / 4, win = W / 4, idx = 1, turn = 0;
+  for (int k = 0; k < 4; ++k) {
+    for (int blk = 0; blk < blocks[k]; ++blk) {
+      const int stride = blk == 0 && k > 0 ? 2 : 1;
+      const bool down = blk == 0;                       // stride 2 or in != 4 planes: every stage's first block
+      conv(idx, cur, Cin, hin, win, width[k], 1, 1, 1, nullptr, T1);
+      launchRxGroupConv(B, hin, win, groups, cg[k], stride, T1, weights[idx + 1], norms + 4 * (idx + 1), eps, 1, T2, s);
+      slot.push_back(2 * (idx + 1));
+      timer.mark();
+      const float* residual = cur;
+      if (down) {
+        conv(idx + 3, cur, Cin, hin, win, outC[k], 1, stride, 0, nullptr, DS);
+        residual = DS;
+      }
+      float* y = blk == blocks[k] - 1 ? outs[k] : R[turn ^= 1];
+      conv(idx + 2, T2, width[k], hs[k], ws[k], outC[k], 1, 1, 0, residual, y);
+      cur = y;
+      Cin = outC[k]; hin = hs[k]; win = ws[k];
+      idx += down ? 4 : 3;
+    }
+  }
+  if (kernelMs) {
+    timer.wait();
+    timer.collect();
+    std::fill(kernelMs, kernelMs + slots, 0.0);
+    for (size_t i = 0; i < slot.size(); ++i) kernelMs[slot[i]] = phaseMs[i];
   }
 }
 

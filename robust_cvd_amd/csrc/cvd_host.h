@@ -822,4 +822,15 @@ void midasDecoderDevice(cvd_handle* h, int B, int features, const int* channels,
                         const float* const* maps, const float* const* weights, const float* const* biases, int nonNegative, float* out,
                         hipStream_t s, double* kernelMs);
 
+// the ResNeXt backbone of MiDaS v2.1 (cvd_resnext.h)
+void resnextGroupedConvDevice(cvd_handle* h, int B, int H, int W, int groups, int channelsPerGroup, int stride, const float* x,
+                              const float* weight, const float* const* norm, float eps, int relu, float* out, hipStream_t s);
+void resnextConvDevice(cvd_handle* h, int B, int H, int W, int inChannels, int outChannels, int kernelSize, int stride, const float* x,
+                       const float* weight, const float* const* norm, float eps, int relu, const float* residual, int split, float* out,
+                       hipStream_t s);
+void resnextMaxPoolDevice(cvd_handle* h, int B, int channels, int H, int W, const float* x, float* out, hipStream_t s);
+void midasBackboneDevice(cvd_handle* h, int B, int H, int W, const int* blocks, int groups, int widthPerGroup, float eps,
+                         const float* images, const float* const* weights, const float* const* norms, float* const* outs,
+                         hipStream_t s, double* kernelMs);
+
 }  // namespace cvd
