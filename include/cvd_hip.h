@@ -906,6 +906,97 @@ int32_t cvd_midas_decoder_timed(cvd_handle* h, int32_t batch, int32_t features, 
                                 const int32_t* widths4, const float* const* maps, const float* const* weights,
                                 const float* const* biases, int32_t non_negative, float* out, void* stream, double* kernel_ms);
 
+/* ---- Backward of the decoder's layers, DESIGN.md §3.21 (csrc/cvd_midas_grad.h): what torch's autograd computes for the reference's
+ * nn.Conv2d(stride 1, padding kernel_size / 2) -- monodepth/midas_v2/blocks.py:39-50 (layerK_rn), 100-107 (ResidualConvUnit),
+ * midas_net.py:36-40 (output_conv) -- and for nn.functional.interpolate(scale_factor=2, mode="bilinear") -- blocks.py:54-84
+ * (Interpolate), 155-157 (FeatureFusionBlock) -- and for the output head; then the whole decoder's training forward and backward as
+ * one call each, which robust_cvd_amd/midas_train.py's MidasNet uses.  f32, DEVICE
+ * arrays, enqueued on `stream`: kernel launches only, no copy, no host synchronisation, no atomics; every output element is written
+ * once in a fixed operation order, so results repeat bit for bit.  Scratch of the handle under the rule of cvd_midas_conv_device.
+ *
+ * Input gradient of one convolution, gy [batch][out_channels][height][width], weight [out_channels][in_channels][k][k] ->
+ * gx [batch][in_channels][height][width]:
+ *   sum = sum_{n,i,j} gy[b][n][y - i + r][x - j + r] weight[n][c][i][j], gy outside the image counting 0
+ *   t   = sum;  add != NULL (like gx): t = t + add;  mask != NULL (like gx): t = mask > 0 ? t : 0   (torch's ReLU: gradient 0 at 0)
+ * (a ResidualConvUnit's input ReLU is the mask; its skip path the addend: (dgrad(g) + gy) [x > 0].)  It runs cvd_midas_conv_device's
+ * kernel on the transposed, flipped filter (a small launch writes it to scratch): the same padding scheme and the same split rule
+ * from K = out_channels k k and height width alone, so a batch's gradients are the bits of its images one by one; the partial sums
+ * are summed in f64 in slice order and rounded once, then the epilogue.  split: 0 = the rule, 1 .. the chunks of K = forced.
+ * Rejected before any device work: null arrays (add, mask may be NULL), sizes < 1, a filter other than 1, 3, a split outside its
+ * range, height width above 2^31, gx overlapping gy, weight, add or mask. */
+int32_t cvd_midas_conv_grad_input_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels,
+                                         int32_t out_channels, int32_t kernel_size, const float* gy, const float* weight, const float* add,
+                                         const float* mask, int32_t split, float* gx, void* stream);
+/* Weight and bias gradient of one convolution, gy as above, x [batch][in_channels][height][width] the convolution's input ->
+ * g_weight [out_channels][in_channels][k][k], g_bias [out_channels] (NULL: not computed):
+ *   g_weight[n][c][i][j] = sum_{b,y,x} gy[b][n][y][x] x'[b][c][y + i - r][x + j - r], x' = max(x, 0) with relu_in, else x, 0 outside
+ *   g_bias[n]            = sum_{b,y,x} gy[b][n][y][x]   (f64 sums in a fixed order, rounded once)
+ * A GEMM over the batch height width pixels on the exact f32 MFMA: fmaf chains of 256 pixels in pixel order, each added to a second
+ * register set as it completes.  split: 0 = the rule, S = a function of (batch height width, out_channels, in_channels k k) alone
+ * (cvd_midas_grad.h: midasWgradSplit); 1 .. 128 = forced (it shrinks to whole chains, no slice empty).  With S > 1 the S slices of the
+ * pixels write partial sums to scratch [S][out_channels][in_channels k k] and a second launch sums them in f64 in the order
+ * s = 0 .. S - 1 and rounds once.
+ * Rejected before any device work: null arrays (g_bias may be NULL), sizes < 1, a filter other than 1, 3, a flag other than 0, 1, a
+ * split outside its range, height width above 2^31, a gradient that overlaps an input or the other gradient. */
+int32_t cvd_midas_conv_grad_weight_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels,
+                                          int32_t out_channels, int32_t kernel_size, const float* gy, const float* x, int32_t relu_in,
+                                          int32_t split, float* g_weight, float* g_bias, void* stream);
+/* Backward of cvd_midas_upsample2x_device: gy [batch][channels][2 height][2 width] -> gx [batch][channels][height][width], ONE launch
+ * in gather form: one thread per element of gx sums the (at most 8 x 8 candidates, classified by the forward's own f32 source
+ * coordinate) outputs that read it, with the forward's f32 weights, rows then columns ascending.  On a 1 x 1 input gx is the sum of
+ * the four gy.  gx must not overlap gy. */
+int32_t cvd_midas_upsample2x_grad_device(cvd_handle* h, int32_t batch, int32_t channels, int32_t height, int32_t width,
+                                         int32_t align_corners, const float* gy, float* gx, void* stream);
+
+/* Backward of cvd_midas_head_device (midas_net.py:38-41), y = relu?(b4 + sum_n w4[n] relu(t_n)), t = output_conv.2(x) + bias2:
+ *   g_s = gy [y > 0] with non_negative, else gy;  g32[n] = g_s w4[n] [t_n > 0]
+ *   g_weight4[n] = sum_p g_s relu(t_n), g_bias4 = sum_p g_s: f64 products and sums, per workgroup then over the workgroups in order
+ *   g_weight2, g_bias2 = the weight gradient above on (g32, x);  gx = the input gradient above on (g32, weight2)
+ * gy [batch][height][width], x and the parameters as cvd_midas_head_device -> gx like x, the four parameter gradients like their
+ * parameters.  The forward never writes t: it is recomputed in scratch by cvd_midas_conv_device's kernel with one slice, whose chain
+ * per element is the head launch's own, so the masks come from the forward's own f32 t; y is recomputed by the head launch.
+ * Rejected before any device work: null arrays, sizes < 1, mid_channels other than 32, a flag other than 0, 1, an output that
+ * overlaps an input or another output. */
+int32_t cvd_midas_head_grad_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels, int32_t mid_channels,
+                                   const float* gy, const float* x, const float* weight2, const float* bias2, const float* weight4,
+                                   const float* bias4, int32_t non_negative, float* gx, float* g_weight2, float* g_bias2, float* g_weight4,
+                                   float* g_bias4, void* stream);
+
+/* cvd_midas_decoder_device for training (midas_net.py:57-74 under autograd): the same launches with the same arguments -- out equals
+ * cvd_midas_decoder_device's bit for bit -- but the activations the backward reads are written to the caller's table instead of
+ * scratch.  saved16: host array of 16 device arrays, shapes as api.midas_saved_shapes:
+ *   0 .. 3   the layerK_rn results [batch][features][heights4[k]][widths4[k]]
+ *   4        refinenet4.resConfUnit2.conv1's result (level 4)
+ *   5 .. 13  for refinenet3, refinenet2, refinenet1 three each at their level: resConfUnit1.conv1's result, the fusion sum
+ *            (resConfUnit2's input), resConfUnit2.conv1's result
+ *   14       output_conv.0's input  [batch][features][2 heights4[0]][2 widths4[0]]
+ *   15       output_conv.0's result [batch][128][2 heights4[0]][2 widths4[0]]
+ * The 128-channel full-resolution tensor (the head's input) is NOT saved: the backward recomputes it from entry 15 with the forward's
+ * own upsampling launch, the same bits, for a quarter of the memory.  Rejected like cvd_midas_decoder_device, and: a null saved
+ * table or entry, a saved tensor that overlaps out or a feature map. */
+int32_t cvd_midas_decoder_train_device(cvd_handle* h, int32_t batch, int32_t features, const int32_t* channels4, const int32_t* heights4,
+                                       const int32_t* widths4, const float* const* maps, const float* const* weights,
+                                       const float* const* biases, int32_t non_negative, float* const* saved16, float* out, void* stream);
+/* The decoder's backward in ONE call: gy [batch][4 heights4[0]][4 widths4[0]], the feature maps, the saved table and the parameters ->
+ * g_weights (21) and g_biases (17) in the order of the weight and bias tables, and g_maps (4, like maps; NULL skips the four
+ * layerK_rn input gradients).  It chains the four entry points above in the reverse of the forward's order (the head on the
+ * recomputed input, output_conv.0, then refinenet1 .. refinenet4 with their layerK_rn), so its results equal theirs bit for bit,
+ * repeat bit for bit, and the map gradients of a batch are those of its images one by one.  Intermediates are scratch of the handle.
+ * Rejected before any device work: null arrays or entries (g_maps may be NULL), sizes < 1, feature maps that are not exact halvings,
+ * a flag other than 0, 1, and what the four entry points reject. */
+int32_t cvd_midas_decoder_backward_device(cvd_handle* h, int32_t batch, int32_t features, const int32_t* channels4, const int32_t* heights4,
+                                          const int32_t* widths4, const float* gy, const float* const* maps, const float* const* saved16,
+                                          const float* const* weights, const float* const* biases, int32_t non_negative,
+                                          float* const* g_weights, float* const* g_biases, float* const* g_maps, void* stream);
+/* The same call for measurement (tools/midas_grad_bench.py): HIP events around every operator call it makes (each one to three
+ * launches: transform or convolution, fold, bias) on `stream` and a host wait; kernel_ms[48]: the stages in the order they run
+ * (api.midas_backward_stages names them), the rest 0, in milliseconds. */
+int32_t cvd_midas_decoder_backward_timed(cvd_handle* h, int32_t batch, int32_t features, const int32_t* channels4, const int32_t* heights4,
+                                         const int32_t* widths4, const float* gy, const float* const* maps, const float* const* saved16,
+                                         const float* const* weights, const float* const* biases, int32_t non_negative,
+                                         float* const* g_weights, float* const* g_biases, float* const* g_maps, void* stream,
+                                         double* kernel_ms);
+
 /* ---- the backbone of MiDaS v2.1 (csrc/cvd_resnext.h): torchvision's ResNet(Bottleneck, blocks, groups,
  * width_per_group) in eval mode -- the ResNeXt-101 32x8d that the reference's monodepth/midas_v2/blocks.py:6-31 builds -- on device
  * arrays, f32, forward only, launches on `stream` with no host synchronisation.  No atomics: a call repeats bit for bit.  An axis of

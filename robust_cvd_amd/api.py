@@ -797,6 +797,100 @@ def midas_check_decoder(map_shapes, weight_shapes, bias_shapes):
     return B, features, channels, [m[2] for m in maps], [m[3] for m in maps]
 
 
+# ---- backward of the decoder's layers (csrc/cvd_midas_grad.h) -----------------------------------------------------
+MIDAS_WGRAD_CHAIN = 256                # pixels of one fmaf chain of the weight gradient
+MIDAS_WGRAD_MAX_SPLIT = 128
+
+
+def midas_wgrad_split(pixels, out_channels, columns):
+    """The split count S of a weight gradient of csrc/cvd_midas_grad.h (midasWgradSplit there) over `pixels` = B H W with
+    `out_channels` rows and `columns` = in_channels kernel_size^2: as many slices of the pixels as bring the 64 x 64 tiles of the
+    weight tensor to 1024 workgroups, each slice whole chains of 256 pixels, at most 128.  A function of the three sizes alone."""
+    tiles = ((int(out_channels) + 63) // 64) * ((int(columns) + 63) // 64)
+    chains = (int(pixels) + MIDAS_WGRAD_CHAIN - 1) // MIDAS_WGRAD_CHAIN
+    want = max(1, min(1024 // tiles, MIDAS_WGRAD_MAX_SPLIT, chains))
+    per = (chains + want - 1) // want
+    return (chains + per - 1) // per
+
+
+def midas_check_conv_grad_input(gy_shape, weight_shape, add_shape=None, mask_shape=None, split=0):
+    """(B, H, W, Cin, N, k) of the input gradient of one convolution: gy [B, N, H, W], weight [N, Cin, k, k] with k in (1, 3), the
+    addend and the mask of gx's shape [B, Cin, H, W] or None, split 0 (the rule) or 1 .. the chunks of K = N k k.  ValueError
+    (before any device work) for anything else."""
+    who = "MiDaS conv grad input"
+    B, N, H, W = _midas_shape4(who, "gy", gy_shape)
+    ws = tuple(int(v) for v in weight_shape)
+    if len(ws) != 4 or ws[2] != ws[3] or ws[2] not in MIDAS_KERNEL_SIZES:
+        raise ValueError(f"{who}: the filter must be square of size {MIDAS_KERNEL_SIZES} (weight {ws})")
+    if ws[0] != N:
+        raise ValueError(f"{who}: gy has {N} channels, the weight {ws} gives {ws[0]}")
+    if ws[1] < 1:
+        raise ValueError(f"{who}: no input channels (weight {ws})")
+    Cin, k = ws[1], ws[2]
+    for name, s in (("addend", add_shape), ("mask", mask_shape)):
+        if s is not None and tuple(int(v) for v in s) != (B, Cin, H, W):
+            raise ValueError(f"{who}: the {name} must be {(B, Cin, H, W)} (got {tuple(s)})")
+    chunks = (N + (32 if k == 1 else 8) - 1) // (32 if k == 1 else 8)
+    if int(split) != split or not 0 <= split <= chunks:
+        raise ValueError(f"{who}: split must be 0 (the rule) or 1 .. {chunks}, the chunks of K (got {split})")
+    return B, H, W, Cin, N, k
+
+
+def midas_check_conv_grad_weight(gy_shape, x_shape, kernel_size, split=0):
+    """(B, H, W, Cin, N, k) of the weight gradient of one convolution: gy [B, N, H, W], x [B, Cin, H, W], k in (1, 3), split 0 (the
+    rule) or 1 .. 128 (a forced split shrinks to whole chains of 256 pixels).  ValueError for anything else."""
+    who = "MiDaS conv grad weight"
+    B, N, H, W = _midas_shape4(who, "gy", gy_shape)
+    B2, Cin, H2, W2 = _midas_shape4(who, "x", x_shape)
+    if (B2, H2, W2) != (B, H, W):
+        raise ValueError(f"{who}: gy {tuple(gy_shape)} and x {tuple(x_shape)} differ in batch or size")
+    if kernel_size not in MIDAS_KERNEL_SIZES:
+        raise ValueError(f"{who}: the filter must be square of size {MIDAS_KERNEL_SIZES} (got {kernel_size})")
+    if int(split) != split or not 0 <= split <= MIDAS_WGRAD_MAX_SPLIT:
+        raise ValueError(f"{who}: split must be 0 (the rule) or 1 .. {MIDAS_WGRAD_MAX_SPLIT} (got {split})")
+    return B, H, W, Cin, N, int(kernel_size)
+
+
+def midas_check_upsample2x_grad(gy_shape):
+    """(B, C, H, W) of the INPUT of the upsampling whose output gradient is gy [B, C, 2 H, 2 W]."""
+    who = "MiDaS upsample2x grad"
+    B, Cn, Ho, Wo = _midas_shape4(who, "gy", gy_shape)
+    if Ho % 2 or Wo % 2:
+        raise ValueError(f"{who}: gy must be (B, C, 2 H, 2 W) (got {tuple(gy_shape)})")
+    if Ho * Wo > 2 ** 31 - 1:
+        raise ValueError(f"{who}: {Ho} x {Wo} output pixels per plane exceed 2^31")
+    return B, Cn, Ho // 2, Wo // 2
+
+
+MIDAS_SAVED = 16                       # tensors of cvd_midas_decoder_train_device's table
+MIDAS_BACKWARD_SLOTS = 48              # kernel_ms of cvd_midas_decoder_backward_timed
+
+
+def midas_saved_shapes(batch, features, heights, widths):
+    """The 16 shapes of the table cvd_midas_decoder_train_device fills, for feature maps of `heights` x `widths` (layer1 first): the
+    four layerK_rn results; refinenet4.resConfUnit2.conv1's result; for refinenet3, 2, 1 each resConfUnit1.conv1's result, the fusion
+    sum and resConfUnit2.conv1's result; output_conv.0's input and its result (the head's input is recomputed from it)."""
+    B, F = int(batch), int(features)
+    level = [(B, F, int(h), int(w)) for h, w in zip(heights, widths)]
+    twice = (2 * int(heights[0]), 2 * int(widths[0]))
+    return level + [level[3]] + [level[k] for k in (2, 1, 0) for _ in range(3)] + [(B, F) + twice, (B, 128) + twice]
+
+
+def midas_backward_stages(with_maps=True):
+    """Names of the operator calls cvd_midas_decoder_backward_device makes, in the order of cvd_midas_decoder_backward_timed's
+    kernel_ms: `<layer>:wgrad` / `<layer>:dgrad` / upsamplings / the head."""
+    P = MIDAS_PARAMETERS
+    out = ["output_conv.1:upsample (recomputed)", "head:backward", "output_conv.1:upsample_grad", P[18] + ":wgrad", P[18] + ":dgrad"]
+    for k in range(4):
+        w0 = 4 if k == 3 else 6 + 4 * (2 - k)
+        u2 = w0 if k == 3 else w0 + 2
+        out += [f"refinenet{k + 1}:upsample_grad", P[u2 + 1] + ":wgrad", P[u2 + 1] + ":dgrad", P[u2] + ":wgrad", P[u2] + ":dgrad"]
+        if k < 3:
+            out += [P[w0 + 1] + ":wgrad", P[w0 + 1] + ":dgrad", P[w0] + ":wgrad", P[w0] + ":dgrad"]
+        out += [P[k] + ":wgrad"] + ([P[k] + ":dgrad"] if with_maps else [])
+    return out
+
+
 # ---- the ResNeXt backbone of MiDaS v2.1 (csrc/cvd_resnext.h, DESIGN.md §3.20) -----------------------------------------------------
 RESNEXT_GROUP_WIDTHS = (8, 16, 32, 64)         # channels per group the grouped kernel is built for
 RESNEXT_DENSE_KERNELS = ((1, 1), (1, 2), (7, 2))       # (kernel_size, stride) of the dense kernel's instantiations
@@ -1080,6 +1174,8 @@ EXPORTED_SYMBOLS = [
     "cvd_raft_corr_pyramid_device", "cvd_raft_corr_lookup_device", "cvd_raft_upsample_flow_device", "cvd_raft_sepconv_gru_device", "cvd_raft_sepconv_gru_timed", "cvd_raft_conv2d_device", "cvd_raft_update_block_device", "cvd_raft_update_block_timed",
     "cvd_raft_encoder_conv_device", "cvd_raft_instance_norm_device", "cvd_raft_encoder_device", "cvd_raft_encoder_timed",
     "cvd_midas_conv_device", "cvd_midas_upsample2x_device", "cvd_midas_head_device", "cvd_midas_decoder_device", "cvd_midas_decoder_timed",
+    "cvd_midas_conv_grad_input_device", "cvd_midas_conv_grad_weight_device", "cvd_midas_upsample2x_grad_device", "cvd_midas_head_grad_device",
+    "cvd_midas_decoder_train_device", "cvd_midas_decoder_backward_device", "cvd_midas_decoder_backward_timed",
     "cvd_resnext_grouped_conv_device", "cvd_resnext_conv_device", "cvd_resnext_maxpool_device", "cvd_midas_backbone_device", "cvd_midas_backbone_timed",
     "cvd_get_summary", "cvd_num_records", "cvd_get_records",
     "cvd_get_kernel_times", "cvd_get_comm_times", "cvd_get_dense_times", "cvd_set_kernel_timing", "cvd_num_active_constraints", "cvd_coarse_debug", "cvd_temporal_debug", "cvd_path_info", "cvd_abi_revision",
@@ -1913,6 +2009,160 @@ class Solver(Binding):
                 raise RuntimeError("midas_head: the device reported an error")
             dev.download(do, out)
         return out
+
+    def midas_conv_grad_input(self, gy, weight, add=None, mask=None, split=0):
+        """Input gradient of one convolution of the MiDaS decoder (csrc/cvd_midas_grad.h): gy [B, N, H, W] f32,
+        weight [N, C, k, k] -> gx [B, C, H, W] = conv_transpose(gy, weight); + add with an addend; zero where mask <= 0 with a mask.
+        split: 0 = the rule (midas_split of K = N k k), else the forced number of slices of K."""
+        import numpy as np
+        gy, weight = np.asarray(gy), np.asarray(weight)
+        add, mask = (None if v is None else np.asarray(v) for v in (add, mask))
+        self._midas_f32("midas_conv_grad_input", [gy, weight, add, mask])
+        B, H, W, Cin, N, k = midas_check_conv_grad_input(gy.shape, weight.shape, None if add is None else add.shape,
+                                                         None if mask is None else mask.shape, split)
+        out = np.zeros((B, Cin, H, W), np.float32)
+        with _DeviceArrays() as dev:
+            dg, dw = dev.upload(np.ascontiguousarray(gy)), dev.upload(np.ascontiguousarray(weight))
+            da, dm = (None if v is None else dev.upload(np.ascontiguousarray(v)) for v in (add, mask))
+            do = dev.alloc(out.nbytes)
+            self._check(self._fn("midas_conv_grad_input_device")(
+                self._h, C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(Cin), C.c_int32(N), C.c_int32(k), dg, dw, da, dm,
+                C.c_int32(split), do, None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("midas_conv_grad_input: the device reported an error")
+            dev.download(do, out)
+        return out
+
+    def midas_conv_grad_weight(self, gy, x, kernel_size, relu_in=False, bias=True, split=0):
+        """Weight and bias gradient of one convolution (csrc/cvd_midas_grad.h): gy [B, N, H, W] f32, x [B, C, H, W] the
+        convolution's input (rectified first under relu_in) -> (gW [N, C, k, k], gbias [N], or None with bias=False).  split: 0 = the
+        rule (midas_wgrad_split), else the forced number of slices of the pixels."""
+        import numpy as np
+        gy, x = np.asarray(gy), np.asarray(x)
+        self._midas_f32("midas_conv_grad_weight", [gy, x])
+        B, H, W, Cin, N, k = midas_check_conv_grad_weight(gy.shape, x.shape, kernel_size, split)
+        gw = np.zeros((N, Cin, k, k), np.float32)
+        gb = np.zeros((N,), np.float32) if bias else None
+        with _DeviceArrays() as dev:
+            dg, dx = dev.upload(np.ascontiguousarray(gy)), dev.upload(np.ascontiguousarray(x))
+            dw = dev.alloc(gw.nbytes)
+            db = dev.alloc(gb.nbytes) if bias else None
+            self._check(self._fn("midas_conv_grad_weight_device")(
+                self._h, C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(Cin), C.c_int32(N), C.c_int32(k), dg, dx,
+                C.c_int32(1 if relu_in else 0), C.c_int32(split), dw, db, None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("midas_conv_grad_weight: the device reported an error")
+            dev.download(dw, gw)
+            if bias:
+                dev.download(db, gb)
+        return gw, gb
+
+    def midas_upsample2x_grad(self, gy, align_corners=True):
+        """Backward of midas_upsample2x (csrc/cvd_midas_grad.h): gy [B, C, 2 H, 2 W] f32 -> gx [B, C, H, W]."""
+        import numpy as np
+        gy = np.asarray(gy)
+        self._midas_f32("midas_upsample2x_grad", [gy])
+        B, Cn, H, W = midas_check_upsample2x_grad(gy.shape)
+        out = np.zeros((B, Cn, H, W), np.float32)
+        with _DeviceArrays() as dev:
+            dg = dev.upload(np.ascontiguousarray(gy))
+            do = dev.alloc(out.nbytes)
+            self._check(self._fn("midas_upsample2x_grad_device")(
+                self._h, C.c_int32(B), C.c_int32(Cn), C.c_int32(H), C.c_int32(W), C.c_int32(1 if align_corners else 0), dg, do, None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("midas_upsample2x_grad: the device reported an error")
+            dev.download(do, out)
+        return out
+
+    def midas_decoder_train(self, maps, weights, biases, non_negative=True):
+        """midas_decoder that also returns the activations the backward needs (cvd_midas_decoder_train_device): -> (out [B, H, W],
+        saved: the 16 arrays of midas_saved_shapes).  out equals midas_decoder's bit for bit."""
+        import numpy as np
+        maps, weights, biases = ([np.asarray(a) for a in v] for v in (maps, weights, biases))
+        self._midas_f32("midas_decoder_train", maps + weights + biases)
+        B, features, channels, heights, widths = midas_check_decoder([v.shape for v in maps], [v.shape for v in weights],
+                                                                         [v.shape for v in biases])
+        out = np.zeros((B, 4 * heights[0], 4 * widths[0]), np.float32)
+        saved = [np.zeros(s, np.float32) for s in midas_saved_shapes(B, features, heights, widths)]
+        with _DeviceArrays() as dev:
+            up = lambda arrays: [dev.upload(np.ascontiguousarray(a)).value for a in arrays]
+            dm, dw, db = (C.c_void_p * 4)(*up(maps)), (C.c_void_p * 21)(*up(weights)), (C.c_void_p * 17)(*up(biases))
+            dsv = [dev.alloc(a.nbytes) for a in saved]
+            do = dev.alloc(out.nbytes)
+            self._check(self._fn("midas_decoder_train_device")(
+                self._h, C.c_int32(B), C.c_int32(features), (C.c_int32 * 4)(*channels), (C.c_int32 * 4)(*heights), (C.c_int32 * 4)(*widths),
+                dm, dw, db, C.c_int32(1 if non_negative else 0), (C.c_void_p * MIDAS_SAVED)(*[p.value for p in dsv]), do, None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("midas_decoder_train: the device reported an error")
+            dev.download(do, out)
+            for p, a in zip(dsv, saved):
+                dev.download(p, a)
+        return out, saved
+
+    def midas_decoder_backward(self, gy, maps, saved, weights, biases, non_negative=True, map_gradients=True, kernel_ms=None):
+        """The decoder's backward in one library call (cvd_midas_decoder_backward_device): gy [B, H, W] f32, the feature maps, the
+        saved table of midas_decoder_train and the parameters -> (weight gradients (21), bias gradients (17), map gradients (4) or
+        None with map_gradients=False).  kernel_ms: a list that receives cvd_midas_decoder_backward_timed's milliseconds."""
+        import numpy as np
+        gy = np.asarray(gy)
+        maps, saved, weights, biases = ([np.asarray(a) for a in v] for v in (maps, saved, weights, biases))
+        self._midas_f32("midas_decoder_backward", [gy] + maps + saved + weights + biases)
+        B, features, channels, heights, widths = midas_check_decoder([v.shape for v in maps], [v.shape for v in weights],
+                                                                         [v.shape for v in biases])
+        if tuple(gy.shape) != (B, 4 * heights[0], 4 * widths[0]):
+            raise ValueError(f"MiDaS decoder backward: gy must be {(B, 4 * heights[0], 4 * widths[0])} (got {tuple(gy.shape)})")
+        want = midas_saved_shapes(B, features, heights, widths)
+        if [tuple(a.shape) for a in saved] != want:
+            raise ValueError(f"MiDaS decoder backward: the saved table must have the shapes {want}")
+        gw, gb = [np.zeros(a.shape, np.float32) for a in weights], [np.zeros(a.shape, np.float32) for a in biases]
+        gm = [np.zeros(a.shape, np.float32) for a in maps] if map_gradients else None
+        with _DeviceArrays() as dev:
+            up = lambda arrays: [dev.upload(np.ascontiguousarray(a)).value for a in arrays]
+            new = lambda arrays: [dev.alloc(a.nbytes) for a in arrays]
+            dg = dev.upload(np.ascontiguousarray(gy))
+            dm, dsv = (C.c_void_p * 4)(*up(maps)), (C.c_void_p * MIDAS_SAVED)(*up(saved))
+            dw, db = (C.c_void_p * 21)(*up(weights)), (C.c_void_p * 17)(*up(biases))
+            pgw, pgb, pgm = new(gw), new(gb), (new(gm) if map_gradients else None)
+            args = (self._h, C.c_int32(B), C.c_int32(features), (C.c_int32 * 4)(*channels), (C.c_int32 * 4)(*heights),
+                    (C.c_int32 * 4)(*widths), dg, dm, dsv, dw, db, C.c_int32(1 if non_negative else 0),
+                    (C.c_void_p * 21)(*[p.value for p in pgw]), (C.c_void_p * 17)(*[p.value for p in pgb]),
+                    (C.c_void_p * 4)(*[p.value for p in pgm]) if map_gradients else None, None)
+            if kernel_ms is None:
+                self._check(self._fn("midas_decoder_backward_device")(*args))
+            else:
+                ms = (C.c_double * MIDAS_BACKWARD_SLOTS)()
+                self._check(self._fn("midas_decoder_backward_timed")(*args, ms))
+                kernel_ms[:] = list(ms)
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("midas_decoder_backward: the device reported an error")
+            for ptrs, arrays in ((pgw, gw), (pgb, gb)) + (((pgm, gm),) if map_gradients else ()):
+                for p, a in zip(ptrs, arrays):
+                    dev.download(p, a)
+        return gw, gb, gm
+
+    def midas_head_grad(self, gy, x, weight2, bias2, weight4, bias4, non_negative=True):
+        """Backward of midas_head (csrc/cvd_midas_grad.h): gy [B, H, W] f32 and the head's inputs -> (gx, gW2, gb2, gW4, gb4) in the
+        shapes of x and the four parameters."""
+        import numpy as np
+        arrays = [np.asarray(v) for v in (x, weight2, bias2, weight4, bias4)]
+        gy = np.asarray(gy)
+        self._midas_f32("midas_head_grad", arrays + [gy])
+        B, H, W, Cin = midas_check_head(*[v.shape for v in arrays])
+        if tuple(gy.shape) != (B, H, W):
+            raise ValueError(f"MiDaS head grad: gy must be {(B, H, W)} (got {tuple(gy.shape)})")
+        outs = [np.zeros(v.shape, np.float32) for v in arrays]
+        with _DeviceArrays() as dev:
+            dg = dev.upload(np.ascontiguousarray(gy))
+            dx, dw2, db2, dw4, db4 = (dev.upload(np.ascontiguousarray(v)) for v in arrays)
+            douts = [dev.alloc(o.nbytes) for o in outs]
+            self._check(self._fn("midas_head_grad_device")(
+                self._h, C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(Cin), C.c_int32(MIDAS_HEAD_MID), dg, dx, dw2, db2, dw4, db4,
+                C.c_int32(1 if non_negative else 0), *douts, None))
+            if _hip_runtime().hipDeviceSynchronize() != 0:
+                raise RuntimeError("midas_head_grad: the device reported an error")
+            for d, o in zip(douts, outs):
+                dev.download(d, o)
+        return tuple(outs)
 
     def midas_decoder(self, maps, weights, biases, non_negative=True, kernel_ms=None):
         """MidasNet.forward behind the backbone (monodepth/midas_v2/midas_net.py:62-74): maps = the four feature

@@ -942,6 +942,56 @@ int32_t cvd_midas_decoder_timed(cvd_handle* h, int32_t batch, int32_t features, 
   CVD_TRY(h, midasDecoderDevice(h, batch, features, channels4, heights4, widths4, maps, weights, biases, non_negative, out,
                                 static_cast<hipStream_t>(stream), kernel_ms));
 }
+// torch autograd's gradients of the same layers: nn.Conv2d (blocks.py:39-50, 100-107; midas_net.py:36-40) with respect to its input and
+// to its weight and bias, and nn.functional.interpolate (blocks.py:54-84, 155-157)
+int32_t cvd_midas_conv_grad_input_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels,
+                                         int32_t out_channels, int32_t kernel_size, const float* gy, const float* weight, const float* add,
+                                         const float* mask, int32_t split, float* gx, void* stream) {
+  CVD_TRY(h, midasConvGradInputDevice(h, batch, height, width, in_channels, out_channels, kernel_size, gy, weight, add, mask, split, gx,
+                                      static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_midas_conv_grad_weight_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels,
+                                          int32_t out_channels, int32_t kernel_size, const float* gy, const float* x, int32_t relu_in,
+                                          int32_t split, float* g_weight, float* g_bias, void* stream) {
+  CVD_TRY(h, midasConvGradWeightDevice(h, batch, height, width, in_channels, out_channels, kernel_size, gy, x, relu_in, split, g_weight,
+                                       g_bias, static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_midas_upsample2x_grad_device(cvd_handle* h, int32_t batch, int32_t channels, int32_t height, int32_t width,
+                                         int32_t align_corners, const float* gy, float* gx, void* stream) {
+  CVD_TRY(h, midasUpsample2xGradDevice(h, batch, channels, height, width, align_corners, gy, gx, static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_midas_head_grad_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels, int32_t mid_channels,
+                                   const float* gy, const float* x, const float* weight2, const float* bias2, const float* weight4,
+                                   const float* bias4, int32_t non_negative, float* gx, float* g_weight2, float* g_bias2, float* g_weight4,
+                                   float* g_bias4, void* stream) {
+  CVD_TRY(h, midasHeadGradDevice(h, batch, height, width, in_channels, mid_channels, gy, x, weight2, bias2, weight4, bias4, non_negative, gx,
+                                 g_weight2, g_bias2, g_weight4, g_bias4, static_cast<hipStream_t>(stream)));
+}
+// MidasNet.forward behind the backbone (midas_net.py:57-74) keeping what torch's autograd would keep, and its backward
+int32_t cvd_midas_decoder_train_device(cvd_handle* h, int32_t batch, int32_t features, const int32_t* channels4, const int32_t* heights4,
+                                       const int32_t* widths4, const float* const* maps, const float* const* weights,
+                                       const float* const* biases, int32_t non_negative, float* const* saved16, float* out, void* stream) {
+  CVD_TRY(h, {
+    if (!saved16) throw std::runtime_error("midas decoder train: null saved table");
+    midasDecoderDevice(h, batch, features, channels4, heights4, widths4, maps, weights, biases, non_negative, out,
+                       static_cast<hipStream_t>(stream), nullptr, saved16);
+  });
+}
+int32_t cvd_midas_decoder_backward_device(cvd_handle* h, int32_t batch, int32_t features, const int32_t* channels4, const int32_t* heights4,
+                                          const int32_t* widths4, const float* gy, const float* const* maps, const float* const* saved16,
+                                          const float* const* weights, const float* const* biases, int32_t non_negative,
+                                          float* const* g_weights, float* const* g_biases, float* const* g_maps, void* stream) {
+  CVD_TRY(h, midasDecoderBackwardDevice(h, batch, features, channels4, heights4, widths4, gy, maps, saved16, weights, biases, non_negative,
+                                        g_weights, g_biases, g_maps, static_cast<hipStream_t>(stream), nullptr));
+}
+int32_t cvd_midas_decoder_backward_timed(cvd_handle* h, int32_t batch, int32_t features, const int32_t* channels4, const int32_t* heights4,
+                                         const int32_t* widths4, const float* gy, const float* const* maps, const float* const* saved16,
+                                         const float* const* weights, const float* const* biases, int32_t non_negative,
+                                         float* const* g_weights, float* const* g_biases, float* const* g_maps, void* stream,
+                                         double* kernel_ms) {
+  CVD_TRY(h, midasDecoderBackwardDevice(h, batch, features, channels4, heights4, widths4, gy, maps, saved16, weights, biases, non_negative,
+                                        g_weights, g_biases, g_maps, static_cast<hipStream_t>(stream), kernel_ms));
+}
 // torchvision's ResNet(Bottleneck, ...) in eval mode, the backbone the reference's monodepth/midas_v2/blocks.py:6-31 builds
 int32_t cvd_resnext_grouped_conv_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t groups,
                                         int32_t channels_per_group, int32_t stride, const float* x, const float* weight,

@@ -3,7 +3,9 @@
 // scene-flow and spatial losses, the parameter regulariser and the optimizer step, the fine-tuning batches, RAFT's correlation pyramid / lookup and convex
 // upsampling (cvd_raftops.h: k_corr_pyramid, k_corr_lookup, k_convex_upsample), the SepConvGRU of RAFT's update block
 // (cvd_raftgru.h: k_gru_gemm), its other convolutions (cvd_raftconv.h: k_raft_conv), RAFT's encoders (cvd_raftenc.h: k_enc_conv,
-// k_instnorm_stats, k_instnorm_apply) and the decoder of MiDaS v2.1 (cvd_midas.h: k_midas_conv, k_midas_fold, k_midas_upsample2x) and its
+// k_instnorm_stats, k_instnorm_apply) and the decoder of MiDaS v2.1 (cvd_midas.h: k_midas_conv, k_midas_fold, k_midas_upsample2x), the backward of its layers
+// (cvd_midas_grad.h: k_midas_wflip, k_midas_dgrad_fold, k_midas_wgrad, k_midas_wgrad_fold, k_midas_bias_grad, k_midas_upsample2x_grad,
+// k_midas_head_grad, k_midas_head_grad_sum) and its
 // ResNeXt backbone (cvd_resnext.h: k_rx_gconv, k_rx_conv, k_rx_fold, k_rx_maxpool).  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
 // through a pointer to the incomplete type).
 #include "cvd_host.h"
@@ -26,6 +28,7 @@
 #include "cvd_raftconv.h"
 #include "cvd_raftenc.h"
 #include "cvd_midas.h"
+#include "cvd_midas_grad.h"
 #include "cvd_resnext.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -147,6 +150,15 @@ struct Frontend {
   DevBuf<double> dEncStats;
   // cvd_midas.h: the decoder's intermediates and the partial sums of a split convolution, under the same rule.
   DevBuf<float> dMidas, dMidasSplit;
+  // cvd_midas_grad.h: the flipped, transposed filter of an input gradient and the partial sums of a split weight gradient, under
+  // the same rule (an input gradient's partial sums lie in dMidasSplit: it runs the forward's convolution).
+  DevBuf<float> dMidasGradW, dMidasGradSplit;
+  // the head's backward: its recomputed pre-activation t, the gradient of t, its recomputed output; the per-workgroup sums
+  DevBuf<float> dMidasHeadGrad;
+  // the one-call decoder backward: the recomputed head input, its gradient, output_conv.0's output gradient, the path gradient and
+  // five rotating tensors of the largest level
+  DevBuf<float> dMidasBackward;
+  DevBuf<double> dMidasHeadPart;
   // cvd_resnext.h: the backbone's intermediates and the partial sums of a split convolution, under the same rule.
   DevBuf<float> dRx, dRxSplit;
 };
@@ -2926,8 +2938,8 @@ void midasHeadDevice(cvd_handle*, int B, int H, int W, int inChannels, int midCh
 // call waits on the host.
 void midasDecoderDevice(cvd_handle* h, int B, int features, const int* channels, const int* heights, const int* widths,
                         const float* const* maps, const float* const* weights, const float* const* biases, int nonNegative, float* out,
-                        hipStream_t s, double* kernelMs) {
-  const char* who = "midas decoder";
+                        hipStream_t s, double* kernelMs, float* const* saved) {
+  const char* who = saved ? "midas decoder train" : "midas decoder";
   if (!channels || !heights || !widths || !maps || !weights || !biases || !out) throw std::runtime_error(fmt("%s: null array", who));
   if (features < 1) throw std::runtime_error(fmt("%s: features must be >= 1 (got %d)", who, features));
   checkFlag(who, "non_negative", nonNegative);
@@ -2982,6 +2994,31 @@ void midasDecoderDevice(cvd_handle* h, int B, int features, const int* channels,
   float* P = base + oP;
   float* H0 = base + oH0;
   float* Hup = base + oH1;
+  // Training: the activations the backward reads go to the caller's table (kMidasSaved tensors, the order of midasSavedIndex) and not
+  // to scratch; the launches and their arguments' values are the same, so the output is the same bits.
+  float *tU1[4] = {T0, T0, T0, T0}, *sumO[4] = {T1, T1, T1, T1}, *tU2[4] = {T0, T0, T0, T0};
+  float* P0 = P;
+  if (saved) {
+    for (int i = 0; i < kMidasSaved; ++i)
+      if (!saved[i]) throw std::runtime_error(fmt("%s: null saved tensor %d", who, i));
+    const size_t big = 128 * 4 * static_cast<size_t>(M[0]);
+    for (int i = 0; i < kMidasSaved; ++i) {
+      const int lvl = i < 4 ? i : i == 4 ? 3 : i < 14 ? 2 - (i - 5) / 3 : 0;
+      const size_t count = i == 14 ? 4 * n[0] : i == 15 ? big : n[lvl];
+      if (rangesOverlap(out, Mout, saved[i], static_cast<long long>(count))) throw std::runtime_error(fmt("%s: out overlaps saved tensor %d", who, i));
+      for (int k = 0; k < 4; ++k)
+        if (rangesOverlap(saved[i], static_cast<long long>(count), maps[k], M[k] * channels[k]))
+          throw std::runtime_error(fmt("%s: saved tensor %d overlaps feature map %d", who, i, k + 1));
+    }
+    for (int k = 0; k < 4; ++k) L[k] = saved[k];
+    tU2[3] = saved[4];
+    for (int k = 2; k >= 0; --k) {
+      const int at = 5 + 3 * (2 - k);
+      tU1[k] = saved[at]; sumO[k] = saved[at + 1]; tU2[k] = saved[at + 2];
+    }
+    P0 = saved[14];
+    H0 = saved[15];
+  }
 
   constexpr int kSlots = 44;
   double phaseMs[kSlots];
@@ -3010,19 +3047,19 @@ void midasDecoderDevice(cvd_handle* h, int B, int features, const int* channels,
     const int w0 = k == 3 ? 4 : 6 + 4 * (2 - k);         // the block's first weight: rn4 has resConfUnit2 only
     const float* o = L[k];
     if (k < 3) {
-      conv(w0, k, L[k], features, features, 1, nullptr, nullptr, T0);           // resConfUnit1.conv1(relu(x1))
-      conv(w0 + 1, k, T0, features, features, 1, L[k], P, T1);                  // path + (conv2(relu(.)) + relu(x1))
-      o = T1;
+      conv(w0, k, L[k], features, features, 1, nullptr, nullptr, tU1[k]);       // resConfUnit1.conv1(relu(x1))
+      conv(w0 + 1, k, tU1[k], features, features, 1, L[k], P, sumO[k]);         // path + (conv2(relu(.)) + relu(x1))
+      o = sumO[k];
     }
     const int u2 = k == 3 ? w0 : w0 + 2;
-    conv(u2, k, o, features, features, 1, nullptr, nullptr, T0);                // resConfUnit2.conv1(relu(o))
-    conv(u2 + 1, k, T0, features, features, 1, o, nullptr, T2);                 // conv2(relu(.)) + relu(o)
-    upsample(3 - k, static_cast<long long>(B) * features, heights[k], widths[k], 1, T2, P);
+    conv(u2, k, o, features, features, 1, nullptr, nullptr, tU2[k]);            // resConfUnit2.conv1(relu(o))
+    conv(u2 + 1, k, tU2[k], features, features, 1, o, nullptr, T2);             // conv2(relu(.)) + relu(o)
+    upsample(3 - k, static_cast<long long>(B) * features, heights[k], widths[k], 1, T2, k == 0 ? P0 : P);
   }
   // output_conv: 0 (features -> 128 at twice level 1), Interpolate, then 2, ReLU, 4 and the last ReLU in the head's launch
   {
     int part = 0;
-    launchMidasConv(B, 2 * H1, 2 * W1, features, 128, 3, P, weights[18], biases[14], 0, 0, nullptr, 0, nullptr,
+    launchMidasConv(B, 2 * H1, 2 * W1, features, 128, 3, P0, weights[18], biases[14], 0, 0, nullptr, 0, nullptr,
                     midasSplitFor(features, 3, 4ll * H1 * W1, 0), fe.dMidasSplit.p, H0, s, [&] {
                       slot[launches++] = 36 + part++;
                       timer.mark();
@@ -3037,6 +3074,314 @@ void midasDecoderDevice(cvd_handle* h, int B, int features, const int* channels,
     timer.collect();
     std::fill(kernelMs, kernelMs + kSlots, 0.0);
     for (int i = 0; i < launches; ++i) kernelMs[slot[i]] = phaseMs[i];
+  }
+}
+
+// ---- Backward of the decoder's layers (cvd_midas_grad.h): the gradients of nn.Conv2d(stride 1, padding k / 2) as the
+// reference's blocks.py:41-159 and midas_net.py:31-74 use it, and of the bilinear x 2 interpolate.  Device arrays on the caller's
+// stream: enqueued launches only. ---------------------------------------------------------------------------------------------------
+// gx = conv(gy, W') on the forward's k_midas_conv, W' the flipped, transposed filter: the forward's split rule (from K = N KS KS and
+// the pixels of one image), chains and f64 fold hold as they stand.  With an addend, a mask or a split the convolution writes its
+// raw sums as partial sums (its S > 1 path, also for one slice) and k_midas_dgrad_fold applies the epilogue.
+void midasConvGradInputDevice(cvd_handle* h, int B, int H, int W, int inChannels, int outChannels, int kernelSize, const float* gy,
+                              const float* weight, const float* add, const float* mask, int split, float* gx, hipStream_t s) {
+  const char* who = "midas conv grad input";
+  const MidasDims d = checkMidasShape(who, B, H, W);
+  checkMidasChannels(who, inChannels, outChannels, kernelSize, d.M);
+  checkMidasChannels(who, outChannels, inChannels, kernelSize, d.M);           // the convolution that runs: N -> Cin
+  const int chunks = midasChunks(outChannels, kernelSize);
+  if (split < 0 || split > chunks)
+    throw std::runtime_error(fmt("%s: split must be 0 (the rule) or 1 .. %d, the chunks of K (got %d)", who, chunks, split));
+  if (!gy || !weight || !gx) throw std::runtime_error(fmt("%s: null array", who));
+  const long long outFloats = d.M * inChannels;
+  const int T = kernelSize * kernelSize;
+  if (rangesOverlap(gx, outFloats, gy, d.M * outChannels)) throw std::runtime_error(fmt("%s: gx overlaps gy", who));
+  if (rangesOverlap(gx, outFloats, weight, static_cast<long long>(inChannels) * outChannels * T))
+    throw std::runtime_error(fmt("%s: gx overlaps the weight", who));
+  if (add && rangesOverlap(gx, outFloats, add, outFloats)) throw std::runtime_error(fmt("%s: gx overlaps the addend", who));
+  if (mask && rangesOverlap(gx, outFloats, mask, outFloats)) throw std::runtime_error(fmt("%s: gx overlaps the mask", who));
+  const int fold = kernelSize == 1 ? MidasShape<1>::kFold : MidasShape<3>::kFold;
+  const int chains = (chunks + fold - 1) / fold;
+  const int want = midasSplitFor(outChannels, kernelSize, d.HW, split);
+  const int per = (chains + want - 1) / want;
+  const int S = (chains + per - 1) / per;                  // (a forced split may shrink: slices are whole chains)
+  const bool folded = S > 1 || add || mask;
+  Frontend& fe = *h->frontend;
+  const size_t wFloats = static_cast<size_t>(inChannels) * outChannels * T;
+  fe.dMidasGradW.ensure(wFloats);
+  if (folded) fe.dMidasSplit.ensure(static_cast<size_t>(S) * static_cast<size_t>(outFloats));
+
+  MidasFlipArgs F{};
+  F.w = weight; F.out = fe.dMidasGradW.p; F.N = outChannels; F.Cin = inChannels; F.total = static_cast<long long>(wFloats);
+  const dim3 flipGrid(static_cast<unsigned>((F.total + kMgThreads - 1) / kMgThreads));
+  if (kernelSize == 1) hipLaunchKernelGGL(k_midas_wflip<1>, flipGrid, dim3(kMgThreads), 0, s, F);
+  else hipLaunchKernelGGL(k_midas_wflip<3>, flipGrid, dim3(kMgThreads), 0, s, F);
+  HIP_CHECK(hipGetLastError());
+
+  MidasConvArgs A{};
+  A.x = gy; A.w = fe.dMidasGradW.p; A.out = gx; A.partial = fe.dMidasSplit.p;
+  A.Cin = outChannels; A.N = inChannels; A.H = H; A.W = W; A.HW = H * W;
+  A.M = d.M;
+  A.S = folded ? std::max(S, 2) : 1;                       // > 1: raw sums to partial `blockIdx.z`, no epilogue
+  A.chunksPerSlice = per * fold;
+  const dim3 grid(static_cast<unsigned>((A.M + kMidasTile - 1) / kMidasTile), static_cast<unsigned>((inChannels + kMidasTile - 1) / kMidasTile),
+                  static_cast<unsigned>(S));
+  const bool vec = (static_cast<long long>(outChannels) * T) % 4 == 0 && (reinterpret_cast<uintptr_t>(A.w) & 15) == 0;
+  if (kernelSize == 1) {
+    if (vec) hipLaunchKernelGGL((k_midas_conv<1, true, false>), grid, dim3(kMidasThreads), 0, s, A);
+    else hipLaunchKernelGGL((k_midas_conv<1, false, false>), grid, dim3(kMidasThreads), 0, s, A);
+  } else {
+    if (vec) hipLaunchKernelGGL((k_midas_conv<3, true, false>), grid, dim3(kMidasThreads), 0, s, A);
+    else hipLaunchKernelGGL((k_midas_conv<3, false, false>), grid, dim3(kMidasThreads), 0, s, A);
+  }
+  HIP_CHECK(hipGetLastError());
+  if (!folded) return;
+  MidasDgradFoldArgs G{};
+  G.partial = fe.dMidasSplit.p; G.add = add; G.mask = mask; G.out = gx; G.S = S; G.total = outFloats;
+  hipLaunchKernelGGL(k_midas_dgrad_fold, dim3(static_cast<unsigned>((G.total + kMgThreads - 1) / kMgThreads)), dim3(kMgThreads), 0, s, G);
+  HIP_CHECK(hipGetLastError());
+}
+
+void midasConvGradWeightDevice(cvd_handle* h, int B, int H, int W, int inChannels, int outChannels, int kernelSize, const float* gy,
+                               const float* x, int reluIn, int split, float* gWeight, float* gBias, hipStream_t s) {
+  const char* who = "midas conv grad weight";
+  const MidasDims d = checkMidasShape(who, B, H, W);
+  checkMidasChannels(who, inChannels, outChannels, kernelSize, d.M);
+  checkFlag(who, "relu_in", reluIn);
+  const long long Q = static_cast<long long>(inChannels) * kernelSize * kernelSize;
+  if ((Q + kWgTile - 1) / kWgTile > 0x7fffffffll || (Q * outChannels + kMgThreads - 1) / kMgThreads > 0x7fffffffll)
+    throw std::runtime_error(fmt("%s: %d x %lld weights exceed the grid", who, outChannels, Q));
+  const long long chains = (d.M + kWgChain - 1) / kWgChain;
+  if (split < 0 || split > kWgMaxSplit)
+    throw std::runtime_error(fmt("%s: split must be 0 (the rule) or 1 .. %d (got %d)", who, kWgMaxSplit, split));
+  if (!gy || !x || !gWeight) throw std::runtime_error(fmt("%s: null array", who));
+  const long long wFloats = Q * outChannels;
+  for (const auto& in : {std::make_pair(gy, d.M * outChannels), std::make_pair(x, d.M * inChannels)}) {
+    if (rangesOverlap(gWeight, wFloats, in.first, in.second)) throw std::runtime_error(fmt("%s: the weight gradient overlaps an input", who));
+    if (gBias && rangesOverlap(gBias, outChannels, in.first, in.second)) throw std::runtime_error(fmt("%s: the bias gradient overlaps an input", who));
+  }
+  if (gBias && rangesOverlap(gBias, outChannels, gWeight, wFloats)) throw std::runtime_error(fmt("%s: the two gradients overlap", who));
+  const long long want = split > 0 ? std::min<long long>(split, chains) : midasWgradSplit(d.M, outChannels, Q);
+  const long long per = (chains + want - 1) / want;
+  const int S = static_cast<int>((chains + per - 1) / per);                    // (a forced split may shrink: slices are whole chains)
+  Frontend& fe = *h->frontend;
+  if (S > 1) fe.dMidasGradSplit.ensure(static_cast<size_t>(S) * static_cast<size_t>(wFloats));
+
+  MidasWgradArgs A{};
+  A.gy = gy; A.x = x; A.out = S > 1 ? fe.dMidasGradSplit.p : gWeight;
+  A.reluIn = reluIn; A.N = outChannels; A.Cin = inChannels; A.Q = static_cast<int>(Q);
+  A.H = H; A.W = W; A.HW = H * W; A.M = d.M;
+  A.chunksPerSlice = static_cast<int>(per) * kWgFold;
+  const dim3 grid(static_cast<unsigned>((Q + kWgTile - 1) / kWgTile), static_cast<unsigned>((outChannels + kWgTile - 1) / kWgTile),
+                  static_cast<unsigned>(S));
+  if (kernelSize == 1) hipLaunchKernelGGL(k_midas_wgrad<1>, grid, dim3(kMgThreads), 0, s, A);
+  else hipLaunchKernelGGL(k_midas_wgrad<3>, grid, dim3(kMgThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+  if (S > 1) {
+    MidasWgradFoldArgs G{};
+    G.partial = fe.dMidasGradSplit.p; G.out = gWeight; G.S = S; G.total = wFloats;
+    hipLaunchKernelGGL(k_midas_wgrad_fold, dim3(static_cast<unsigned>((G.total + kMgThreads - 1) / kMgThreads)), dim3(kMgThreads), 0, s, G);
+    HIP_CHECK(hipGetLastError());
+  }
+  if (gBias) {
+    MidasBiasGradArgs Bg{};
+    Bg.gy = gy; Bg.out = gBias; Bg.B = B; Bg.N = outChannels; Bg.HW = H * W;
+    hipLaunchKernelGGL(k_midas_bias_grad, dim3(static_cast<unsigned>(outChannels)), dim3(kMgThreads), 0, s, Bg);
+    HIP_CHECK(hipGetLastError());
+  }
+}
+
+// gy [B][channels][2 H][2 W] -> gx [B][channels][H][W]
+void midasUpsample2xGradDevice(cvd_handle*, int B, int channels, int H, int W, int alignCorners, const float* gy, float* gx,
+                               hipStream_t s) {
+  const char* who = "midas upsample2x grad";
+  if (B < 1 || channels < 1 || H < 1 || W < 1)
+    throw std::runtime_error(fmt("%s: batch, channels, height and width must be >= 1 (got %d, %d, %d, %d)", who, B, channels, H, W));
+  checkFlag(who, "align_corners", alignCorners);
+  const long long planes = static_cast<long long>(B) * channels;
+  checkMidasUpsampleSize(who, planes, H, W);
+  if (!gy || !gx) throw std::runtime_error(fmt("%s: null array", who));
+  const long long n = planes * H * W;
+  if (rangesOverlap(gx, n, gy, 4 * n)) throw std::runtime_error(fmt("%s: gx overlaps gy", who));
+  MidasUpsampleGradArgs A{};
+  A.gy = gy; A.out = gx; A.H = H; A.W = W; A.total = n;
+  const dim3 grid(static_cast<unsigned>((n + kMgThreads - 1) / kMgThreads));
+  if (alignCorners) hipLaunchKernelGGL(k_midas_upsample2x_grad<true>, grid, dim3(kMgThreads), 0, s, A);
+  else hipLaunchKernelGGL(k_midas_upsample2x_grad<false>, grid, dim3(kMgThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+}
+
+// The output head's backward (midas_net.py:38-41: output_conv.2, ReLU, output_conv.4, ReLU under non_negative).  The forward never
+// writes the 32-channel tensor, so it is RECOMPUTED here with the forward's arithmetic: k_midas_conv<3, VEC, false> with one slice
+// runs, per output element, the head instantiation's own chain (the same chunks in the same order, folded every kFold chunks) and
+// adds the bias in the same operation, so its t is the head's, bit for bit; the head's output for the last ReLU's mask is the head
+// launch itself.  Then the pointwise kernel, the two-stage sums for output_conv.4, and the weight and input gradients of
+// output_conv.2 through the entry points above on the gradient of t.
+void midasHeadGradDevice(cvd_handle* h, int B, int H, int W, int inChannels, int midChannels, const float* gy, const float* x,
+                         const float* weight2, const float* bias2, const float* weight4, const float* bias4, int nonNegative, float* gx,
+                         float* gWeight2, float* gBias2, float* gWeight4, float* gBias4, hipStream_t s) {
+  const char* who = "midas head grad";
+  const MidasDims d = checkMidasShape(who, B, H, W);
+  if ((d.M + kMidasHeadPixels - 1) / kMidasHeadPixels > 0x7fffffffll) throw std::runtime_error(fmt("%s: %lld pixels exceed the grid", who, d.M));
+  if (midChannels != kMidasHeadMid) throw std::runtime_error(fmt("%s: mid_channels must be %d (got %d)", who, kMidasHeadMid, midChannels));
+  checkMidasChannels(who, inChannels, kMidasHeadMid, 3, d.M);
+  checkFlag(who, "non_negative", nonNegative);
+  if (!gy || !x || !weight2 || !bias2 || !weight4 || !bias4 || !gx || !gWeight2 || !gBias2 || !gWeight4 || !gBias4)
+    throw std::runtime_error(fmt("%s: null array", who));
+  static_assert(kHeadMid == kMidasHeadMid, "one width");
+  const long long Q = static_cast<long long>(inChannels) * 9;
+  const std::pair<const float*, long long> ins[] = {{gy, d.M}, {x, d.M * inChannels}, {weight2, Q * kHeadMid}, {bias2, kHeadMid},
+                                                     {weight4, kHeadMid}, {bias4, 1}};
+  const std::pair<const float*, long long> outs[] = {{gx, d.M * inChannels}, {gWeight2, Q * kHeadMid}, {gBias2, kHeadMid},
+                                                      {gWeight4, kHeadMid}, {gBias4, 1}};
+  for (int o = 0; o < 5; ++o) {
+    for (const auto& in : ins)
+      if (rangesOverlap(outs[o].first, outs[o].second, in.first, in.second)) throw std::runtime_error(fmt("%s: output %d overlaps an input", who, o));
+    for (int o2 = 0; o2 < o; ++o2)
+      if (rangesOverlap(outs[o].first, outs[o].second, outs[o2].first, outs[o2].second))
+        throw std::runtime_error(fmt("%s: outputs %d and %d overlap", who, o2, o));
+  }
+  // every scratch buffer at its size before the first launch (the two entry points below then find theirs large enough)
+  Frontend& fe = *h->frontend;
+  const size_t M32 = static_cast<size_t>(d.M) * kHeadMid;
+  const long long groups = (d.M + kMgThreads - 1) / kMgThreads;
+  fe.dMidasHeadGrad.ensure(2 * M32 + static_cast<size_t>(d.M));
+  fe.dMidasHeadPart.ensure(static_cast<size_t>(groups) * kHeadSums);
+  fe.dMidasGradW.ensure(static_cast<size_t>(Q) * kHeadMid);
+  const int Sw = midasWgradSplit(d.M, kHeadMid, Q);
+  if (Sw > 1) fe.dMidasGradSplit.ensure(static_cast<size_t>(Sw) * static_cast<size_t>(Q) * kHeadMid);
+  {
+    const int Sd = midasSplitFor(kHeadMid, 3, d.HW, 0);
+    if (Sd > 1) fe.dMidasSplit.ensure(static_cast<size_t>(Sd) * static_cast<size_t>(d.M) * inChannels);
+  }
+  float* t = fe.dMidasHeadGrad.p;
+  float* g32 = t + M32;
+  float* y = g32 + M32;
+  launchMidasConv(B, H, W, inChannels, kMidasHeadMid, 3, x, weight2, bias2, 0, 0, nullptr, 0, nullptr, 1, nullptr, t, s, [] {});
+  if (nonNegative) launchMidasHead(B, H, W, inChannels, x, weight2, bias2, weight4, bias4, 1, y, s);
+  MidasHeadGradArgs A{};
+  A.gy = gy; A.y = y; A.t = t; A.w4 = weight4; A.g32 = g32; A.partial = fe.dMidasHeadPart.p;
+  A.nonNegative = nonNegative; A.HW = H * W; A.M = d.M;
+  hipLaunchKernelGGL(k_midas_head_grad, dim3(static_cast<unsigned>(groups)), dim3(kMgThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+  MidasHeadSumArgs G{};
+  G.partial = fe.dMidasHeadPart.p; G.gW4 = gWeight4; G.gb4 = gBias4; G.groups = static_cast<int>(groups);
+  hipLaunchKernelGGL(k_midas_head_grad_sum, dim3(1), dim3(64), 0, s, G);
+  HIP_CHECK(hipGetLastError());
+  midasConvGradWeightDevice(h, B, H, W, inChannels, kMidasHeadMid, 3, g32, x, 0, 0, gWeight2, gBias2, s);
+  midasConvGradInputDevice(h, B, H, W, inChannels, kMidasHeadMid, 3, g32, weight2, nullptr, nullptr, 0, gx, s);
+}
+
+// The decoder's backward in ONE call (cvd_midas_decoder_backward_device): from gy [B][4 H_1][4 W_1], the saved table of
+// cvd_midas_decoder_train_device and the parameters to the 21 weight and 17 bias gradients and (gMaps non-null) the four feature-map
+// gradients.  It chains the four operators above in the reverse of the forward's order; its results are theirs bit for bit.  The
+// 128-channel full-resolution tensor is not saved: it is recomputed from output_conv.0's saved result by the forward's own upsampling
+// launch (44 MB per frame less in the table for one more 0.03 ms launch).  kernelMs (measurement only, may be null): one entry per
+// stage in the order they run, kMidasBackwardStages of them; with it the call waits on the host.
+void midasDecoderBackwardDevice(cvd_handle* h, int B, int features, const int* channels, const int* heights, const int* widths,
+                                const float* gy, const float* const* maps, const float* const* saved, const float* const* weights,
+                                const float* const* biases, int nonNegative, float* const* gWeights, float* const* gBiases,
+                                float* const* gMaps, hipStream_t s, double* kernelMs) {
+  const char* who = "midas decoder backward";
+  if (!channels || !heights || !widths || !gy || !maps || !saved || !weights || !biases || !gWeights || !gBiases)
+    throw std::runtime_error(fmt("%s: null array", who));
+  if (features < 1) throw std::runtime_error(fmt("%s: features must be >= 1 (got %d)", who, features));
+  checkFlag(who, "non_negative", nonNegative);
+  long long M[4];
+  for (int k = 0; k < 4; ++k) {
+    const MidasDims d = checkMidasShape(who, B, heights[k], widths[k]);
+    M[k] = d.M;
+    if (channels[k] < 1) throw std::runtime_error(fmt("%s: channels of feature map %d must be >= 1 (got %d)", who, k + 1, channels[k]));
+    checkMidasChannels(who, channels[k], features, 3, d.M);
+    if (k > 0 && (heights[k - 1] != 2 * heights[k] || widths[k - 1] != 2 * widths[k]))
+      throw std::runtime_error(fmt("%s: feature map %d is %d x %d, not twice map %d's %d x %d", who, k, heights[k - 1], widths[k - 1], k + 1,
+                                   heights[k], widths[k]));
+    if (!maps[k]) throw std::runtime_error(fmt("%s: null feature map %d", who, k + 1));
+    if (gMaps && !gMaps[k]) throw std::runtime_error(fmt("%s: null feature-map gradient %d", who, k + 1));
+  }
+  const int H1 = heights[0], W1 = widths[0];
+  if (static_cast<long long>(H1) * W1 > 0x7fffffffll / 16)
+    throw std::runtime_error(fmt("%s: %d x %d output pixels per image exceed 2^31", who, 4 * H1, 4 * W1));
+  checkMidasUpsampleSize(who, static_cast<long long>(B) * std::max(features, 128), 2 * H1, 2 * W1);
+  for (int i = 0; i < 21; ++i)
+    if (!weights[i] || !gWeights[i]) throw std::runtime_error(fmt("%s: null weight or weight gradient %d", who, i));
+  for (int i = 0; i < 17; ++i)
+    if (!biases[i] || !gBiases[i]) throw std::runtime_error(fmt("%s: null bias or bias gradient %d", who, i));
+  for (int i = 0; i < kMidasSaved; ++i)
+    if (!saved[i]) throw std::runtime_error(fmt("%s: null saved tensor %d", who, i));
+
+  const size_t F = static_cast<size_t>(features), n0 = F * static_cast<size_t>(M[0]);
+  const size_t big = 128 * 16 * static_cast<size_t>(M[0]), quarter = 128 * 4 * static_cast<size_t>(M[0]);
+  Frontend& fe = *h->frontend;
+  fe.dMidasBackward.ensure(2 * big + quarter + 4 * n0 + 5 * n0);
+  float* Hup = fe.dMidasBackward.p;
+  float* gHup = Hup + big;
+  float* gH0 = gHup + big;
+  float* gPath = gH0 + quarter;             // [B][F][2 H_1][2 W_1]
+  float* X[5];
+  for (int i = 0; i < 5; ++i) X[i] = gPath + 4 * n0 + static_cast<size_t>(i) * n0;
+
+  int stage = 0;
+  double phaseMs[kMidasBackwardStages];
+  KernelTimer timer(s, kernelMs ? phaseMs : nullptr, kMidasBackwardStages);
+  timer.mark();
+  const auto done = [&] { ++stage; timer.mark(); };
+  const auto wgrad = [&](int idx, int k, int Cin, int N, int Hk, int Wk, const float* g, const float* x, int reluIn) {
+    midasConvGradWeightDevice(h, B, Hk, Wk, Cin, N, 3, g, x, reluIn, 0, gWeights[idx], idx < 4 ? nullptr : gBiases[idx - 4], s);
+    (void)k;
+    done();
+  };
+  const auto dgrad = [&](int idx, int Cin, int N, int Hk, int Wk, const float* g, const float* add, const float* mask, float* gx) {
+    midasConvGradInputDevice(h, B, Hk, Wk, Cin, N, 3, g, weights[idx], add, mask, 0, gx, s);
+    done();
+  };
+  // the head: its input recomputed, then its backward; output_conv.0 behind the half-pixel upsampling
+  launchMidasUpsample(static_cast<long long>(B) * 128, 2 * H1, 2 * W1, 0, saved[15], Hup, s);
+  done();
+  midasHeadGradDevice(h, B, 4 * H1, 4 * W1, 128, kMidasHeadMid, gy, Hup, weights[19], biases[15], weights[20], biases[16], nonNegative, gHup,
+                      gWeights[19], gBiases[15], gWeights[20], gBiases[16], s);
+  done();
+  midasUpsample2xGradDevice(h, B, 128, 2 * H1, 2 * W1, 0, gHup, gH0, s);
+  done();
+  wgrad(18, 0, features, 128, 2 * H1, 2 * W1, gH0, saved[14], 0);
+  dgrad(18, features, 128, 2 * H1, 2 * W1, gH0, nullptr, nullptr, gPath);
+  // refinenet1 .. refinenet4: the reverse of the forward's order
+  const float* gP = gPath;
+  for (int k = 0; k < 4; ++k) {
+    const int Hk = heights[k], Wk = widths[k];
+    const int w0 = k == 3 ? 4 : 6 + 4 * (2 - k);
+    const int u2 = k == 3 ? w0 : w0 + 2;
+    const int at = 5 + 3 * (2 - k);
+    const float* o = k == 3 ? saved[3] : saved[at + 1];       // resConfUnit2's input
+    const float* t2 = k == 3 ? saved[4] : saved[at + 2];
+    float* g = X[0];
+    float* g1 = X[1];
+    float* go = X[2 + (k & 1)];                                // (the next level's path gradient: not this level's)
+    float* grn = X[4];
+    midasUpsample2xGradDevice(h, B, features, Hk, Wk, 1, gP, g, s);
+    done();
+    wgrad(u2 + 1, k, features, features, Hk, Wk, g, t2, 1);
+    dgrad(u2 + 1, features, features, Hk, Wk, g, nullptr, t2, g1);
+    wgrad(u2, k, features, features, Hk, Wk, g1, o, 1);
+    dgrad(u2, features, features, Hk, Wk, g1, g, o, go);     // (conv1's input gradient + the skip) [o > 0]
+    const float* gL = go;
+    if (k < 3) {                                               // o = path + resConfUnit1(layerK_rn's result): go flows to both
+      const float* t1 = saved[at];
+      wgrad(w0 + 1, k, features, features, Hk, Wk, go, t1, 1);
+      dgrad(w0 + 1, features, features, Hk, Wk, go, nullptr, t1, g1);
+      wgrad(w0, k, features, features, Hk, Wk, g1, saved[k], 1);
+      dgrad(w0, features, features, Hk, Wk, g1, go, saved[k], grn);
+      gL = grn;
+    }
+    wgrad(k, k, channels[k], features, Hk, Wk, gL, maps[k], 0);
+    if (gMaps) dgrad(k, channels[k], features, Hk, Wk, gL, nullptr, nullptr, gMaps[k]);
+    gP = go;
+  }
+  if (kernelMs) {
+    timer.wait();
+    timer.collect();
+    std::fill(kernelMs, kernelMs + kMidasBackwardStages, 0.0);
+    std::copy(phaseMs, phaseMs + stage, kernelMs);
   }
 }
 

@@ -820,7 +820,21 @@ void midasHeadDevice(cvd_handle* h, int B, int H, int W, int inChannels, int mid
                      const float* bias2, const float* weight4, const float* bias4, int nonNegative, float* out, hipStream_t s);
 void midasDecoderDevice(cvd_handle* h, int B, int features, const int* channels, const int* heights, const int* widths,
                         const float* const* maps, const float* const* weights, const float* const* biases, int nonNegative, float* out,
-                        hipStream_t s, double* kernelMs);
+                        hipStream_t s, double* kernelMs, float* const* saved = nullptr);
+// the backward of its layers (cvd_midas_grad.h)
+void midasConvGradInputDevice(cvd_handle* h, int B, int H, int W, int inChannels, int outChannels, int kernelSize, const float* gy,
+                              const float* weight, const float* add, const float* mask, int split, float* gx, hipStream_t s);
+void midasConvGradWeightDevice(cvd_handle* h, int B, int H, int W, int inChannels, int outChannels, int kernelSize, const float* gy,
+                               const float* x, int reluIn, int split, float* gWeight, float* gBias, hipStream_t s);
+void midasUpsample2xGradDevice(cvd_handle* h, int B, int channels, int H, int W, int alignCorners, const float* gy, float* gx,
+                               hipStream_t s);
+void midasHeadGradDevice(cvd_handle* h, int B, int H, int W, int inChannels, int midChannels, const float* gy, const float* x,
+                         const float* weight2, const float* bias2, const float* weight4, const float* bias4, int nonNegative, float* gx,
+                         float* gWeight2, float* gBias2, float* gWeight4, float* gBias4, hipStream_t s);
+void midasDecoderBackwardDevice(cvd_handle* h, int B, int features, const int* channels, const int* heights, const int* widths,
+                                const float* gy, const float* const* maps, const float* const* saved, const float* const* weights,
+                                const float* const* biases, int nonNegative, float* const* gWeights, float* const* gBiases,
+                                float* const* gMaps, hipStream_t s, double* kernelMs);
 
 // the ResNeXt backbone of MiDaS v2.1 (cvd_resnext.h)
 void resnextGroupedConvDevice(cvd_handle* h, int B, int H, int W, int groups, int channelsPerGroup, int stride, const float* x,
