@@ -1053,6 +1053,78 @@ int32_t cvd_midas_backbone_timed(cvd_handle* h, int32_t batch, int32_t height, i
                                  int32_t width_per_group, float eps, const float* images, const float* const* weights,
                                  const float* const* norms, float* const* outs4, void* stream, double* kernel_ms);
 
+/* ---- the same backbone in training (csrc/cvd_resnext_grad.h): nn.BatchNorm2d on batch statistics and what torch's
+ * autograd computes for the backbone's layers, on device arrays, f32, launches on `stream` with no host synchronisation.  No atomics:
+ * every reduction runs in a fixed order in f64 and is rounded once, so a call repeats bit for bit.  Scratch is the handle's (calls
+ * on one device are ordered on one stream).  `height` and `width` are those of the layer's INPUT; ho = (height - 1) / stride + 1.
+ * Every entry point rejects, before any device work and with an error that names the value: null arrays, sizes < 1, outputs that
+ * overlap an input or each other, and (channels per group, stride, kernel_size) combinations that are not built. ---- */
+/* nn.BatchNorm2d behind a convolution called with a null norm: c [batch][channels][height][width] is its raw output.
+ *   training != 0: mean and biased variance of each channel over M = batch height width in f64 (sums of x and x^2, dealt to slices by
+ *   a rule of (channels, M) and added in slice order); save_mean and save_invstd = 1 / sqrt(var + eps) rounded once to f32;
+ *   running = (1 - momentum) running + momentum stat with the unbiased variance M / (M - 1).  M = 1 is rejected.
+ *   training == 0: save_mean = running_mean, save_invstd = 1 / sqrt(running_var + eps); nothing else is updated.
+ * Then y = (c - save_mean) save_invstd gamma + beta; max(y, 0) where relu != 0; with a residual (or null) max(residual + y, 0). */
+int32_t cvd_resnext_norm_train_device(cvd_handle* h, int32_t batch, int32_t channels, int32_t height, int32_t width, const float* c,
+                                      const float* gamma, const float* beta, float* running_mean, float* running_var, double eps,
+                                      double momentum, int32_t training, int32_t relu, const float* residual, float* save_mean,
+                                      float* save_invstd, float* y, void* stream);
+/* Its backward.  y (or null): the tensor the forward wrote, given where the forward applied a ReLU or the residual form; then
+ * g = gy where y > 0, else 0.  g_beta = sum g, g_gamma = sum g xhat with xhat = (c - mean) invstd, f64 sums rounded once.
+ * training != 0: gc = gamma invstd (g - g_beta / M - xhat g_gamma / M); else gc = g gamma invstd.  g_residual (or null) = g. */
+int32_t cvd_resnext_norm_grad_device(cvd_handle* h, int32_t batch, int32_t channels, int32_t height, int32_t width, const float* gy,
+                                     const float* c, const float* y, const float* mean, const float* invstd, const float* gamma,
+                                     int32_t training, float* gc, float* g_gamma, float* g_beta, float* g_residual, void* stream);
+/* The grouped 3 x 3 convolution of cvd_resnext_grouped_conv_device: gy [batch][groups channels_per_group][ho][wo] ->
+ * gx [batch][groups channels_per_group][height][width] (ONE launch, gather form), resp. with the convolution's input x ->
+ * g_weight [groups channels_per_group][channels_per_group][3][3].  split: 0 = the rule -- the output pixels are dealt to as many
+ * slices of whole chains of 256 pixels as bring the launch to 1024 workgroups, at most 128; a function of the pixel and weight
+ * counts alone -- otherwise the forced slice count (1 .. 128; it shrinks to whole chains). */
+int32_t cvd_resnext_grouped_conv_grad_input_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t groups,
+                                                   int32_t channels_per_group, int32_t stride, const float* gy, const float* weight,
+                                                   float* gx, void* stream);
+int32_t cvd_resnext_grouped_conv_grad_weight_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t groups,
+                                                    int32_t channels_per_group, int32_t stride, const float* gy, const float* x,
+                                                    int32_t split, float* g_weight, void* stream);
+/* The dense convolutions of cvd_resnext_conv_device.  Input gradient: kernel_size 1 at stride 1 or 2 (the stem's images need none):
+ * gx = conv_transpose(gy, weight) + add (add or null: [batch][in_channels][height][width], the residual branch's gradient); at
+ * stride 2 gx is exactly `add` (or zero) at the odd positions.  Weight gradient: kernel_size 1 at stride 1 or 2, and kernel_size 7
+ * at stride 2.  The 1 x 1 paths run cvd_midas_conv_grad_input_device / _grad_weight_device (at stride 2 around a scatter resp. a
+ * gather); split is the weight gradient's, as there resp. as above for the stem. */
+int32_t cvd_resnext_conv_grad_input_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels,
+                                           int32_t out_channels, int32_t kernel_size, int32_t stride, const float* gy, const float* weight,
+                                           const float* add, float* gx, void* stream);
+int32_t cvd_resnext_conv_grad_weight_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels,
+                                            int32_t out_channels, int32_t kernel_size, int32_t stride, const float* gy, const float* x,
+                                            int32_t split, float* g_weight, void* stream);
+/* Backward of cvd_resnext_maxpool_device: x [batch][channels][height][width] its input, gy [batch][channels][ho][wo] ->
+ * gx [batch][channels][height][width].  Each window's gradient goes to its argmax as torch picks it (row-major scan, padding
+ * excluded, the first maximum wins, a NaN wins). */
+int32_t cvd_resnext_maxpool_grad_device(cvd_handle* h, int32_t batch, int32_t channels, int32_t height, int32_t width, const float* x,
+                                        const float* gy, float* gx, void* stream);
+/* One torchvision Bottleneck (v1.5) per call, training form: conv1 1 x 1 in_channels -> mid_channels, bn1, ReLU; conv2 grouped 3 x 3
+ * with the stride, bn2, ReLU; downsample.0 1 x 1 with the stride and downsample.1 where downsample != 0; conv3 1 x 1 -> out_channels,
+ * bn3, + identity, ReLU.
+ *   weights    host array of the 3 (4) device weights: conv1, conv2, conv3 (, downsample.0)
+ *   norms      host array of 4 device vectors per convolution {weight, bias, running_mean, running_var}; the running statistics
+ *              of a norm whose flag in `training` (host array, one per convolution) is != 0 are updated
+ *   saved      host array of 4 caller-owned device tensors per convolution {c, mean, invstd, y}: the raw convolution output, the
+ *              two saved vectors and the post-activation tensor; y of conv3 is the block's OUTPUT, y of downsample.0 the identity
+ *              (shapes: api.resnext_block_saved_shapes).  Everything is saved, nothing is recomputed.
+ * The backward writes gx (or null: skipped) [batch][in_channels][height][width], and per convolution g_weights, g_gammas, g_betas;
+ * `gammas` is the host array of the norms' weights.  Both calls run the operator entry points above in order (the forward's
+ * convolutions are cvd_resnext_conv_device / _grouped_conv_device with a null norm), so their results equal the chained operator
+ * calls' bit for bit; the gradients between the operators are scratch of the handle. */
+int32_t cvd_resnext_block_train_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels,
+                                       int32_t mid_channels, int32_t out_channels, int32_t groups, int32_t stride, int32_t downsample,
+                                       const float* x, const float* const* weights, float* const* norms, double eps, double momentum,
+                                       const int32_t* training, float* const* saved, void* stream);
+int32_t cvd_resnext_block_backward_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels,
+                                          int32_t mid_channels, int32_t out_channels, int32_t groups, int32_t stride, int32_t downsample,
+                                          const float* gy, const float* x, const float* const* weights, const float* const* gammas,
+                                          const float* const* saved, const int32_t* training, float* gx, float* const* g_weights,
+                                          float* const* g_gammas, float* const* g_betas, void* stream);
+
 /* ---- measurement hooks (bench.py) --------------------------------------------------------------------- */
 /* Average duration (ms) of the dominant kernels over the last solve, measured with HIP events on the
  * solver's own stream: fills {evaluate_assemble, matvec_pairs, matvec_finish, cg_update, block_inverse,

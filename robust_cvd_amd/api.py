@@ -1055,6 +1055,220 @@ def resnext_check_backbone(image_shape, blocks, groups, width_per_group, weight_
     return B, H, W, table, [(B, 256 << k, H >> (k + 2), W >> (k + 2)) for k in range(4)]
 
 
+# ---- training of the backbone (csrc/cvd_resnext_grad.h) ----------------------------------------------------------
+RESNEXT_NORM_CHUNK = 1024              # elements of a channel a slice of a batch norm reduction holds at least
+RESNEXT_NORM_MAX_SPLIT = 64
+RESNEXT_WGRAD_CHAIN = 256              # output pixels of one chain of the grouped / stem weight gradient
+RESNEXT_WGRAD_MAX_SPLIT = 128
+RESNEXT_MOMENTUM = 0.1
+
+
+def resnext_norm_split(channels, count):
+    """The slices per channel of a batch norm reduction of csrc/cvd_resnext_grad.h (rxgNormSplit there) over `count` = B H W elements
+    of each of `channels` channels: as many as bring the launch to 1024 workgroups, each whole chunks of 1024 elements, at most 64.
+    A function of the two sizes alone."""
+    chunks = (int(count) + RESNEXT_NORM_CHUNK - 1) // RESNEXT_NORM_CHUNK
+    want = max(1, min(1024 // int(channels), RESNEXT_NORM_MAX_SPLIT, chunks))
+    per = (chunks + want - 1) // want
+    return (chunks + per - 1) // per
+
+
+def resnext_wgrad_split(pixels, elements):
+    """The slices of the grouped 3 x 3 and the stem's weight gradient (rxgWgradSplit there) over `pixels` = B Ho Wo output pixels for
+    `elements` weights: as many slices of whole chains of 256 pixels as bring the launch (a thread per weight, 256 a workgroup) to
+    1024 workgroups, at most 128.  A function of the two sizes alone."""
+    groups = (int(elements) + 255) // 256
+    chains = (int(pixels) + RESNEXT_WGRAD_CHAIN - 1) // RESNEXT_WGRAD_CHAIN
+    want = max(1, min(1024 // groups, RESNEXT_WGRAD_MAX_SPLIT, chains))
+    per = (chains + want - 1) // want
+    return (chains + per - 1) // per
+
+
+def resnext_check_norm_train(c_shape, vector_shapes, eps=RESNEXT_EPS, momentum=RESNEXT_MOMENTUM, training=True, residual_shape=None):
+    """(B, N, H, W) of nn.BatchNorm2d on c [B, N, H, W] with the four [N] vectors RESNEXT_NORM_VECTORS; ValueError (before any device
+    work) for anything else, for momentum None (the cumulative average has no kernel) and, in training mode, for one value per
+    channel, which torch refuses too."""
+    who = "ResNeXt norm"
+    B, N, H, W = _midas_shape4(who, "c", c_shape)
+    _resnext_norm(who, vector_shapes, eps, N)
+    if momentum is None:
+        raise ValueError(f"{who}: momentum None (the cumulative moving average) has no kernel")
+    if not 0.0 <= float(momentum) <= 1.0:
+        raise ValueError(f"{who}: momentum must lie in [0, 1] (got {momentum})")
+    if training and B * H * W < 2:
+        raise ValueError(f"{who}: training mode needs more than 1 value per channel (got c {tuple(c_shape)})")
+    if residual_shape is not None and tuple(int(v) for v in residual_shape) != (B, N, H, W):
+        raise ValueError(f"{who}: the residual must be {(B, N, H, W)} (got {tuple(residual_shape)})")
+    return B, N, H, W
+
+
+def resnext_check_norm_grad(gy_shape, c_shape, y_shape, vector_shapes, training=True):
+    """(B, N, H, W) of the batch norm's backward: gy, c and y (or None) of one shape, mean, invstd and gamma [N]."""
+    who = "ResNeXt norm grad"
+    B, N, H, W = _midas_shape4(who, "gy", gy_shape)
+    for name, s in (("c", c_shape), ("y", y_shape)):
+        if s is not None and tuple(int(v) for v in s) != (B, N, H, W):
+            raise ValueError(f"{who}: {name} must be {(B, N, H, W)} (got {tuple(s)})")
+    got = [tuple(int(v) for v in s) for s in vector_shapes]
+    if len(got) != 3 or any(g != (N,) for g in got):
+        raise ValueError(f"{who}: mean, invstd and gamma must have shape ({N},) (got {got})")
+    if training and B * H * W < 2:
+        raise ValueError(f"{who}: training mode needs more than 1 value per channel (got gy {tuple(gy_shape)})")
+    return B, N, H, W
+
+
+def _resnext_grouped_weight(who, channels, weight_shape):
+    ws = tuple(int(v) for v in weight_shape)
+    if len(ws) != 4 or ws[2:] != (3, 3):
+        raise ValueError(f"{who}: the filter must be 3 x 3 (weight {ws})")
+    cg = ws[1]
+    if ws[0] != channels or cg < 1 or channels % cg:
+        raise ValueError(f"{who}: {channels} channels are no whole groups of the weight {ws}")
+    if cg not in RESNEXT_GROUP_WIDTHS:
+        raise ValueError(f"{who}: channels per group must be one of {RESNEXT_GROUP_WIDTHS} (got {cg})")
+    return channels // cg, cg
+
+
+def _resnext_out_size(who, gy_shape, B, N, H, W, stride):
+    want = (B, N, (H - 1) // stride + 1, (W - 1) // stride + 1)
+    if tuple(int(v) for v in gy_shape) != want:
+        raise ValueError(f"{who}: gy must be {want} for an input of {H} x {W} at stride {stride} (got {tuple(gy_shape)})")
+
+
+def _resnext_wgrad_split(who, split):
+    if int(split) != split or not 0 <= split <= RESNEXT_WGRAD_MAX_SPLIT:
+        raise ValueError(f"{who}: split must be 0 (the rule) or 1 .. {RESNEXT_WGRAD_MAX_SPLIT} (got {split})")
+
+
+def resnext_check_grouped_conv_grad_input(gy_shape, weight_shape, x_size, stride=1):
+    """(B, H, W, groups, Cg) of the grouped convolution's input gradient: x_size = (H, W) of its input, gy [B, G Cg, Ho, Wo]."""
+    who = "ResNeXt grouped conv grad input"
+    B, N, _, _ = _midas_shape4(who, "gy", gy_shape)
+    H, W = (int(v) for v in x_size)
+    if H < 1 or W < 1:
+        raise ValueError(f"{who}: the input size must be >= 1 (got {H} x {W})")
+    G, cg = _resnext_grouped_weight(who, N, weight_shape)
+    stride = _resnext_stride(who, stride)
+    _resnext_out_size(who, gy_shape, B, N, H, W, stride)
+    return B, H, W, G, cg
+
+
+def resnext_check_grouped_conv_grad_weight(gy_shape, x_shape, channels_per_group, stride=1, split=0):
+    """(B, H, W, groups, Cg) of the grouped convolution's weight gradient: gy [B, G Cg, Ho, Wo], x [B, G Cg, H, W]."""
+    who = "ResNeXt grouped conv grad weight"
+    B, N, H, W = _midas_shape4(who, "x", x_shape)
+    G, cg = _resnext_grouped_weight(who, N, (N, int(channels_per_group), 3, 3))
+    stride = _resnext_stride(who, stride)
+    _resnext_out_size(who, gy_shape, B, N, H, W, stride)
+    _resnext_wgrad_split(who, split)
+    return B, H, W, G, cg
+
+
+def resnext_check_conv_grad_input(gy_shape, weight_shape, x_size, stride=1, add_shape=None):
+    """(B, H, W, Cin, N) of a 1 x 1 convolution's input gradient at stride 1 or 2 (the stem's is not built)."""
+    who = "ResNeXt conv grad input"
+    B, N, _, _ = _midas_shape4(who, "gy", gy_shape)
+    H, W = (int(v) for v in x_size)
+    if H < 1 or W < 1:
+        raise ValueError(f"{who}: the input size must be >= 1 (got {H} x {W})")
+    ws = tuple(int(v) for v in weight_shape)
+    stride = _resnext_stride(who, stride)
+    if len(ws) != 4 or ws[2:] != (1, 1):
+        raise ValueError(f"{who}: kernel_size must be 1: the stem's input gradient is not built (weight {ws})")
+    if ws[0] != N or ws[1] < 1:
+        raise ValueError(f"{who}: gy has {N} channels, the weight is {ws}")
+    _resnext_out_size(who, gy_shape, B, N, H, W, stride)
+    if add_shape is not None and tuple(int(v) for v in add_shape) != (B, ws[1], H, W):
+        raise ValueError(f"{who}: the addend must be {(B, ws[1], H, W)} (got {tuple(add_shape)})")
+    return B, H, W, ws[1], N
+
+
+def resnext_check_conv_grad_weight(gy_shape, x_shape, kernel_size, stride=1, split=0):
+    """(B, H, W, Cin, N, k) of a dense convolution's weight gradient, (k, stride) in RESNEXT_DENSE_KERNELS."""
+    who = "ResNeXt conv grad weight"
+    B, Cin, H, W = _midas_shape4(who, "x", x_shape)
+    stride = _resnext_stride(who, stride)
+    if (kernel_size, stride) not in RESNEXT_DENSE_KERNELS:
+        raise ValueError(f"{who}: (kernel_size, stride) must be one of {RESNEXT_DENSE_KERNELS} (got {(kernel_size, stride)})")
+    gs = tuple(int(v) for v in gy_shape)
+    if len(gs) != 4 or gs[1] < 1:
+        raise ValueError(f"{who}: gy must be (B, N, Ho, Wo) (got {gs})")
+    _resnext_out_size(who, gy_shape, B, gs[1], H, W, stride)
+    _resnext_wgrad_split(who, split)
+    return B, H, W, Cin, gs[1], int(kernel_size)
+
+
+def resnext_check_maxpool_grad(x_shape, gy_shape):
+    """(B, C, H, W) of the pool's backward: x its input, gy [B, C, Ho, Wo]."""
+    who = "ResNeXt maxpool grad"
+    B, Cn, H, W = _midas_shape4(who, "x", x_shape)
+    _resnext_out_size(who, gy_shape, B, Cn, H, W, 2)
+    return B, Cn, H, W
+
+
+def resnext_block_saved_shapes(batch, height, width, in_channels, mid_channels, out_channels, stride=1, downsample=False):
+    """The shapes of the table cvd_resnext_block_train_device fills, for a Bottleneck on x [batch, in_channels, height, width]: per
+    convolution (conv1, conv2, conv3 and, with a downsample branch, downsample.0) its raw output c, the saved mean and invstd, and
+    the post-activation tensor -- conv3's is the block's output, downsample.0's the identity."""
+    B, H, W = int(batch), int(height), int(width)
+    stride = _resnext_stride("ResNeXt block", stride)
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    per = [(mid_channels, H, W), (mid_channels, Ho, Wo), (out_channels, Ho, Wo)] + ([(out_channels, Ho, Wo)] if downsample else [])
+    out = []
+    for n, h, w in per:
+        out += [(B, int(n), h, w), (int(n),), (int(n),), (B, int(n), h, w)]
+    return out
+
+
+def resnext_check_block(x_shape, weight_shapes, norm_shapes, stride=1, eps=RESNEXT_EPS, momentum=RESNEXT_MOMENTUM, training=True):
+    """(B, H, W, Cin, width, out, groups, stride, downsample, training flags) of one Bottleneck: weights conv1 [width, Cin, 1, 1],
+    conv2 [width, Cg, 3, 3], conv3 [out, width, 1, 1] and optionally downsample.0 [out, Cin, 1, 1]; four [N] norm vectors each."""
+    who = "ResNeXt block"
+    B, Cin, H, W = _midas_shape4(who, "x", x_shape)
+    ws = [tuple(int(v) for v in s) for s in weight_shapes]
+    if len(ws) not in (3, 4) or len(norm_shapes) != len(ws):
+        raise ValueError(f"{who}: three or four weights and as many norms are expected (got {len(ws)}, {len(norm_shapes)})")
+    stride = _resnext_stride(who, stride)
+    width, out = ws[0][0], ws[2][0]
+    if ws[0] != (width, Cin, 1, 1) or ws[2] != (out, width, 1, 1):
+        raise ValueError(f"{who}: conv1 / conv3 must be {(width, Cin, 1, 1)} / {(out, width, 1, 1)} (got {ws[0]}, {ws[2]})")
+    G, _cg = _resnext_grouped_weight(who, width, ws[1])
+    down = len(ws) == 4
+    if down and ws[3] != (out, Cin, 1, 1):
+        raise ValueError(f"{who}: downsample.0 must be {(out, Cin, 1, 1)} (got {ws[3]})")
+    if not down and (stride != 1 or Cin != out):
+        raise ValueError(f"{who}: without a downsample branch stride must be 1 and in == out channels (got {stride}, {Cin}, {out})")
+    flags = [bool(training)] * len(ws) if isinstance(training, (bool, int)) else [bool(t) for t in training]
+    if len(flags) != len(ws):
+        raise ValueError(f"{who}: one training flag per norm is expected (got {len(flags)})")
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    for i, (n, hw) in enumerate(zip((width, width, out, out), ((H, W), (Ho, Wo), (Ho, Wo), (Ho, Wo)))):
+        if i < len(ws):
+            resnext_check_norm_train((B, n) + hw, norm_shapes[i], eps, momentum, flags[i])
+    return B, H, W, Cin, width, out, G, stride, down, flags
+
+
+def resnext_saved_bytes(height, width, batch=1, blocks=RESNEXT101_32X8D[0], groups=RESNEXT101_32X8D[1],
+                        width_per_group=RESNEXT101_32X8D[2]):
+    """Bytes the training forward of the whole backbone keeps for its backward at `batch` images of height x width: the stem's c and
+    post-activation and its pooled output, then every block's table (resnext_block_saved_shapes); a block's input is the previous
+    block's output and is counted once."""
+    import math
+    H, W = (int(height) - 1) // 2 + 1, (int(width) - 1) // 2 + 1
+    floats = 2 * batch * 64 * H * W + 2 * 64
+    H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    floats += batch * 64 * H * W
+    cin = 64
+    for k, count in enumerate(blocks):
+        planes = 64 << k
+        mid, out = planes * int(width_per_group) // 64 * int(groups), 4 * planes
+        for i in range(count):
+            stride = 2 if (i == 0 and k > 0) else 1
+            floats += sum(math.prod(s) for s in resnext_block_saved_shapes(batch, H, W, cin, mid, out, stride, i == 0))
+            H, W, cin = (H - 1) // stride + 1, (W - 1) // stride + 1, out
+    return 4 * floats
+
+
 class _DeviceArrays:
     """Raw device buffers of the numpy mirror of a `*_device` entry point (null stream, blocking copies); freed on exit."""
 
@@ -1177,6 +1391,9 @@ EXPORTED_SYMBOLS = [
     "cvd_midas_conv_grad_input_device", "cvd_midas_conv_grad_weight_device", "cvd_midas_upsample2x_grad_device", "cvd_midas_head_grad_device",
     "cvd_midas_decoder_train_device", "cvd_midas_decoder_backward_device", "cvd_midas_decoder_backward_timed",
     "cvd_resnext_grouped_conv_device", "cvd_resnext_conv_device", "cvd_resnext_maxpool_device", "cvd_midas_backbone_device", "cvd_midas_backbone_timed",
+    "cvd_resnext_norm_train_device", "cvd_resnext_norm_grad_device", "cvd_resnext_grouped_conv_grad_input_device",
+    "cvd_resnext_grouped_conv_grad_weight_device", "cvd_resnext_conv_grad_input_device", "cvd_resnext_conv_grad_weight_device",
+    "cvd_resnext_maxpool_grad_device", "cvd_resnext_block_train_device", "cvd_resnext_block_backward_device",
     "cvd_get_summary", "cvd_num_records", "cvd_get_records",
     "cvd_get_kernel_times", "cvd_get_comm_times", "cvd_get_dense_times", "cvd_set_kernel_timing", "cvd_num_active_constraints", "cvd_coarse_debug", "cvd_temporal_debug", "cvd_path_info", "cvd_abi_revision",
     "cvd_block_inverse_debug", "cvd_dense_inverse_debug", "cvd_epipolar_debug", "cvd_flow_masks_debug",
@@ -2264,6 +2481,205 @@ class Solver(Binding):
                 raise RuntimeError("resnext_maxpool: the device reported an error")
             dev.download(do, out)
         return out
+
+    def _rxg_run(self, who, name, dev, scalars, tail, outs):
+        """One `*_device` call of csrc/cvd_resnext_grad.h on uploaded arrays: scalars, then the device pointers `tail`, the null
+        stream; downloads `outs` = [(device pointer, host array)]."""
+        self._check(self._fn(name)(self._h, *scalars, *tail, None))
+        if _hip_runtime().hipDeviceSynchronize() != 0:
+            raise RuntimeError(f"{who}: the device reported an error")
+        for d, a in outs:
+            dev.download(d, a)
+
+    def resnext_norm_train(self, c, norm, eps=RESNEXT_EPS, momentum=RESNEXT_MOMENTUM, training=True, relu=False, residual=None):
+        """nn.BatchNorm2d on the raw convolution output c [B, N, H, W] f32 (csrc/cvd_resnext_grad.h); norm = (weight,
+        bias, running_mean, running_var).  training: batch statistics, else the running ones.  y = (c - mean) invstd weight + bias,
+        ReLU under relu, max(residual + y, 0) with a residual -> (y, save_mean, save_invstd, running_mean, running_var), the last
+        two after the call (the inputs are not modified)."""
+        import numpy as np
+        c = np.asarray(c)
+        norm = [np.asarray(a) for a in norm]
+        residual = None if residual is None else np.asarray(residual)
+        self._midas_f32("resnext_norm_train", [c, residual] + norm)
+        B, N, H, W = resnext_check_norm_train(c.shape, [a.shape for a in norm], eps, momentum, training,
+                                              None if residual is None else residual.shape)
+        y = np.zeros((B, N, H, W), np.float32)
+        vec = [np.zeros((N,), np.float32) for _ in range(4)]
+        with _DeviceArrays() as dev:
+            dc = dev.upload(np.ascontiguousarray(c))
+            dn = [dev.upload(np.ascontiguousarray(a)) for a in norm]
+            dr = None if residual is None else dev.upload(np.ascontiguousarray(residual))
+            dm, di, dy = dev.alloc(4 * N), dev.alloc(4 * N), dev.alloc(y.nbytes)
+            self._rxg_run("resnext_norm_train", "resnext_norm_train_device", dev,
+                          [C.c_int32(B), C.c_int32(N), C.c_int32(H), C.c_int32(W)],
+                          [dc, dn[0], dn[1], dn[2], dn[3], C.c_double(eps), C.c_double(momentum), C.c_int32(1 if training else 0),
+                           C.c_int32(1 if relu else 0), dr, dm, di, dy],
+                          [(dy, y), (dm, vec[0]), (di, vec[1]), (dn[2], vec[2]), (dn[3], vec[3])])
+        return (y, *vec)
+
+    def resnext_norm_grad(self, gy, c, mean, invstd, gamma, y=None, training=True, residual=False):
+        """Backward of resnext_norm_train: gy, c [B, N, H, W] f32, the saved mean and invstd, the norm's weight; y = the layer's output
+        where the forward applied a ReLU or the residual form (the mask is y > 0) -> (gc, g_gamma, g_beta, g_residual or None)."""
+        import numpy as np
+        gy, c, mean, invstd, gamma = (np.asarray(a) for a in (gy, c, mean, invstd, gamma))
+        y = None if y is None else np.asarray(y)
+        self._midas_f32("resnext_norm_grad", [gy, c, mean, invstd, gamma, y])
+        B, N, H, W = resnext_check_norm_grad(gy.shape, c.shape, None if y is None else y.shape, [mean.shape, invstd.shape, gamma.shape],
+                                             training)
+        gc = np.zeros((B, N, H, W), np.float32)
+        gg, gb = np.zeros((N,), np.float32), np.zeros((N,), np.float32)
+        gr = np.zeros((B, N, H, W), np.float32) if residual else None
+        with _DeviceArrays() as dev:
+            dg, dc, dm, di, dw = (dev.upload(np.ascontiguousarray(a)) for a in (gy, c, mean, invstd, gamma))
+            dy = None if y is None else dev.upload(np.ascontiguousarray(y))
+            do, dgg, dgb = dev.alloc(gc.nbytes), dev.alloc(4 * N), dev.alloc(4 * N)
+            dr = dev.alloc(gc.nbytes) if residual else None
+            self._rxg_run("resnext_norm_grad", "resnext_norm_grad_device", dev, [C.c_int32(B), C.c_int32(N), C.c_int32(H), C.c_int32(W)],
+                          [dg, dc, dy, dm, di, dw, C.c_int32(1 if training else 0), do, dgg, dgb, dr],
+                          [(do, gc), (dgg, gg), (dgb, gb)] + ([(dr, gr)] if residual else []))
+        return gc, gg, gb, gr
+
+    def resnext_grouped_conv_grad_input(self, gy, weight, x_size, stride=1):
+        """Input gradient of resnext_grouped_conv: gy [B, G Cg, Ho, Wo] f32, weight [G Cg, Cg, 3, 3], x_size = (H, W) of the
+        convolution's input -> gx [B, G Cg, H, W]."""
+        import numpy as np
+        gy, weight = np.asarray(gy), np.asarray(weight)
+        self._midas_f32("resnext_grouped_conv_grad_input", [gy, weight])
+        B, H, W, G, cg = resnext_check_grouped_conv_grad_input(gy.shape, weight.shape, x_size, stride)
+        stride = _resnext_stride("resnext_grouped_conv_grad_input", stride)
+        gx = np.zeros((B, G * cg, H, W), np.float32)
+        with _DeviceArrays() as dev:
+            dg, dw = dev.upload(np.ascontiguousarray(gy)), dev.upload(np.ascontiguousarray(weight))
+            do = dev.alloc(gx.nbytes)
+            self._rxg_run("resnext_grouped_conv_grad_input", "resnext_grouped_conv_grad_input_device", dev,
+                          [C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(G), C.c_int32(cg), C.c_int32(stride)], [dg, dw, do],
+                          [(do, gx)])
+        return gx
+
+    def resnext_grouped_conv_grad_weight(self, gy, x, channels_per_group, stride=1, split=0):
+        """Weight gradient of resnext_grouped_conv: gy [B, G Cg, Ho, Wo] f32, x [B, G Cg, H, W] -> gW [G Cg, Cg, 3, 3].  split: 0 =
+        the rule (resnext_wgrad_split), else the forced number of slices of the pixels."""
+        import numpy as np
+        gy, x = np.asarray(gy), np.asarray(x)
+        self._midas_f32("resnext_grouped_conv_grad_weight", [gy, x])
+        B, H, W, G, cg = resnext_check_grouped_conv_grad_weight(gy.shape, x.shape, channels_per_group, stride, split)
+        stride = _resnext_stride("resnext_grouped_conv_grad_weight", stride)
+        gw = np.zeros((G * cg, cg, 3, 3), np.float32)
+        with _DeviceArrays() as dev:
+            dg, dx = dev.upload(np.ascontiguousarray(gy)), dev.upload(np.ascontiguousarray(x))
+            do = dev.alloc(gw.nbytes)
+            self._rxg_run("resnext_grouped_conv_grad_weight", "resnext_grouped_conv_grad_weight_device", dev,
+                          [C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(G), C.c_int32(cg), C.c_int32(stride)],
+                          [dg, dx, C.c_int32(split), do], [(do, gw)])
+        return gw
+
+    def resnext_conv_grad_input(self, gy, weight, x_size, stride=1, add=None):
+        """Input gradient of a 1 x 1 convolution of resnext_conv at stride 1 or 2: gy [B, N, Ho, Wo] f32, weight [N, C, 1, 1], x_size =
+        (H, W) -> gx [B, C, H, W] = conv_transpose(gy) + add."""
+        import numpy as np
+        gy, weight = np.asarray(gy), np.asarray(weight)
+        add = None if add is None else np.asarray(add)
+        self._midas_f32("resnext_conv_grad_input", [gy, weight, add])
+        B, H, W, Cin, N = resnext_check_conv_grad_input(gy.shape, weight.shape, x_size, stride, None if add is None else add.shape)
+        stride = _resnext_stride("resnext_conv_grad_input", stride)
+        gx = np.zeros((B, Cin, H, W), np.float32)
+        with _DeviceArrays() as dev:
+            dg, dw = dev.upload(np.ascontiguousarray(gy)), dev.upload(np.ascontiguousarray(weight))
+            da = None if add is None else dev.upload(np.ascontiguousarray(add))
+            do = dev.alloc(gx.nbytes)
+            self._rxg_run("resnext_conv_grad_input", "resnext_conv_grad_input_device", dev,
+                          [C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(Cin), C.c_int32(N), C.c_int32(1), C.c_int32(stride)],
+                          [dg, dw, da, do], [(do, gx)])
+        return gx
+
+    def resnext_conv_grad_weight(self, gy, x, kernel_size, stride=1, split=0):
+        """Weight gradient of a dense convolution of resnext_conv: gy [B, N, Ho, Wo] f32, x [B, C, H, W], (kernel_size, stride) in
+        RESNEXT_DENSE_KERNELS -> gW [N, C, k, k]."""
+        import numpy as np
+        gy, x = np.asarray(gy), np.asarray(x)
+        self._midas_f32("resnext_conv_grad_weight", [gy, x])
+        B, H, W, Cin, N, k = resnext_check_conv_grad_weight(gy.shape, x.shape, kernel_size, stride, split)
+        stride = _resnext_stride("resnext_conv_grad_weight", stride)
+        gw = np.zeros((N, Cin, k, k), np.float32)
+        with _DeviceArrays() as dev:
+            dg, dx = dev.upload(np.ascontiguousarray(gy)), dev.upload(np.ascontiguousarray(x))
+            do = dev.alloc(gw.nbytes)
+            self._rxg_run("resnext_conv_grad_weight", "resnext_conv_grad_weight_device", dev,
+                          [C.c_int32(B), C.c_int32(H), C.c_int32(W), C.c_int32(Cin), C.c_int32(N), C.c_int32(k), C.c_int32(stride)],
+                          [dg, dx, C.c_int32(split), do], [(do, gw)])
+        return gw
+
+    def resnext_maxpool_grad(self, x, gy):
+        """Backward of resnext_maxpool: x [B, C, H, W] f32 its input, gy [B, C, Ho, Wo] -> gx [B, C, H, W]; a window's gradient goes to
+        its first maximum in row-major order, as torch's."""
+        import numpy as np
+        x, gy = np.asarray(x), np.asarray(gy)
+        self._midas_f32("resnext_maxpool_grad", [x, gy])
+        B, Cn, H, W = resnext_check_maxpool_grad(x.shape, gy.shape)
+        gx = np.zeros((B, Cn, H, W), np.float32)
+        with _DeviceArrays() as dev:
+            dx, dg = dev.upload(np.ascontiguousarray(x)), dev.upload(np.ascontiguousarray(gy))
+            do = dev.alloc(gx.nbytes)
+            self._rxg_run("resnext_maxpool_grad", "resnext_maxpool_grad_device", dev,
+                          [C.c_int32(B), C.c_int32(Cn), C.c_int32(H), C.c_int32(W)], [dx, dg, do], [(do, gx)])
+        return gx
+
+    def resnext_block_train(self, x, weights, norms, stride=1, eps=RESNEXT_EPS, momentum=RESNEXT_MOMENTUM, training=True):
+        """One Bottleneck in training form, ONE library call (cvd_resnext_block_train_device): x [B, C, H, W] f32, weights = conv1,
+        conv2, conv3 (and downsample.0), norms = (weight, bias, running_mean, running_var) per convolution, training = one flag or
+        one per norm -> (out, saved, running): the block's output, the saved table (resnext_block_saved_shapes; saved[11] is out)
+        and the (running_mean, running_var) per norm after the call.  The inputs are not modified."""
+        import numpy as np
+        x = np.asarray(x)
+        weights = [np.asarray(a) for a in weights]
+        norms = [[np.asarray(a) for a in four] for four in norms]
+        self._midas_f32("resnext_block_train", [x] + weights + [a for four in norms for a in four])
+        B, H, W, Cin, width, out, G, stride, down, flags = resnext_check_block(
+            x.shape, [a.shape for a in weights], [[a.shape for a in four] for four in norms], stride, eps, momentum, training)
+        n = len(weights)
+        saved = [np.zeros(s, np.float32) for s in resnext_block_saved_shapes(B, H, W, Cin, width, out, stride, down)]
+        with _DeviceArrays() as dev:
+            dx = dev.upload(np.ascontiguousarray(x))
+            dw = (C.c_void_p * n)(*[dev.upload(np.ascontiguousarray(a)).value for a in weights])
+            dn = [dev.upload(np.ascontiguousarray(a)) for four in norms for a in four]
+            ds = [dev.alloc(a.nbytes) for a in saved]
+            running = [[np.zeros_like(four[2]), np.zeros_like(four[3])] for four in norms]
+            self._rxg_run("resnext_block_train", "resnext_block_train_device", dev,
+                          [C.c_int32(v) for v in (B, H, W, Cin, width, out, G, stride, int(down))],
+                          [dx, dw, (C.c_void_p * (4 * n))(*[d.value for d in dn]), C.c_double(eps), C.c_double(momentum),
+                           (C.c_int32 * n)(*[int(f) for f in flags]), (C.c_void_p * (4 * n))(*[d.value for d in ds])],
+                          list(zip(ds, saved)) + [(dn[4 * i + 2 + j], running[i][j]) for i in range(n) for j in range(2)])
+        return saved[11], saved, running
+
+    def resnext_block_backward(self, gy, x, weights, gammas, saved, stride=1, training=True, input_gradient=True):
+        """Backward of resnext_block_train, ONE library call (cvd_resnext_block_backward_device): gy of the output's shape, the
+        block's input, weights, the norms' weights and the saved table -> (gx or None, [gW], [g_gamma], [g_beta])."""
+        import numpy as np
+        gy, x = np.asarray(gy), np.asarray(x)
+        weights, gammas, saved = ([np.asarray(a) for a in v] for v in (weights, gammas, saved))
+        self._midas_f32("resnext_block_backward", [gy, x] + weights + gammas + saved)
+        fake = [[g.shape] * 4 for g in gammas]
+        B, H, W, Cin, width, out, G, stride, down, flags = resnext_check_block(x.shape, [a.shape for a in weights], fake, stride,
+                                                                               training=training)
+        shapes = resnext_block_saved_shapes(B, H, W, Cin, width, out, stride, down)
+        if [a.shape for a in saved] != shapes or gy.shape != shapes[11]:
+            raise ValueError(f"resnext_block_backward: the saved table must be {shapes} and gy {shapes[11]}")
+        n = len(weights)
+        gx = np.zeros(x.shape, np.float32) if input_gradient else None
+        gw = [np.zeros(a.shape, np.float32) for a in weights]
+        gg, gb = ([np.zeros(a.shape, np.float32) for a in gammas] for _ in range(2))
+        with _DeviceArrays() as dev:
+            table = lambda arrays: (C.c_void_p * len(arrays))(*[dev.upload(np.ascontiguousarray(a)).value for a in arrays])
+            dgy, dx = dev.upload(np.ascontiguousarray(gy)), dev.upload(np.ascontiguousarray(x))
+            dgx = dev.alloc(gx.nbytes) if input_gradient else None
+            outs = [[dev.alloc(a.nbytes) for a in group] for group in (gw, gg, gb)]
+            self._rxg_run("resnext_block_backward", "resnext_block_backward_device", dev,
+                          [C.c_int32(v) for v in (B, H, W, Cin, width, out, G, stride, int(down))],
+                          [dgy, dx, table(weights), table(gammas), table(saved), (C.c_int32 * n)(*[int(f) for f in flags]), dgx]
+                          + [(C.c_void_p * n)(*[d.value for d in group]) for group in outs],
+                          ([(dgx, gx)] if input_gradient else []) + [(d, a) for group, arrays in zip(outs, (gw, gg, gb))
+                                                                     for d, a in zip(group, arrays)])
+        return gx, gw, gg, gb
 
     def midas_backbone(self, images, weights, norms, blocks=RESNEXT101_32X8D[0], groups=RESNEXT101_32X8D[1],
                        width_per_group=RESNEXT101_32X8D[2], eps=RESNEXT_EPS, kernel_ms=None):

@@ -1021,6 +1021,64 @@ int32_t cvd_midas_backbone_timed(cvd_handle* h, int32_t batch, int32_t height, i
   CVD_TRY(h, midasBackboneDevice(h, batch, height, width, blocks4, groups, width_per_group, eps, images, weights, norms, outs4,
                                  static_cast<hipStream_t>(stream), kernel_ms));
 }
+// the same backbone in training: nn.BatchNorm2d on batch statistics, and torch autograd's gradients of its layers
+int32_t cvd_resnext_norm_train_device(cvd_handle* h, int32_t batch, int32_t channels, int32_t height, int32_t width, const float* c,
+                                      const float* gamma, const float* beta, float* running_mean, float* running_var, double eps,
+                                      double momentum, int32_t training, int32_t relu, const float* residual, float* save_mean,
+                                      float* save_invstd, float* y, void* stream) {
+  CVD_TRY(h, resnextNormTrainDevice(h, batch, channels, height, width, c, gamma, beta, running_mean, running_var, eps, momentum, training,
+                                    relu, residual, save_mean, save_invstd, y, static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_resnext_norm_grad_device(cvd_handle* h, int32_t batch, int32_t channels, int32_t height, int32_t width, const float* gy,
+                                     const float* c, const float* y, const float* mean, const float* invstd, const float* gamma,
+                                     int32_t training, float* gc, float* g_gamma, float* g_beta, float* g_residual, void* stream) {
+  CVD_TRY(h, resnextNormGradDevice(h, batch, channels, height, width, gy, c, y, mean, invstd, gamma, training, gc, g_gamma, g_beta,
+                                   g_residual, static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_resnext_grouped_conv_grad_input_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t groups,
+                                                   int32_t channels_per_group, int32_t stride, const float* gy, const float* weight,
+                                                   float* gx, void* stream) {
+  CVD_TRY(h, resnextGroupedConvGradInputDevice(h, batch, height, width, groups, channels_per_group, stride, gy, weight, gx,
+                                               static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_resnext_grouped_conv_grad_weight_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t groups,
+                                                    int32_t channels_per_group, int32_t stride, const float* gy, const float* x,
+                                                    int32_t split, float* g_weight, void* stream) {
+  CVD_TRY(h, resnextGroupedConvGradWeightDevice(h, batch, height, width, groups, channels_per_group, stride, gy, x, split, g_weight,
+                                                static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_resnext_conv_grad_input_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels,
+                                           int32_t out_channels, int32_t kernel_size, int32_t stride, const float* gy, const float* weight,
+                                           const float* add, float* gx, void* stream) {
+  CVD_TRY(h, resnextConvGradInputDevice(h, batch, height, width, in_channels, out_channels, kernel_size, stride, gy, weight, add, gx,
+                                        static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_resnext_conv_grad_weight_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels,
+                                            int32_t out_channels, int32_t kernel_size, int32_t stride, const float* gy, const float* x,
+                                            int32_t split, float* g_weight, void* stream) {
+  CVD_TRY(h, resnextConvGradWeightDevice(h, batch, height, width, in_channels, out_channels, kernel_size, stride, gy, x, split, g_weight,
+                                         static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_resnext_maxpool_grad_device(cvd_handle* h, int32_t batch, int32_t channels, int32_t height, int32_t width, const float* x,
+                                        const float* gy, float* gx, void* stream) {
+  CVD_TRY(h, resnextMaxPoolGradDevice(h, batch, channels, height, width, x, gy, gx, static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_resnext_block_train_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels,
+                                       int32_t mid_channels, int32_t out_channels, int32_t groups, int32_t stride, int32_t downsample,
+                                       const float* x, const float* const* weights, float* const* norms, double eps, double momentum,
+                                       const int32_t* training, float* const* saved, void* stream) {
+  CVD_TRY(h, resnextBlockTrainDevice(h, batch, height, width, in_channels, mid_channels, out_channels, groups, stride, downsample, x,
+                                     weights, norms, eps, momentum, training, saved, static_cast<hipStream_t>(stream)));
+}
+int32_t cvd_resnext_block_backward_device(cvd_handle* h, int32_t batch, int32_t height, int32_t width, int32_t in_channels,
+                                          int32_t mid_channels, int32_t out_channels, int32_t groups, int32_t stride, int32_t downsample,
+                                          const float* gy, const float* x, const float* const* weights, const float* const* gammas,
+                                          const float* const* saved, const int32_t* training, float* gx, float* const* g_weights,
+                                          float* const* g_gammas, float* const* g_betas, void* stream) {
+  CVD_TRY(h, resnextBlockBackwardDevice(h, batch, height, width, in_channels, mid_channels, out_channels, groups, stride, downsample, gy,
+                                        x, weights, gammas, saved, training, gx, g_weights, g_gammas, g_betas,
+                                        static_cast<hipStream_t>(stream)));
+}
 int32_t cvd_get_summary(cvd_handle* h, cvd_solve_summary* s) { CVD_TRY(h, *s = h->summary); }
 int32_t cvd_num_records(cvd_handle* h) { return h ? static_cast<int32_t>(h->records.size()) : 0; }
 int32_t cvd_get_records(cvd_handle* h, cvd_iteration_record* out) {

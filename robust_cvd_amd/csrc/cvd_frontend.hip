@@ -6,7 +6,9 @@
 // k_instnorm_stats, k_instnorm_apply) and the decoder of MiDaS v2.1 (cvd_midas.h: k_midas_conv, k_midas_fold, k_midas_upsample2x), the backward of its layers
 // (cvd_midas_grad.h: k_midas_wflip, k_midas_dgrad_fold, k_midas_wgrad, k_midas_wgrad_fold, k_midas_bias_grad, k_midas_upsample2x_grad,
 // k_midas_head_grad, k_midas_head_grad_sum) and its
-// ResNeXt backbone (cvd_resnext.h: k_rx_gconv, k_rx_conv, k_rx_fold, k_rx_maxpool).  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
+// ResNeXt backbone (cvd_resnext.h: k_rx_gconv, k_rx_conv, k_rx_fold, k_rx_maxpool) with its training form and backward
+// (cvd_resnext_grad.h: k_rxg_norm_stats, k_rxg_norm_finish, k_rxg_norm_apply, k_rxg_norm_grad_sums, k_rxg_norm_grad_finish,
+// k_rxg_norm_grad_apply, k_rxg_gconv_dgrad, k_rxg_wgrad, k_rxg_wgrad_fold, k_rxg_gather2, k_rxg_scatter2, k_rxg_maxpool_grad).  The only unit that includes their kernel headers and the only one that knows their device state (Frontend; the handle owns it
 // through a pointer to the incomplete type).
 #include "cvd_host.h"
 #include "cvd_dense.h"
@@ -30,6 +32,7 @@
 #include "cvd_midas.h"
 #include "cvd_midas_grad.h"
 #include "cvd_resnext.h"
+#include "cvd_resnext_grad.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
@@ -161,6 +164,12 @@ struct Frontend {
   DevBuf<double> dMidasHeadPart;
   // cvd_resnext.h: the backbone's intermediates and the partial sums of a split convolution, under the same rule.
   DevBuf<float> dRx, dRxSplit;
+  // cvd_resnext_grad.h: the strided 1 x 1 convolution's gathered input resp. unscattered gradient, and the f64 partial sums of the
+  // batch norm's reductions and of a weight gradient, under the same rule.
+  DevBuf<float> dRxGrad;
+  DevBuf<double> dRxGradSums;
+  // the one-call block backward: the gradients between its operators
+  DevBuf<float> dRxBlock;
 };
 
 std::shared_ptr<Frontend> makeFrontend() { return std::make_shared<Frontend>(); }
@@ -3711,6 +3720,397 @@ void midasBackboneDevice(cvd_handle* h, int B, int H, int W, const int* blocks, 
     std::fill(kernelMs, kernelMs + slots, 0.0);
     for (size_t i = 0; i < slot.size(); ++i) kernelMs[slot[i]] = phaseMs[i];
   }
+}
+
+// ---- Training of the backbone (cvd_resnext_grad.h): nn.BatchNorm2d in training and in eval mode with its backward,
+// and the backward of the backbone's convolutions and of its pool.  Device arrays on the caller's stream: enqueued launches only. -----
+namespace {
+struct RxgNormPlan {
+  int S;
+  long long perSlice;
+};
+
+RxgNormPlan rxgNormPlan(int N, long long M) {
+  const long long chunks = (M + kRgNormChunk - 1) / kRgNormChunk;
+  const int want = rxgNormSplit(N, M);
+  const long long per = (chunks + want - 1) / want;
+  return {static_cast<int>((chunks + per - 1) / per), per * kRgNormChunk};
+}
+
+// channelGrid: the caller puts the channels on grid.y (the two batch norm reductions)
+long long checkRxgPlanes(const char* who, int B, int channels, int H, int W, bool channelGrid = false) {
+  if (B < 1 || channels < 1 || H < 1 || W < 1)
+    throw std::runtime_error(fmt("%s: batch, channels, height and width must be >= 1 (got %d, %d, %d, %d)", who, B, channels, H, W));
+  const long long HW = static_cast<long long>(H) * W;
+  if (HW > 0x7fffffffll) throw std::runtime_error(fmt("%s: %d x %d pixels per image exceed 2^31", who, H, W));
+  if (channelGrid && channels > 65535) throw std::runtime_error(fmt("%s: %d channels exceed the grid", who, channels));
+  const long long total = HW * B * channels;
+  if ((total + kRgThreads - 1) / kRgThreads > 0x7fffffffll)
+    throw std::runtime_error(fmt("%s: %lld elements exceed the grid", who, total));
+  return total;
+}
+
+template <int KS, int STRIDE>
+void launchRxgWgradK(const RxgConvArgs& A, dim3 grid, hipStream_t s) {
+  hipLaunchKernelGGL((k_rxg_wgrad<KS, STRIDE>), grid, dim3(kRgThreads), 0, s, A);
+}
+
+// The weight gradient of a (grouped) ks x ks convolution on k_rxg_wgrad and its fold.  Checked by the callers.
+void launchRxgWgrad(Frontend& fe, int B, int H, int W, int Cin, int N, int cg, int ng, int ks, int stride, const float* gy, const float* x,
+                    int split, float* gWeight, hipStream_t s) {
+  RxgConvArgs A{};
+  A.gy = gy; A.x = x;
+  A.Cin = Cin; A.N = N; A.CG = cg; A.NG = ng;
+  A.H = H; A.W = W; A.HW = H * W;
+  A.Ho = (H - 1) / stride + 1; A.Wo = (W - 1) / stride + 1; A.HWo = A.Ho * A.Wo;
+  A.M = static_cast<long long>(A.HWo) * B;
+  A.elements = static_cast<long long>(N) * cg * ks * ks;
+  const long long chains = (A.M + kRgWgradChain - 1) / kRgWgradChain;
+  const long long want = split > 0 ? std::min<long long>(split, chains) : rxgWgradSplit(A.M, A.elements);
+  const long long per = (chains + want - 1) / want;
+  const int S = static_cast<int>((chains + per - 1) / per);                      // (a forced split may shrink: slices are whole chains)
+  A.chainsPerSlice = per;
+  fe.dRxGradSums.ensure(static_cast<size_t>(S) * static_cast<size_t>(A.elements));
+  A.partial = fe.dRxGradSums.p;
+  const dim3 grid(static_cast<unsigned>((A.elements + kRgThreads - 1) / kRgThreads), static_cast<unsigned>(S));
+  if (ks == 7) launchRxgWgradK<7, 2>(A, grid, s);
+  else if (stride == 1) launchRxgWgradK<3, 1>(A, grid, s);
+  else launchRxgWgradK<3, 2>(A, grid, s);
+  HIP_CHECK(hipGetLastError());
+  RxgFoldArgs F{};
+  F.partial = fe.dRxGradSums.p; F.out = gWeight; F.S = S; F.total = A.elements;
+  hipLaunchKernelGGL(k_rxg_wgrad_fold, dim3(static_cast<unsigned>((F.total + kRgThreads - 1) / kRgThreads)), dim3(kRgThreads), 0, s, F);
+  HIP_CHECK(hipGetLastError());
+}
+
+template <int CG>
+void launchRxgGroupDgradK(const RxgConvArgs& A, int stride, dim3 grid, hipStream_t s) {
+  if (stride == 1) hipLaunchKernelGGL((k_rxg_gconv_dgrad<CG, 1>), grid, dim3(kRgThreads), 0, s, A);
+  else hipLaunchKernelGGL((k_rxg_gconv_dgrad<CG, 2>), grid, dim3(kRgThreads), 0, s, A);
+}
+}  // namespace
+
+// nn.BatchNorm2d on the raw convolution output c [B][N][H][W]: y = (c - mean) invstd gamma + beta, ReLU under relu, with a residual
+// max(residual + y, 0).  training: the batch statistics (written to saveMean / saveInvstd, the running statistics updated with
+// `momentum`); else the running statistics (saveMean / saveInvstd receive what the expression used, for the backward).
+void resnextNormTrainDevice(cvd_handle* h, int B, int channels, int H, int W, const float* c, const float* gamma, const float* beta,
+                            float* runningMean, float* runningVar, double eps, double momentum, int training, int relu,
+                            const float* residual, float* saveMean, float* saveInvstd, float* y, hipStream_t s) {
+  const char* who = "resnext norm train";
+  const long long total = checkRxgPlanes(who, B, channels, H, W, true);
+  checkFlag(who, "training", training);
+  checkFlag(who, "relu", relu);
+  if (!(eps > 0.0)) throw std::runtime_error(fmt("%s: eps must be > 0 (got %g)", who, eps));
+  if (!(momentum >= 0.0 && momentum <= 1.0)) throw std::runtime_error(fmt("%s: momentum must lie in [0, 1] (got %g)", who, momentum));
+  const long long M = total / channels;
+  if (training && M < 2)
+    throw std::runtime_error(fmt("%s: training mode needs more than 1 value per channel (got batch %d of %d x %d)", who, B, H, W));
+  if (!c || !gamma || !beta || !runningMean || !runningVar || !saveMean || !saveInvstd || !y) throw std::runtime_error(fmt("%s: null array", who));
+  if (rangesOverlap(y, total, c, total)) throw std::runtime_error(fmt("%s: y overlaps c", who));
+  if (residual && rangesOverlap(y, total, residual, total)) throw std::runtime_error(fmt("%s: y overlaps the residual", who));
+  const std::pair<const float*, const char*> vectors[] = {{gamma, "gamma"}, {beta, "beta"}, {runningMean, "running_mean"},
+                                                          {runningVar, "running_var"}, {saveMean, "save_mean"}, {saveInvstd, "save_invstd"}};
+  for (const auto& v : vectors)
+    if (rangesOverlap(y, total, v.first, channels)) throw std::runtime_error(fmt("%s: y overlaps %s", who, v.second));
+  for (int i = 2; i < 6; ++i) {
+    if (rangesOverlap(vectors[i].first, channels, c, total)) throw std::runtime_error(fmt("%s: %s overlaps c", who, vectors[i].second));
+    for (int j = 0; j < i; ++j)
+      if (rangesOverlap(vectors[i].first, channels, vectors[j].first, channels))
+        throw std::runtime_error(fmt("%s: %s overlaps %s", who, vectors[i].second, vectors[j].second));
+  }
+  Frontend& fe = *h->frontend;
+  const RxgNormPlan plan = rxgNormPlan(channels, M);
+  RxgNormArgs A{};
+  A.c = c; A.gamma = gamma; A.beta = beta; A.residual = residual; A.mean = saveMean; A.invstd = saveInvstd; A.out = y;
+  A.relu = relu; A.training = training;
+  A.N = channels; A.HW = H * W; A.S = plan.S; A.perSlice = plan.perSlice; A.M = M; A.total = total;
+  if (training) {
+    fe.dRxGradSums.ensure(static_cast<size_t>(channels) * plan.S * 2);
+    A.partial = fe.dRxGradSums.p;
+    hipLaunchKernelGGL(k_rxg_norm_stats, dim3(static_cast<unsigned>(plan.S), static_cast<unsigned>(channels)), dim3(kRgThreads), 0, s, A);
+    HIP_CHECK(hipGetLastError());
+  }
+  RxgNormFinishArgs F{};
+  F.partial = fe.dRxGradSums.p; F.runningMean = runningMean; F.runningVar = runningVar; F.mean = saveMean; F.invstd = saveInvstd;
+  F.eps = eps; F.momentum = momentum; F.training = training; F.N = channels; F.S = plan.S; F.M = M;
+  hipLaunchKernelGGL(k_rxg_norm_finish, dim3(static_cast<unsigned>((channels + kRgThreads - 1) / kRgThreads)), dim3(kRgThreads), 0, s, F);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_rxg_norm_apply, dim3(static_cast<unsigned>((total + kRgThreads - 1) / kRgThreads)), dim3(kRgThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+}
+
+// Its backward: g = gy [y > 0] with the layer's output y (null: g = gy); gBeta = sum g, gGamma = sum g xhat; gc; gResidual = g.
+void resnextNormGradDevice(cvd_handle* h, int B, int channels, int H, int W, const float* gy, const float* c, const float* y,
+                           const float* mean, const float* invstd, const float* gamma, int training, float* gc, float* gGamma,
+                           float* gBeta, float* gResidual, hipStream_t s) {
+  const char* who = "resnext norm grad";
+  const long long total = checkRxgPlanes(who, B, channels, H, W, true);
+  checkFlag(who, "training", training);
+  const long long M = total / channels;
+  if (training && M < 2)
+    throw std::runtime_error(fmt("%s: training mode needs more than 1 value per channel (got batch %d of %d x %d)", who, B, H, W));
+  if (!gy || !c || !mean || !invstd || !gamma || !gc || !gGamma || !gBeta) throw std::runtime_error(fmt("%s: null array", who));
+  const std::pair<const float*, long long> inputs[] = {{gy, total}, {c, total}, {y, y ? total : 0}, {mean, channels},
+                                                       {invstd, channels}, {gamma, channels}};
+  const std::pair<const float*, long long> outputs[] = {{gc, total}, {gGamma, channels}, {gBeta, channels},
+                                                        {gResidual, gResidual ? total : 0}};
+  for (int i = 0; i < 4; ++i) {
+    if (!outputs[i].first) continue;
+    for (const auto& in : inputs)
+      if (in.first && rangesOverlap(outputs[i].first, outputs[i].second, in.first, in.second))
+        throw std::runtime_error(fmt("%s: output %d overlaps an input", who, i));
+    for (int j = 0; j < i; ++j)
+      if (outputs[j].first && rangesOverlap(outputs[i].first, outputs[i].second, outputs[j].first, outputs[j].second))
+        throw std::runtime_error(fmt("%s: output %d overlaps output %d", who, i, j));
+  }
+  Frontend& fe = *h->frontend;
+  const RxgNormPlan plan = rxgNormPlan(channels, M);
+  fe.dRxGradSums.ensure(static_cast<size_t>(channels) * plan.S * 2);
+  RxgNormArgs A{};
+  A.c = c; A.y = y; A.gy = gy; A.gamma = gamma; A.mean = mean; A.invstd = invstd; A.gbeta = gBeta; A.ggamma = gGamma;
+  A.out = gc; A.outResidual = gResidual; A.partial = fe.dRxGradSums.p; A.training = training;
+  A.N = channels; A.HW = H * W; A.S = plan.S; A.perSlice = plan.perSlice; A.M = M; A.total = total;
+  hipLaunchKernelGGL(k_rxg_norm_grad_sums, dim3(static_cast<unsigned>(plan.S), static_cast<unsigned>(channels)), dim3(kRgThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+  RxgNormGradFinishArgs F{};
+  F.partial = fe.dRxGradSums.p; F.gbeta = gBeta; F.ggamma = gGamma; F.N = channels; F.S = plan.S;
+  hipLaunchKernelGGL(k_rxg_norm_grad_finish, dim3(static_cast<unsigned>((channels + kRgThreads - 1) / kRgThreads)), dim3(kRgThreads), 0, s, F);
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_rxg_norm_grad_apply, dim3(static_cast<unsigned>((total + kRgThreads - 1) / kRgThreads)), dim3(kRgThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+}
+
+// gy [B][G cg][Ho][Wo], weight [G cg][cg][3][3] -> gx [B][G cg][H][W]
+void resnextGroupedConvGradInputDevice(cvd_handle*, int B, int H, int W, int groups, int channelsPerGroup, int stride, const float* gy,
+                                       const float* weight, float* gx, hipStream_t s) {
+  const char* who = "resnext grouped conv grad input";
+  const RxDims d = checkRxShape(who, B, H, W, stride);
+  checkRxGroups(who, groups, channelsPerGroup, d.HW * B);
+  if (!gy || !weight || !gx) throw std::runtime_error(fmt("%s: null array", who));
+  const long long N = static_cast<long long>(groups) * channelsPerGroup;
+  if (rangesOverlap(gx, d.HW * B * N, gy, d.M * N)) throw std::runtime_error(fmt("%s: gx overlaps gy", who));
+  if (rangesOverlap(gx, d.HW * B * N, weight, N * channelsPerGroup * 9)) throw std::runtime_error(fmt("%s: gx overlaps the weight", who));
+  RxgConvArgs A{};
+  A.gy = gy; A.w = weight; A.out = gx;
+  A.Cin = A.N = static_cast<int>(N); A.CG = A.NG = channelsPerGroup;
+  A.H = H; A.W = W; A.HW = H * W; A.Ho = d.Ho; A.Wo = d.Wo; A.HWo = static_cast<int>(d.HWo);
+  A.M = d.HW * B;
+  const dim3 grid(static_cast<unsigned>((A.M + kRgTile - 1) / kRgTile), static_cast<unsigned>((N + kRgGroupTileN - 1) / kRgGroupTileN));
+  switch (channelsPerGroup) {
+    case 8: launchRxgGroupDgradK<8>(A, stride, grid, s); break;
+    case 16: launchRxgGroupDgradK<16>(A, stride, grid, s); break;
+    case 32: launchRxgGroupDgradK<32>(A, stride, grid, s); break;
+    default: launchRxgGroupDgradK<64>(A, stride, grid, s); break;
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// gy [B][G cg][Ho][Wo], x [B][G cg][H][W] -> gWeight [G cg][cg][3][3]
+void resnextGroupedConvGradWeightDevice(cvd_handle* h, int B, int H, int W, int groups, int channelsPerGroup, int stride, const float* gy,
+                                        const float* x, int split, float* gWeight, hipStream_t s) {
+  const char* who = "resnext grouped conv grad weight";
+  const RxDims d = checkRxShape(who, B, H, W, stride);
+  checkRxGroups(who, groups, channelsPerGroup, d.HW * B);
+  if (split < 0 || split > kRgWgradMaxSplit)
+    throw std::runtime_error(fmt("%s: split must be 0 (the rule) or 1 .. %d (got %d)", who, kRgWgradMaxSplit, split));
+  if (!gy || !x || !gWeight) throw std::runtime_error(fmt("%s: null array", who));
+  const long long N = static_cast<long long>(groups) * channelsPerGroup, wFloats = N * channelsPerGroup * 9;
+  if (rangesOverlap(gWeight, wFloats, gy, d.M * N) || rangesOverlap(gWeight, wFloats, x, d.HW * B * N))
+    throw std::runtime_error(fmt("%s: the weight gradient overlaps an input", who));
+  launchRxgWgrad(*h->frontend, B, H, W, static_cast<int>(N), static_cast<int>(N), channelsPerGroup, channelsPerGroup, 3, stride, gy, x,
+                 split, gWeight, s);
+}
+
+// The dense convolutions' input gradient: 1 x 1 at stride 1 or 2 (the stem's images need none).  gy [B][N][Ho][Wo], weight
+// [N][Cin][1][1], add (or null) [B][Cin][H][W] -> gx [B][Cin][H][W] = conv_transpose(gy) + add.  Stride 1 is the decoder's input
+// gradient; stride 2 runs it at Ho x Wo into scratch and k_rxg_scatter2 places it at the even positions.
+void resnextConvGradInputDevice(cvd_handle* h, int B, int H, int W, int inChannels, int outChannels, int kernelSize, int stride,
+                                const float* gy, const float* weight, const float* add, float* gx, hipStream_t s) {
+  const char* who = "resnext conv grad input";
+  const RxDims d = checkRxShape(who, B, H, W, stride);
+  if (kernelSize != 1) throw std::runtime_error(fmt("%s: kernel_size must be 1: the stem's input gradient is not built (got %d)", who, kernelSize));
+  checkRxChannels(who, inChannels, outChannels, 1, stride, d.M);
+  if (stride == 1) {
+    midasConvGradInputDevice(h, B, H, W, inChannels, outChannels, 1, gy, weight, add, nullptr, 0, gx, s);
+    return;
+  }
+  const long long total = checkRxgPlanes(who, B, inChannels, H, W);
+  if (!gy || !weight || !gx) throw std::runtime_error(fmt("%s: null array", who));
+  if (rangesOverlap(gx, total, gy, d.M * outChannels)) throw std::runtime_error(fmt("%s: gx overlaps gy", who));
+  if (rangesOverlap(gx, total, weight, static_cast<long long>(inChannels) * outChannels)) throw std::runtime_error(fmt("%s: gx overlaps the weight", who));
+  if (add && rangesOverlap(gx, total, add, total)) throw std::runtime_error(fmt("%s: gx overlaps the addend", who));
+  Frontend& fe = *h->frontend;
+  fe.dRxGrad.ensure(static_cast<size_t>(d.M) * inChannels);
+  midasConvGradInputDevice(h, B, d.Ho, d.Wo, inChannels, outChannels, 1, gy, weight, nullptr, nullptr, 0, fe.dRxGrad.p, s);
+  RxgStrideArgs A{};
+  A.in = fe.dRxGrad.p; A.add = add; A.out = gx; A.H = H; A.W = W; A.Ho = d.Ho; A.Wo = d.Wo; A.total = total;
+  hipLaunchKernelGGL(k_rxg_scatter2, dim3(static_cast<unsigned>((total + kRgThreads - 1) / kRgThreads)), dim3(kRgThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+}
+
+// The dense convolutions' weight gradient: gy [B][N][Ho][Wo], x [B][Cin][H][W] -> gWeight [N][Cin][k][k].  1 x 1 at stride 1 is the
+// decoder's weight gradient; at stride 2 the same on x gathered at the even positions; the 7 x 7 stem runs k_rxg_wgrad.
+void resnextConvGradWeightDevice(cvd_handle* h, int B, int H, int W, int inChannels, int outChannels, int kernelSize, int stride,
+                                 const float* gy, const float* x, int split, float* gWeight, hipStream_t s) {
+  const char* who = "resnext conv grad weight";
+  const RxDims d = checkRxShape(who, B, H, W, stride);
+  checkRxChannels(who, inChannels, outChannels, kernelSize, stride, d.M);
+  if (kernelSize == 7 && (split < 0 || split > kRgWgradMaxSplit))       // (the 1 x 1 paths' split is checked by the path they run)
+    throw std::runtime_error(fmt("%s: split must be 0 (the rule) or 1 .. %d (got %d)", who, kRgWgradMaxSplit, split));
+  if (kernelSize == 1 && stride == 1) {
+    midasConvGradWeightDevice(h, B, H, W, inChannels, outChannels, 1, gy, x, 0, split, gWeight, nullptr, s);
+    return;
+  }
+  if (!gy || !x || !gWeight) throw std::runtime_error(fmt("%s: null array", who));
+  const long long wFloats = static_cast<long long>(inChannels) * outChannels * kernelSize * kernelSize;
+  if (rangesOverlap(gWeight, wFloats, gy, d.M * outChannels) || rangesOverlap(gWeight, wFloats, x, d.HW * B * inChannels))
+    throw std::runtime_error(fmt("%s: the weight gradient overlaps an input", who));
+  Frontend& fe = *h->frontend;
+  if (kernelSize == 7) {
+    if ((wFloats + kRgThreads - 1) / kRgThreads > 0x7fffffffll) throw std::runtime_error(fmt("%s: %lld weights exceed the grid", who, wFloats));
+    launchRxgWgrad(fe, B, H, W, inChannels, outChannels, inChannels, outChannels, 7, 2, gy, x, split, gWeight, s);
+    return;
+  }
+  checkRxgPlanes(who, B, inChannels, d.Ho, d.Wo);
+  fe.dRxGrad.ensure(static_cast<size_t>(d.M) * inChannels);
+  RxgStrideArgs A{};
+  A.in = x; A.out = fe.dRxGrad.p; A.H = H; A.W = W; A.Ho = d.Ho; A.Wo = d.Wo; A.total = d.M * inChannels;
+  hipLaunchKernelGGL(k_rxg_gather2, dim3(static_cast<unsigned>((A.total + kRgThreads - 1) / kRgThreads)), dim3(kRgThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+  midasConvGradWeightDevice(h, B, d.Ho, d.Wo, inChannels, outChannels, 1, gy, fe.dRxGrad.p, 0, split, gWeight, nullptr, s);
+}
+
+// x [B][channels][H][W], gy [B][channels][Ho][Wo] -> gx [B][channels][H][W]
+void resnextMaxPoolGradDevice(cvd_handle*, int B, int channels, int H, int W, const float* x, const float* gy, float* gx, hipStream_t s) {
+  const char* who = "resnext maxpool grad";
+  const long long total = checkRxgPlanes(who, B, channels, H, W);
+  const RxDims d = checkRxShape(who, B, H, W, 2);
+  if (!x || !gy || !gx) throw std::runtime_error(fmt("%s: null array", who));
+  const long long planes = static_cast<long long>(B) * channels;
+  if (rangesOverlap(gx, total, x, total)) throw std::runtime_error(fmt("%s: gx overlaps x", who));
+  if (rangesOverlap(gx, total, gy, planes * d.HWo)) throw std::runtime_error(fmt("%s: gx overlaps gy", who));
+  RxgPoolArgs A{};
+  A.x = x; A.gy = gy; A.out = gx; A.H = H; A.W = W; A.Ho = d.Ho; A.Wo = d.Wo; A.total = total;
+  hipLaunchKernelGGL(k_rxg_maxpool_grad, dim3(static_cast<unsigned>((total + kRgThreads - 1) / kRgThreads)), dim3(kRgThreads), 0, s, A);
+  HIP_CHECK(hipGetLastError());
+}
+
+// ---- One Bottleneck per call.  weights: conv1, conv2, conv3 (and downsample.0); norms: 4 vectors per convolution {weight, bias,
+// running_mean, running_var}; training: one flag per norm; saved: 4 tensors per convolution {c, mean, invstd, post-activation}, the
+// post-activation of conv3 being the block's output (api.resnext_block_saved_shapes).  Both calls run the operator entry points
+// above in order, so their results are the chained operators' bit for bit. ---------------------------------------------------------
+namespace {
+struct RxBlockDims {
+  int n, cg, Ho, Wo;
+  long long mIn, mOut;
+};
+
+RxBlockDims checkRxBlock(const char* who, int B, int H, int W, int inChannels, int width, int outChannels, int groups, int stride,
+                         int downsample) {
+  const RxDims d = checkRxShape(who, B, H, W, stride);
+  checkFlag(who, "downsample", downsample);
+  if (inChannels < 1 || width < 1 || outChannels < 1 || groups < 1)
+    throw std::runtime_error(fmt("%s: in_channels, width, out_channels and groups must be >= 1 (got %d, %d, %d, %d)", who, inChannels,
+                                 width, outChannels, groups));
+  if (width % groups) throw std::runtime_error(fmt("%s: width %d is no whole groups of %d", who, width, groups));
+  if (!downsample && (stride != 1 || inChannels != outChannels))
+    throw std::runtime_error(fmt("%s: without a downsample branch stride must be 1 and in_channels == out_channels (got %d, %d, %d)", who,
+                                 stride, inChannels, outChannels));
+  checkRxGroups(who, groups, width / groups, d.HW * B);
+  return {downsample ? 4 : 3, width / groups, d.Ho, d.Wo, d.HW * B, d.M};
+}
+}  // namespace
+
+void resnextBlockTrainDevice(cvd_handle* h, int B, int H, int W, int inChannels, int width, int outChannels, int groups, int stride,
+                             int downsample, const float* x, const float* const* weights, float* const* norms, double eps,
+                             double momentum, const int* training, float* const* saved, hipStream_t s) {
+  const char* who = "resnext block train";
+  const RxBlockDims d = checkRxBlock(who, B, H, W, inChannels, width, outChannels, groups, stride, downsample);
+  if (!x || !weights || !norms || !training || !saved) throw std::runtime_error(fmt("%s: null array", who));
+  for (int i = 0; i < d.n; ++i) {
+    if (!weights[i]) throw std::runtime_error(fmt("%s: null weight %d", who, i));
+    for (int j = 0; j < 4; ++j) {
+      if (!norms[4 * i + j]) throw std::runtime_error(fmt("%s: null norm vector %d of convolution %d", who, j, i));
+      if (!saved[4 * i + j]) throw std::runtime_error(fmt("%s: null saved tensor %d of convolution %d", who, j, i));
+    }
+  }
+  const long long counts[4] = {d.mIn * width, d.mOut * width, d.mOut * outChannels, d.mOut * outChannels};
+  for (int i = 0; i < d.n; ++i)
+    for (int j = 0; j < 4; j += 3) {
+      if (rangesOverlap(saved[4 * i + j], counts[i], x, d.mIn * inChannels))
+        throw std::runtime_error(fmt("%s: saved tensor %d of convolution %d overlaps x", who, j, i));
+      for (int k = 0; k < 4 * i + j; ++k)
+        if (k % 4 == 0 || k % 4 == 3)
+          if (rangesOverlap(saved[4 * i + j], counts[i], saved[k], counts[k / 4]))
+            throw std::runtime_error(fmt("%s: saved tensors %d and %d overlap", who, 4 * i + j, k));
+    }
+  const float fe = static_cast<float>(eps);
+  const auto norm = [&](int i, int channels, int hh, int ww, int relu, const float* residual) {
+    resnextNormTrainDevice(h, B, channels, hh, ww, saved[4 * i], norms[4 * i], norms[4 * i + 1], norms[4 * i + 2], norms[4 * i + 3], eps,
+                           momentum, training[i], relu, residual, saved[4 * i + 1], saved[4 * i + 2], saved[4 * i + 3], s);
+  };
+  resnextConvDevice(h, B, H, W, inChannels, width, 1, 1, x, weights[0], nullptr, fe, 0, nullptr, 0, saved[0], s);
+  norm(0, width, H, W, 1, nullptr);
+  resnextGroupedConvDevice(h, B, H, W, groups, d.cg, stride, saved[3], weights[1], nullptr, fe, 0, saved[4], s);
+  norm(1, width, d.Ho, d.Wo, 1, nullptr);
+  const float* identity = x;
+  if (downsample) {
+    resnextConvDevice(h, B, H, W, inChannels, outChannels, 1, stride, x, weights[3], nullptr, fe, 0, nullptr, 0, saved[12], s);
+    norm(3, outChannels, d.Ho, d.Wo, 0, nullptr);
+    identity = saved[15];
+  }
+  resnextConvDevice(h, B, d.Ho, d.Wo, width, outChannels, 1, 1, saved[7], weights[2], nullptr, fe, 0, nullptr, 0, saved[8], s);
+  norm(2, outChannels, d.Ho, d.Wo, 0, identity);
+}
+
+// gy [B][out][Ho][Wo] -> gx (or null) [B][in][H][W], gWeights[n], gGammas[n], gBetas[n]: bn3 (mask = the block's output, which yields
+// the residual branch's gradient), conv3, bn2, conv2, bn1, conv1; conv1's input gradient takes that gradient, or the downsample
+// branch's input gradient, as its addend.
+void resnextBlockBackwardDevice(cvd_handle* h, int B, int H, int W, int inChannels, int width, int outChannels, int groups, int stride,
+                                int downsample, const float* gy, const float* x, const float* const* weights, const float* const* gammas,
+                                const float* const* saved, const int* training, float* gx, float* const* gWeights,
+                                float* const* gGammas, float* const* gBetas, hipStream_t s) {
+  const char* who = "resnext block backward";
+  const RxBlockDims d = checkRxBlock(who, B, H, W, inChannels, width, outChannels, groups, stride, downsample);
+  if (!gy || !x || !weights || !gammas || !saved || !training || !gWeights || !gGammas || !gBetas)
+    throw std::runtime_error(fmt("%s: null array", who));
+  for (int i = 0; i < d.n; ++i) {
+    if (!weights[i] || !gammas[i] || !gWeights[i] || !gGammas[i] || !gBetas[i]) throw std::runtime_error(fmt("%s: null array of convolution %d", who, i));
+    for (int j = 0; j < 4; ++j)
+      if (!saved[4 * i + j]) throw std::runtime_error(fmt("%s: null saved tensor %d of convolution %d", who, j, i));
+  }
+  Frontend& fe = *h->frontend;
+  const size_t big = static_cast<size_t>(d.mOut) * outChannels, mid = static_cast<size_t>(d.mOut) * width,
+               wide = static_cast<size_t>(d.mIn) * width, in = static_cast<size_t>(d.mIn) * inChannels;
+  fe.dRxBlock.ensure(3 * big + 2 * mid + 2 * wide + in);
+  float* gc3 = fe.dRxBlock.p;
+  float* gres = gc3 + big;
+  float* gcd = gres + big;
+  float* g2 = gcd + big;
+  float* gc2 = g2 + mid;
+  float* g1 = gc2 + mid;
+  float* gc1 = g1 + wide;
+  float* gxd = gc1 + wide;
+  const auto norm = [&](int i, int channels, int hh, int ww, const float* g, bool mask, float* gc, float* gr) {
+    resnextNormGradDevice(h, B, channels, hh, ww, g, saved[4 * i], mask ? saved[4 * i + 3] : nullptr, saved[4 * i + 1], saved[4 * i + 2],
+                          gammas[i], training[i], gc, gGammas[i], gBetas[i], gr, s);
+  };
+  norm(2, outChannels, d.Ho, d.Wo, gy, true, gc3, gres);
+  resnextConvGradWeightDevice(h, B, d.Ho, d.Wo, width, outChannels, 1, 1, gc3, saved[7], 0, gWeights[2], s);
+  resnextConvGradInputDevice(h, B, d.Ho, d.Wo, width, outChannels, 1, 1, gc3, weights[2], nullptr, g2, s);
+  norm(1, width, d.Ho, d.Wo, g2, true, gc2, nullptr);
+  resnextGroupedConvGradWeightDevice(h, B, H, W, groups, d.cg, stride, gc2, saved[3], 0, gWeights[1], s);
+  resnextGroupedConvGradInputDevice(h, B, H, W, groups, d.cg, stride, gc2, weights[1], g1, s);
+  norm(0, width, H, W, g1, true, gc1, nullptr);
+  resnextConvGradWeightDevice(h, B, H, W, inChannels, width, 1, 1, gc1, x, 0, gWeights[0], s);
+  const float* add = gres;
+  if (downsample) {
+    norm(3, outChannels, d.Ho, d.Wo, gres, false, gcd, nullptr);
+    resnextConvGradWeightDevice(h, B, H, W, inChannels, outChannels, 1, stride, gcd, x, 0, gWeights[3], s);
+    if (gx) resnextConvGradInputDevice(h, B, H, W, inChannels, outChannels, 1, stride, gcd, weights[3], nullptr, gxd, s);
+    add = gxd;
+  }
+  if (gx) resnextConvGradInputDevice(h, B, H, W, inChannels, width, 1, 1, gc1, weights[0], add, gx, s);
 }
 
 // One kernel of this translation unit's code object is looked up at handle creation: the HIP runtime loads a unit's device

@@ -846,5 +846,28 @@ void resnextMaxPoolDevice(cvd_handle* h, int B, int channels, int H, int W, cons
 void midasBackboneDevice(cvd_handle* h, int B, int H, int W, const int* blocks, int groups, int widthPerGroup, float eps,
                          const float* images, const float* const* weights, const float* const* norms, float* const* outs,
                          hipStream_t s, double* kernelMs);
+// its training form and backward (cvd_resnext_grad.h)
+void resnextNormTrainDevice(cvd_handle* h, int B, int channels, int H, int W, const float* c, const float* gamma, const float* beta,
+                            float* runningMean, float* runningVar, double eps, double momentum, int training, int relu,
+                            const float* residual, float* saveMean, float* saveInvstd, float* y, hipStream_t s);
+void resnextNormGradDevice(cvd_handle* h, int B, int channels, int H, int W, const float* gy, const float* c, const float* y,
+                           const float* mean, const float* invstd, const float* gamma, int training, float* gc, float* gGamma,
+                           float* gBeta, float* gResidual, hipStream_t s);
+void resnextGroupedConvGradInputDevice(cvd_handle* h, int B, int H, int W, int groups, int channelsPerGroup, int stride, const float* gy,
+                                       const float* weight, float* gx, hipStream_t s);
+void resnextGroupedConvGradWeightDevice(cvd_handle* h, int B, int H, int W, int groups, int channelsPerGroup, int stride, const float* gy,
+                                        const float* x, int split, float* gWeight, hipStream_t s);
+void resnextConvGradInputDevice(cvd_handle* h, int B, int H, int W, int inChannels, int outChannels, int kernelSize, int stride,
+                                const float* gy, const float* weight, const float* add, float* gx, hipStream_t s);
+void resnextConvGradWeightDevice(cvd_handle* h, int B, int H, int W, int inChannels, int outChannels, int kernelSize, int stride,
+                                 const float* gy, const float* x, int split, float* gWeight, hipStream_t s);
+void resnextMaxPoolGradDevice(cvd_handle* h, int B, int channels, int H, int W, const float* x, const float* gy, float* gx, hipStream_t s);
+void resnextBlockTrainDevice(cvd_handle* h, int B, int H, int W, int inChannels, int width, int outChannels, int groups, int stride,
+                             int downsample, const float* x, const float* const* weights, float* const* norms, double eps,
+                             double momentum, const int* training, float* const* saved, hipStream_t s);
+void resnextBlockBackwardDevice(cvd_handle* h, int B, int H, int W, int inChannels, int width, int outChannels, int groups, int stride,
+                                int downsample, const float* gy, const float* x, const float* const* weights, const float* const* gammas,
+                                const float* const* saved, const int* training, float* gx, float* const* gWeights,
+                                float* const* gGammas, float* const* gBetas, hipStream_t s);
 
 }  // namespace cvd

@@ -19,10 +19,12 @@ module names and state-dict keys, and accept training mode and tensors that requ
 dropout, so .train() and .eval() compute the same function.  The forward values are those of the forward-only classes bit for bit
 (the same launches).  A convolution with the epilogue ReLU flag has no differentiable path here; the decoder never uses it.
 
-The backbone of MidasNet is either a stock-torch module with layer1 .. layer4, run by torch under autograd (it receives the gradients
-of the four feature maps), or a native midas.ResNeXt with freeze_backbone=True: its parameters do not require grad, it stays in eval
-mode whatever .train() is called on the net, and it runs under no_grad, so the four layerK_rn input gradients -- the most expensive
-ones -- are skipped.  A native ResNeXt that is not frozen is refused: the backbone's backward has no kernel yet.
+The backbone of MidasNet is a stock-torch module with layer1 .. layer4, run by torch under autograd (it receives the gradients of the
+four feature maps); or a native midas.ResNeXt with freeze_backbone=True: its parameters do not require grad, it stays in eval mode
+whatever .train() is called on the net, and it runs under no_grad, so the four layerK_rn input gradients -- the most expensive ones
+-- are skipped; or a ResNeXt of THIS module (csrc/cvd_resnext_grad.h), which trains: batch-statistics norms in
+training mode, every one of the 624-key parameters receives a gradient (midas_v21(path) builds that net, the reference's fine-tuning
+form).  A forward-only midas.ResNeXt that is not frozen is refused: that class has no backward.
 
 MidasNet.decode is ONE library call forward (cvd_midas_decoder_train_device, which writes the activations the backward needs into a
 table of 16 tensors kept by autograd) and ONE backward (cvd_midas_decoder_backward_device); the block classes chain the operators.
@@ -277,6 +279,207 @@ class FeatureFusionBlock(midas.FeatureFusionBlock):
         return upsample2x(self.resConfUnit2(output), True)
 
 
+# ---- the backbone in training (csrc/cvd_resnext_grad.h) -------------------------------------------------------------
+def _rx_bare_conv(x, weight, stride, groups):
+    """The raw output of a backbone convolution: the forward kernels of csrc/cvd_resnext.h called with a null norm."""
+    if groups > 1:
+        B, H, W, G, cg, Ho, Wo = api.resnext_check_grouped_conv(x.shape, weight.shape, stride)
+        out = torch.empty((B, G * cg, Ho, Wo), dtype=torch.float32, device=x.device)
+        midas._call(x.device, "resnext_grouped_conv_device", _i32(B), _i32(H), _i32(W), _i32(G), _i32(cg), _i32(stride), tc.ptr(x),
+                    tc.ptr(weight), None, C.c_float(api.RESNEXT_EPS), _i32(0), tc.ptr(out))
+        return out
+    B, H, W, Cin, N, k, Ho, Wo = api.resnext_check_conv(x.shape, weight.shape, stride)
+    out = torch.empty((B, N, Ho, Wo), dtype=torch.float32, device=x.device)
+    midas._call(x.device, "resnext_conv_device", _i32(B), _i32(H), _i32(W), _i32(Cin), _i32(N), _i32(k), _i32(stride), tc.ptr(x),
+                tc.ptr(weight), None, C.c_float(api.RESNEXT_EPS), _i32(0), None, _i32(0), tc.ptr(out))
+    return out
+
+
+def _rx_norm(who, c, bn, relu, residual=None):
+    """nn.BatchNorm2d `bn` on c in the mode of bn.training (each norm follows its own flag, as torch's) -> (y, mean, invstd); the
+    running statistics and num_batches_tracked are updated in training mode."""
+    midas._check_norm(who, bn)
+    four = midas._norm_vectors(bn)
+    B, N, H, W = api.resnext_check_norm_train(c.shape, [t.shape for t in four], bn.eps, bn.momentum, bn.training,
+                                              None if residual is None else residual.shape)
+    if not (bn.running_mean.is_contiguous() and bn.running_var.is_contiguous()):
+        raise ValueError(f"{who}: the running statistics must be contiguous")
+    gamma, beta = _plain(bn.weight), _plain(bn.bias)
+    y = torch.empty_like(c)
+    mean, invstd = (torch.empty((N,), dtype=torch.float32, device=c.device) for _ in range(2))
+    midas._call(c.device, "resnext_norm_train_device", _i32(B), _i32(N), _i32(H), _i32(W), tc.ptr(c), tc.ptr(gamma), tc.ptr(beta),
+                tc.ptr(bn.running_mean), tc.ptr(bn.running_var), C.c_double(bn.eps), C.c_double(bn.momentum),
+                _i32(1 if bn.training else 0), _i32(1 if relu else 0), tc.ptr(residual), tc.ptr(mean), tc.ptr(invstd), tc.ptr(y))
+    if bn.training:
+        bn.num_batches_tracked.add_(1)
+    return y, mean, invstd
+
+
+def _rx_norm_grad(gy, c, y, mean, invstd, gamma, training, residual=False):
+    B, N, H, W = api.resnext_check_norm_grad(gy.shape, c.shape, None if y is None else y.shape, [mean.shape, invstd.shape, gamma.shape],
+                                             training)
+    gc = torch.empty_like(c)
+    gg, gb = (torch.empty((N,), dtype=torch.float32, device=c.device) for _ in range(2))
+    gr = torch.empty_like(c) if residual else None
+    midas._call(c.device, "resnext_norm_grad_device", _i32(B), _i32(N), _i32(H), _i32(W), tc.ptr(gy), tc.ptr(c), tc.ptr(y), tc.ptr(mean),
+                tc.ptr(invstd), tc.ptr(gamma), _i32(1 if training else 0), tc.ptr(gc), tc.ptr(gg), tc.ptr(gb), tc.ptr(gr))
+    return gc, gg, gb, gr
+
+
+def _rx_conv_grad_weight(gy, x, weight, stride, groups):
+    B, _, H, W = x.shape
+    gw = torch.empty_like(weight)
+    if groups > 1:
+        _, _, _, G, cg = api.resnext_check_grouped_conv_grad_weight(gy.shape, x.shape, weight.shape[1], stride)
+        midas._call(x.device, "resnext_grouped_conv_grad_weight_device", _i32(B), _i32(H), _i32(W), _i32(G), _i32(cg), _i32(stride),
+                    tc.ptr(gy), tc.ptr(x), _i32(0), tc.ptr(gw))
+        return gw
+    _, _, _, Cin, N, k = api.resnext_check_conv_grad_weight(gy.shape, x.shape, weight.shape[2], stride)
+    midas._call(x.device, "resnext_conv_grad_weight_device", _i32(B), _i32(H), _i32(W), _i32(Cin), _i32(N), _i32(k), _i32(stride),
+                tc.ptr(gy), tc.ptr(x), _i32(0), tc.ptr(gw))
+    return gw
+
+
+class _BlockFn(torch.autograd.Function):
+    """One Bottleneck: ONE library call forward (cvd_resnext_block_train_device, which fills the saved table: per convolution its
+    raw output, mean, invstd and post-activation tensor -- the ReLU masks are the tensors the forward wrote) and ONE backward
+    (cvd_resnext_block_backward_device).  Arguments: the module, x, then per convolution (conv1, conv2, conv3, downsample.0) its
+    weight and its norm's weight and bias."""
+
+    @staticmethod
+    def forward(ctx, block, x, *params):
+        x = _plain(x)
+        params = [_plain(p) for p in params]
+        bns = [block.bn1, block.bn2, block.bn3] + ([] if block.downsample is None else [block.downsample[1]])
+        n = len(bns)
+        for bn in bns:
+            midas._check_norm("Bottleneck", bn)
+            if bn.eps != bns[0].eps or bn.momentum != bns[0].momentum:
+                raise ValueError("Bottleneck: the norms of a block must share eps and momentum")
+            if not (bn.running_mean.is_contiguous() and bn.running_var.is_contiguous()):
+                raise ValueError("Bottleneck: the running statistics must be contiguous")
+        weights = params[0::3]
+        norms = [[params[3 * i + 1], params[3 * i + 2], bn.running_mean, bn.running_var] for i, bn in enumerate(bns)]
+        dims = api.resnext_check_block(x.shape, [w.shape for w in weights], [[t.shape for t in four] for four in norms],
+                                       block.conv2.stride[0], bns[0].eps, bns[0].momentum, [bn.training for bn in bns])
+        B, H, W, Cin, width, out, G, stride, down, flags = dims
+        saved = [torch.empty(sh, dtype=torch.float32, device=x.device)
+                 for sh in api.resnext_block_saved_shapes(B, H, W, Cin, width, out, stride, down)]
+        ctx.dims = dims
+        ctx.scalars = [_i32(v) for v in (B, H, W, Cin, width, out, G, stride, int(down))]
+        midas._call(x.device, "resnext_block_train_device", *ctx.scalars, tc.ptr(x), _table(weights),
+                    _table([t for four in norms for t in four]), C.c_double(bns[0].eps), C.c_double(bns[0].momentum),
+                    (_i32 * n)(*[int(f) for f in flags]), _table(saved))
+        for bn in bns:
+            if bn.training:
+                bn.num_batches_tracked.add_(1)
+        ctx.save_for_backward(x, *params, *saved)
+        return saved[11]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        flags = ctx.dims[9]
+        n = len(flags)
+        kept = ctx.saved_tensors
+        x, params, saved = kept[0], kept[1:1 + 3 * n], kept[1 + 3 * n:]
+        gy = gy.contiguous()
+        weights, gammas = params[0::3], params[1::3]
+        gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        gw, gg, gb = ([torch.empty_like(t) for t in group] for group in (weights, gammas, gammas))
+        midas._call(x.device, "resnext_block_backward_device", *ctx.scalars, tc.ptr(gy), tc.ptr(x), _table(weights), _table(gammas),
+                    _table(saved), (_i32 * n)(*[int(f) for f in flags]), tc.ptr(gx), _table(gw), _table(gg), _table(gb))
+        grads = [t for three in zip(gw, gg, gb) for t in three]
+        return (None, gx, *[g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:])])
+
+
+class _StemFn(torch.autograd.Function):
+    """conv1 7 x 7 / 2, bn1, ReLU, the pool; the images receive no gradient (that kernel is not built)."""
+
+    @staticmethod
+    def forward(ctx, stem, x, weight, gamma, beta):
+        x, weight, gamma = _plain(x), _plain(weight), _plain(gamma)
+        c = _rx_bare_conv(x, weight, 2, 1)
+        y, mean, invstd = _rx_norm("ResNeXt.layer1.1", c, stem[1], True)
+        ctx.training = stem[1].training
+        ctx.save_for_backward(x, weight, gamma, c, y, mean, invstd)
+        return midas._rx_maxpool(y)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gp):
+        x, weight, gamma, c, y, mean, invstd = ctx.saved_tensors
+        gp = gp.contiguous()
+        B, Cn, H, W = api.resnext_check_maxpool_grad(y.shape, gp.shape)
+        gyv = torch.empty_like(y)
+        midas._call(y.device, "resnext_maxpool_grad_device", _i32(B), _i32(Cn), _i32(H), _i32(W), tc.ptr(y), tc.ptr(gp), tc.ptr(gyv))
+        gc, gg, gb, _ = _rx_norm_grad(gyv, c, y, mean, invstd, gamma, ctx.training)
+        gw = _rx_conv_grad_weight(gc, x, weight, 2, 1)
+        return None, None, gw, gg, gb
+
+
+class Bottleneck(midas.Bottleneck):
+    """midas.Bottleneck with a backward: the same members and state-dict keys.  Each norm follows its own .training flag: batch
+    statistics (the running ones and num_batches_tracked updated) or the running statistics."""
+
+    def forward(self, x):
+        _check("Bottleneck", {"x": x, **midas._tensors(self)})
+        convs = [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)]
+        if self.downsample is not None:
+            convs.append((self.downsample[0], self.downsample[1]))
+        return _BlockFn.apply(self, x, *[t for conv, bn in convs for t in (conv.weight, bn.weight, bn.bias)])
+
+
+class _Stem(midas._Stem):
+    def forward(self, x):
+        _check("ResNeXt.layer1", {"x": x, **midas._tensors(self)})
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise ValueError("ResNeXt.layer1: the images require grad, and the stem's input gradient has no kernel")
+        return self[4](_StemFn.apply(self, x, self[0].weight, self[1].weight, self[1].bias))
+
+
+class ResNeXt(midas.ResNeXt):
+    """midas.ResNeXt with a backward: the same modules and the reference checkpoint's 624 `pretrained.*` keys.
+    layer1 .. layer4 run their stages under autograd, a torch.autograd.Function per block; .train() runs the norms on batch
+    statistics as the reference's fine-tuning does, .eval() with parameters that require grad is the frozen-statistics form.  In
+    eval mode with grad mode off, forward(x) is midas.ResNeXt's one-call inference path."""
+
+    def __init__(self, blocks=api.RESNEXT101_32X8D[0], groups=api.RESNEXT101_32X8D[1], width_per_group=api.RESNEXT101_32X8D[2]):
+        super().__init__(blocks, groups, width_per_group)
+        # (the parent's constructor builds its own forward-only blocks: the same members, so the class alone changes.  Both
+        # classes are module-level and importable, which copy.deepcopy and pickling of the net rely on.)
+        for m in self.modules():
+            if type(m) is midas.Bottleneck:
+                m.__class__ = Bottleneck
+            elif type(m) is midas._Stem:
+                m.__class__ = _Stem
+
+    def forward(self, x):
+        who = "ResNeXt"
+        if not torch.is_grad_enabled() and not any(m.training for m in self.modules()):
+            return super().forward(x)
+        _check(who, {"x": x})
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"{who}: x must be (B, 3, H, W) (got {tuple(x.shape)})")
+        if x.shape[2] % 32 or x.shape[3] % 32:
+            raise ValueError(f"{who}: height and width must be multiples of 32 (got {x.shape[2]} x {x.shape[3]})")
+        maps = []
+        for k in (1, 2, 3, 4):
+            maps.append(getattr(self, f"layer{k}")(maps[-1] if maps else x))
+        return maps
+
+
+def resnext101_32x8d():
+    """The architecture of the reference's `resnext101_32x8d_wsl` backbone with a backward, with no weights: nothing is fetched."""
+    return ResNeXt(*api.RESNEXT101_32X8D)
+
+
+def midas_v21(path=None, freeze_backbone=False):
+    """The reference's MidasNet(path) (midas_net.py:13-29) as depth_fine_tuning.py trains it: the native backbone and decoder, every
+    parameter trainable unless freeze_backbone."""
+    return MidasNet(path, backbone=resnext101_32x8d(), freeze_backbone=freeze_backbone)
+
+
 class MidasNet(midas.MidasNet):
     """midas.MidasNet with a differentiable decoder: the same modules, names and 42 `scratch.*` state-dict keys, so the reference's
     checkpoint and its `save` round-trip.  freeze_backbone: see the module's text."""
@@ -305,9 +508,9 @@ class MidasNet(midas.MidasNet):
         self.non_negative = bool(non_negative)
         self.freeze_backbone = bool(freeze_backbone)
         native = isinstance(self.pretrained, midas.ResNeXt)
-        if native and not self.freeze_backbone:
-            raise ValueError("MidasNet: training the native ResNeXt backbone has no kernel yet (its backward is not built): pass "
-                             "freeze_backbone=True, or a stock-torch backbone")
+        if native and not isinstance(self.pretrained, ResNeXt) and not self.freeze_backbone:
+            raise ValueError("MidasNet: training the forward-only midas.ResNeXt backbone has no kernel yet (that class has no "
+                             "backward): pass a midas_train.ResNeXt, freeze_backbone=True, or a stock-torch backbone")
         if self.freeze_backbone:
             for p in self.pretrained.parameters():
                 p.requires_grad_(False)
